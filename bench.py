@@ -10,13 +10,16 @@ resident in HBM: dvs_pack_features -> forward -> backward -> (RCCL SUM all-reduc
 -> fused clip_grad_norm_(1.0) + Adam(lr 1e-4), in train mode with dropout 0.15 — i.e. train_batch() of
 experiments/03_synthetic_12/main.py:95-118 including its loss.item() host read.  Workload: BASELINE configs[1]/metric
 shape: synthetic n=12, card=12, batch 4096 per GPU (weak scaling: global batch = 4096 * N, one gradient all-reduce).
-With N > 1 the same run also times the strong-scaling reading of the metric (GLOBAL batch 4096,
+With N > 1 and --full the same run also times the strong-scaling reading of the metric (GLOBAL batch 4096,
 4096 / N DAGs per GPU) and reports it as the "strong" object of the same line; `--scaling strong` makes that the headline.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel (per-kernel durations measured with
-HIP events on the launch stream inside libdvs_hip.so; `frac` on SURVEY §8d's algorithmic FLOPs, i.e. WITHOUT the
-backward's recompute, `hfu` with it) and "cpu_baseline" (the oracle = CPU port of the reference step, timed on this box's
-host cores on a bounded sample; rank 0 at N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, ...); `--dump-outputs DIR` first writes what the last timed step returned (see dump_outputs).  `--full`
+adds what the headline does not need, measured after the timed region: "kernels" and "roofline" for the dominant
+kernel (per-kernel durations measured with HIP events on the launch stream inside libdvs_hip.so, in separate untimed
+steps; `frac` on SURVEY §8d's algorithmic FLOPs, i.e. WITHOUT the backward's recompute, `hfu` with it), "hbm_roofline",
+the other scaling reading at N > 1, and "cpu_baseline" (the oracle = CPU port of the reference step, timed on the host's
+cores on a bounded sample; rank 0 at N=1 only, `--no-cpu-baseline` drops it).
 """
 import argparse
 import json
@@ -200,6 +203,23 @@ def cpu_baseline(graphs, feats, steps: int = 5, warmup: int = 3):
                       f"B={B} batch, torch CPU fp32, {cores} threads", "ms_per_step": dt * 1e3}
 
 
+def dump_outputs(out_dir: str, last, model):
+    """What a caller of the timed path holds after its last step: train_batch's (loss, recon, kld) and the model it
+    updated, i.e. every parameter and its .grad, flattened and concatenated in model.parameters() order (independent of
+    the padding of the device's flat buffer).  Inputs, initial weights and dropout streams are seeded, so the same
+    arguments give the same inputs on every run."""
+    import numpy as np
+    loss_value, recon, kld = last
+    params = list(model.parameters())
+    arrays = {"loss": np.array([loss_value, float(recon), float(kld)], dtype=np.float64),     # [total, recon, kld]
+              "params": torch.cat([p.detach().reshape(-1) for p in params]).float().cpu().numpy(),
+              "grads": torch.cat([p.grad.detach().reshape(-1) for p in params]).float().cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,11 +231,16 @@ def main():
                     help="n12 = the BASELINE metric shape (default); the others are the remaining BASELINE configs")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --batch DAGs per GPU (global = batch * N); strong: --batch DAGs in total (SURVEY §8d's "
-                         "reading of the metric: global 4096, 4096 / N per GPU).  With N > 1 the other one is timed too "
-                         "and reported as a secondary object of the same line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "reading of the metric: global 4096, 4096 / N per GPU).  With --full and N > 1 the other one is "
+                         "timed too and reported as a secondary object of the same line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the RCCL code path even with one rank (checks init / all-reduce plumbing on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure per-kernel durations and the roofline, the other scaling "
+                         "reading (N > 1) and the CPU baseline (N = 1); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss scalars, parameters, gradient) as DIR/<name>.npy")
     args = ap.parse_args()
     global N_VERT, CARD, DENSITY
     N_VERT, CARD, default_batch, DENSITY, workload_desc = WORKLOADS[args.workload]
@@ -266,7 +291,8 @@ def main():
 
     def timed_run(local_batch: int, steps: int, warmup: int):
         """One model + one resident batch of `local_batch` DAGs per rank; W untimed + K timed train steps bracketed by
-        barrier + synchronize, MAX over ranks.  Returns (seconds, last loss, model, step fn, graphs, host features)."""
+        barrier + synchronize, MAX over ranks.  Returns (seconds, what the last step returned, model, step fn, graphs,
+        host features)."""
         torch.manual_seed(42)      # experiments/03_synthetic_12/main.py:122-124: same initial weights on every rank
         model = PaceVaeV3(max_num_vertices=N_VERT, vertex_label_cardinality=CARD, vertices_embedding_size=32,
                           num_heads=8, num_layers=3, ff_hidden_size=64, latent_layer_size=32, fc_hidden=32,
@@ -283,38 +309,43 @@ def main():
         sync()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss_value, _, _ = step()
+            last = step()
         sync()
         dt = time.perf_counter() - t0
         if distributed:
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, loss_value, model, step, graphs, feats
+        return dt, last, model, step, graphs, feats
 
     # headline region
     local_batch = args.batch if args.scaling == "weak" else args.batch // world
     global_batch = local_batch * world
     log(f"{args.scaling} scaling: {local_batch} DAGs per GPU, global batch {global_batch}; warm-up + timed region")
-    dt, loss_value, model, step, graphs, feats = timed_run(local_batch, args.steps, args.warmup)
+    dt, last, model, step, graphs, feats = timed_run(local_batch, args.steps, args.warmup)
+    loss_value = last[0]
     ms_per_step = dt / args.steps * 1e3
     value = global_batch * args.steps / dt
     log(f"timed region done: {ms_per_step:.3f} ms/step")
-
-    # ---- per-kernel durations (HIP events on the launch stream), separate untimed steps --------------------------------
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, last, model)
+        log(f"outputs of the last timed step written: {', '.join(names)}")
     lib = dl.load()
-    lib.dvs_profile_enable(1)
-    prof_steps = 3
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    prof = dl.profile_collect(lib)
-    lib.dvs_profile_enable(0)
-    sync()
 
-    # ---- the other scaling mode, same process, N > 1 only (at N = 1 they coincide) --------------------------------------
+    # ---- --full: per-kernel durations (HIP events on the launch stream), separate untimed steps --------------------------
+    if args.full:
+        prof_steps = 3
+        lib.dvs_profile_enable(1)
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        prof = dl.profile_collect(lib)
+        lib.dvs_profile_enable(0)
+        sync()
+
+    # ---- --full: the other scaling mode, same process, N > 1 only (at N = 1 they coincide) -------------------------------
     other = None
-    if world > 1:
+    if args.full and world > 1:
         o_mode = "strong" if args.scaling == "weak" else "weak"
         o_local = args.batch // world if o_mode == "strong" else args.batch
         del step
@@ -327,48 +358,8 @@ def main():
 
     if rank == 0:
         N, C = N_VERT + 3, CARD + 3
-        P = sum(p.numel() for p in model.parameters())
-        algo, executed = algo_flops_per_dag(N, C)
-        kern = {k: {"launches_per_step": c // prof_steps, "avg_us": 1e3 * ms / c, "ms_per_step": ms / prof_steps}
-                for k, (c, ms) in prof.items()}
-        dom = max(kern, key=lambda k: kern[k]["ms_per_step"])
-        dom_key = dom if dom in executed else (dom[:-2] if dom.endswith("_w") else dom)      # wide-path kernels: same algorithmic work
-        per_launch_s = kern[dom]["avg_us"] * 1e-6
-        ach = algo.get(dom_key, 0.0) * local_batch / per_launch_s / 1e12
-        hfu = executed.get(dom_key, 0.0) * local_batch / per_launch_s / 1e12
-        step_flops = 3e6 * {8: 5.71, 11: 7.74, 12: 8.46, 37: 34.0}[N_VERT]      # 3 x forward MFLOP per DAG
-        bpd = bytes_per_dag(N, C, P, local_batch)
-        per_gpu_rate = value / world
-        traffic, traffic_step, traffic_src = pmc_traffic(dom, args.workload, local_batch)
-        busy, wait, sq_src = pmc_mfma_busy(dom, args.workload, local_batch)
-        roofline = {
-            "bound": "mfma", "kernel": dom, "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-            "frac": ach / PEAK_F32_MFMA_TFLOPS,
-            "frac_note": "algorithmic FLOPs of SURVEY.md 8d (backward = 2 x forward of the ops the launch owns, recompute NOT "
-                         "counted) / HIP-event launch duration / fp32 matrix peak; arithmetic is delivered at fp32 accuracy, most "
-                         "of it on the bf16 pipe with split operands, so this is delivered arithmetic, not pipe utilisation",
-            "hfu": hfu / PEAK_F32_MFMA_TFLOPS, "hfu_note": "same with the backward's recompute of forward quantities counted",
-            "traffic": traffic, "traffic_source": traffic_src,
-            "traffic_note": "HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE passes collected by "
-                            "the builder (tools/collect_profiles.sh) and replayed from the committed file; not measured in this run",
-            "avg_launch_us": kern[dom]["avg_us"], "launches_per_step": kern[dom]["launches_per_step"],
-            "algorithmic_flops_per_dag": algo.get(dom_key, 0.0), "executed_flops_per_dag": executed.get(dom_key, 0.0),
-            **({"phases": STACK_PHASES[dom_key]} if dom_key in STACK_PHASES else {}),
-            **({"mfma_pipe_busy": busy, "waves_waiting": wait, "counters_source": sq_src} if sq_src else {}),
-            "whole_step": {"tflops": per_gpu_rate * step_flops / 1e12,
-                           "frac_f32_mfma_peak": per_gpu_rate * step_flops / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                           "hbm_algorithmic_GBs": per_gpu_rate * bpd / 1e9,
-                           "gpu_kernel_ms_per_step": sum(k["ms_per_step"] for k in kern.values())}}
-        # the north star's contract figure, lifted to the top level: achieved fraction of the HBM roofline on ALGORITHMIC bytes
-        # (bytes_per_DAG x DAGs/s / 8 TB/s), and how much more than that the counters say really moves
-        hbm = {"algorithmic_bytes_per_dag": bpd, "algorithmic_GBs_per_gpu": per_gpu_rate * bpd / 1e9,
-               "frac_hbm_peak": per_gpu_rate * bpd / 1e9 / PEAK_HBM_GBS, "peak_GBs": PEAK_HBM_GBS}
-        if traffic_step:
-            hbm.update({"counter_bytes_per_step": traffic_step, "counter_GBs": traffic_step / (ms_per_step * 1e-3) / 1e9,
-                        "counter_frac_hbm_peak": traffic_step / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                        "traffic_over_algorithmic": traffic_step / (bpd * local_batch), "counter_source": traffic_src})
-        # Which reading of BASELINE.json's metric the headline is (the line always says; with N > 1 the OTHER reading is timed in
-        # the same process and attached under its own key, so one launch per N gives the driver both curves):
+        # Which reading of BASELINE.json's metric the headline is (the line always says; with --full and N > 1 the OTHER reading
+        # is timed in the same process and attached under its own key, so one launch per N gives both curves):
         #   weak   — 4096 DAGs PER GPU (global batch 4096 N): the reading this file has reported since round 1 and the one
         #            the driver's weak-scaling efficiency is computed on; one gradient all-reduce per step either way.
         #   strong — SURVEY.md 8d's reading: GLOBAL batch 4096, 4096 / N DAGs per GPU.  Below 1024 DAGs per GPU a step is
@@ -390,16 +381,59 @@ def main():
                                                     and os.environ.get("DVS_WAVES_PER_WG") != "8") else 8,
                        "parallelism": f"dp{world}" if world > 1 else "single",
                        "last_loss_per_dag": loss_value / global_batch},
-            "frac_hbm_peak": hbm["frac_hbm_peak"],
-            "hbm_roofline": hbm,
-            "roofline": roofline,
-            "kernels": {k: round(v["ms_per_step"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])},
         }
-        if other is not None:
-            out[other["scaling"]] = other
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(graphs, feats)
-            out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+        if args.full:
+            P = sum(p.numel() for p in model.parameters())
+            algo, executed = algo_flops_per_dag(N, C)
+            kern = {k: {"launches_per_step": c // prof_steps, "avg_us": 1e3 * ms / c, "ms_per_step": ms / prof_steps}
+                    for k, (c, ms) in prof.items()}
+            dom = max(kern, key=lambda k: kern[k]["ms_per_step"])
+            dom_key = dom if dom in executed else (dom[:-2] if dom.endswith("_w") else dom)      # wide-path kernels: same algorithmic work
+            per_launch_s = kern[dom]["avg_us"] * 1e-6
+            ach = algo.get(dom_key, 0.0) * local_batch / per_launch_s / 1e12
+            hfu = executed.get(dom_key, 0.0) * local_batch / per_launch_s / 1e12
+            step_flops = 3e6 * {8: 5.71, 11: 7.74, 12: 8.46, 37: 34.0}[N_VERT]      # 3 x forward MFLOP per DAG
+            bpd = bytes_per_dag(N, C, P, local_batch)
+            per_gpu_rate = value / world
+            traffic, traffic_step, traffic_src = pmc_traffic(dom, args.workload, local_batch)
+            busy, wait, sq_src = pmc_mfma_busy(dom, args.workload, local_batch)
+            roofline = {
+                "bound": "mfma", "kernel": dom, "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                "frac": ach / PEAK_F32_MFMA_TFLOPS,
+                "frac_note": "algorithmic FLOPs of SURVEY.md 8d (backward = 2 x forward of the ops the launch owns, recompute NOT "
+                             "counted) / HIP-event launch duration / fp32 matrix peak; arithmetic is delivered at fp32 accuracy, most "
+                             "of it on the bf16 pipe with split operands, so this is delivered arithmetic, not pipe utilisation",
+                "hfu": hfu / PEAK_F32_MFMA_TFLOPS, "hfu_note": "same with the backward's recompute of forward quantities counted",
+                "traffic": traffic, "traffic_source": traffic_src,
+                "traffic_note": "HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE passes collected by "
+                                "the builder (tools/collect_profiles.sh) and replayed from the committed file; not measured in this run",
+                "avg_launch_us": kern[dom]["avg_us"], "launches_per_step": kern[dom]["launches_per_step"],
+                "algorithmic_flops_per_dag": algo.get(dom_key, 0.0), "executed_flops_per_dag": executed.get(dom_key, 0.0),
+                **({"phases": STACK_PHASES[dom_key]} if dom_key in STACK_PHASES else {}),
+                **({"mfma_pipe_busy": busy, "waves_waiting": wait, "counters_source": sq_src} if sq_src else {}),
+                "whole_step": {"tflops": per_gpu_rate * step_flops / 1e12,
+                               "frac_f32_mfma_peak": per_gpu_rate * step_flops / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                               "hbm_algorithmic_GBs": per_gpu_rate * bpd / 1e9,
+                               "gpu_kernel_ms_per_step": sum(k["ms_per_step"] for k in kern.values())}}
+            # the north star's contract figure, lifted to the top level: achieved fraction of the HBM roofline on ALGORITHMIC bytes
+            # (bytes_per_DAG x DAGs/s / 8 TB/s), and how much more than that the counters say really moves
+            hbm = {"algorithmic_bytes_per_dag": bpd, "algorithmic_GBs_per_gpu": per_gpu_rate * bpd / 1e9,
+                   "frac_hbm_peak": per_gpu_rate * bpd / 1e9 / PEAK_HBM_GBS, "peak_GBs": PEAK_HBM_GBS}
+            if traffic_step:
+                hbm.update({"counter_bytes_per_step": traffic_step, "counter_GBs": traffic_step / (ms_per_step * 1e-3) / 1e9,
+                            "counter_frac_hbm_peak": traffic_step / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                            "traffic_over_algorithmic": traffic_step / (bpd * local_batch), "counter_source": traffic_src})
+            out.update({
+                "frac_hbm_peak": hbm["frac_hbm_peak"],
+                "hbm_roofline": hbm,
+                "roofline": roofline,
+                "kernels": {k: round(v["ms_per_step"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])},
+            })
+            if other is not None:
+                out[other["scaling"]] = other
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(graphs, feats)
+                out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -15,7 +15,7 @@ mkdir -p $OUT
 ARGS="--workload $WL --batch $BATCH"
 cd /tmp && cd $ROOT
 
-python3 bench.py $ARGS --steps 50 --warmup 10 > $OUT/${TAG}_bench_${SFX}.json 2> $OUT/bench_${SFX}.err || exit 1
+python3 bench.py --full $ARGS --steps 50 --warmup 10 > $OUT/${TAG}_bench_${SFX}.json 2> $OUT/bench_${SFX}.err || exit 1
 echo "bench done"
 
 # the same command as the bench line above (50 timed steps behind 10 warm-up steps); the statistics cover the timed steps only

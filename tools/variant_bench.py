@@ -12,7 +12,7 @@ import sys, runpy
 sys.path.insert(0, ".")
 from dags_vae_search_amd import _lib as dl
 dl.LIB_NAME = "libdvs_%s.so"
-sys.argv = ["bench.py", "--steps", "100", "--warmup", "20", "--no-cpu-baseline"] + %r
+sys.argv = ["bench.py", "--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--full"] + %r
 runpy.run_path("bench.py", run_name="__main__")
 '''
 extra = []
