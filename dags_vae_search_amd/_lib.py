@@ -21,6 +21,7 @@ CLIP_SCRATCH_FLOATS = 4096  # DVS_CLIP_SCRATCH_FLOATS
 RECORD_BYTES = 96         # one-tile path; record_bytes(lib, shape) gives the size that applies
 LOSS_FLOATS = 5           # DVS_LOSS_FLOATS: total, recon, kld, non-finite flag, invalid-features flag
 ABI_VERSION = 202         # DVS_VERSION of include/dvs.h this binding was written against
+GP_ACQ_MAX_INDUCING = 1023  # DVS_GP_ACQ_MAX_INDUCING
 
 
 class DvsShape(Structure):
@@ -94,6 +95,11 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.dvs_gp_kernel_backward.restype = c_int
     lib.dvs_gp_kernel_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, ctypes.c_double,
                                            ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.dvs_gp_acquire.restype = c_int
+    # (batch, n_inducing, dim, ld, x, inducing, weights [P | alpha], c0, outputscale, lengthscale, constant, best, xi,
+    #  mean, var, ei, grad (nullable), stream)
+    lib.dvs_gp_acquire.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p] + [ctypes.c_double] * 6 + \
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dvs_clip_adam.restype = c_int
     # (n, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, max_norm, scratch, guard, stream)
     lib.dvs_clip_adam.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
@@ -110,7 +116,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

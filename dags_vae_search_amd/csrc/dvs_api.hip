@@ -1034,6 +1034,27 @@ extern "C" int dvs_gp_kernel_backward(int32_t na, int32_t nb, int32_t dim, int32
     return call_end("dvs_gp_kernel_backward");
 }
 
+// Weak: the host-emulation build of the test suite (tests/emu/build.py) compiles a fixed list of sources without
+// k_gp_acq.hip; there the entry point exists (the binding stays complete) and reports that the kernel is not built.
+extern "C" int dvs_gp_acquire_impl(int Q, int M, int D, int ld, const float* x, const float* z, const double* W, double c0,
+                                   double outputscale, double lengthscale, double constant, double best, double xi,
+                                   double* mean, double* var, double* ei, float* grad, void* stream) __attribute__((weak));
+extern "C" int dvs_gp_acquire(int32_t batch, int32_t n_inducing, int32_t dim, int32_t ld, const float* x, const float* inducing,
+                              const double* weights, double c0, double outputscale, double lengthscale, double constant,
+                              double best, double xi, double* mean, double* var, double* ei, float* grad, void* stream) {
+    if (int e = gp_check("dvs_gp_acquire", batch, n_inducing, dim, outputscale, lengthscale)) return e;
+    if (n_inducing > DVS_GP_ACQ_MAX_INDUCING) return fail(2, "dvs_gp_acquire: n_inducing must be <= 1023");
+    if (ld < n_inducing + 1) return fail(12, "dvs_gp_acquire: ld must be >= n_inducing + 1 (P | alpha)");
+    if (!(c0 >= 0.0)) return fail(12, "dvs_gp_acquire: c0 must be >= 0");
+    if (!x || !inducing || !weights || !mean || !var || !ei) return fail(10, "dvs_gp_acquire: null pointer");
+    if (!dvs_gp_acquire_impl) return fail(20, "dvs_gp_acquire: k_gp_acq.hip is not part of this build");
+    call_begin();
+    if (int e = dvs_gp_acquire_impl(batch, n_inducing, dim, ld, x, inducing, weights, c0, outputscale, lengthscale, constant,
+                                    best, xi, mean, var, ei, grad, stream))
+        return e;
+    return call_end("dvs_gp_acquire");
+}
+
 extern "C" int dvs_debug_activation(const dvs_shape* s, const void* workspace, int slot, float* out, void* stream) {
     if (int e = check_shape(s)) return e;
     const int64_t P = dvs_make_layout(s->n_tokens, s->n_classes, nullptr, 0, nullptr).total;

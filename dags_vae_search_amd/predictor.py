@@ -17,11 +17,16 @@ train step (``dvs_clip_adam``) over the flat float32 parameter vector [inducing 
 raw_outputscale, raw_lengthscale].  No autograd graph.  Parity with gpytorch is unpinned (not installed; oracle/gp.py restates
 the objective and checks this gradient by autograd; tests pin the training dynamics against the reference's SHIPPED
 hyper-parameters, which this loop reproduces from gpytorch's default initialisation).
+
+``fit_posterior`` / ``posterior`` / ``expected_improvement`` add the predictive variance and the expected improvement that
+the latent-space search (search.py) maximises: the matrices are solved once in float64 with ``torch.linalg``, the
+per-query work (mean, variance, EI and its gradient) is one HIP launch (csrc/k_gp_acq.hip: ``dvs_gp_acquire``).
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from dataclasses import dataclass
 from typing import Dict
 
 import torch
@@ -102,6 +107,21 @@ def vfe_loss_and_grad(lib, stream, X: torch.Tensor, y: torch.Tensor, flat: torch
     return F / n, grad
 
 
+VARIANCE_KINDS = ("sor", "dtc")
+
+
+@dataclass
+class GPPosterior:
+    """Marginal predictive distribution at B query points (the ``.mean`` / ``.variance`` / ``.stddev`` of gpytorch's
+    ``MultivariateNormal``; no covariance between the points).  float64 [B] on the device."""
+    mean: torch.Tensor
+    variance: torch.Tensor
+
+    @property
+    def stddev(self) -> torch.Tensor:
+        return self.variance.sqrt()
+
+
 class GPRegressionModel:
     def __init__(self, train_x: torch.Tensor, train_y: torch.Tensor, likelihood=None, device="cuda"):
         self.device = torch.device(device)
@@ -111,6 +131,8 @@ class GPRegressionModel:
         # gpytorch defaults: softplus(0) for the positive parameters, zero mean constant
         self.noise, self.outputscale, self.lengthscale, self.constant = 0.6932 + 1e-4, 0.6931, 0.6931, 0.0
         self._alpha = None
+        self._alpha_jitter = None
+        self._post = None
         self.lib = dl.load()
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -122,6 +144,7 @@ class GPRegressionModel:
         self.constant = float(sd["mean_module.raw_constant"].double().reshape(-1)[0])
         self.inducing_points = sd["covar_module.inducing_points"].to(self.device, torch.float32).contiguous()
         self._alpha = None
+        self._post = None
         return self
 
     def _kernel64(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -135,6 +158,7 @@ class GPRegressionModel:
         Kuf = self._kernel64(Z, self.train_x)
         A = Kuu + Kuf @ Kuf.T / self.noise
         self._alpha = (torch.linalg.solve(A, Kuf @ (self.train_y - self.constant)) / self.noise).contiguous()
+        self._alpha_jitter = jitter
         return self
 
     def eval(self):
@@ -198,6 +222,7 @@ class GPRegressionModel:
         self.noise, self.constant, self.outputscale, self.lengthscale = _sp(rn) + 1e-4, rc, _sp(ro), _sp(rl)
         self.inducing_points = flat[:M * D].view(M, D).clone()
         self._alpha = None
+        self._post = None
 
     def predict(self, x: torch.Tensor) -> torch.Tensor:
         """``model(x).mean`` of the reference for latent vectors x [B, dim] -> float64 [B], computed by k_gp_predict."""
@@ -216,6 +241,124 @@ class GPRegressionModel:
                                                    p(out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                  "dvs_gp_predict")
         return out
+
+
+    # ---- predictive variance and expected improvement (latent-space search) -------------------------------------------
+    def set_train_data(self, inputs: torch.Tensor, targets: torch.Tensor):
+        """gpytorch's ``set_train_data``: replace the training rows (the search appends its new (latent, BIC) rows).
+        Inducing points and hyper-parameters stay; the cached mean weights and posterior are dropped."""
+        inputs = inputs.to(self.device, torch.float64)
+        targets = targets.to(self.device, torch.float64).reshape(-1)
+        if inputs.dim() != 2 or inputs.shape[1] != self.inducing_points.shape[1] or inputs.shape[0] != targets.shape[0]:
+            raise AssertionError(f"Expected inputs [n, {self.inducing_points.shape[1]}] and targets [n], got "
+                                 f"{tuple(inputs.shape)} and {tuple(targets.shape)}")
+        self.train_x, self.train_y = inputs, targets
+        self._alpha = None
+        self._post = None
+        return self
+
+    def fit_posterior(self, jitter: float = 1e-6):
+        """What ``dvs_gp_acquire`` needs, solved once in float64 on the device: the mean weights alpha (``fit()``, same
+        result) and, per variance kind, a symmetric M x M matrix P and a constant c0 with var(x) = c0 + k_x^T P k_x,
+        k_x = [o exp(-|x - z_m|^2 / (2 l^2))]_m.  With A = K_uu + K_uf K_fu / s^2 (the matrix ``fit`` solves):
+          "sor"  P = Sigma = s^2 (s^2 K_uu + K_uf K_fu)^-1 = A^-1, c0 = 0.  gpytorch's InducingPointKernel in eval mode uses
+                 the test prior Q_** = k_*^T K_uu^-1 k_*, and by Woodbury its predictive variance is k_*^T Sigma k_*.  This
+                 is READ FROM GPYTORCH'S DOCUMENTED SEMANTICS and is UNPINNED: gpytorch is not installed and the
+                 reference ships no predictive variances.  It falls to 0 away from the inducing points.
+          "dtc"  P = Sigma - K_uu^-1, c0 = o (clamped at 0 by the kernel): the prior variance o is kept away from the
+                 inducing points.
+        ``observation_noise=True`` at query time adds s^2 to c0 (gpytorch's ``likelihood(model(x)).variance``).  Both
+        kinds are stored as one row-major [M][M + 1] matrix [P | alpha]."""
+        if self._alpha is None or self._alpha_jitter != jitter:          # alpha and P from the same K_uu
+            self.fit(jitter)
+        Z = self.inducing_points.double()
+        M = Z.shape[0]
+        if M > dl.GP_ACQ_MAX_INDUCING:
+            raise ValueError(f"dvs_gp_acquire takes at most {dl.GP_ACQ_MAX_INDUCING} inducing points, got {M}")
+        eye = torch.eye(M, dtype=torch.float64, device=self.device)
+        Kuu = self._kernel64(Z, Z) + jitter * eye
+        Kuf = self._kernel64(Z, self.train_x)
+        A = Kuu + Kuf @ Kuf.T / self.noise
+        sigma = torch.linalg.inv(A)
+        sigma = 0.5 * (sigma + sigma.T)
+        kinv = torch.linalg.inv(Kuu)
+        kinv = 0.5 * (kinv + kinv.T)
+        post = {}
+        for kind, P, c0 in (("sor", sigma, 0.0), ("dtc", sigma - kinv, self.outputscale)):
+            W = torch.empty(M, M + 1, dtype=torch.float64, device=self.device)
+            W[:, :M] = P
+            W[:, M] = self._alpha
+            post[kind] = (W.contiguous(), c0)
+        self._post = post
+        return self
+
+    def _acquire(self, x: torch.Tensor, best: float = 0.0, xi: float = 0.0, variance: str = "sor",
+                 observation_noise: bool = False, grad: bool = False, out=None):
+        """One ``dvs_gp_acquire`` launch: (mean, var, ei, dEI/dx or None).  ``out``: optional preallocated
+        (mean, var, ei, grad) buffers of the right shapes (the ascent loop reuses them)."""
+        if variance not in VARIANCE_KINDS:
+            raise ValueError(f"variance must be one of {VARIANCE_KINDS}, got {variance!r}")
+        if self.device.type != "cuda":
+            raise RuntimeError("dags_vae_search_amd.predictor evaluates the acquisition only on the GPU (there is no CPU path)")
+        if self._post is None:
+            self.fit_posterior()
+        W, c0 = self._post[variance]
+        if observation_noise:
+            c0 = c0 + self.noise
+        if not x.is_cuda:
+            x = x.to(self.device)
+        x = x.to(torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.inducing_points.shape[1]:
+            raise AssertionError(f"Expected latent vectors of size {self.inducing_points.shape[1]}, got {tuple(x.shape)}")
+        B, D = x.shape
+        M = self.inducing_points.shape[0]
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            out = (torch.empty(B, **f64), torch.empty(B, **f64), torch.empty(B, **f64),
+                   torch.empty(B, D, dtype=torch.float32, device=self.device) if grad else None)
+        mean, var, ei, g = out
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        dl.check(self.lib, self.lib.dvs_gp_acquire(B, M, D, M + 1, p(x), p(self.inducing_points), p(W), float(c0),
+                                                   self.outputscale, self.lengthscale, self.constant, float(best), float(xi),
+                                                   p(mean), p(var), p(ei), p(g) if grad else None,
+                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                 "dvs_gp_acquire")
+        return mean, var, ei, (g if grad else None)
+
+    def posterior(self, x: torch.Tensor, variance: str = "sor", observation_noise: bool = False) -> GPPosterior:
+        """Predictive mean and variance at x [B, dim] (``model(x)`` / ``likelihood(model(x))`` of the reference's gpytorch
+        model, marginals only): one ``dvs_gp_acquire`` launch.  ``variance``: "sor" (default) or "dtc", see
+        ``fit_posterior``."""
+        mean, var, _, _ = self._acquire(x, variance=variance, observation_noise=observation_noise)
+        return GPPosterior(mean, var)
+
+    def __call__(self, x: torch.Tensor) -> GPPosterior:
+        return self.posterior(x)
+
+    def expected_improvement(self, x: torch.Tensor, best: float, xi: float = 0.0, variance: str = "sor", grad: bool = False,
+                             observation_noise: bool = False):
+        """EI = (mu - best - xi) Phi(u) + sigma phi(u), u = (mu - best - xi) / sigma, of a MAXIMISATION (bnlearn's BIC:
+        higher is better) -> float64 [B]; with ``grad=True`` also dEI/dx (float32 [B, dim]).  Where sigma <= 1e-12 o
+        (SoR far from the inducing points) the limit is used: EI = max(mu - best - xi, 0), and the gradient is d mu / dx
+        where mu - best - xi > 0, else 0."""
+        _, _, ei, g = self._acquire(x, best, xi, variance, observation_noise, grad)
+        return (ei, g) if grad else ei
+
+
+def expected_improvement_host(mean, std, best: float, xi: float = 0.0, floor: float = 0.0):
+    """Float64 numpy restatement of the EI closed form the kernel evaluates (``GPRegressionModel.expected_improvement``),
+    for reporting on the host: EI = imp Phi(imp / std) + std phi(imp / std), imp = mean - best - xi; std <= floor (the
+    kernel's floor is 1e-12 * outputscale): EI = max(imp, 0)."""
+    import numpy as np
+    mean = np.asarray(mean, np.float64)
+    std = np.asarray(std, np.float64)
+    imp = mean - best - xi
+    ok = std > floor
+    s = np.where(ok, std, 1.0)
+    u = imp / s
+    Phi = 0.5 * np.vectorize(math.erfc, otypes=[np.float64])(-u / math.sqrt(2.0))
+    phi = np.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
+    return np.where(ok, imp * Phi + s * phi, np.maximum(imp, 0.0))
 
 
 def train_predictor(X: torch.Tensor, y: torch.Tensor, iterations: int = 10000, lr: float = 0.01,

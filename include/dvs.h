@@ -224,6 +224,23 @@ int dvs_gp_kernel_backward(int32_t na, int32_t nb, int32_t dim, int32_t symmetri
                            double outputscale, double lengthscale, const double* G, double* dxa, double* row_sums,
                            void* stream);
 
+/* Acquisition of the same predictor for latent-space Bayesian optimisation (dags_vae_search_amd/search.py; the reference
+ * stops before its search, experiments/01_bn_asia/main.py ends at train_predictor).  One launch, `batch` queries x:
+ *   mean[b] = constant + k_b . alpha,  var[b] = max(c0 + k_b^T P k_b, 0),  k_b[m] = outputscale exp(-|x_b - z_m|^2 / (2 l^2)),
+ *   ei[b]   = imp Phi(imp / sigma) + sigma phi(imp / sigma),  imp = mean[b] - best - xi,  sigma = sqrt(var[b])
+ * (expected improvement of a maximisation: bnlearn's BIC, higher is better); sigma <= 1e-12 outputscale: ei = max(imp, 0).
+ * grad (nullable): dEI/dx [batch][dim] (device f32) = sum_m (Phi alpha_m + phi / sigma (P k)_m) k_m (z_m - x_b) / l^2
+ * (d mean / dx where sigma is below the floor and imp > 0, else 0).  weights: device f64 [n_inducing][ld], ld >= n_inducing
+ * + 1: columns 0 .. n_inducing-1 hold the symmetric P, column n_inducing holds alpha (predictor.py: fit_posterior).
+ * x: device f32 [batch][dim]; inducing: device f32 [n_inducing][dim]; mean / var / ei: device f64 [batch].  dim <= 32,
+ * n_inducing <= DVS_GP_ACQ_MAX_INDUCING (the k block of 16 queries lives in one CU's LDS).  fp64 throughout, the
+ * batch x n_inducing kernel matrix is never written to memory; fixed summation order (bitwise reproducible).  (Added in ABI 202 as a
+ * pure addition: the version number stays.) */
+#define DVS_GP_ACQ_MAX_INDUCING 1023
+int dvs_gp_acquire(int32_t batch, int32_t n_inducing, int32_t dim, int32_t ld, const float* x, const float* inducing,
+                   const double* weights, double c0, double outputscale, double lengthscale, double constant, double best,
+                   double xi, double* mean, double* var, double* ei, float* grad, void* stream);
+
 /* Optional per-kernel timing for the benchmark's roofline leg: while enabled, every kernel launch is bracketed by
  * HIP events recorded on its own stream; dvs_profile_collect waits for them and returns, per kernel name, the
  * number of launches and their summed duration in milliseconds (rows of `name_stride` chars).  Process-global
