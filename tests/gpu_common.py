@@ -7,6 +7,18 @@ from oracle import pace_oracle as po
 from tests.helpers import load_golden, rel
 
 
+def device_cus():
+    """compute units the library sizes its persistent grids by (dvs_device_cus: every grid is capped at this many
+    workgroups, so a batch above cap x DAGs-per-workgroup runs in several passes)."""
+    from dags_vae_search_amd import _lib
+    return int(_lib.load().dvs_device_cus())
+
+
+def default_waves(B):
+    """workgroup width the one-tile stack kernels pick for a batch of B DAGs (dvs_api.hip: waves_per_wg)."""
+    return 4 if B <= 4 * device_cus() else 8
+
+
 def gpu_forward(cfg, params, graphs, training=False, dropout=0.15, eps=None, seed=0):
     from dags_vae_search_amd.engine import PaceEngine
     dev = torch.device("cuda:0")

@@ -180,3 +180,41 @@ def test_emu_edge_sizes_forward_and_gradients(n, card, B, train):
     total, recon, kld, ref = _oracle_grads(cfg, params, f_np, **kw)
     assert rel(losses[0], total) < 1e-4 and rel(losses[2], kld) < 1e-4
     _check_grads(grads, ref, 1e-3)
+
+
+@pytest.mark.parametrize("name,B,nw", [("n12c12", 17, 8), ("n12c12", 9, 4), ("n37c37", 5, None)],
+                         ids=["n12c12-B=17-nw8", "n12c12-B=9-nw4", "n37c37-B=5-wide"])
+def test_emu_gradients_past_one_pass(name, B, nw, monkeypatch):
+    """Every persistent grid is capped at dvs_device_cus() workgroups (2 on the emulator), so these batches make the
+    workgroups loop: 17 DAGs at 8 waves (8 per workgroup and pass) leave one DAG for a second pass, 9 at 4 waves the same,
+    5 on the wide path's workgroup-per-DAG kernels give a workgroup up to three DAGs.  Eval-mode gradients vs the oracle."""
+    if nw is not None:
+        monkeypatch.setenv("DVS_WAVES_PER_WG", str(nw))
+    cfg, params, graphs, z = load_golden(name)
+    graphs = graphs[:B]
+    f_np = ofeat.dense_features(graphs, cfg.card)
+    m = EmuModel(cfg, {k: v.numpy() for k, v in params.items()}, B, training=False)
+    assert m.pack(f_np) == 0
+    m.forward()
+    grads, flat = m.backward(1.0, 0.005)
+    assert not np.isnan(flat).any()
+    _, _, _, ref = _oracle_grads(cfg, params, f_np, training=False)
+    _check_grads(grads, ref, 1e-3)
+
+
+def test_emu_train_mode_dropout_past_one_pass(monkeypatch):
+    """dropout 0.15 + counter-based eps at 17 DAGs, 8 waves: the second pass's DAG draws its masks and noise under its
+    global index (dag_offset 3 + 16)."""
+    monkeypatch.setenv("DVS_WAVES_PER_WG", "8")
+    cfg, params, graphs, z = load_golden("n12c12")
+    B = 17
+    f_np = ofeat.dense_features(graphs[:B], cfg.card)
+    m = EmuModel(cfg, {k: v.numpy() for k, v in params.items()}, B, training=True, dropout=0.15, seed=4242, dag_offset=3)
+    assert m.pack(f_np) == 0
+    losses, _, _ = m.forward()
+    grads, _ = m.backward(1.0, 0.005)
+    masks = DeviceMasks(4242, 0.15, dag_offset=3)
+    total, recon, kld, ref = _oracle_grads(cfg, params, f_np, training=True, eps=torch.from_numpy(masks.eps(B)),
+                                           masks=masks)
+    assert rel(losses[0], total) < 1e-4 and rel(losses[2], kld) < 1e-4
+    _check_grads(grads, ref, 2e-3)

@@ -6,6 +6,7 @@ import torch
 from oracle import features as ofeat
 from oracle import pace_oracle as po
 from oracle.rng import DeviceMasks
+from tests.gpu_common import default_waves
 from tests.helpers import CONFIGS, EDGE_SHAPES, grad_err, graphs_from, load_golden, load_npz, rel
 from tests.relu_trace import grad_errors, oracle_on_device_piece, record
 
@@ -25,13 +26,45 @@ def build_model(cfg, params, dropout=0.15):
     return m.to(DEV)
 
 
+# The one-tile shapes (N <= 16 tokens, C <= 16 classes) run the stack kernels at either workgroup width
+# (dvs_api.hip: waves_per_wg): the narrow 4-wave mapping that the golden batches (B <= 4 x #CU) pick by themselves, and the
+# 8-wave mapping of large batches, forced here through DVS_WAVES_PER_WG (read on every call).  Wide shapes always take 8 waves.
+ONE_TILE = ["asia", "asia_rand", "n12c1", "n12c12", "n13c5"]
+
+
+def widths(cases, one_tile=lambda case: True):
+    """parametrize `cases` over the workgroup width: the narrow width keeps the case's own id, the forced 8-wave twin gets
+    the suffix -nw8; cases that are not one-tile run once at their fixed width (None: DVS_WAVES_PER_WG left alone)."""
+    out = []
+    for case in cases:
+        case = case if isinstance(case, tuple) else (case,)
+        cid = "-".join(str(x) for x in case)
+        if one_tile(case):
+            out += [pytest.param(*case, 4, id=cid), pytest.param(*case, 8, id=cid + "-nw8")]
+        else:
+            out.append(pytest.param(*case, None, id=cid))
+    return out
+
+
+@pytest.fixture
+def waves_per_wg(request, monkeypatch):
+    """Workgroup width of the one-tile stack kernels for this test (indirect parameter, see widths()); returns the width the
+    kernels run at (8 on the wide path)."""
+    nw = getattr(request, "param", None)
+    if nw is None:
+        monkeypatch.delenv("DVS_WAVES_PER_WG", raising=False)
+        return 8
+    monkeypatch.setenv("DVS_WAVES_PER_WG", str(nw))
+    return nw
+
+
 def feats_for(model, graphs):
     from dags_vae_search_amd import LabeledGraph
     return model.prepare_features([g if isinstance(g, LabeledGraph) else LabeledGraph(*g) for g in graphs])
 
 
-@pytest.mark.parametrize("name", list(CONFIGS))
-def test_loss_direct_and_autograd_match_reference_golden(name):
+@pytest.mark.parametrize("name,waves_per_wg", widths(list(CONFIGS), lambda c: c[0] in ONE_TILE), indirect=["waves_per_wg"])
+def test_loss_direct_and_autograd_match_reference_golden(name, waves_per_wg):
     cfg, params, graphs, z = load_golden(name)
     model = build_model(cfg, params).eval()
     total, recon, kld = model.loss_direct(feats_for(model, graphs))
@@ -40,12 +73,12 @@ def test_loss_direct_and_autograd_match_reference_golden(name):
     assert abs(recon.item() - float(z["eval/recon"])) < 1e-4 * max(1.0, abs(float(z["eval/recon"])))
     total.backward()
     err, worst = grad_err({k: p.grad for k, p in model.named_parameters()}, z, "eval/grad/")
-    record(f"golden_eval[{name}]", elbo_rel=rel(total.item(), z["eval/total"]), grad_err=err, worst=worst)
+    record(f"golden_eval[{name},nw={waves_per_wg}]", elbo_rel=rel(total.item(), z["eval/total"]), grad_err=err, worst=worst)
     assert err < GRAD_BOUND, (worst, err)
 
 
-@pytest.mark.parametrize("name", ["n12c12", "asia_rand"])
-def test_train_mode_dropout0_injected_eps_and_one_step(name):
+@pytest.mark.parametrize("name,waves_per_wg", widths(["n12c12", "asia_rand"]), indirect=["waves_per_wg"])
+def test_train_mode_dropout0_injected_eps_and_one_step(name, waves_per_wg):
     """train mode, dropout 0, reference's captured eps -> golden loss/gradients, then golden clip+Adam step, through
     BOTH optimiser paths: stock torch.optim.Adam over the autograd-wrapped kernels and the fused flat-buffer Adam."""
     from dags_vae_search_amd import optim as dopt
@@ -78,7 +111,7 @@ def test_train_mode_dropout0_injected_eps_and_one_step(name):
             unsure_total += int((~sure).sum())
             if sure.any():
                 worst = max(worst, float(err[sure].max()))
-        record(f"adam_step[{name},{tag}]", pinned_worst=worst, own_gradient_formula_worst=worst_formula,
+        record(f"adam_step[{name},{tag},nw={waves_per_wg}]", pinned_worst=worst, own_gradient_formula_worst=worst_formula,
                unpinned_fraction=unsure_total / n_total)
         assert worst < 1e-6
         assert worst_formula < 1.0               # in units of the fp32 rounding allowance above
@@ -93,7 +126,7 @@ def test_train_mode_dropout0_injected_eps_and_one_step(name):
     assert rel(total.item(), z["train0/total"]) < 1e-4
     total.backward()
     err, worst = grad_err({k: p.grad for k, p in model.named_parameters()}, z, "train0/grad/")
-    record(f"golden_train0[{name}]", elbo_rel=rel(total.item(), z["train0/total"]), grad_err=err, worst=worst)
+    record(f"golden_train0[{name},nw={waves_per_wg}]", elbo_rel=rel(total.item(), z["train0/total"]), grad_err=err, worst=worst)
     assert err < GRAD_BOUND, (worst, err)
     torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
     opt.step()
@@ -108,10 +141,11 @@ def test_train_mode_dropout0_injected_eps_and_one_step(name):
     check_step(model2, "fused", {k: p.grad for k, p in model2.named_parameters()})      # k_adam clips .grad in place
 
 
-def dropout_on_parity(tag, model, params, cfg, graphs, seed, dag_offset, bound=GRAD_BOUND):
+def dropout_on_parity(tag, model, params, cfg, graphs, seed, dag_offset, bound=GRAD_BOUND, dtype=None):
     """Train mode, dropout ON, the device's own masks injected into the oracle: ELBO < 1e-4, gradients within `bound` of
     the tensor maximum on the SAME linear piece of the network (tests/relu_trace.py: ReLU sign disagreements at
-    near-zero pre-activations are counted, must be genuine ties, and the oracle is re-evaluated on the device's piece)."""
+    near-zero pre-activations are counted, must be genuine ties, and the oracle is re-evaluated on the device's piece).
+    `dtype` = torch.float64 runs the oracle in double precision (batches of thousands of DAGs)."""
     B = len(graphs)
     model.train()
     model.zero_grad(set_to_none=True)        # .grad may alias flat_grads of an earlier fused step: autograd accumulates
@@ -123,7 +157,7 @@ def dropout_on_parity(tag, model, params, cfg, graphs, seed, dag_offset, bound=G
     masks = DeviceMasks((seed << 32) | 1, 0.15, dag_offset=dag_offset)          # PaceVaeV3._next_seed: (seed << 32) | step
     f_cpu = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in f.items()}
     t, k, g_piece, g_plain, info = oracle_on_device_piece(model, params, cfg, f_cpu, B, True,
-                                                          eps=torch.from_numpy(masks.eps(B)), masks=masks)
+                                                          eps=torch.from_numpy(masks.eps(B)), masks=masks, dtype=dtype)
     got = {n: p.grad for n, p in model.named_parameters()}
     err, worst, _ = grad_errors(got, g_piece)
     err_plain, worst_plain, _ = grad_errors(got, g_plain)
@@ -136,15 +170,17 @@ def dropout_on_parity(tag, model, params, cfg, graphs, seed, dag_offset, bound=G
     assert err < bound, (worst, err, info)
 
 
-@pytest.mark.parametrize("name,B,seed", [("n12c12", 48, 77), ("asia_rand", 32, 77), ("n12c12", 48, 5), ("n12c12", 48, 6)])
-def test_train_mode_dropout_on_matches_oracle_with_device_masks(name, B, seed):
+@pytest.mark.parametrize("name,B,seed,waves_per_wg",
+                         widths([("n12c12", 48, 77), ("asia_rand", 32, 77), ("n12c12", 48, 5), ("n12c12", 48, 6)]),
+                         indirect=["waves_per_wg"])
+def test_train_mode_dropout_on_matches_oracle_with_device_masks(name, B, seed, waves_per_wg):
     cfg, params, graphs, z = load_golden(name)
     model = build_model(cfg, params, dropout=0.15)
-    dropout_on_parity(f"dropout_on[{name},B={B},seed={seed}]", model, params, cfg, graphs[:B], seed, 5)
+    dropout_on_parity(f"dropout_on[{name},B={B},seed={seed},nw={waves_per_wg}]", model, params, cfg, graphs[:B], seed, 5)
 
 
-@pytest.mark.parametrize("name", EDGE_SHAPES)
-def test_edge_of_range_shapes_dropout_on_and_compact_front_end(name):
+@pytest.mark.parametrize("name,waves_per_wg", widths(EDGE_SHAPES, lambda c: c[0] in ONE_TILE), indirect=["waves_per_wg"])
+def test_edge_of_range_shapes_dropout_on_and_compact_front_end(name, waves_per_wg):
     """Edges of the token range include/dvs.h promises (N = 16: full tile; 17: one valid row in the second tile; 32: two
     full tiles; 48: maximum, with 48 classes), two of them with card != n (pace.py:1159-1160,1188-1191,1921-1970).  The
     eval-mode ELBO and all 108 gradients of these fixtures against the REFERENCE's outputs run through the CONFIGS
@@ -155,7 +191,7 @@ def test_edge_of_range_shapes_dropout_on_and_compact_front_end(name):
     from dags_vae_search_amd.dist import shard_features
     cfg, params, graphs, z = load_golden(name)
     model = build_model(cfg, params, dropout=0.15)
-    dropout_on_parity(f"dropout_on[{name},B={len(graphs)},seed=13]", model, params, cfg, graphs, 13, 3)
+    dropout_on_parity(f"dropout_on[{name},B={len(graphs)},seed=13,nw={waves_per_wg}]", model, params, cfg, graphs, 13, 3)
     model.eval()
     f = feats_for(model, graphs)
     cb = encode_graphs(graphs, cfg.n).to(DEV)
@@ -248,7 +284,7 @@ def test_full_size_properties_n12_b4096():
     assert (tot - g1).abs().max().item() < 2e-4 * g1.abs().max().item()
     # one 512-DAG slice of the SAME batch (global DAG indices 1536..2047, i.e. the masks the full batch drew) against the
     # CPU oracle: train mode, dropout on, ELBO + all 108 gradients (the headline shape had no oracle comparison)
-    dropout_on_parity("full_size_n12_b4096_slice512", model, params, cfg, graphs[1536:2048], 1, 1536)
+    dropout_on_parity(f"full_size_n12_b4096_slice512,nw={default_waves(512)}", model, params, cfg, graphs[1536:2048], 1, 1536)
     opt = dopt.Adam(model.parameters(), lr=1e-3).attach(model)
     first = None
     for step in range(12):
@@ -282,8 +318,19 @@ def test_asia_b4096_elbo_matches_cpu_oracle():
     assert rel(total.item(), t) < 1e-4 and rel(kld.item(), k) < 1e-4
 
 
-def test_sachs_shape_n11():
-    """BASELINE config 4's model shape (sachs: n=11, card=11, N=14 tokens) against the oracle, fwd + gradients."""
+def test_sachs_shape_n11(monkeypatch):
+    """BASELINE config 4's model shape (sachs: n=11, card=11, N=14 tokens) against the oracle, fwd + gradients: at the
+    narrow width this batch picks by itself (4 waves); test_sachs_shape_n11_nw8: the same at 8 waves."""
+    monkeypatch.setenv("DVS_WAVES_PER_WG", "4")
+    _sachs_shape_n11(4)
+
+
+def test_sachs_shape_n11_nw8(monkeypatch):
+    monkeypatch.setenv("DVS_WAVES_PER_WG", "8")
+    _sachs_shape_n11(8)
+
+
+def _sachs_shape_n11(nw):
     from dags_vae_search_amd.synthetic import synthetic_dags
     cfg = po.PaceConfig(n=11, card=11)
     params = po.init_params(cfg, seed=11)
@@ -301,7 +348,7 @@ def test_sachs_shape_n11():
     for name, p in model.named_parameters():
         ref = P[name].grad.numpy()
         worst = max(worst, float(np.abs(p.grad.cpu().numpy() - ref).max()) / max(float(np.abs(ref).max()), 1e-4 * scale))
-    record("sachs_n11_eval", elbo_rel=rel(total.item(), t.detach()), grad_err=worst)
+    record(f"sachs_n11_eval,nw={nw}", elbo_rel=rel(total.item(), t.detach()), grad_err=worst)
     assert worst < GRAD_BOUND
 
 
@@ -375,7 +422,7 @@ def test_alarm_n37_b2048_wide_path():
     # dropout-on gradients on the last 24 DAGs (they include the chains), several mask draws: round 1 saw 3.0e-3 on
     # encoder.layers.2.linear1.weight under one draw and < 1e-4 under others — isolated ReLU ties (tests/relu_trace.py)
     for seed in (9, 10, 11):
-        dropout_on_parity(f"dropout_on[alarm n37,B=24,seed={seed}]", model, params, cfg, graphs[-24:], seed, 3)
+        dropout_on_parity(f"dropout_on[alarm n37,B=24,seed={seed},nw=8]", model, params, cfg, graphs[-24:], seed, 3)
     # full-size properties
     model.seed(1)
     l1 = model.loss_and_grad(f).clone()
