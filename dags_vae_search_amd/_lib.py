@@ -79,6 +79,10 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     # (shape, params, n_params, workspace, workspace_bytes, records, records_bytes, z, uniforms, state, state_bytes, stream)
     lib.dvs_decode.argtypes = [P(DvsShape), c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]
+    lib.dvs_match_decoded.restype = c_int
+    # (batch, n_vars, card, repeats, preds_are_u64, labels, preds, states, state_bytes, budget, flags, stream)
+    lib.dvs_match_decoded.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_int32, c_void_p, c_void_p]
     lib.dvs_debug_launch.restype = c_int
     lib.dvs_debug_launch.argtypes = [c_size_t, c_void_p]
     lib.dvs_bic_scores.restype = c_int
@@ -116,7 +120,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

@@ -959,6 +959,32 @@ extern "C" int dvs_decode(const dvs_shape* s, const float* params, int64_t n_par
     return call_end("dvs_decode");
 }
 
+// k_match_decoded lives in k_decode.hip (csrc/dvs_match.h)
+extern "C" int dvs_match_decoded_impl(int B, int n, int card, int R, int wide, const uint8_t* labels, const void* preds,
+                                      const void* states, int budget, uint8_t* flags, void* stream);
+extern "C" int dvs_match_decoded(int32_t batch, int32_t n_vars, int32_t card, int32_t repeats, int32_t preds_are_u64,
+                                 const uint8_t* labels, const void* preds, const void* states, size_t state_bytes,
+                                 int32_t budget, uint8_t* flags, void* stream) {
+    if (batch <= 0 || repeats <= 0) return fail(2, "dvs_match_decoded: batch and repeats must be > 0");
+    if ((int64_t)batch * repeats > (int64_t)1 << 30) return fail(2, "dvs_match_decoded: batch * repeats must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_match_decoded: n_vars must be in [1, 45]");
+    if (card < 1 || card > 45) return fail(3, "dvs_match_decoded: card must be in [1, 45]");
+    if (!preds_are_u64 && n_vars > 16) return fail(12, "dvs_match_decoded: 16-bit predecessor rows hold at most 16 vertices");
+    if (budget < 1) return fail(12, "dvs_match_decoded: budget must be >= 1");
+    if (!labels || !preds || !states || !flags) return fail(10, "dvs_match_decoded: null pointer");
+    const size_t need = (size_t)batch * repeats * sizeof(dvs_decode_state);
+    if (state_bytes < need) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "dvs_match_decoded: state_bytes < batch * repeats * DVS_DECODE_STATE_BYTES = %zu", need);
+        return fail(14, msg);
+    }
+    call_begin();
+    if (int e = dvs_match_decoded_impl(batch, n_vars, card, repeats, preds_are_u64 ? 1 : 0, labels, preds, states, budget,
+                                       flags, stream))
+        return e;
+    return call_end("dvs_match_decoded");
+}
+
 extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
                                    double* local, double* out, int* status, void* stream);
 extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,

@@ -13,6 +13,7 @@
 #include "dvs_wide.h"
 
 #include "dvs_decode.h"
+#include "dvs_match.h"          // reconstruction judging of the decoded rows (k_match_decoded)
 
 // per-wave scratch for the record build (lane 0) and the sampling (all lanes)
 struct DecScratch {

@@ -419,17 +419,10 @@ class PaceVaeV3(nn.Module):
             return mu + torch.randn_like(std) * epsilon_scale * std
         return mu
 
-    def decode(self, z: torch.Tensor, uniforms: Optional[torch.Tensor] = None, strict: bool = True):
-        """Generation (pace.py:1666-1749), batched on the device: returns one LabeledGraph per row of ``z``.
-
-        The reference grows igraph objects on the host and samples with numpy's / torch's global generators; here the
-        N-2 step loop runs in HIP (csrc/k_decode.hip) and draws from the model's counter-based generator
-        (``model.seed``), or from ``uniforms`` ([B, N, N], see include/dvs.h) when given.  Quirks kept: no start->input
-        edge in the grown graph, the last vertex is hooked to the loose ends only if its SAMPLED type was `output`,
-        edges into the first user vertex are dropped by the PACE -> labelled conversion (pace.py:1298).  A graph that
-        samples `output` early stops growing; the reference then fails with IndexError inside
-        from_pace_graph_to_labeled_graph — so does this (``strict=True``); ``strict=False`` returns None for those."""
-        import numpy as np
+    def decode_states(self, z: torch.Tensor, uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The generation of ``decode`` without the conversion to graph objects: the raw device ``dvs_decode_state``
+        records, uint8 [B, DECODE_STATE_BYTES] (include/dvs.h), for device-side consumers such as
+        ``recon.match_decoded``.  Same draws and the same seed / step bookkeeping as ``decode``."""
         eng = self._eng()
         dev = self.flat_params.device
         z = z.to(dev, torch.float32).contiguous()
@@ -444,32 +437,22 @@ class PaceVaeV3(nn.Module):
         self._step += 1
         shape = eng.shape(B, training=False, dropout=self.dropout, dag_offset=self.dag_offset,
                           seed=(self._seed << 32) | (self._step & 0xFFFFFFFF))
-        raw = eng.decode(shape, self.flat_params, z, uniforms).cpu().numpy()
+        state = eng.decode(shape, self.flat_params, z, uniforms)
         self._fwd_generation += 1
-        labels = raw[:, 384:432].astype(np.int64) - 3
-        nv = raw[:, 432:436].copy().view(np.int32)[:, 0]
-        if strict and (nv < N).any():
-            raise IndexError("vertex index out of range")            # igraph's error at pace.py:1296
-        # edges u -> v between user vertices (PACE ids 2 .. N-2), v == 2 skipped (pace.py:1298): unpack the little-endian
-        # 64-bit parent rows into a [B, v, u] bit cube and keep its strict lower triangle
-        cube = np.unpackbits(raw[:, :384].reshape(B, 48, 8), axis=2, bitorder="little")          # [B, 48 (v), 64 (u)]
-        vs = np.arange(3, N - 1)
-        us = np.arange(2, N - 2)
-        bits = cube[:, 3:N - 1, 2:N - 2] & (us[None, None, :] < vs[None, :, None])
-        bb, vi, ui = np.nonzero(bits)
-        starts = np.searchsorted(bb, np.arange(B + 1))
-        ev = (vs[vi] - 2).tolist()
-        eu = (us[ui] - 2).tolist()
-        lab_lists = labels[:, 2:N - 1].tolist()
-        full = (nv >= N).tolist()
-        out = []
-        for b in range(B):
-            if not full[b]:
-                out.append(None)
-                continue
-            lo, hi = starts[b], starts[b + 1]
-            out.append(feat.LabeledGraph(lab_lists[b], list(zip(eu[lo:hi], ev[lo:hi]))))
-        return out
+        return state
+
+    def decode(self, z: torch.Tensor, uniforms: Optional[torch.Tensor] = None, strict: bool = True):
+        """Generation (pace.py:1666-1749), batched on the device: returns one LabeledGraph per row of ``z``.
+
+        The reference grows igraph objects on the host and samples with numpy's / torch's global generators; here the
+        N-2 step loop runs in HIP (csrc/k_decode.hip) and draws from the model's counter-based generator
+        (``model.seed``), or from ``uniforms`` ([B, N, N], see include/dvs.h) when given.  Quirks kept: no start->input
+        edge in the grown graph, the last vertex is hooked to the loose ends only if its SAMPLED type was `output`,
+        edges into the first user vertex are dropped by the PACE -> labelled conversion (pace.py:1298).  A graph that
+        samples `output` early stops growing; the reference then fails with IndexError inside
+        from_pace_graph_to_labeled_graph — so does this (``strict=True``); ``strict=False`` returns None for those."""
+        raw = self.decode_states(z, uniforms).cpu().numpy()
+        return graphs_from_states(raw, self._max_num_vertices, strict)
 
     # ---- loss (pace.py:1974-2046) -------------------------------------------------------------------------------
     def loss_direct(self, features: Dict, beta: float = 0.005, eps: Optional[torch.Tensor] = None):
@@ -534,3 +517,36 @@ class PaceVaeV3(nn.Module):
         eng.loss_backward(shape, self.flat_params, self._gcoef, grads, clip_scratch=clip_scratch)
         self.bind_flat_grads()            # host-only (re-points .grad views if an optimiser cleared them); GPU is busy
         return losses
+
+
+def graphs_from_states(raw, n_tokens: int, strict: bool = False):
+    """Host conversion of raw ``dvs_decode_state`` rows (numpy uint8 [B, DECODE_STATE_BYTES]) into LabeledGraph objects,
+    as ``PaceVaeV3.decode`` returns them (pace.py:1290-1305): None for a row that stopped growing early (``strict``:
+    IndexError instead)."""
+    import numpy as np
+    N = n_tokens
+    B = raw.shape[0]
+    labels = raw[:, 384:432].astype(np.int64) - 3
+    nv = raw[:, 432:436].copy().view(np.int32)[:, 0]
+    if strict and (nv < N).any():
+        raise IndexError("vertex index out of range")            # igraph's error at pace.py:1296
+    # edges u -> v between user vertices (PACE ids 2 .. N-2), v == 2 skipped (pace.py:1298): unpack the little-endian
+    # 64-bit parent rows into a [B, v, u] bit cube and keep its strict lower triangle
+    cube = np.unpackbits(raw[:, :384].reshape(B, 48, 8), axis=2, bitorder="little")          # [B, 48 (v), 64 (u)]
+    vs = np.arange(3, N - 1)
+    us = np.arange(2, N - 2)
+    bits = cube[:, 3:N - 1, 2:N - 2] & (us[None, None, :] < vs[None, :, None])
+    bb, vi, ui = np.nonzero(bits)
+    starts = np.searchsorted(bb, np.arange(B + 1))
+    ev = (vs[vi] - 2).tolist()
+    eu = (us[ui] - 2).tolist()
+    lab_lists = labels[:, 2:N - 1].tolist()
+    full = (nv >= N).tolist()
+    out = []
+    for b in range(B):
+        if not full[b]:
+            out.append(None)
+            continue
+        lo, hi = starts[b], starts[b + 1]
+        out.append(feat.LabeledGraph(lab_lists[b], list(zip(eu[lo:hi], ev[lo:hi]))))
+    return out

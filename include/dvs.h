@@ -178,6 +178,20 @@ int dvs_decode(const dvs_shape* s, const float* params, int64_t n_params, void* 
                void* records, size_t records_bytes, const float* z, const float* uniforms, void* state_out,
                size_t state_bytes, void* stream);
 
+/* Reconstruction judging of decoded rows (the toolkit.is_valid_graph / graph_equals loop of batch_test,
+ * experiments/03_synthetic_12/main.py:200-217) on the device.  Targets in the row codec of dvs_build_records: labels device u8
+ * [batch][n_vars], preds device [batch][n_vars] (u16, or u64 when preds_are_u64; bit u of preds[v] <=> edge u -> v); states:
+ * device dvs_decode_state [batch * repeats] as dvs_decode leaves them, row k decoded from target k / repeats (user vertex i =
+ * PACE vertex i + 2, label - 3, edge u -> v (u < v) <=> bit u + 2 of parents[v + 2]).  flags: device u8 [batch * repeats],
+ * bit 0 valid (nv == n_vars + 3 and every label in [0, card)), bit 1 isomorphic ignoring labels, bit 2 label-preserving
+ * isomorphic, bit 3 undecided (an exact search visited more than `budget` nodes; bits 1-2 are then unspecified).  A row with
+ * nv < n_vars + 3 gets 0.  Exact: "isomorphic" only from a verified complete mapping, "not isomorphic" only from an
+ * isomorphism invariant (colour refinement) or an exhausted search.  1 <= n_vars, card <= 45; batch * repeats <= 2^30.
+ * (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_match_decoded(int32_t batch, int32_t n_vars, int32_t card, int32_t repeats, int32_t preds_are_u64,
+                      const uint8_t* labels, const void* preds, const void* states, size_t state_bytes,
+                      int32_t budget, uint8_t* flags, void* stream);
+
 /* BIC of B discrete Bayesian-network structures on one data set (replaces BNLearnWrapper.score,
  * src/problem/bn/bnlearn.py:27-61 = `Rscript bnlearn_score.R`: bnlearn::score(net, data, type = "bic")).
  * data: device u64 [n_samples][ceil(n_vars/16)], variable i's level code (0..15) in bits 4*(i%16).. of word i/16;
