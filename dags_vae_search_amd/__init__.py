@@ -12,5 +12,6 @@ from .records import CompactBatch, CompactDagDataset, encode_graphs  # noqa: F40
 from .bic import BNLearnWrapper  # noqa: F401
 from .predictor_data import create_predictor_dataset, generate_predictor_graphs_batch, prepare_predictor_data  # noqa: F401
 from .datasets import LabeledDagDatasetInMemory, LabeledDagDatasetInMemoryTest  # noqa: F401
-from .search import SearchResult, latent_bo_search, optimize_acquisition  # noqa: F401
+from .search import (SearchResult, StructureSet, decoded_structures, generation_metrics, latent_bo_search,  # noqa: F401
+                     optimize_acquisition)
 from .recon import evaluate_reconstruction, match_decoded  # noqa: F401

@@ -22,6 +22,7 @@ RECORD_BYTES = 96         # one-tile path; record_bytes(lib, shape) gives the si
 LOSS_FLOATS = 5           # DVS_LOSS_FLOATS: total, recon, kld, non-finite flag, invalid-features flag
 ABI_VERSION = 202         # DVS_VERSION of include/dvs.h this binding was written against
 GP_ACQ_MAX_INDUCING = 1023  # DVS_GP_ACQ_MAX_INDUCING
+STRUCT_HASH_INVALID = 0x7FFFFFFFFFFFFFFF  # DVS_STRUCT_HASH_INVALID
 
 
 class DvsShape(Structure):
@@ -83,6 +84,15 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     # (batch, n_vars, card, repeats, preds_are_u64, labels, preds, states, state_bytes, budget, flags, stream)
     lib.dvs_match_decoded.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_int32, c_void_p, c_void_p]
+    lib.dvs_decoded_structures.restype = c_int
+    # (batch, n_vars, preds_are_u64, states, state_bytes, hash_mask, flags, labels, preds, keys, keys_bytes, hashes, stream)
+    lib.dvs_decoded_structures.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_size_t, c_uint64, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_structset_filter.restype = c_int
+    # (batch, n_vars, sorted_hashes, order, keys, keys_bytes, flags, seen_count, seen_hashes, seen_keys, seen_keys_bytes,
+    #  out, stream)
+    lib.dvs_structset_filter.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.dvs_debug_launch.restype = c_int
     lib.dvs_debug_launch.argtypes = [c_size_t, c_void_p]
     lib.dvs_bic_scores.restype = c_int
@@ -120,7 +130,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_bic_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

@@ -985,6 +985,57 @@ extern "C" int dvs_match_decoded(int32_t batch, int32_t n_vars, int32_t card, in
     return call_end("dvs_match_decoded");
 }
 
+// k_decoded_structures / k_structset_filter live in k_decode.hip (csrc/dvs_structs.h)
+extern "C" int dvs_decoded_structures_impl(int B, int n, int wide, const void* states, uint64_t hash_mask, uint8_t* flags,
+                                           uint8_t* labels, void* preds, uint64_t* keys, uint64_t* hashes, void* stream);
+extern "C" int dvs_structset_filter_impl(int B, int n, const uint64_t* sorted_hashes, const int64_t* order,
+                                         const uint64_t* keys, const uint8_t* flags, int S, const uint64_t* seen_hashes,
+                                         const uint64_t* seen_keys, uint8_t* out, void* stream);
+static int fail_size(const char* what, size_t need) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s = %zu", what, need);
+    return fail(14, msg);
+}
+extern "C" int dvs_decoded_structures(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const void* states,
+                                      size_t state_bytes, uint64_t hash_mask, uint8_t* flags, uint8_t* labels, void* preds,
+                                      uint64_t* keys, size_t keys_bytes, uint64_t* hashes, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_decoded_structures: batch must be > 0");
+    if (batch > 1 << 30) return fail(2, "dvs_decoded_structures: batch must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_decoded_structures: n_vars must be in [1, 45]");
+    if (!preds_are_u64 && n_vars > 16) return fail(12, "dvs_decoded_structures: 16-bit predecessor rows hold at most 16 vertices");
+    if (!states || !flags || !labels || !preds || !keys || !hashes) return fail(10, "dvs_decoded_structures: null pointer");
+    if (state_bytes < (size_t)batch * sizeof(dvs_decode_state))
+        return fail_size("dvs_decoded_structures: state_bytes < batch * DVS_DECODE_STATE_BYTES", (size_t)batch * sizeof(dvs_decode_state));
+    if (keys_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_decoded_structures: keys_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    call_begin();
+    if (int e = dvs_decoded_structures_impl(batch, n_vars, preds_are_u64 ? 1 : 0, states, hash_mask, flags, labels, preds, keys,
+                                            hashes, stream))
+        return e;
+    return call_end("dvs_decoded_structures");
+}
+
+extern "C" int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_t* sorted_hashes, const int64_t* order,
+                                    const uint64_t* keys, size_t keys_bytes, const uint8_t* flags, int32_t seen_count,
+                                    const uint64_t* seen_hashes, const uint64_t* seen_keys, size_t seen_keys_bytes,
+                                    uint8_t* out, void* stream) {
+    if (batch < 0 || seen_count < 0) return fail(2, "dvs_structset_filter: batch and seen_count must be >= 0");
+    if (batch > 1 << 30) return fail(2, "dvs_structset_filter: batch must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_structset_filter: n_vars must be in [1, 45]");
+    if (batch == 0) return 0;                    // an empty batch: nothing to judge, nothing is enqueued
+    if (!sorted_hashes || !order || !keys || !flags || !out) return fail(10, "dvs_structset_filter: null pointer");
+    if (seen_count > 0 && (!seen_hashes || !seen_keys)) return fail(10, "dvs_structset_filter: null pointer (seen set)");
+    if (keys_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_structset_filter: keys_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    if (seen_keys_bytes < (size_t)seen_count * n_vars * 8)
+        return fail_size("dvs_structset_filter: seen_keys_bytes < seen_count * n_vars * 8", (size_t)seen_count * n_vars * 8);
+    call_begin();
+    if (int e = dvs_structset_filter_impl(batch, n_vars, sorted_hashes, order, keys, flags, seen_count, seen_hashes, seen_keys,
+                                          out, stream))
+        return e;
+    return call_end("dvs_structset_filter");
+}
+
 extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
                                    double* local, double* out, int* status, void* stream);
 extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,

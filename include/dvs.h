@@ -192,6 +192,42 @@ int dvs_match_decoded(int32_t batch, int32_t n_vars, int32_t card, int32_t repea
                       const uint8_t* labels, const void* preds, const void* states, size_t state_bytes,
                       int32_t budget, uint8_t* flags, void* stream);
 
+/* Search candidates on the device (dags_vae_search_amd/search.py, candidates="device"; csrc/dvs_structs.h): what the host
+ * stage between decode and BIC computes per decoded row (graphs_from_states -> is_search_valid -> encode_graphs ->
+ * structure_key), for states: device dvs_decode_state [batch] as dvs_decode leaves them (same vertex / edge convention as
+ * dvs_match_decoded; edges go from a lower to a higher vertex, so a row is acyclic by construction).
+ * flags: device u8 [batch], bit 0 search-valid: nv == n_vars + 3 and the user labels are a permutation of 0..n_vars-1;
+ *   else one reason: bit 1 short row, bit 2 a label outside 0..n_vars-1 (a PACE label below 3 included), bit 3 repeated label.
+ * labels / preds: the row codec of dvs_build_records, device u8 [batch][n_vars] and [batch][n_vars] u16 (u64 when
+ *   preds_are_u64), byte-identical to the host's encode_graphs of the decoded graph on valid rows.
+ * keys: device u64 [batch][n_vars] (keys_bytes >= batch * n_vars * 8), the structure in data-set variable indices:
+ *   bit label[u] of keys[b][label[v]] <=> edge u -> v, i.e. what dvs_bic_parent_masks makes of the codec — ready for
+ *   dvs_bic_scores — and in bijection with the Bayesian-network structure whatever vertex order the decoder grew.
+ * hashes: device u64 [batch]: a fixed mixing function of the key words in variable order, & hash_mask & (2^63 - 1)
+ *   (pass all ones in production; a small mask forces collisions for tests).  63 bits: signed and unsigned sorts agree.
+ * Invalid rows get zero labels / preds / keys and the hash DVS_STRUCT_HASH_INVALID, which sorts last.
+ * 1 <= n_vars <= 45; batch <= 2^30.  (Added in ABI 202 as a pure addition: the version number stays.) */
+#define DVS_STRUCT_HASH_INVALID 0x7fffffffffffffffull
+int dvs_decoded_structures(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const void* states, size_t state_bytes,
+                           uint64_t hash_mask, uint8_t* flags, uint8_t* labels, void* preds, uint64_t* keys,
+                           size_t keys_bytes, uint64_t* hashes, void* stream);
+
+/* Exact, deterministic "new structure" filter of such a batch against a device-resident set of structures already seen
+ * (the `seen` set of search.new_structures).  sorted_hashes: device u64 [batch], the batch's hashes in ascending order;
+ * order: device i64 [batch], the row index of every sorted position, from a STABLE sort (equal hashes keep row order);
+ * keys (keys_bytes >= batch * n_vars * 8) / flags: as dvs_decoded_structures wrote them, in row order.  The set: seen_hashes
+ * device u64 [seen_count] ascending, seen_keys device u64 [seen_count][n_vars] (seen_keys_bytes >= seen_count * n_vars * 8);
+ * both may be NULL when seen_count == 0.  out: device u8 [batch] in row order: 1 new (bit 0 of flags set, key not in the
+ * set, no row of smaller index in the batch has the same key), 2 key in the set, 4 duplicate of an earlier row (not in the
+ * set), 0 flags bit 0 clear.  Equality is decided on the full key, never on the hash: results do not depend on hash
+ * collisions, only the time does (a row is compared with every different key of equal hash that sorts before it; equal
+ * keys stop at the first).  No atomics: the output is a pure function of the inputs, two calls give equal bytes.
+ * batch == 0 returns 0 and enqueues nothing.  (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_t* sorted_hashes, const int64_t* order,
+                         const uint64_t* keys, size_t keys_bytes, const uint8_t* flags, int32_t seen_count,
+                         const uint64_t* seen_hashes, const uint64_t* seen_keys, size_t seen_keys_bytes, uint8_t* out,
+                         void* stream);
+
 /* BIC of B discrete Bayesian-network structures on one data set (replaces BNLearnWrapper.score,
  * src/problem/bn/bnlearn.py:27-61 = `Rscript bnlearn_score.R`: bnlearn::score(net, data, type = "bic")).
  * data: device u64 [n_samples][ceil(n_vars/16)], variable i's level code (0..15) in bits 4*(i%16).. of word i/16;
