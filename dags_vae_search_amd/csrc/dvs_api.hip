@@ -541,7 +541,6 @@ struct FwdGrids {
     int nw;         // waves per workgroup of the one-tile stack kernels (waves_per_wg)
     int chain;      // k_fwd_stack / k_attn_fwd / narrow k_ffn_fwd, k_embed_fwd, k_loss_fwd: nw tiles per workgroup and pass
     int tiles16;    // 16-wave tile-parallel kernels (k_ffn_fwd, one-tile k_embed_fwd)
-    int attn;       // one-tile k_attn_fwd (DVS_ATTN_FWD_THREADS / 64 waves per workgroup)
     int tiles8;     // 8-wave tile-parallel kernels (one-tile k_attn_fwd / k_embed_fwd / k_loss_fwd)
     int tiles4;     // 4-wave tile-parallel kernels (k_embed_fwd_w)
     int dags;       // workgroup-per-DAG kernels of the wide path
@@ -553,7 +552,6 @@ static FwdGrids fwd_grids(const DvsDims& d, bool wide) {
     g.nw = waves_per_wg(d, wide);
     g.chain = grid_for(d.B * d.NT, g.nw);
     g.tiles16 = grid_for(d.B * d.NT, 16);
-    g.attn = grid_for(d.B * d.NT, dvs_attn_fwd_waves());
     g.tiles8 = grid_for(d.B * d.NT, 8);
     g.tiles4 = grid_for(d.B * d.NT, 4);
     g.dags = grid_for(d.B, 1);
@@ -568,7 +566,7 @@ static void launch_embed_fwd(const EmbedArgs& e, const FwdGrids& g, dvs_stream_t
 static void launch_attn_fwd(const AttnArgs& a, const FwdGrids& g, dvs_stream_t st) {
     if (g.wide) dvs_launch_attn_fwd_w(a, g.dags, st);
     else if (g.nw == 4) dvs_launch_attn_fwd(a, g.chain, 4, st);
-    else dvs_launch_attn_fwd(a, g.attn, 8, st);
+    else dvs_launch_attn_fwd(a, g.tiles8, 8, st);
 }
 // One-tile path: the sublayers of the encoder / decoder are chained into one launch each (k_fwd_stack); the wide path and
 // DVS_SPLIT_STACK=1 (per-phase profiling) launch every sublayer on its own.

@@ -36,20 +36,6 @@ __device__ __forceinline__ float* dvs_bwd_epi(char* smem) { return (float*)(smem
 DVS_STAMP_DECL(dvs_stamps_bwd);
 #endif
 
-#ifndef DVS_TOUCH_MODE
-#define DVS_TOUCH_MODE 2
-#endif
-// -DDVS_TOUCH_ROUND (experiment): inside the DAG loop every wave touches the cold tile of its NEXT round at the top of the
-// current one (one load instruction, dvs_touch_first's idea applied within a phase)
-#ifdef DVS_TOUCH_ROUND
-#define DVS_ROUND_TOUCH(name, buf, tile_now, tile_next, ntiles, L) \
-    const float name = (buf)[(size_t)((tile_next) < (ntiles) ? (tile_next) : (tile_now)) * 1024 + (size_t)(L).lane * 16]
-#define DVS_ROUND_TOUCH_DONE(name) asm volatile("" ::"v"(name))
-#else
-#define DVS_ROUND_TOUCH(name, buf, tile_now, tile_next, ntiles, L) ((void)0)
-#define DVS_ROUND_TOUCH_DONE(name) ((void)0)
-#endif
-
 // ---- LDS layouts of the three phase kinds ----------------------------------------------------------------------------
 struct FfnBLds {
     // bf16x3 images (dvs_bf16.h) of W2^T and W1^T (d hidden, d x); W1 as the bf16x6 triple k_ffn_fwd uses: the hidden is
@@ -185,6 +171,23 @@ template <class PP>
 __device__ __forceinline__ void dvs_tail_commit(const DvsBwdTail& t, PP next, bool has_next, char* smem) {
     if (has_next && dvs_tid() < DVS_PF_THREADS) dvs_prefetch_commit<false>(t.pf, next, smem, dvs_tid(), DVS_PF_THREADS);
 }
+// The tail around the phase's own gradient flush (which stays inline in each phase: stage partials above DVS_BWD_EPI_FLOOR,
+// barrier, sum and store).  Opening, written out in each phase (stamps 2-4): the older group issues the next plan's image
+// loads FIRST, then every wave touches its first cold tiles of the next phase (dvs_stage.h) — ahead of the prefetch the cold
+// reads delay the issue of the 73 KB of image loads, which for the short phases sits on the critical path (no touch / ahead /
+// behind: 0 / -2.1 / -2.3 %; touching the next ROUND's tile inside the DAG loop as well: +0.4 %, dropped) — then
+// the barrier behind which no wave reads this phase's images or slots any more.  (Folding those three calls into one helper
+// moves register numbering and s_waitcnt placement of k_bwd_stack — hipcc simplifies a helper before it inlines it — so they
+// stay where they are until that is measured.)  Close, below (stamps 5-6): behind the flush the older group commits the
+// plan below the floor, which does not touch what the flush still reads; the touched values stay live to the very end.
+template <class PP>
+__device__ __forceinline__ void dvs_bwd_tail_end(const DvsBwdTail& tail, const DvsTouch& touch, PP mine, PP next, bool has_next,
+                                                 char* smem) {
+    DVS_STAMP(dvs_stamps_bwd, mine, 5);
+    dvs_tail_commit(tail, next, has_next, smem);
+    DVS_STAMP(dvs_stamps_bwd, mine, 6);
+    dvs_touch_done(touch);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // FFN sublayer backward (autograd of pace.py:62-65 / 151-153).  Recomputes h = drop(relu(W1 x + b1)) from the saved
@@ -192,6 +195,8 @@ __device__ __forceinline__ void dvs_tail_commit(const DvsBwdTail& t, PP next, bo
 // ---------------------------------------------------------------------------------------------------------
 // 8 waves per workgroup, one DAG per wave per iteration; weight gradients are accumulated cooperatively
 // (dvs_coop_dw_bf): ~150 registers per lane, two waves per SIMD, so one wave's VALU phases overlap the other's MFMAs.
+// (The two leave a phase's opening barrier in lock-step and drift half a round apart by themselves; holding the younger
+// group back by a fixed delay to start them apart cost +0.9 ... +12 %)
 // The gradient products (d hidden, d x, and the weight gradients) run on the bf16 matrix pipe as bf16x3: gradient
 // parity is bounded at 2e-3 of the tensor maximum (tests), two orders of magnitude above their ~1e-5 error, whereas
 // the forward keeps fp32-accurate bf16x6 products for the 1e-4 ELBO contract and the hidden is recomputed with them.
@@ -221,8 +226,6 @@ __device__ __forceinline__ void dvs_ffn_bwd_phase(const FfnBwdArgs& a, char* sme
     dvs_bf16* const bslots = (dvs_bf16*)l.slots;                        // a [hi | lo] bf16 pair fills one fp32 scratch tile
     constexpr int BSTRIDE = 2 * 2 * DVS_SCR;                            // bf16 elements between the slots of two waves
     bool gate = !stage_mine;                               // chained: the barrier that publishes this phase's images (DVS_PHASE_GATE)
-    DVS_PHASE_GATE_INIT(gate);
-    dvs_stagger(L.wave);
     for (int base = dvs_bid() * NW; base < B; base += gridDim.x * NW) {
         const int dag = base + L.wave;                     // tile index
         const bool live = dag < B;
@@ -232,7 +235,6 @@ __device__ __forceinline__ void dvs_ffn_bwd_phase(const FfnBwdArgs& a, char* sme
         const int Nl = live ? N : 0;                       // a wave without a tile carries all-zero tiles
         f4 x[4], xhat[4], gp[4];
         float rstd;
-        DVS_ROUND_TOUCH(rt, a.xin, dg, dg + gridDim.x * NW, B, L);
         {
             DvsRawX rx;
             dvs_load_x_issue(rx, a.xin, a.ln, dg, L);      // the COLD load of the round (a saved forward activation; the gradient
@@ -310,24 +312,13 @@ __device__ __forceinline__ void dvs_ffn_bwd_phase(const FfnBwdArgs& a, char* sme
             dvs_ln_bwd_core(dx, xhat, rstd, l.lg, L);
         }
         if (live) dvs_store_tile(a.gout, dag, dx, L);
-        DVS_ROUND_TOUCH_DONE(rt);
         if (base == dvs_bid() * NW) DVS_STAMP(dvs_stamps_bwd, mine, 7);      // end of the first round (tools/phase_stamps.py)
     }
     DVS_PHASE_GATE(gate);                                  // a workgroup without a tile
-    DVS_STAMP(dvs_stamps_bwd, mine, 2);
-    // every wave touches its first tiles of the next phase (dvs_stage.h) — BEHIND the older group's image prefetch: ahead of it
-    // the cold reads delay the issue of the 73 KB of image loads, which for the short phases sits on the critical path
-    // (DVS_TOUCH_MODE: 0 none, 1 ahead of the prefetch, 2 behind it; A/B builds)
-#if DVS_TOUCH_MODE == 1
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#endif
     DvsBwdTail tail;
+    DVS_STAMP(dvs_stamps_bwd, mine, 2);
     dvs_tail_issue(tail, next, has_next);
-#if DVS_TOUCH_MODE == 2
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#elif DVS_TOUCH_MODE == 0
-    const DvsTouch touch = {{0.f, 0.f}};
-#endif
+    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);      // behind the prefetch: dvs_bwd_tail_end
     DVS_STAMP(dvs_stamps_bwd, mine, 3);
     dvs_lds_barrier();
     DVS_STAMP(dvs_stamps_bwd, mine, 4);
@@ -361,10 +352,7 @@ __device__ __forceinline__ void dvs_ffn_bwd_phase(const FfnBwdArgs& a, char* sme
         const int64_t off = k == 0 ? a.o_l1_b : k == 1 ? a.o_l2_b : k == 2 ? a.o_ln_g : k == 3 ? a.o_ln_b : k == 4 ? a.o_own_g : a.o_own_b;
         if (off >= 0) slab[off + f] = s;
     }
-    DVS_STAMP(dvs_stamps_bwd, mine, 5);
-    dvs_tail_commit(tail, next, has_next, smem);       // below DVS_BWD_EPI_FLOOR: does not touch what the flush still reads
-    DVS_STAMP(dvs_stamps_bwd, mine, 6);
-    dvs_touch_done(touch);
+    dvs_bwd_tail_end(tail, touch, mine, next, has_next, smem);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -401,7 +389,6 @@ __device__ __forceinline__ void dvs_proj_bwd_phase(const ProjBwdArgs& a, char* s
     dvs_bf16* myB = myA0 + 4 * DVS_PKB;
     DvsGroup G = {gcount + (L.wave >> 2), 0};
     bool gate = !stage_mine;                               // chained: the barrier that publishes this phase's images (DVS_PHASE_GATE)
-    DVS_PHASE_GATE_INIT(gate);
     f4 aW[NPROJ][4], ab[NPROJ];
     float vgam = 0.f, vbet = 0.f;
 #pragma unroll
@@ -410,7 +397,6 @@ __device__ __forceinline__ void dvs_proj_bwd_phase(const ProjBwdArgs& a, char* s
 #pragma unroll
         for (int i = 0; i < 4; ++i) aW[p][i] = f4_zero();
     }
-    dvs_stagger(L.wave);
     for (int base = dvs_bid() * NW; base < B; base += gridDim.x * NW) {
         const int dag = base + L.wave;               // tile index
         const bool live = dag < B;
@@ -418,7 +404,6 @@ __device__ __forceinline__ void dvs_proj_bwd_phase(const ProjBwdArgs& a, char* s
         const int Nl = live ? dvs_tile_of((int)dg, a.dims).Nl : 0;
         f4 x[4], xhat[4], dx[4];
         float rstd;
-        DVS_ROUND_TOUCH(rt, a.xin, dg, dg + gridDim.x * NW, B, L);
         {
             DvsRawX rx;
             dvs_load_x_issue(rx, a.xin, a.ln, dg, L);      // the cold load of the round
@@ -491,24 +476,13 @@ __device__ __forceinline__ void dvs_proj_bwd_phase(const ProjBwdArgs& a, char* s
                 dvs_store_tile(a.gout2, dag, dx2, L);
             }
         }
-        DVS_ROUND_TOUCH_DONE(rt);
         if (base == dvs_bid() * NW) DVS_STAMP(dvs_stamps_bwd, mine, 7);
     }
     DVS_PHASE_GATE(gate);                                  // a workgroup without a tile
-    DVS_STAMP(dvs_stamps_bwd, mine, 2);
-    // every wave touches its first tiles of the next phase (dvs_stage.h) — BEHIND the older group's image prefetch: ahead of it
-    // the cold reads delay the issue of the 73 KB of image loads, which for the short phases sits on the critical path
-    // (DVS_TOUCH_MODE: 0 none, 1 ahead of the prefetch, 2 behind it; A/B builds)
-#if DVS_TOUCH_MODE == 1
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#endif
     DvsBwdTail tail;
+    DVS_STAMP(dvs_stamps_bwd, mine, 2);
     dvs_tail_issue(tail, next, has_next);
-#if DVS_TOUCH_MODE == 2
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#elif DVS_TOUCH_MODE == 0
-    const DvsTouch touch = {{0.f, 0.f}};
-#endif
+    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);      // behind the prefetch: dvs_bwd_tail_end
     DVS_STAMP(dvs_stamps_bwd, mine, 3);
     dvs_lds_barrier();
     DVS_STAMP(dvs_stamps_bwd, mine, 4);
@@ -540,10 +514,7 @@ __device__ __forceinline__ void dvs_proj_bwd_phase(const ProjBwdArgs& a, char* s
         if (k < NPROJ) slab[a.o_b + 64 * k + (so ? dvs_pi(f) : f)] = s;
         else if (a.o_ln_g >= 0) slab[(k == NPROJ ? a.o_ln_g : a.o_ln_b) + f] = s;
     }
-    DVS_STAMP(dvs_stamps_bwd, mine, 5);
-    dvs_tail_commit(tail, next, has_next, smem);
-    DVS_STAMP(dvs_stamps_bwd, mine, 6);
-    dvs_touch_done(touch);
+    dvs_bwd_tail_end(tail, touch, mine, next, has_next, smem);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -637,7 +608,6 @@ __device__ __forceinline__ void dvs_attn_bwd_phase(const AttnBwdArgs& a, char* s
     // round's loads, as the FFN / projection phases do) it cost this phase, which sits at the 256-register limit, 15 spills
     bool gate = !stage_mine;
     DVS_PHASE_GATE(gate);
-    dvs_stagger(L.wave);
     for (int base = dvs_bid() * NW; base < B; base += gridDim.x * NW) {
         const int dag = base + L.wave;
         const bool live = dag < B;
@@ -846,20 +816,10 @@ __device__ __forceinline__ void dvs_attn_bwd_phase(const AttnBwdArgs& a, char* s
         dvs_group_barrier(G, L);
         if (base == dvs_bid() * NW) DVS_STAMP(dvs_stamps_bwd, mine, 7);
     }
-    DVS_STAMP(dvs_stamps_bwd, mine, 2);
-    // every wave touches its first tiles of the next phase (dvs_stage.h) — BEHIND the older group's image prefetch: ahead of it
-    // the cold reads delay the issue of the 73 KB of image loads, which for the short phases sits on the critical path
-    // (DVS_TOUCH_MODE: 0 none, 1 ahead of the prefetch, 2 behind it; A/B builds)
-#if DVS_TOUCH_MODE == 1
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#endif
     DvsBwdTail tail;
+    DVS_STAMP(dvs_stamps_bwd, mine, 2);
     dvs_tail_issue(tail, next, has_next);
-#if DVS_TOUCH_MODE == 2
-    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);
-#elif DVS_TOUCH_MODE == 0
-    const DvsTouch touch = {{0.f, 0.f}};
-#endif
+    const DvsTouch touch = dvs_touch_first(next, has_next, NW, L.wave, L.lane);      // behind the prefetch: dvs_bwd_tail_end
     DVS_STAMP(dvs_stamps_bwd, mine, 3);
     dvs_lds_barrier();
     DVS_STAMP(dvs_stamps_bwd, mine, 4);
@@ -880,9 +840,6 @@ __device__ __forceinline__ void dvs_attn_bwd_phase(const AttnBwdArgs& a, char* s
         for (int w = 0; w < NW; ++w) s += red[w * 64 + dvs_tid()];
         slab[a.o_out_b + dvs_tid()] = s;
     }
-    DVS_STAMP(dvs_stamps_bwd, mine, 5);
-    dvs_tail_commit(tail, next, has_next, smem);
-    DVS_STAMP(dvs_stamps_bwd, mine, 6);
-    dvs_touch_done(touch);
+    dvs_bwd_tail_end(tail, touch, mine, next, has_next, smem);
 }
 

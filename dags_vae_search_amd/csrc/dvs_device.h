@@ -113,21 +113,6 @@ __device__ __forceinline__ void dvs_lds_barrier() {
 #endif
 }
 
-// Stagger (experiment knob, -DDVS_STAGGER=n: n x 64 cycles): the two waves of a SIMD (one of each wave group) leave a phase's
-// opening barrier in lock-step and run the same instruction stream, so both want the matrix pipe, then both the VALU; the
-// younger wave's FIRST DAG of a phase took 37 k cycles against 22 k once the two had drifted apart (round 1).
-// Holding the younger group back by a fraction of a DAG de-phases them from the start.
-#ifndef DVS_STAGGER
-#define DVS_STAGGER 0
-#endif
-__device__ __forceinline__ void dvs_stagger(int wave) {
-#if !defined(DVS_EMU) && DVS_STAGGER > 0
-    if (wave >= 4) {
-        for (int i = 0; i < DVS_STAGGER / 16; ++i) __builtin_amdgcn_s_sleep(16);      // 16 x 64 cycles per step
-    }
-#endif
-}
-
 #ifdef DVS_EMU
 #define DVS_SCHED_FENCE() ((void)0)
 #else

@@ -137,7 +137,6 @@ static_assert(sizeof(FwdStackArgs) <= 4096, "kernel argument block limit");
 // nw: waves per workgroup, 8 or 4 (dvs_api.hip: dvs_waves_per_wg); grid sized for nw DAGs per workgroup and pass
 void dvs_launch_fwd_stack(const FwdStackArgs& s, int tag, int grid, int nw, dvs_stream_t st);   // tag 0 encoder, 1 decoder (profile names)
 void dvs_launch_attn_fwd(const AttnArgs& a, int grid, int nw, dvs_stream_t st);
-int dvs_attn_fwd_waves();
 void dvs_launch_ffn_fwd(const FfnArgs& a, int grid, int nw, dvs_stream_t st);
 void dvs_launch_latent_fwd(const LatentArgs& a, dvs_stream_t st);
 void dvs_launch_loss_fwd(const LossArgs& a, int grid, int nw, dvs_stream_t st);
@@ -265,12 +264,8 @@ __device__ __forceinline__ void dvs_load_x(f4 (&x)[4], f4 (&xhat)[4], float& rst
 // that round's global loads (nothing in LDS has been touched yet — the loads are the only work ahead of it), so their latency
 // overlaps the wait for the slowest wave of the previous phase and for the commit.  `pending` is false when the phase staged
 // its own images (first phase of a launch, per-phase kernels); a workgroup without a DAG takes the barrier behind its loop.
-// -DDVS_GATE_UPFRONT (A/B builds, tools/build_variant.sh): every phase takes the barrier before its DAG loop, as round 2 did.
-#ifdef DVS_GATE_UPFRONT
-#define DVS_PHASE_GATE_INIT(pending) DVS_PHASE_GATE(pending)
-#else
-#define DVS_PHASE_GATE_INIT(pending) ((void)0)
-#endif
+// Taking it before the DAG loop in every phase, as round 2 did, measured no different by itself; only the
+// attention backward, at the 256-register limit, still does (dvs_bwd_phases.h).
 #define DVS_PHASE_GATE(pending)      \
     do {                             \
         if (pending) {               \

@@ -51,8 +51,31 @@ constexpr int DVS_STAMP_IDS = 8, DVS_STAMP_PHASES = 32, DVS_STAMP_WAVES = 8, DVS
             buf[(((size_t)dvs_bid() * DVS_STAMP_WAVES + (dvs_tid() >> 6)) * DVS_STAMP_PHASES + ((pp)->phase & 31)) *          \
                     DVS_STAMP_IDS + (id)] = __builtin_amdgcn_s_memtime();                                                    \
     } while (0)
+// Inner budgets of single kernels (tools/attn_stamps.py, loss_stamps.py, wide_stamps.py): lane 0 of every wave ADDS the cycles
+// since its previous stamp (`last`, a local of the kernel) to slot k of buf[workgroup < 256][wave < nw][ids]
+#define DVS_ACC_STAMP_DECL(name) __device__ unsigned long long name[256 * 8 * 8]
+#define DVS_ACC_STAMP_AT(buf, last, nw, ids, k)                                                                             \
+    do {                                                                                                                    \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                                       \
+        if ((dvs_tid() & 63) == 0 && dvs_bid() < 256) buf[(dvs_bid() * (nw) + (dvs_tid() >> 6)) * (ids) + (k)] += now_ - last; \
+        last = now_;                                                                                                        \
+    } while (0)
+#define DVS_ACC_STAMP(buf, last, k) DVS_ACC_STAMP_AT(buf, last, 8, 8, k)
+// host side: copy the stamp array dvs_stamps_<name> out (and clear it) — looked up by name through ctypes by the tools
+#define DVS_STAMP_READER(name)                                                                                              \
+    extern "C" int dvs_debug_read_stamps_##name(void* out, size_t bytes, int clear) {                                       \
+        if (bytes > sizeof(dvs_stamps_##name)) bytes = sizeof(dvs_stamps_##name);                                           \
+        if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_##name), bytes) != hipSuccess) return 1;                         \
+        void* p = nullptr;                                                                                                  \
+        if (clear && (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_##name)) != hipSuccess ||                               \
+                      hipMemset(p, 0, sizeof(dvs_stamps_##name)) != hipSuccess))                                            \
+            return 2;                                                                                                       \
+        return 0;                                                                                                           \
+    }
 #else
 #define DVS_STAMP(buf, pp, id) ((void)0)
+#define DVS_ACC_STAMP(buf, last, k) ((void)0)
+#define DVS_ACC_STAMP_AT(buf, last, nw, ids, k) ((void)0)
 #endif
 
 // Plans are built on the HOST by the launchers (the LDS layout functions are __host__ __device__) and travel in the kernel

@@ -191,13 +191,5 @@ void dvs_launch_reduce_slabs(const ReduceArgs& a, dvs_stream_t st) {
 }
 
 #ifdef DVS_STAMPS
-extern "C" int dvs_debug_read_stamps_bwd(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_bwd)) bytes = sizeof(dvs_stamps_bwd);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_bwd), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_bwd)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_bwd)) != hipSuccess) return 2;
-    }
-    return 0;
-}
+DVS_STAMP_READER(bwd)
 #endif

@@ -10,24 +10,9 @@
 #ifdef DVS_STAMPS
 // inner budget of k_loss_bwd (tools/loss_stamps.py): cycles summed over the wave's DAGs, per (workgroup, wave, segment)
 __device__ unsigned long long dvs_stamps_lossb[256 * 4 * 12];
-#define LBSTAMP(k)                                                                                                         \
-    do {                                                                                                                   \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                                      \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) dvs_stamps_lossb[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 12 + (k)] += now_ - lst_; \
-        lst_ = now_;                                                                                                       \
-    } while (0)
-extern "C" int dvs_debug_read_stamps_lossb(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_lossb)) bytes = sizeof(dvs_stamps_lossb);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_lossb), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_lossb)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_lossb)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-#else
-#define LBSTAMP(k) ((void)0)
+DVS_STAMP_READER(lossb)
 #endif
+#define LBSTAMP(k) DVS_ACC_STAMP_AT(dvs_stamps_lossb, lst_, 4, 12, k)      // 4 waves, ids 0-9
 __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan) {
 #ifdef DVS_STAMPS
     unsigned long long lst_ = __builtin_amdgcn_s_memtime();

@@ -320,16 +320,9 @@ struct DvsLatTag { int phase; };
 __device__ const DvsLatTag dvs_lat_tag = {6};
 #define DVS_LAT_STAMP(id) DVS_STAMP(dvs_stamps_fwd, &dvs_lat_tag, id)
 // inner budget of the attention forward DAG loop: cycles summed over DAGs and phases, per (workgroup, wave, segment)
-__device__ unsigned long long dvs_stamps_attn[256 * 8 * 8];
-#define ASTAMP(k)                                                                                                   \
-    do {                                                                                                            \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                               \
-        if ((dvs_tid() & 63) == 0 && dvs_bid() < 256) dvs_stamps_attn[(dvs_bid() * 8 + (dvs_tid() >> 6)) * 8 + (k)] += now_ - ast_; \
-        ast_ = now_;                                                                                                \
-    } while (0)
-#else
-#define ASTAMP(k) ((void)0)
+DVS_ACC_STAMP_DECL(dvs_stamps_attn);
 #endif
+#define ASTAMP(k) DVS_ACC_STAMP(dvs_stamps_attn, ast_, k)
 #include "dvs_latent.h"
 struct AttnLds {
     dvs_bf16 *Win, *Wout;                     // bf16x6 image triples (dvs_bf16.h); in-projection rows / out-projection columns in slot order
@@ -438,9 +431,22 @@ __device__ __forceinline__ f4 attn_drop_T(f4 p, uint32_t key, int h, const DvsDr
     return p;
 }
 
-#ifndef DVS_ATTN_FWD_THREADS
-#define DVS_ATTN_FWD_THREADS 512
-#endif
+// Tail of both forward phases in a chained launch: the older wave group fetches the next phase's images while it waits for the
+// younger one (dvs_stage.h) and commits them behind the barrier; the next phase's gate publishes them.  mine: stamps only.
+template <class PP>
+__device__ __forceinline__ void dvs_fwd_tail(PP next, bool has_next, char* smem, PP mine) {
+    if (has_next) {
+        DvsPrefetch<DVS_PF_FWD_TAIL> pf;
+        const bool fetcher = dvs_tid() < DVS_PF_THREADS;
+        if (fetcher) dvs_prefetch_issue<false>(pf, next, dvs_tid(), DVS_PF_THREADS);
+        DVS_STAMP(dvs_stamps_fwd, mine, 3);
+        dvs_lds_barrier();               // every wave is done with this phase's images
+        DVS_STAMP(dvs_stamps_fwd, mine, 4);
+        if (fetcher) dvs_prefetch_commit<false>(pf, next, smem, dvs_tid(), DVS_PF_THREADS);
+        DVS_STAMP(dvs_stamps_fwd, mine, 6);
+    }
+}
+
 // mine / stage_mine, next / has_next: staging plans of this phase and of the one that follows in a chained launch
 // (dvs_stage.h): the next phase's images are fetched into registers behind this phase's DAG loop, ahead of the barrier.
 // NW: waves per workgroup the phase is compiled for (8, or 4 in the narrow mapping of small batches, dvs_api.hip): sizes the
@@ -462,8 +468,6 @@ __device__ __forceinline__ void dvs_attn_fwd_phase(const AttnArgs& a, char* smem
     unsigned long long ast_ = __builtin_amdgcn_s_memtime();
 #endif
     bool gate = !stage_mine;                 // chained: the barrier that publishes this phase's images (DVS_PHASE_GATE)
-    DVS_PHASE_GATE_INIT(gate);
-    dvs_stagger(L.wave);
     // every wave of the workgroup runs the same number of rounds (the gate is a workgroup barrier): a wave beyond the batch
     // in the last round skips its DAG inside the round
     for (int base = dvs_bid() * L.nwaves; base < a.dims.B; base += gridDim.x * L.nwaves) {
@@ -540,27 +544,7 @@ __device__ __forceinline__ void dvs_attn_fwd_phase(const AttnArgs& a, char* smem
     }
     DVS_PHASE_GATE(gate);                    // a workgroup without a DAG
     DVS_STAMP(dvs_stamps_fwd, mine, 2);
-    if (has_next) {
-        // the older wave group fetches the next phase's images while it waits for the younger one (dvs_stage.h)
-        DvsPrefetch<DVS_PF_FWD_TAIL> pf;
-        const bool fetcher = dvs_tid() < DVS_PF_THREADS;
-        if (fetcher) dvs_prefetch_issue<false>(pf, next, dvs_tid(), DVS_PF_THREADS);
-        DVS_STAMP(dvs_stamps_fwd, mine, 3);
-        dvs_lds_barrier();               // every wave is done with this phase's images
-        DVS_STAMP(dvs_stamps_fwd, mine, 4);
-#ifdef DVS_STAMPS_ICACHE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DVS_STAMP(dvs_stamps_fwd, mine, 5);
-#endif
-        if (fetcher) dvs_prefetch_commit<false>(pf, next, smem, dvs_tid(), DVS_PF_THREADS);
-        DVS_STAMP(dvs_stamps_fwd, mine, 6);
-#ifdef DVS_STAMPS_ICACHE
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (fetcher) dvs_prefetch_commit<false>(pf, next, smem, dvs_tid(), DVS_PF_THREADS);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        DVS_STAMP(dvs_stamps_fwd, mine, 7);
-#endif
-    }
+    dvs_fwd_tail(next, has_next, smem, mine);
 }
 
 template <int NW>
@@ -569,7 +553,6 @@ __global__ __launch_bounds__(64 * NW) void k_attn_fwd(AttnArgs a, DvsStagePlan p
     dvs_attn_fwd_phase<NW>(a, smem, &plan, true, &plan, false);
 }
 
-int dvs_attn_fwd_waves() { return DVS_ATTN_FWD_THREADS / 64; }
 void dvs_launch_attn_fwd(const AttnArgs& a, int grid, int nw, dvs_stream_t st) {
     const size_t lds = attn_lds_bytes();
     DvsStagePlan plan;
@@ -578,8 +561,8 @@ void dvs_launch_attn_fwd(const AttnArgs& a, int grid, int nw, dvs_stream_t st) {
         DVS_SET_LDS(k_attn_fwd<4>, lds);
         DVS_LAUNCH_AS("k_attn_fwd", k_attn_fwd<4>, dim3(grid), dim3(256), lds, st, a, plan);
     } else {
-        DVS_SET_LDS(k_attn_fwd<DVS_ATTN_FWD_THREADS / 64>, lds);
-        DVS_LAUNCH_AS("k_attn_fwd", k_attn_fwd<DVS_ATTN_FWD_THREADS / 64>, dim3(grid), dim3(DVS_ATTN_FWD_THREADS), lds, st, a, plan);
+        DVS_SET_LDS(k_attn_fwd<8>, lds);
+        DVS_LAUNCH_AS("k_attn_fwd", k_attn_fwd<8>, dim3(grid), dim3(512), lds, st, a, plan);
     }
 }
 
@@ -631,8 +614,6 @@ __device__ __forceinline__ void dvs_ffn_fwd_phase(const FfnArgs& a, char* smem, 
     const DvsDrop D = dvs_drop_of(a.dims);
     const int ntiles = a.dims.B * a.dims.NT;
     bool gate = !stage_mine;                 // chained: the barrier that publishes this phase's images (DVS_PHASE_GATE)
-    DVS_PHASE_GATE_INIT(gate);
-    dvs_stagger(L.wave);
     for (int base = dvs_bid() * L.nwaves; base < ntiles; base += gridDim.x * L.nwaves) {      // uniform round count (gate)
         const int tile = base + L.wave;
         if (tile >= ntiles) {
@@ -688,27 +669,7 @@ __device__ __forceinline__ void dvs_ffn_fwd_phase(const FfnArgs& a, char* smem, 
     }
     DVS_PHASE_GATE(gate);                    // a workgroup without a tile
     DVS_STAMP(dvs_stamps_fwd, mine, 2);
-    if (has_next) {
-        // the older wave group fetches the next phase's images while it waits for the younger one (dvs_stage.h)
-        DvsPrefetch<DVS_PF_FWD_TAIL> pf;
-        const bool fetcher = dvs_tid() < DVS_PF_THREADS;
-        if (fetcher) dvs_prefetch_issue<false>(pf, next, dvs_tid(), DVS_PF_THREADS);
-        DVS_STAMP(dvs_stamps_fwd, mine, 3);
-        dvs_lds_barrier();               // every wave is done with this phase's images
-        DVS_STAMP(dvs_stamps_fwd, mine, 4);
-#ifdef DVS_STAMPS_ICACHE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DVS_STAMP(dvs_stamps_fwd, mine, 5);
-#endif
-        if (fetcher) dvs_prefetch_commit<false>(pf, next, smem, dvs_tid(), DVS_PF_THREADS);
-        DVS_STAMP(dvs_stamps_fwd, mine, 6);
-#ifdef DVS_STAMPS_ICACHE
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (fetcher) dvs_prefetch_commit<false>(pf, next, smem, dvs_tid(), DVS_PF_THREADS);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        DVS_STAMP(dvs_stamps_fwd, mine, 7);
-#endif
-    }
+    dvs_fwd_tail(next, has_next, smem, mine);
 }
 
 // 16 waves per workgroup (4 waves per SIMD): at B = 4096 every wave owns exactly one DAG.  nw = 4 (narrow mapping): the
@@ -807,22 +768,6 @@ void dvs_launch_unfrag(const float* frag, float* out, int B, dvs_stream_t st) {
 }
 
 #ifdef DVS_STAMPS
-extern "C" int dvs_debug_read_stamps_attn(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_attn)) bytes = sizeof(dvs_stamps_attn);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_attn), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_attn)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_attn)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-extern "C" int dvs_debug_read_stamps_fwd(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_fwd)) bytes = sizeof(dvs_stamps_fwd);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_fwd), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_fwd)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_fwd)) != hipSuccess) return 2;
-    }
-    return 0;
-}
+DVS_STAMP_READER(attn)
+DVS_STAMP_READER(fwd)
 #endif

@@ -31,25 +31,10 @@ void dvs_launch_latent_fwd(const LatentArgs& a, dvs_stream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 #ifdef DVS_STAMPS
 // inner budget of k_loss_fwd (tools/loss_stamps.py): cycles summed over the wave's DAGs, per (workgroup, wave, segment)
-__device__ unsigned long long dvs_stamps_loss[256 * 8 * 8];
-#define LSTAMP(k)                                                                                                          \
-    do {                                                                                                                   \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                                      \
-        if ((dvs_tid() & 63) == 0 && dvs_bid() < 256) dvs_stamps_loss[(dvs_bid() * 8 + (dvs_tid() >> 6)) * 8 + (k)] += now_ - lst_; \
-        lst_ = now_;                                                                                                       \
-    } while (0)
-extern "C" int dvs_debug_read_stamps_loss(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_loss)) bytes = sizeof(dvs_stamps_loss);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_loss), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_loss)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_loss)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-#else
-#define LSTAMP(k) ((void)0)
+DVS_ACC_STAMP_DECL(dvs_stamps_loss);
+DVS_STAMP_READER(loss)
 #endif
+#define LSTAMP(k) DVS_ACC_STAMP(dvs_stamps_loss, lst_, k)
 __global__ __launch_bounds__(512) void k_loss_fwd(LossArgs a, DvsStagePlan plan) {
 #ifdef DVS_STAMPS
     unsigned long long lst_ = __builtin_amdgcn_s_memtime();

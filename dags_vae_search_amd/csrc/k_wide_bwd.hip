@@ -46,44 +46,15 @@ static_assert(ATTNWB_FLOATS * 4 <= 160 * 1024, "k_attn_bwd_w LDS");
 
 #ifdef DVS_STAMPS
 // per-stage s_memtime totals of k_attn_bwd_w (tools/wide_stamps.py): [workgroup][wave][stage], summed over DAGs and launches
-__device__ unsigned long long dvs_stamps_wb[256 * 8 * 8];
-#define WBSTAMP(k)                                                                                          \
-    do {                                                                                                    \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                       \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) dvs_stamps_wb[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] += now_ - wst_; \
-        wst_ = now_;                                                                                        \
-    } while (0)
-extern "C" int dvs_debug_read_stamps_wb(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_wb)) bytes = sizeof(dvs_stamps_wb);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_wb), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_wb)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_wb)) != hipSuccess) return 2;
-    }
-    return 0;
-}
+DVS_ACC_STAMP_DECL(dvs_stamps_wb);
+DVS_STAMP_READER(wb)
 // ... and of the two head kernels: ids 0-3 k_embed_bwd_w (tile stage, barrier, scatters, barrier), 4-7 k_loss_bwd_w (heads + U / V,
 // pass 1 incl. barrier, pass 2 incl. barrier, edge matrices + d h + store incl. barrier)
-__device__ unsigned long long dvs_stamps_wc[256 * 8 * 8];
-#define WCSTAMP(k)                                                                                          \
-    do {                                                                                                    \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                       \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) dvs_stamps_wc[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] += now_ - wst_; \
-        wst_ = now_;                                                                                        \
-    } while (0)
-extern "C" int dvs_debug_read_stamps_wc(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_wc)) bytes = sizeof(dvs_stamps_wc);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_wc), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_wc)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_wc)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-#else
-#define WBSTAMP(k) ((void)0)
-#define WCSTAMP(k) ((void)0)
+DVS_ACC_STAMP_DECL(dvs_stamps_wc);
+DVS_STAMP_READER(wc)
 #endif
+#define WBSTAMP(k) DVS_ACC_STAMP(dvs_stamps_wb, wst_, k)
+#define WCSTAMP(k) DVS_ACC_STAMP(dvs_stamps_wc, wst_, k)
 
 // ---- MFMA core of the wide attention backward ----------------------------------------------------------------------------
 // Wave h owns head h: it touches ONLY the head's 8 feature columns c0 = 8h .. of the parked [48][DVS_LD] buffers, so the eight

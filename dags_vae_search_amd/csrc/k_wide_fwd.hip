@@ -296,25 +296,10 @@ constexpr size_t ATTNW_BYTES = 3 * 256 * DVS_LDB * sizeof(dvs_bf16) + (192 + 64 
 
 
 #ifdef DVS_STAMPS
-__device__ unsigned long long dvs_stamps_w[256 * 8 * 8];
-#define WSTAMP(k)                                                                                           \
-    do {                                                                                                    \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                       \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) dvs_stamps_w[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] += now_ - wst_; \
-        wst_ = now_;                                                                                        \
-    } while (0)
-extern "C" int dvs_debug_read_stamps_w(void* out, size_t bytes, int clear) {
-    if (bytes > sizeof(dvs_stamps_w)) bytes = sizeof(dvs_stamps_w);
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dvs_stamps_w), bytes) != hipSuccess) return 1;
-    if (clear) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(dvs_stamps_w)) != hipSuccess || hipMemset(p, 0, sizeof(dvs_stamps_w)) != hipSuccess) return 2;
-    }
-    return 0;
-}
-#else
-#define WSTAMP(k) ((void)0)
+DVS_ACC_STAMP_DECL(dvs_stamps_w);
+DVS_STAMP_READER(w)
 #endif
+#define WSTAMP(k) DVS_ACC_STAMP(dvs_stamps_w, wst_, k)
 
 __global__ __launch_bounds__(512) void k_attn_fwd_w(AttnArgs a) {
     DVS_DYN_LDS(smem);
