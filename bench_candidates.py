@@ -167,13 +167,13 @@ def stage_leg(model, n, z, sets, reps, states=None):
     return out
 
 
-def search_leg():
+def search_leg(metric="bic"):
     from dags_vae_search_amd import BNLearnWrapper, LabeledGraph, latent_bo_search
     from dags_vae_search_amd.predictor import GPRegressionModel
     from tests.helpers import graphs_from, load_npz
     fix = load_npz("asia_predictor.npz")
     graphs = [LabeledGraph(list(l), list(e)) for l, e in graphs_from(load_npz("asia_predictor_graphs.npz"), 8)][:256]
-    ev = BNLearnWrapper("asia", "bic", data=load_npz("bn_asia_data.npz")["data"])
+    ev = BNLearnWrapper("asia", metric, data=load_npz("bn_asia_data.npz")["data"])
     out = {}
     for name, batch, cand in (("64x4_host", 64, "host"), ("64x4_device", 64, "device"), ("4096x4_device", 4096, "device")):
         vae = _model(8, "asia_ckpt110.npz")
@@ -197,6 +197,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "search_candidates_bench.json"))
     ap.add_argument("--set-size", type=int, default=SET_SIZE)
+    ap.add_argument("--metric", default="bic", help="the search leg's score type (BNLearnWrapper metric_name)")
     args = ap.parse_args()
     from tests.helpers import load_npz
     res = {"bench": "search_candidates", "device": torch.cuda.get_device_name(0), "reps": args.reps,
@@ -223,7 +224,8 @@ def main():
     pick = np.random.default_rng(5).integers(0, len(pool), 4096)
     made = torch.from_numpy(states_of([pool[i] for i in pick], 37)).to(DEV)
     res["n37_4096_handmade_valid"] = stage_leg(m37, 37, None, sets37, args.reps, states=made)
-    res["search_iteration_asia"] = search_leg()
+    res["search_iteration_asia"] = search_leg(args.metric)
+    res["metric"] = args.metric
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -77,6 +77,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--iterations", type=int, default=3)
+    ap.add_argument("--metric", default="bic", help="the evaluator's score type (BNLearnWrapper metric_name)")
     args = ap.parse_args()
     from tests.helpers import graphs_from, load_npz
     fix = load_npz("asia_predictor.npz")
@@ -119,7 +120,7 @@ def main():
     vae = PaceVaeV3(8, 8, 32, 8, 3, 64, 32, 32, 0.15)
     vae.load_state_dict({k: torch.from_numpy(ck[k]) for k in ck.files})
     vae = vae.to("cuda:0").eval()
-    ev = BNLearnWrapper("asia", "bic", data=load_npz("bn_asia_data.npz")["data"])
+    ev = BNLearnWrapper("asia", args.metric, data=load_npz("bn_asia_data.npz")["data"])
     sgp = _gp(x[:1024], y[:1024])
     cfg = dict(iterations=args.iterations, batch_size=64, n_starts=1024, steps=50, lr=0.02, decode_tries=4, seed=0)
     t0 = time.perf_counter()
@@ -128,7 +129,7 @@ def main():
     last = res.history[-1]
     out = {"metric": "dvs_gp_acquire ms (Q = 16384, M = 500, D = 32, with dEI/dx)", "value": rows[1]["kernel_ms"],
            "unit": "ms", "acquire": rows,
-           "search_iteration": {"config": dict(cfg, initial_graphs=len(graphs)), "iteration": last.iteration,
+           "search_iteration": {"config": dict(cfg, initial_graphs=len(graphs), metric=args.metric), "iteration": last.iteration,
                                 "ms": {k: round(v, 3) for k, v in last.timings_ms.items()},
                                 "seconds": last.seconds, "n_candidates": last.n_candidates, "n_valid": last.n_valid,
                                 "n_new": last.n_new, "best_score": last.best_score, "ei_max": last.ei_max,

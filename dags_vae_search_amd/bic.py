@@ -1,15 +1,21 @@
-"""Batched BIC scorer for discrete Bayesian networks on the GPU.
+"""Batched scorer for discrete Bayesian networks on the GPU: BIC and bnlearn's other decomposable scores.
 
 Mirror of the reference's ``BNLearnWrapper`` (src/problem/bn/bnlearn.py:10-61): ``score(labeled_graph)`` returns
 ``bnlearn::score(net, data, type="bic")`` of the DAG whose vertex v stands for data-set variable ``labels[v]``.  The
 reference starts one ``Rscript`` per graph; here ``score_batch`` scores thousands of structures in one HIP launch
 (csrc/k_bic.hip: LDS contingency counts + fp64 log-likelihood).  The data set is passed in (the reference pulls it from
 R's ``data(asia)``; its CSV copies are data/bn_asia/target.csv, data/bn_sachs/target.csv).
+
+The reference hands ``metric_name`` to bnlearn unseen (bnlearn_scripts/bnlearn_score.R); built here are ``bic`` (the
+default, dvs_bic_scores) and, through dvs_bn_scores, ``loglik``, ``aic``, ``bde`` (BDeu), ``bds``, ``k2`` and ``bdj`` with
+bnlearn's arguments ``k`` (aic, bic) and ``iss`` (bde, bds) — definitions in include/dvs.h.  All of them are to be
+maximised, as the search (search.py) and the predictor data (predictor_data.py) assume.
 """
 from __future__ import annotations
 
 import csv
 import ctypes
+import math
 from typing import List, Sequence
 
 import numpy as np
@@ -31,15 +37,32 @@ def load_discrete_csv(path: str):
     return names, np.stack(cols, 1)
 
 
+PENALISED_SCORES = ("aic", "bic")        # take k
+DIRICHLET_SCORES = ("bde", "bds")        # take iss
+
+
 class BNLearnWrapper:
-    def __init__(self, dataset_name: str, metric_name: str = "bic", data=None, device="cuda"):
-        """``data``: path of a CSV with a header row of variable names, or a level-coded integer array [S, n]."""
-        if metric_name != "bic":
-            raise NotImplementedError(f"only the 'bic' score is built (got {metric_name!r})")
+    def __init__(self, dataset_name: str, metric_name: str = "bic", data=None, device="cuda", *, iss=None, k=None):
+        """``data``: path of a CSV with a header row of variable names, or a level-coded integer array [S, n].
+        ``metric_name``: one of ``_lib.SCORE_TYPES``; ``k``: the penalty coefficient of aic (default 1) / bic (default
+        log(S) / 2); ``iss``: the imaginary sample size of bde / bds (default 1)."""
+        if metric_name not in dl.SCORE_TYPES:
+            raise NotImplementedError(f"built scores: {', '.join(sorted(dl.SCORE_TYPES))} (got {metric_name!r})")
+        if iss is not None and metric_name not in DIRICHLET_SCORES:
+            raise ValueError(f"iss is the argument of {' / '.join(DIRICHLET_SCORES)}, not of {metric_name!r}")
+        if k is not None and metric_name not in PENALISED_SCORES:
+            raise ValueError(f"k is the argument of {' / '.join(PENALISED_SCORES)}, not of {metric_name!r}")
+        if iss is not None and not (math.isfinite(iss) and iss > 0):
+            raise ValueError(f"iss must be finite and > 0 (got {iss!r})")
+        if k is not None and not (math.isfinite(k) and k >= 0):
+            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
         if data is None:
             raise ValueError("pass data=<csv path or level-coded array>: the reference's R data sets are not bundled")
         self.dataset_name = dataset_name
         self.metric_name = metric_name
+        self.iss, self.k = iss, k
+        arg = iss if iss is not None else k
+        self._score_arg = float("nan") if arg is None else float(arg)      # NaN: the type's default (include/dvs.h)
         arr = load_discrete_csv(data)[1] if isinstance(data, str) else np.asarray(data)
         if arr.ndim != 2 or arr.shape[1] > dl.MAX_TOKENS or arr.min() < 0 or arr.max() > 15:
             raise ValueError("data must be [samples, n_vars <= 48] with level codes 0..15")
@@ -68,26 +91,32 @@ class BNLearnWrapper:
         masks = self._parent_masks(labeled_graphs, label_key)
         return self.score_masks(torch.from_numpy(masks.view(np.int64))).cpu().tolist()
 
-    def score_masks(self, parents: torch.Tensor) -> torch.Tensor:
-        """parents: int64 [B, n_vars] bit rows in data-set variable indices (bit u of [b, v] <=> u -> v); -> f64 [B]."""
+    def score_masks(self, parents: torch.Tensor, local: bool = False):
+        """parents: int64 [B, n_vars] bit rows in data-set variable indices (bit u of [b, v] <=> u -> v); -> f64 [B], or
+        with ``local`` (scores f64 [B], per-variable local scores f64 [B, n_vars])."""
         parents = parents.to(self.device).contiguous()
         B = parents.shape[0]
         scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
         out = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        dl.check(self.lib, self.lib.dvs_bic_scores(B, self.n_vars, self.n_samples, p(self._data), p(self._card), p(parents),
-                                                   p(scratch), p(out), p(status),
-                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                 "dvs_bic_scores")
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.metric_name == "bic" and self.k is None:
+            dl.check(self.lib, self.lib.dvs_bic_scores(B, self.n_vars, self.n_samples, p(self._data), p(self._card), p(parents),
+                                                       p(scratch), p(out), p(status), stream), "dvs_bic_scores")
+        else:
+            dl.check(self.lib, self.lib.dvs_bn_scores(B, self.n_vars, self.n_samples, p(self._data), p(self._card), p(parents),
+                                                      dl.SCORE_TYPES[self.metric_name], self._score_arg, p(scratch), p(out),
+                                                      p(status), stream), "dvs_bn_scores")
         if int(status.item()) & 16:
             raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
                              "cells; sorted samples: 16 384 samples, 63 key bits)")
-        return out
+        return (out, scratch) if local else out
 
     def score_compact(self, batch) -> torch.Tensor:
-        """BIC of a ``CompactBatch`` (records.py) that lives on the device -> float64 [B] on the device: the relabelling
-        (dvs_bic_parent_masks) and the scoring (dvs_bic_scores) are both HIP launches, nothing touches the host."""
+        """Score of a ``CompactBatch`` (records.py) that lives on the device -> float64 [B] on the device: the relabelling
+        (dvs_bic_parent_masks) and the scoring (dvs_bic_scores / dvs_bn_scores) are both HIP launches, nothing touches
+        the host."""
         labels = batch.labels.to(self.device).contiguous()
         preds = batch.preds.to(self.device).contiguous()
         B, n = labels.shape

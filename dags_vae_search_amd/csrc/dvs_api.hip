@@ -1046,6 +1046,42 @@ extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, 
     return call_end("dvs_bic_scores");
 }
 
+extern "C" int dvs_bn_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
+                                  int type, double arg, double* local, double* out, int* status, void* stream);
+extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                             const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                             int32_t* status, void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores: n_vars must be in [1, 48]");
+    if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bn_scores: null pointer");
+    const bool dflt = score_arg != score_arg;               // NaN: the type's default
+    double arg = score_arg;
+    switch (score_type) {
+        case DVS_SCORE_LOGLIK:
+        case DVS_SCORE_K2:
+        case DVS_SCORE_BDJ:
+            if (!dflt) return fail(13, "dvs_bn_scores: loglik, k2 and bdj take no argument (score_arg must be NaN)");
+            arg = 0.0;                                      // loglik is the penalised likelihood at k = 0
+            break;
+        case DVS_SCORE_AIC:
+        case DVS_SCORE_BIC:
+            if (!dflt && !(score_arg >= 0.0 && isfinite(score_arg))) return fail(13, "dvs_bn_scores: k must be finite and >= 0");
+            if (dflt && score_type == DVS_SCORE_AIC) arg = 1.0;      // bic's default, log(S) / 2, is taken on the device
+            break;
+        case DVS_SCORE_BDE:
+        case DVS_SCORE_BDS:
+            if (!dflt && !(score_arg > 0.0 && isfinite(score_arg))) return fail(13, "dvs_bn_scores: iss must be finite and > 0");
+            if (dflt) arg = 1.0;
+            break;
+        default:
+            return fail(12, "dvs_bn_scores: score_type is not a dvs_score_type");
+    }
+    call_begin();
+    if (int e = dvs_bn_scores_impl(batch, n_vars, n_samples, data, card, parents, score_type, arg, scratch, out, status, stream))
+        return e;
+    return call_end("dvs_bn_scores");
+}
+
 extern "C" int dvs_bic_parent_masks_impl(int B, int n, int wide, const uint8_t* labels, const void* preds, uint64_t* parents,
                                          int* status, void* stream);
 extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,

@@ -8,6 +8,17 @@
 // not fit LDS, sorted as 64-bit keys), then the log-likelihood terms are summed in fp64 in a fixed order (integer
 // counts are exact, so the score does not depend on the atomics' order).
 // Integer/byte work bound by LDS atomics and L2 reads — no MFMA.
+//
+// The same counts give bnlearn's other decomposable discrete scores (dvs_bn_scores; definitions in include/dvs.h).  The
+// kernel is a template over the score FAMILY, which selects the per-cell term and what is added to the sum:
+//   family 0, penalised log-likelihood (loglik, aic, bic):  sum_{j,k} N_jk log(N_jk / N_j) - k (r - 1) q
+//   family 1, Bayesian Dirichlet (bde, bds, k2, bdj):
+//       sum_j [ lgamma(a_j) - lgamma(a_j + N_j) + sum_k ( lgamma(a_jk + N_jk) - lgamma(a_jk) ) ],  a_j = r a_jk
+// Only occupied cells (N_jk > 0) and observed configurations (N_j > 0) are visited — every other cell contributes exactly
+// zero to each of these scores — so the sort path serves both families.  bds needs the number of observed configurations
+// before the sum: one more pass over the table rows (dense) or over the sorted keys (sort), an integer count.  lgamma is
+// the device math library's, in fp64; its two arguments that do not depend on the cell, lgamma(a_j) and lgamma(a_jk), are
+// taken once per workgroup.  Family 1 is VALU-bound by lgamma (two per occupied cell and row) — no MFMA there either.
 #include "dvs_kernels.h"
 
 constexpr int BIC_MAX_BINS = 36864;          // q_v * r_v histogram bins that fit LDS (144 KB of u32 counters)
@@ -20,7 +31,18 @@ struct BicArgs {
     double* local;               // [B][n] scratch: local scores
     double* out;                 // [B]
     int* status;
+    int type;                    // dvs_score_type; family 1 reads it for the prior
+    double arg;                  // family 0: k (NaN: log(S) / 2, taken on the device as dvs_bic_scores always has); family 1: iss
 };
+
+__device__ __forceinline__ double bn_lgamma(double x) {
+#ifdef DVS_EMU
+    int sign;                    // the emulator runs workgroups on several host threads: libm's lgamma writes a global
+    return lgamma_r(x, &sign);
+#else
+    return lgamma(x);
+#endif
+}
 
 __device__ __forceinline__ int bic_level(const uint64_t* row, int var) { return (int)((row[var >> 4] >> (4 * (var & 15))) & 15ull); }
 
@@ -42,17 +64,42 @@ __device__ __forceinline__ int bic_lower_bound(const uint64_t* keys, int n, uint
     return lo;
 }
 
+// Family 1's prior, once per workgroup after the counting pass (all threads call it: it holds two barriers).
+//   bde: a_j = iss / q    bds: a_j = iss / (observed configurations)    k2: a_jk = 1    bdj: a_jk = 1/2;    a_j = r a_jk
+__device__ __forceinline__ void bn_prior(const BicArgs& a, int r, double q, const int* qobs, double* aj, double* ajk,
+                                         double* lg_aj, double* lg_ajk) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double x, y;
+        if (a.type == DVS_SCORE_K2 || a.type == DVS_SCORE_BDJ) {
+            y = a.type == DVS_SCORE_K2 ? 1.0 : 0.5;
+            x = y * (double)r;
+        } else {
+            x = a.arg / (a.type == DVS_SCORE_BDS ? (double)*qobs : q);
+            y = x / (double)r;
+        }
+        *aj = x;
+        *ajk = y;
+        *lg_aj = bn_lgamma(x);
+        *lg_ajk = bn_lgamma(y);
+    }
+    __syncthreads();
+}
+
 // Two counting strategies, chosen per (DAG, variable):
 //   histogram: q_v * r_v <= BIC_MAX_BINS cells fit LDS -> integer atomics into the dense table (the common case);
 //   sort:      larger parent sets (sachs: >= 9 ternary parents) are sparse — at most S cells are occupied — so the
 //              bit-packed 64-bit (configuration, state) keys of the S samples are bitonic-sorted in LDS and the counts
 //              are run lengths found by binary search.
+template <int FAMILY>
 __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
     DVS_DYN_LDS(smem);
     __shared__ double red[256];
     __shared__ int par_id[48], par_stride[48], par_shift[48];
     __shared__ int s_np, s_mode, s_rbits;
     __shared__ double s_q;
+    __shared__ int s_qobs;                                   // family 1, bds: parent configurations observed in the data
+    __shared__ double s_aj, s_ajk, s_lg_aj, s_lg_ajk;        // family 1: the prior's a_j, a_jk and their lgamma
     const int v = blockIdx.x % a.n, dag = blockIdx.x / a.n;
     const int r = a.card[v];
     if (threadIdx.x == 0) {
@@ -79,6 +126,7 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
         s_q = q;
         s_mode = mode;
         s_rbits = bic_bits(r);
+        if (FAMILY == 1) s_qobs = 0;
     }
     __syncthreads();
     const int np = s_np, mode = s_mode;
@@ -102,14 +150,38 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
             atomicAdd(&hist[key * r + bic_level(row, v)], 1u);
         }
         __syncthreads();
-        for (int j = threadIdx.x; j < q; j += blockDim.x) {
-            unsigned nj = 0;
-            for (int k = 0; k < r; ++k) nj += hist[j * r + k];
-            if (nj == 0) continue;
-            const double dn = (double)nj;
-            for (int k = 0; k < r; ++k) {
-                const unsigned c = hist[j * r + k];
-                if (c) acc += (double)c * log((double)c / dn);
+        if constexpr (FAMILY == 0) {
+            for (int j = threadIdx.x; j < q; j += blockDim.x) {
+                unsigned nj = 0;
+                for (int k = 0; k < r; ++k) nj += hist[j * r + k];
+                if (nj == 0) continue;
+                const double dn = (double)nj;
+                for (int k = 0; k < r; ++k) {
+                    const unsigned c = hist[j * r + k];
+                    if (c) acc += (double)c * log((double)c / dn);
+                }
+            }
+        } else {
+            if (a.type == DVS_SCORE_BDS) {
+                int seen = 0;
+                for (int j = threadIdx.x; j < q; j += blockDim.x) {
+                    unsigned nj = 0;
+                    for (int k = 0; k < r; ++k) nj += hist[j * r + k];
+                    seen += nj != 0;
+                }
+                if (seen) atomicAdd(&s_qobs, seen);
+            }
+            bn_prior(a, r, s_q, &s_qobs, &s_aj, &s_ajk, &s_lg_aj, &s_lg_ajk);
+            const double aj = s_aj, ajk = s_ajk, lg_aj = s_lg_aj, lg_ajk = s_lg_ajk;
+            for (int j = threadIdx.x; j < q; j += blockDim.x) {
+                unsigned nj = 0;
+                for (int k = 0; k < r; ++k) nj += hist[j * r + k];
+                if (nj == 0) continue;
+                acc += lg_aj - bn_lgamma(aj + (double)nj);
+                for (int k = 0; k < r; ++k) {
+                    const unsigned c = hist[j * r + k];
+                    if (c) acc += bn_lgamma(ajk + (double)c) - lg_ajk;
+                }
             }
         }
     } else {
@@ -141,13 +213,34 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
                 }
                 __syncthreads();
             }
-        for (int i = threadIdx.x; i < S; i += blockDim.x) {
-            const uint64_t key = keys[i];
-            if (i > 0 && keys[i - 1] == key) continue;                 // not the first sample of its (j, k) cell
-            const int c = bic_lower_bound(keys, S, key + 1) - i;
-            const uint64_t j0 = (key >> rbits) << rbits;
-            const int nj = bic_lower_bound(keys, S, j0 + (1ull << rbits)) - bic_lower_bound(keys, S, j0);
-            acc += (double)c * log((double)c / (double)nj);
+        if constexpr (FAMILY == 0) {
+            for (int i = threadIdx.x; i < S; i += blockDim.x) {
+                const uint64_t key = keys[i];
+                if (i > 0 && keys[i - 1] == key) continue;                 // not the first sample of its (j, k) cell
+                const int c = bic_lower_bound(keys, S, key + 1) - i;
+                const uint64_t j0 = (key >> rbits) << rbits;
+                const int nj = bic_lower_bound(keys, S, j0 + (1ull << rbits)) - bic_lower_bound(keys, S, j0);
+                acc += (double)c * log((double)c / (double)nj);
+            }
+        } else {
+            if (a.type == DVS_SCORE_BDS) {
+                int seen = 0;
+                for (int i = threadIdx.x; i < S; i += blockDim.x)
+                    seen += i == 0 || (keys[i - 1] >> rbits) != (keys[i] >> rbits);   // first sample of its configuration
+                if (seen) atomicAdd(&s_qobs, seen);
+            }
+            bn_prior(a, r, s_q, &s_qobs, &s_aj, &s_ajk, &s_lg_aj, &s_lg_ajk);
+            const double aj = s_aj, ajk = s_ajk, lg_aj = s_lg_aj, lg_ajk = s_lg_ajk;
+            for (int i = threadIdx.x; i < S; i += blockDim.x) {
+                const uint64_t key = keys[i];
+                if (i > 0 && keys[i - 1] == key) continue;                 // not the first sample of its (j, k) cell
+                const int c = bic_lower_bound(keys, S, key + 1) - i;
+                acc += bn_lgamma(ajk + (double)c) - lg_ajk;
+                if (i > 0 && (keys[i - 1] >> rbits) == (key >> rbits)) continue;   // not the first cell of its configuration
+                const uint64_t j0 = (key >> rbits) << rbits;
+                const int nj = bic_lower_bound(keys, S, j0 + (1ull << rbits)) - i;
+                acc += lg_aj - bn_lgamma(aj + (double)nj);
+            }
         }
     }
     red[threadIdx.x] = acc;
@@ -156,8 +249,14 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0)
-        a.local[(size_t)dag * a.n + v] = red[0] - 0.5 * log((double)a.S) * (double)(r - 1) * s_q;
+    if (threadIdx.x == 0) {
+        if constexpr (FAMILY == 0) {
+            const double k = a.arg != a.arg ? 0.5 * log((double)a.S) : a.arg;
+            a.local[(size_t)dag * a.n + v] = red[0] - k * (double)(r - 1) * s_q;
+        } else {
+            a.local[(size_t)dag * a.n + v] = red[0];
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
@@ -170,14 +269,22 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
 
 void dvs_launch_bic(const BicArgs& a, dvs_stream_t st) {
     const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    DVS_SET_LDS(k_bic_local, lds);
-    DVS_LAUNCH(k_bic_local, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
+    if (a.type <= DVS_SCORE_BIC) {
+        DVS_SET_LDS(k_bic_local<0>, lds);
+        DVS_LAUNCH_AS("k_bic_local", k_bic_local<0>, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
+    } else {
+        DVS_SET_LDS(k_bic_local<1>, lds);
+        DVS_LAUNCH_AS("k_bn_local_dirichlet", k_bic_local<1>, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
+    }
     DVS_LAUNCH(k_bic_sum, dim3((a.B + 255) / 256), dim3(256), 0, st, a);
 }
 
-extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
-                                   double* local, double* out, int* status, void* stream) {
+// type: dvs_score_type; arg: the resolved k (loglik 0, aic, bic; NaN = log(S) / 2 taken on the device) or iss (bde, bds)
+extern "C" int dvs_bn_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
+                                  int type, double arg, double* local, double* out, int* status, void* stream) {
     BicArgs a;
+    a.type = type;
+    a.arg = arg;
     a.B = B;
     a.n = n;
     a.S = S;
@@ -190,6 +297,10 @@ extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, co
     a.status = status;
     dvs_launch_bic(a, (dvs_stream_t)stream);
     return 0;
+}
+extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
+                                   double* local, double* out, int* status, void* stream) {
+    return dvs_bn_scores_impl(B, n, S, data, card, parents, DVS_SCORE_BIC, __builtin_nan(""), local, out, status, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

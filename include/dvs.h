@@ -239,6 +239,38 @@ int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_t* sorted_h
 int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
                    const uint64_t* parents, double* scratch, double* out, int32_t* status, void* stream);
 
+/* bnlearn's other decomposable discrete scores from the same counts (the reference passes metric_name straight to
+ * bnlearn::score(net, data, type = metric_name), bnlearn_scripts/bnlearn_score.R; mirror: BNLearnWrapper(metric_name=...)).
+ * Per variable, with N_jk the count of parent configuration j and level k, N_j = sum_k N_jk, r the variable's level count,
+ * q the product of its parents' level counts and S = n_samples, the local score is
+ *   DVS_SCORE_LOGLIK  sum N_jk log(N_jk / N_j)
+ *   DVS_SCORE_AIC     loglik - k (r - 1) q                                  score_arg = k >= 0, default 1
+ *   DVS_SCORE_BIC     loglik - k (r - 1) q                                  score_arg = k >= 0, default log(S) / 2
+ *   DVS_SCORE_BDE     sum_j [ lgamma(a_j) - lgamma(a_j + N_j) + sum_k ( lgamma(a_jk + N_jk) - lgamma(a_jk) ) ]  (BDeu)
+ *                     with a_jk = iss / (r q), a_j = iss / q                score_arg = iss > 0, default 1
+ *   DVS_SCORE_BDS     as BDE with q replaced by the number of parent configurations observed in the data
+ *   DVS_SCORE_K2      as BDE with a_jk = 1, a_j = r                         no argument
+ *   DVS_SCORE_BDJ     as BDE with a_jk = 1/2, a_j = r / 2                   no argument
+ * and the score of a structure is the sum over its variables (uniform graph prior: nothing added).  Empty cells and
+ * unobserved configurations contribute exactly zero.  score_arg = NaN asks for the type's default and is the only value
+ * the types without an argument take.  Everything else — buffers, limits, status bit 4, scratch = the local scores
+ * [B][n_vars] — is dvs_bic_scores'; DVS_SCORE_BIC with NaN gives the bytes dvs_bic_scores gives.  Checked before anything
+ * is enqueued: code 12 for a score_type that is not in the enum, 13 for a score_arg the type does not take (iss not
+ * finite or <= 0, k negative or not finite, any number for a type without an argument).  fp64 throughout, fixed summation
+ * order: two calls give equal bytes.  (Added in ABI 202 as a pure addition: the version number stays.) */
+typedef enum dvs_score_type {
+    DVS_SCORE_LOGLIK = 0,
+    DVS_SCORE_AIC = 1,
+    DVS_SCORE_BIC = 2,
+    DVS_SCORE_BDE = 3,
+    DVS_SCORE_BDS = 4,
+    DVS_SCORE_K2 = 5,
+    DVS_SCORE_BDJ = 6
+} dvs_score_type;
+int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                  const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                  int32_t* status, void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
