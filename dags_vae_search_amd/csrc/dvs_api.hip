@@ -1,5 +1,6 @@
 // C ABI (include/dvs.h): parameter/workspace layout and the launch sequences of the PACE-VAE step.
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -8,6 +9,7 @@
 #include "dvs_backward.h"
 #include "dvs_wide.h"
 #include "dvs_wimg.h"
+#include "dvs_decode.h"
 
 static thread_local char g_err[256] = "";
 
@@ -15,6 +17,7 @@ static thread_local char g_err[256] = "";
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 namespace {
 struct ProfRec {
@@ -112,13 +115,19 @@ static int call_end(const char* fn) {
     t_hip_err = 0;
     return 20;
 }
-#ifndef DVS_EMU
 #define DVS_HIP_CALL(expr)                                                             \
     do {                                                                               \
         const hipError_t dvs_ce_ = (expr);                                             \
         if (dvs_ce_ != hipSuccess) dvs_note_hip_error(#expr, (int)dvs_ce_, hipGetErrorString(dvs_ce_)); \
     } while (0)
+// device-to-device copy on the call's stream (the emulator header brings its own shim)
+static void copy_out(void* dst, const void* src, size_t bytes, dvs_stream_t st) {
+#ifdef DVS_EMU
+    DVS_HIP_CALL(hipMemcpyAsyncD2D(dst, src, bytes, st));
+#else
+    DVS_HIP_CALL(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
 #endif
+}
 
 extern "C" int dvs_version(void) { return DVS_VERSION; }
 extern "C" const char* dvs_last_error(void) { return g_err; }
@@ -140,12 +149,16 @@ struct LayoutBuilder {
     int64_t off = 0;
     dvs_param_entry* table;
     int cap, count = 0;
-    int64_t add(const char* name, int rows, int cols) {
+    // the name is formatted only when a table asks for it: the entry points want the offsets alone, once per call
+    int64_t add(int rows, int cols, const char* fmt, ...) {
         const int64_t o = off;
         if (table && count < cap) {
             dvs_param_entry& e = table[count];
             memset(&e, 0, sizeof(e));
-            snprintf(e.name, sizeof(e.name), "%s", name);
+            va_list ap;
+            va_start(ap, fmt);
+            vsnprintf(e.name, sizeof(e.name), fmt, ap);
+            va_end(ap);
             e.offset = o;
             e.rows = rows;
             e.cols = cols;
@@ -163,61 +176,54 @@ DvsLayout dvs_make_layout(int N, int C, dvs_param_entry* table, int cap, int* co
     b.table = table;
     b.cap = cap;
     DvsLayout l;
-    char nm[96];
-    auto attn = [&](const char* prefix, DvsAttnP& p) {
-        snprintf(nm, sizeof(nm), "%s.in_proj_weight", prefix);  p.in_w = b.add(nm, 192, 64);
-        snprintf(nm, sizeof(nm), "%s.in_proj_bias", prefix);    p.in_b = b.add(nm, 192, 0);
-        snprintf(nm, sizeof(nm), "%s.out_proj.weight", prefix); p.out_w = b.add(nm, 64, 64);
-        snprintf(nm, sizeof(nm), "%s.out_proj.bias", prefix);   p.out_b = b.add(nm, 64, 0);
+    auto attn = [&](const char* stack, int i, const char* which, DvsAttnP& p) {
+        p.in_w = b.add(192, 64, "%s.layers.%d.%s.in_proj_weight", stack, i, which);
+        p.in_b = b.add(192, 0, "%s.layers.%d.%s.in_proj_bias", stack, i, which);
+        p.out_w = b.add(64, 64, "%s.layers.%d.%s.out_proj.weight", stack, i, which);
+        p.out_b = b.add(64, 0, "%s.layers.%d.%s.out_proj.bias", stack, i, which);
     };
-    auto ffn = [&](const char* prefix, DvsFfnP& p) {
-        snprintf(nm, sizeof(nm), "%s.linear1.weight", prefix); p.l1_w = b.add(nm, 64, 64);
-        snprintf(nm, sizeof(nm), "%s.linear1.bias", prefix);   p.l1_b = b.add(nm, 64, 0);
-        snprintf(nm, sizeof(nm), "%s.linear2.weight", prefix); p.l2_w = b.add(nm, 64, 64);
-        snprintf(nm, sizeof(nm), "%s.linear2.bias", prefix);   p.l2_b = b.add(nm, 64, 0);
+    auto ffn = [&](const char* stack, int i, DvsFfnP& p) {
+        p.l1_w = b.add(64, 64, "%s.layers.%d.linear1.weight", stack, i);
+        p.l1_b = b.add(64, 0, "%s.layers.%d.linear1.bias", stack, i);
+        p.l2_w = b.add(64, 64, "%s.layers.%d.linear2.weight", stack, i);
+        p.l2_b = b.add(64, 0, "%s.layers.%d.linear2.bias", stack, i);
     };
-    auto norm = [&](const char* prefix, int k, DvsNormP& p) {
-        snprintf(nm, sizeof(nm), "%s.norm%d.weight", prefix, k); p.w = b.add(nm, 64, 0);
-        snprintf(nm, sizeof(nm), "%s.norm%d.bias", prefix, k);   p.b = b.add(nm, 64, 0);
+    auto norm = [&](const char* stack, int i, int k, DvsNormP& p) {
+        p.w = b.add(64, 0, "%s.layers.%d.norm%d.weight", stack, i, k);
+        p.b = b.add(64, 0, "%s.layers.%d.norm%d.bias", stack, i, k);
     };
-    l.W1 = b.add("vertex_position_embed.W1", 2 * N, 64);
-    l.W2 = b.add("vertex_position_embed.W2", 64, 32);
-    l.lab_w = b.add("vertex_label_embed.0.weight", 32, C);
-    l.lab_b = b.add("vertex_label_embed.0.bias", 32, 0);
-    char pre[64], pre2[80];
+    l.W1 = b.add(2 * N, 64, "vertex_position_embed.W1");
+    l.W2 = b.add(64, 32, "vertex_position_embed.W2");
+    l.lab_w = b.add(32, C, "vertex_label_embed.0.weight");
+    l.lab_b = b.add(32, 0, "vertex_label_embed.0.bias");
     for (int i = 0; i < DVS_LAYERS; ++i) {
-        snprintf(pre, sizeof(pre), "encoder.layers.%d", i);
-        snprintf(pre2, sizeof(pre2), "%s.self_attn", pre);
-        attn(pre2, l.enc[i].sa);
-        ffn(pre, l.enc[i].ff);
-        norm(pre, 1, l.enc[i].n1);
-        norm(pre, 2, l.enc[i].n2);
+        attn("encoder", i, "self_attn", l.enc[i].sa);
+        ffn("encoder", i, l.enc[i].ff);
+        norm("encoder", i, 1, l.enc[i].n1);
+        norm("encoder", i, 2, l.enc[i].n2);
     }
-    l.fc1_w = b.add("fc1.weight", 32, N * 64);
-    l.fc1_b = b.add("fc1.bias", 32, 0);
-    l.fc2_w = b.add("fc2.weight", 32, N * 64);
-    l.fc2_b = b.add("fc2.bias", 32, 0);
+    l.fc1_w = b.add(32, N * 64, "fc1.weight");
+    l.fc1_b = b.add(32, 0, "fc1.bias");
+    l.fc2_w = b.add(32, N * 64, "fc2.weight");
+    l.fc2_b = b.add(32, 0, "fc2.bias");
     for (int i = 0; i < DVS_LAYERS; ++i) {
-        snprintf(pre, sizeof(pre), "decoder.layers.%d", i);
-        snprintf(pre2, sizeof(pre2), "%s.self_attn", pre);
-        attn(pre2, l.dec[i].sa);
-        snprintf(pre2, sizeof(pre2), "%s.multihead_attn", pre);
-        attn(pre2, l.dec[i].ca);
-        ffn(pre, l.dec[i].ff);
-        norm(pre, 1, l.dec[i].n1);
-        norm(pre, 2, l.dec[i].n2);
-        norm(pre, 3, l.dec[i].n3);
+        attn("decoder", i, "self_attn", l.dec[i].sa);
+        attn("decoder", i, "multihead_attn", l.dec[i].ca);
+        ffn("decoder", i, l.dec[i].ff);
+        norm("decoder", i, 1, l.dec[i].n1);
+        norm("decoder", i, 2, l.dec[i].n2);
+        norm("decoder", i, 3, l.dec[i].n3);
     }
-    l.node0_w = b.add("add_node.0.weight", 32, 64);
-    l.node0_b = b.add("add_node.0.bias", 32, 0);
-    l.node2_w = b.add("add_node.2.weight", C, 32);
-    l.node2_b = b.add("add_node.2.bias", C, 0);
-    l.edge0_w = b.add("add_edge.0.weight", 64, 128);
-    l.edge0_b = b.add("add_edge.0.bias", 64, 0);
-    l.edge2_w = b.add("add_edge.2.weight", 1, 64);
-    l.edge2_b = b.add("add_edge.2.bias", 1, 0);
-    l.fc3_w = b.add("fc3.weight", N * 64, 32);
-    l.fc3_b = b.add("fc3.bias", N * 64, 0);
+    l.node0_w = b.add(32, 64, "add_node.0.weight");
+    l.node0_b = b.add(32, 0, "add_node.0.bias");
+    l.node2_w = b.add(C, 32, "add_node.2.weight");
+    l.node2_b = b.add(C, 0, "add_node.2.bias");
+    l.edge0_w = b.add(64, 128, "add_edge.0.weight");
+    l.edge0_b = b.add(64, 0, "add_edge.0.bias");
+    l.edge2_w = b.add(1, 64, "add_edge.2.weight");
+    l.edge2_b = b.add(1, 0, "add_edge.2.bias");
+    l.fc3_w = b.add(N * 64, 32, "fc3.weight");
+    l.fc3_b = b.add(N * 64, 0, "fc3.bias");
     l.total = b.off;
     if (count) *count = b.count;
     return l;
@@ -273,43 +279,11 @@ static int check_shape(const dvs_shape* s) {
     return 0;
 }
 
-static bool is_wide(const dvs_shape* s);
-static int64_t param_floats(const dvs_shape* s) { return dvs_make_layout(s->n_tokens, s->n_classes, nullptr, 0, nullptr).total; }
-int dvs_num_slabs();
-
-// Caller-owned buffers against what the shape needs (include/dvs.h: code 14); nothing has been enqueued yet.
-// Pass a negative / zero "have" for a buffer the entry point does not take.
-static int check_buffers(const dvs_shape* s, const char* fn, bool has_records, size_t records_bytes, bool has_params,
-                         int64_t n_params, bool has_ws, size_t workspace_bytes) {
-    char msg[240];
-    if (has_records) {
-        const size_t need = (size_t)s->batch * ((s->n_tokens > DVS_MAXTOK || s->n_classes > 16) ? sizeof(DvsRecordW) : sizeof(DvsRecord));
-        if (records_bytes < need) {
-            snprintf(msg, sizeof(msg), "%s: records_bytes %zu < batch * dvs_record_bytes = %zu", fn, records_bytes, need);
-            return fail(14, msg);
-        }
-    }
-    if (has_params) {
-        const int64_t need = param_floats(s);
-        if (n_params < need) {
-            snprintf(msg, sizeof(msg), "%s: n_params %lld < dvs_param_count = %lld", fn, (long long)n_params, (long long)need);
-            return fail(14, msg);
-        }
-    }
-    if (has_ws) {
-        const size_t need = dvs_make_workspace(s->batch, (s->n_tokens + 15) / 16, param_floats(s), dvs_num_slabs(), is_wide(s)).total_floats * sizeof(float);
-        if (workspace_bytes < need) {
-            snprintf(msg, sizeof(msg), "%s: workspace_bytes %zu < dvs_workspace_bytes = %zu", fn, workspace_bytes, need);
-            return fail(14, msg);
-        }
-    }
-    return 0;
-}
-
 // One-tile path: a wave owns a whole DAG (N, C <= 16).  Wide path: NT tiles of 16 tokens per DAG, cross-token kernels
 // of dvs_wide.h (also taken when only the class count exceeds one tile).
 static bool is_wide(const dvs_shape* s) { return s->n_tokens > DVS_MAXTOK || s->n_classes > 16; }
 static int tiles_of(const dvs_shape* s) { return (s->n_tokens + 15) / 16; }
+static size_t record_size(bool wide) { return wide ? sizeof(DvsRecordW) : sizeof(DvsRecord); }
 
 static DvsDims make_dims(const dvs_shape* s) {
     DvsDims d;
@@ -330,16 +304,15 @@ static DvsDims make_dims(const dvs_shape* s) {
     return d;
 }
 
-static int grid_for(int units, int per_wg = 8) {   // persistent forward kernels: `per_wg` units (tiles / DAGs) per pass
-    const int cus = dvs_device_cus();
-    const int want = (units + per_wg - 1) / per_wg;
-    const int cap = cus > 0 ? cus : 256;
-    return want < cap ? want : cap;
-}
-
-int dvs_num_slabs() {   // backward kernels run on at most this many workgroups (one gradient slab each); sizes the workspace
+// Backward kernels run on at most this many workgroups (one gradient slab each): sizes the workspace and caps every
+// persistent grid.
+static int num_slabs() {
     const int cus = dvs_device_cus();
     return cus > 0 ? cus : 256;
+}
+static int grid_for(int units, int per_wg, int cap) {   // persistent kernels: `per_wg` units (tiles / DAGs) per pass
+    const int want = (units + per_wg - 1) / per_wg;
+    return want < cap ? want : cap;
 }
 
 // Waves per workgroup of the one-tile stack kernels (k_fwd_stack / k_bwd_stack and their per-phase twins).  8: two waves per
@@ -347,20 +320,110 @@ int dvs_num_slabs() {   // backward kernels run on at most this many workgroups 
 // 4 x #CU DAGs (1 024 on an MI355X: a 4 096 batch cut over 4 or 8 GPUs) half of the CUs or more would idle while the others
 // run two waves per SIMD, so the NARROW mapping takes over: 4 waves (one cooperative weight-gradient group), 4 DAGs per
 // workgroup, twice the workgroups, one wave per SIMD.  DVS_WAVES_PER_WG=4|8 forces either (A/B runs, tests).
-static int waves_per_wg(const DvsDims& d, bool wide) {
+static int waves_per_wg(const DvsDims& d, bool wide, int nslab) {
     const char* env = getenv("DVS_WAVES_PER_WG");         // read per call: the tests switch it between calls
     const int force = env ? atoi(env) : 0;
     if (wide) return 8;
     if (force == 4 || force == 8) return force;
-    return d.B <= 4 * dvs_num_slabs() ? 4 : 8;
+    return d.B <= 4 * nslab ? 4 : 8;
 }
 // Workgroups of the backward kernels = gradient slabs that are written (and reduced) this step: all of them from 4 x #CU
 // DAGs up; fewer for smaller batches, so that k_reduce_slabs does not stream slabs of zeros.
-static int active_slabs(const DvsDims& d, bool wide) {
-    const int all = dvs_num_slabs();
-    if (wide) return all;
+static int active_slabs(const DvsDims& d, bool wide, int nslab) {
+    if (wide) return nslab;
     const int want = (d.B + 3) / 4;          // the narrowest backward kernels own 4 DAGs per workgroup and pass
-    return want < all ? want : all;
+    return want < nslab ? want : nslab;
+}
+
+// A/B switches, read once per process.  DVS_SPLIT_STACK=1 (per-phase profiling): every sublayer is a launch of its own.
+// DVS_LATENT_KERNELS=1: the latent block keeps its own launches.
+static bool env_on(const char* name) {
+    const char* v = getenv(name);
+    return v && atoi(v) != 0;
+}
+static bool split_stack() {
+    static const bool on = env_on("DVS_SPLIT_STACK");
+    return on;
+}
+static bool latent_kernels_off() {
+    static const bool on = env_on("DVS_LATENT_KERNELS");
+    return on;
+}
+// The latent block rides the encoder chain (forward: its last phase, backward: ahead of its first), in the same launch.  Only
+// on the 8-wave mapping: a narrow workgroup owns 4 DAGs, a quarter of an MFMA column group.
+static bool latent_in_chain(bool chain, int nw) { return chain && !latent_kernels_off() && nw == 8; }
+
+// launch grids of the forward kernels
+struct FwdGrids {
+    int chain;      // k_fwd_stack / k_attn_fwd / narrow k_ffn_fwd, k_embed_fwd, k_loss_fwd: nw tiles per workgroup and pass
+    int tiles16;    // 16-wave tile-parallel kernels (k_ffn_fwd, one-tile k_embed_fwd)
+    int tiles8;     // 8-wave tile-parallel kernels (one-tile k_attn_fwd / k_embed_fwd / k_loss_fwd)
+    int tiles4;     // 4-wave tile-parallel kernels (k_embed_fwd_w)
+    int dags;       // workgroup-per-DAG kernels of the wide path
+    int dags2;      // ... those that fit two workgroups per CU (k_loss_fwd_w)
+    int dec4;       // k_decode_step: 4 DAGs per workgroup and pass
+};
+
+// ---- call context: what every launch of the train step, of dvs_encode and of dvs_decode is filled from ---------------------
+struct Step {
+    DvsDims d;
+    DvsLayout L;
+    DvsWorkspace W;
+    bool wide;
+    const float* P;             // flat parameters
+    float* ws;                  // workspace
+    const DvsRecord* rec;
+    dvs_stream_t st;
+    int nw;                     // waves per workgroup of the one-tile stack kernels (waves_per_wg)
+    FwdGrids g;
+    int slabs;                  // workgroups of every backward kernel (active_slabs)
+};
+// After check_shape(); layout and workspace are computed here, once per call.
+static Step make_step(const dvs_shape* s, const void* records, const float* params, void* workspace, void* stream) {
+    Step c;
+    c.d = make_dims(s);
+    c.L = dvs_make_layout(c.d.N, c.d.C, nullptr, 0, nullptr);
+    c.wide = is_wide(s);
+    const int nslab = num_slabs();
+    c.W = dvs_make_workspace(c.d.B, c.d.NT, c.L.total, nslab, c.wide);
+    c.P = params;
+    c.ws = (float*)workspace;
+    c.rec = (const DvsRecord*)records;
+    c.st = (dvs_stream_t)stream;
+    c.nw = waves_per_wg(c.d, c.wide, nslab);
+    const int tiles = c.d.B * c.d.NT;
+    c.g.chain = grid_for(tiles, c.nw, nslab);
+    c.g.tiles16 = grid_for(tiles, 16, nslab);
+    c.g.tiles8 = grid_for(tiles, 8, nslab);
+    c.g.tiles4 = grid_for(tiles, 4, nslab);
+    c.g.dags = grid_for(c.d.B, 1, nslab);
+    c.g.dags2 = c.d.B < 2 * c.g.dags ? c.d.B : 2 * c.g.dags;
+    c.g.dec4 = grid_for(c.d.B, 4, nslab);
+    c.slabs = active_slabs(c.d, c.wide, nslab);
+    return c;
+}
+
+// Caller-owned buffers against what the shape needs (include/dvs.h: code 14); nothing has been enqueued yet.
+static int check_records(const char* fn, size_t records_bytes, int batch, bool wide) {
+    const size_t need = (size_t)batch * record_size(wide);
+    if (records_bytes >= need) return 0;
+    char msg[240];
+    snprintf(msg, sizeof(msg), "%s: records_bytes %zu < batch * dvs_record_bytes = %zu", fn, records_bytes, need);
+    return fail(14, msg);
+}
+static int check_buffers(const Step& c, const char* fn, size_t records_bytes, int64_t n_params, size_t workspace_bytes) {
+    if (int e = check_records(fn, records_bytes, c.d.B, c.wide)) return e;
+    char msg[240];
+    if (n_params < c.L.total) {
+        snprintf(msg, sizeof(msg), "%s: n_params %lld < dvs_param_count = %lld", fn, (long long)n_params, (long long)c.L.total);
+        return fail(14, msg);
+    }
+    const size_t need = c.W.total_floats * sizeof(float);
+    if (workspace_bytes < need) {
+        snprintf(msg, sizeof(msg), "%s: workspace_bytes %zu < dvs_workspace_bytes = %zu", fn, workspace_bytes, need);
+        return fail(14, msg);
+    }
+    return 0;
 }
 
 extern "C" int64_t dvs_param_count(const dvs_shape* s) {
@@ -377,13 +440,12 @@ extern "C" int dvs_param_table(const dvs_shape* s, dvs_param_entry* out, int cap
 
 extern "C" size_t dvs_workspace_bytes(const dvs_shape* s) {
     if (check_shape(s)) return 0;
-    const int64_t P = dvs_make_layout(s->n_tokens, s->n_classes, nullptr, 0, nullptr).total;
-    return dvs_make_workspace(s->batch, tiles_of(s), P, dvs_num_slabs(), is_wide(s)).total_floats * sizeof(float);
+    return make_step(s, nullptr, nullptr, nullptr, nullptr).W.total_floats * sizeof(float);
 }
 
 extern "C" size_t dvs_record_bytes(const dvs_shape* s) {
     if (check_shape(s)) return 0;
-    return is_wide(s) ? sizeof(DvsRecordW) : sizeof(DvsRecord);
+    return record_size(is_wide(s));
 }
 
 extern "C" int dvs_pack_features(const dvs_shape* s, const float* label_onehot, const float* pos_onehot,
@@ -392,7 +454,7 @@ extern "C" int dvs_pack_features(const dvs_shape* s, const float* label_onehot, 
     if (int e = check_shape(s)) return e;
     if (!label_onehot || !pos_onehot || !adjacency || !target_masks || !records || !status)
         return fail(10, "dvs_pack_features: null pointer");
-    if (int e = check_buffers(s, "dvs_pack_features", true, records_bytes, false, 0, false, 0)) return e;
+    if (int e = check_records("dvs_pack_features", records_bytes, s->batch, is_wide(s))) return e;
     call_begin();
     PackArgs a;
     a.B = s->batch;
@@ -413,7 +475,7 @@ extern "C" int dvs_build_records(const dvs_shape* s, const uint8_t* labels, cons
                                  size_t records_bytes, int32_t* status, void* stream) {
     if (int e = check_shape(s)) return e;
     if (!labels || !preds || !records || !status) return fail(10, "dvs_build_records: null pointer");
-    if (int e = check_buffers(s, "dvs_build_records", true, records_bytes, false, 0, false, 0)) return e;
+    if (int e = check_records("dvs_build_records", records_bytes, s->batch, is_wide(s))) return e;
     call_begin();
     if (is_wide(s)) {
         BuildWArgs a;
@@ -455,8 +517,131 @@ static inline int blk_dec_cross(int layer) { return 4 + 2 * layer; }
 static inline int blk_enc_ffn(int layer) { return layer; }
 static inline int blk_dec_ffn(int layer) { return 3 + layer; }
 
-static void prepare_images(const DvsLayout& L, int N, int C, bool wide, const float* params, float* ws, const DvsWorkspace& W,
-                           dvs_stream_t st) {
+static inline const void* wimg_attn(const Step& c, int block) { return (const dvs_bf16*)(c.ws + c.W.wimg) + img_attn(block); }
+static inline const void* wimg_ffn(const Step& c, int block) { return (const dvs_bf16*)(c.ws + c.W.wimg) + img_ffn(block); }
+
+// ---- argument blocks: one builder each, from the call context plus what varies -------------------------------------------
+// LayerNorm of the sublayer (or embedding) that wrote `slot`, applied in its consumer's prologue; no norm: identity
+static DvsLN ln_of(const Step& c, int slot, const DvsNormP* n) {
+    if (!n) return DvsLN{nullptr, nullptr, nullptr};
+    return DvsLN{c.ws + c.W.stats[slot], c.P + n->w, c.P + n->b};
+}
+
+// forward: the caller sets `out` (and out2 / site2); backward: gout, slab and the gradient offsets
+static EmbedArgs embed_args(const Step& c, int site) {
+    EmbedArgs e;
+    memset(&e, 0, sizeof(e));
+    e.dims = c.d;
+    e.rec = c.rec;
+    e.W1 = c.P + c.L.W1;
+    e.W2 = c.P + c.L.W2;
+    e.lab_w = c.P + c.L.lab_w;
+    e.lab_b = c.P + c.L.lab_b;
+    e.embimg = (const float*)((const dvs_bf16*)(c.ws + c.W.wimg) + DVS_WIMG_EMB);
+    e.site = site;
+    return e;
+}
+
+// in / out: activation slots; norm: LayerNorm of the producer of `in` (null: an embedding); kv: null = self-attention;
+// dropout sites site0 (probabilities), site0 + 1 (output)
+static AttnArgs attn_args(const Step& c, const DvsAttnP& p, int block, int in, const DvsNormP* norm, const float* kv, int out,
+                          int site0) {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dims = c.d;
+    a.rec = c.rec;
+    a.xin = c.ws + c.W.act[in];
+    a.ln = ln_of(c, in, norm);
+    a.kv = kv;
+    a.in_w = c.P + p.in_w;
+    a.in_b = c.P + p.in_b;
+    a.out_w = c.P + p.out_w;
+    a.out_b = c.P + p.out_b;
+    a.wimg = wimg_attn(c, block);
+    a.qkv = c.wide ? c.ws + c.W.qkv[block] : nullptr;      // parked for the backward
+    a.out_pre = c.ws + c.W.act[out];
+    a.out_stats = c.ws + c.W.stats[out];
+    a.site_prob = site0;
+    a.site_post = site0 + 1;
+    return a;
+}
+
+// dropout sites site0 (hidden), site0 + 1 (output)
+static FfnArgs ffn_args(const Step& c, const DvsFfnP& p, int block, int in, const DvsNormP& norm, int out, int site0) {
+    FfnArgs f;
+    memset(&f, 0, sizeof(f));
+    f.dims = c.d;
+    f.xin = c.ws + c.W.act[in];
+    f.ln = ln_of(c, in, &norm);
+    f.l1_w = c.P + p.l1_w;
+    f.l1_b = c.P + p.l1_b;
+    f.l2_w = c.P + p.l2_w;
+    f.l2_b = c.P + p.l2_b;
+    f.wimg = wimg_ffn(c, block);
+    f.out_pre = c.ws + c.W.act[out];
+    f.out_stats = c.ws + c.W.stats[out];
+    f.site_hidden = site0;
+    f.site_post = site0 + 1;
+    return f;
+}
+
+static LatentArgs latent_args(const Step& c, const float* eps, bool with_mem) {
+    LatentArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dims = c.d;
+    a.xenc = c.ws + c.W.enc_out;
+    a.fc1_w = c.P + c.L.fc1_w;
+    a.fc1_b = c.P + c.L.fc1_b;
+    a.fc2_w = c.P + c.L.fc2_w;
+    a.fc2_b = c.P + c.L.fc2_b;
+    a.fc3_w = c.P + c.L.fc3_w;
+    a.fc3_b = c.P + c.L.fc3_b;
+    a.limg = c.ws + c.W.limg;
+    a.eps_in = eps;
+    a.mu = c.ws + c.W.mu;
+    a.logvar = c.ws + c.W.logvar;
+    a.z = c.ws + c.W.z;
+    a.epsv = c.ws + c.W.epsv;
+    a.mem = with_mem ? c.ws + c.W.mem : nullptr;
+    a.dag_loss = c.ws + c.W.dag_loss;
+    return a;
+}
+
+// add_node / add_edge parameters as LossArgs, DecodeArgs and the head block of the weight images (DvsLossHeadArgs) name them
+template <class A>
+static void head_params(const Step& c, A& a) {
+    a.node0_w = c.P + c.L.node0_w;
+    a.node0_b = c.P + c.L.node0_b;
+    a.node2_w = c.P + c.L.node2_w;
+    a.node2_b = c.P + c.L.node2_b;
+    a.edge0_b = c.P + c.L.edge0_b;
+    a.edge2_w = c.P + c.L.edge2_w;
+    a.edge2_b = c.P + c.L.edge2_b;
+}
+// ... and the head's input for the kernels that run it (LossArgs, DecodeArgs): the last decoder sublayer under its LayerNorm
+template <class A>
+static void head_input(const Step& c, A& a) {
+    const int last = slot_dec(DVS_LAYERS - 1, 2);
+    a.xin = c.ws + c.W.act[last];
+    a.ln = ln_of(c, last, &c.L.dec[DVS_LAYERS - 1].n3);
+    a.edge0_w = c.P + c.L.edge0_w;
+    head_params(c, a);
+}
+
+static LossArgs loss_args(const Step& c) {
+    LossArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dims = c.d;
+    a.rec = c.rec;
+    head_input(c, a);
+    a.wimg = (const dvs_bf16*)(c.ws + c.W.wimg) + DVS_WIMG_LOSS;
+    a.dag_loss = c.ws + c.W.dag_loss;
+    return a;
+}
+
+static void prepare_images(const Step& c) {
+    const DvsLayout& L = c.L;
+    const bool wide = c.wide;
     DvsImgJobs J;
     J.count = 0;
     auto add = [&](int64_t src, size_t dst, int rows, int flags) {
@@ -497,90 +682,61 @@ static void prepare_images(const DvsLayout& L, int N, int C, bool wide, const fl
         add(L.edge0_w, DVS_WIMG_LOSS + DvsLossImg::WaT, 64, 8 | 1);
         add(L.edge0_w + 64, DVS_WIMG_LOSS + DvsLossImg::WbT, 64, 8 | 1);
     }
+    dvs_bf16* wimg = (dvs_bf16*)(c.ws + c.W.wimg);
     DvsLatImgArgs lat;
-    lat.fc1_w = params + L.fc1_w;
-    lat.fc2_w = params + L.fc2_w;
-    lat.fc3_w = params + L.fc3_w;
-    lat.fc3_b = params + L.fc3_b;
-    lat.img = ws + W.limg;
-    lat.N = N;
-    lat.NT = (N + 15) / 16;
+    lat.fc1_w = c.P + L.fc1_w;
+    lat.fc2_w = c.P + L.fc2_w;
+    lat.fc3_w = c.P + L.fc3_w;
+    lat.fc3_b = c.P + L.fc3_b;
+    lat.img = c.ws + c.W.limg;
+    lat.N = c.d.N;
+    lat.NT = c.d.NT;
     DvsLossHeadArgs head;
     memset(&head, 0, sizeof(head));
     if (!wide) {
-        head.node0_w = params + L.node0_w;
-        head.node0_b = params + L.node0_b;
-        head.node2_w = params + L.node2_w;
-        head.node2_b = params + L.node2_b;
-        head.edge0_b = params + L.edge0_b;
-        head.edge2_w = params + L.edge2_w;
-        head.edge2_b = params + L.edge2_b;
-        head.ln_g = params + L.dec[DVS_LAYERS - 1].n3.w;
-        head.ln_b = params + L.dec[DVS_LAYERS - 1].n3.b;
-        head.dst = (float*)((dvs_bf16*)(ws + W.wimg) + DVS_WIMG_LOSS + DvsLossImg::Head);
-        head.C = C;
-        head.W1 = params + L.W1;
-        head.W2 = params + L.W2;
-        head.lab_w = params + L.lab_w;
-        head.lab_b = params + L.lab_b;
-        head.dst_emb = (float*)((dvs_bf16*)(ws + W.wimg) + DVS_WIMG_EMB);
-        head.N = N;
+        head_params(c, head);
+        head.ln_g = c.P + L.dec[DVS_LAYERS - 1].n3.w;
+        head.ln_b = c.P + L.dec[DVS_LAYERS - 1].n3.b;
+        head.dst = (float*)(wimg + DVS_WIMG_LOSS + DvsLossImg::Head);
+        head.C = c.d.C;
+        head.W1 = c.P + L.W1;
+        head.W2 = c.P + L.W2;
+        head.lab_w = c.P + L.lab_w;
+        head.lab_b = c.P + L.lab_b;
+        head.dst_emb = (float*)(wimg + DVS_WIMG_EMB);
+        head.N = c.d.N;
     }
-    dvs_launch_prepare_images(J, params, (dvs_bf16*)(ws + W.wimg), lat, head, st);
-}
-static inline const void* wimg_attn(const float* ws, const DvsWorkspace& W, int block) {
-    return (const dvs_bf16*)(ws + W.wimg) + img_attn(block);
-}
-static inline const void* wimg_ffn(const float* ws, const DvsWorkspace& W, int block) {
-    return (const dvs_bf16*)(ws + W.wimg) + img_ffn(block);
+    dvs_launch_prepare_images(J, c.P, wimg, lat, head, c.st);
 }
 
-// launch grids of the forward kernels
-struct FwdGrids {
-    bool wide;
-    int nw;         // waves per workgroup of the one-tile stack kernels (waves_per_wg)
-    int chain;      // k_fwd_stack / k_attn_fwd / narrow k_ffn_fwd, k_embed_fwd, k_loss_fwd: nw tiles per workgroup and pass
-    int tiles16;    // 16-wave tile-parallel kernels (k_ffn_fwd, one-tile k_embed_fwd)
-    int tiles8;     // 8-wave tile-parallel kernels (one-tile k_attn_fwd / k_embed_fwd / k_loss_fwd)
-    int tiles4;     // 4-wave tile-parallel kernels (k_embed_fwd_w)
-    int dags;       // workgroup-per-DAG kernels of the wide path
-    int dags2;      // ... those that fit two workgroups per CU
-};
-static FwdGrids fwd_grids(const DvsDims& d, bool wide) {
-    FwdGrids g;
-    g.wide = wide;
-    g.nw = waves_per_wg(d, wide);
-    g.chain = grid_for(d.B * d.NT, g.nw);
-    g.tiles16 = grid_for(d.B * d.NT, 16);
-    g.tiles8 = grid_for(d.B * d.NT, 8);
-    g.tiles4 = grid_for(d.B * d.NT, 4);
-    g.dags = grid_for(d.B, 1);
-    g.dags2 = d.B < 2 * g.dags ? d.B : 2 * g.dags;      // kernels that fit two workgroups per CU (k_loss_fwd_w)
-    return g;
+// ---- forward launcher by (wide, nw): the wide kernels; the narrow mapping (4 waves, the chain's grid); the 8-wave mapping ----
+static void launch_embed_fwd(const Step& c, const EmbedArgs& e) {
+    if (c.wide) dvs_launch_embed_fwd_w(e, c.g.tiles4, c.st);
+    else if (c.nw == 4) dvs_launch_embed_fwd(e, c.g.chain, 4, c.st);
+    else dvs_launch_embed_fwd(e, c.g.tiles16, 16, c.st);
 }
-static void launch_embed_fwd(const EmbedArgs& e, const FwdGrids& g, dvs_stream_t st) {
-    if (g.wide) dvs_launch_embed_fwd_w(e, g.tiles4, st);
-    else if (g.nw == 4) dvs_launch_embed_fwd(e, g.chain, 4, st);
-    else dvs_launch_embed_fwd(e, g.tiles16, 16, st);
+static void launch_attn_fwd(const Step& c, const AttnArgs& a) {
+    if (c.wide) dvs_launch_attn_fwd_w(a, c.g.dags, c.st);
+    else if (c.nw == 4) dvs_launch_attn_fwd(a, c.g.chain, 4, c.st);
+    else dvs_launch_attn_fwd(a, c.g.tiles8, 8, c.st);
 }
-static void launch_attn_fwd(const AttnArgs& a, const FwdGrids& g, dvs_stream_t st) {
-    if (g.wide) dvs_launch_attn_fwd_w(a, g.dags, st);
-    else if (g.nw == 4) dvs_launch_attn_fwd(a, g.chain, 4, st);
-    else dvs_launch_attn_fwd(a, g.tiles8, 8, st);
+static void launch_ffn_fwd(const Step& c, const FfnArgs& f) {      // token-local: one kernel serves both paths
+    if (c.nw == 4) dvs_launch_ffn_fwd(f, c.g.chain, 4, c.st);
+    else dvs_launch_ffn_fwd(f, c.g.tiles16, 16, c.st);
+}
+static void launch_loss_fwd(const Step& c, const LossArgs& a) {
+    if (c.wide) dvs_launch_loss_fwd_w(a, c.g.dags2, c.st);
+    else if (c.nw == 4) dvs_launch_loss_fwd(a, c.g.chain, 4, c.st);
+    else dvs_launch_loss_fwd(a, c.g.tiles8, 8, c.st);
 }
 // One-tile path: the sublayers of the encoder / decoder are chained into one launch each (k_fwd_stack); the wide path and
-// DVS_SPLIT_STACK=1 (per-phase profiling) launch every sublayer on its own.
+// DVS_SPLIT_STACK=1 launch every sublayer on its own.
 struct FwdChain {
     FwdStackArgs stack;
-    const FwdGrids& g;
-    dvs_stream_t st;
+    const Step& c;
     int tag;
     bool chain;
-    FwdChain(const FwdGrids& grids, int tag_, dvs_stream_t st_) : g(grids), st(st_), tag(tag_) {
-        static const bool split_env = getenv("DVS_SPLIT_STACK") && atoi(getenv("DVS_SPLIT_STACK")) != 0;
-        memset(&stack, 0, sizeof(stack));
-        chain = !g.wide && !split_env;
-    }
+    FwdChain(const Step& step, int tag_) : c(step), tag(tag_), chain(!step.wide && !split_stack()) { memset(&stack, 0, sizeof(stack)); }
     FwdPhase& next(int kind) {
         if (stack.nphase == DVS_FWD_STACK_PHASES) flush();
         FwdPhase& ph = stack.ph[stack.nphase++];
@@ -589,210 +745,72 @@ struct FwdChain {
     }
     void attn(const AttnArgs& a) {
         if (chain) next(DVS_FPH_ATTN).u.a = a;
-        else launch_attn_fwd(a, g, st);
+        else launch_attn_fwd(c, a);
     }
     void ffn(const FfnArgs& f) {
         if (chain) next(DVS_FPH_FFN).u.f = f;
-        else if (g.nw == 4 && !g.wide) dvs_launch_ffn_fwd(f, g.chain, 4, st);
-        else dvs_launch_ffn_fwd(f, g.tiles16, 16, st);
+        else launch_ffn_fwd(c, f);
     }
     // the latent block as the last phase of the encoder chain (the workgroups of the chain own 16 DAGs each: one MFMA
     // group); false: not chained, the caller launches k_latent_fwd
     bool latent(const LatentArgs& l) {
-        static const bool off = getenv("DVS_LATENT_KERNELS") && atoi(getenv("DVS_LATENT_KERNELS")) != 0;   // A/B: own launches
-        // (narrow mapping: a workgroup owns 4 DAGs, a quarter of an MFMA column group: the latent block keeps its own launch)
-        if (!chain || off || g.nw != 8 || stack.nphase == 0 || stack.nphase == DVS_FWD_STACK_PHASES) return false;
+        if (!latent_in_chain(chain, c.nw) || stack.nphase == 0 || stack.nphase == DVS_FWD_STACK_PHASES) return false;
         next(DVS_FPH_LATENT).u.l = l;
         return true;
     }
     void flush() {
-        if (stack.nphase > 0) dvs_launch_fwd_stack(stack, tag, g.chain, g.nw, st);
+        if (stack.nphase > 0) dvs_launch_fwd_stack(stack, tag, c.g.chain, c.nw, c.st);
         stack.nphase = 0;
     }
 };
 
 // dec_embed: also write the decoder-side embedding (slot 7, dropout sites 2 / 3) from the same launch (one-tile path)
 // lat: the latent block's arguments; it runs as the last phase of the encoder chain when there is one, as k_latent_fwd otherwise
-static void encoder_forward(const DvsDims& d, const DvsLayout& L, const DvsWorkspace& W, const DvsRecord* rec,
-                            const float* P, float* ws, const FwdGrids& grid, dvs_stream_t st, const LatentArgs& lat,
-                            bool dec_embed = false, bool save_qkv = false) {
-    EmbedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.dims = d;
-    e.rec = rec;
-    e.W1 = P + L.W1;
-    e.W2 = P + L.W2;
-    e.lab_w = P + L.lab_w;
-    e.lab_b = P + L.lab_b;
-    e.embimg = (const float*)((const dvs_bf16*)(ws + W.wimg) + DVS_WIMG_EMB);
-    e.out = ws + W.act[0];
-    e.site = 0;
+// save_qkv: the wide attention kernels park q, k, v for the backward
+static void encoder_forward(const Step& c, const LatentArgs& lat, bool dec_embed = false, bool save_qkv = false) {
+    EmbedArgs e = embed_args(c, 0);
+    e.out = c.ws + c.W.act[0];
     if (dec_embed) {
-        e.out2 = ws + W.act[7];
+        e.out2 = c.ws + c.W.act[7];
         e.site2 = 2;
     }
-    launch_embed_fwd(e, grid, st);
-    FwdChain chain(grid, 0, st);
-    DvsLN ln = {nullptr, nullptr, nullptr};
+    launch_embed_fwd(c, e);
+    FwdChain chain(c, 0);
+    const DvsNormP* norm = nullptr;
     int prev = 0;
     for (int i = 0; i < DVS_LAYERS; ++i) {
-        AttnArgs a;
-        memset(&a, 0, sizeof(a));
-        a.dims = d;
-        a.rec = rec;
-        a.xin = ws + W.act[prev];
-        a.ln = ln;
-        a.kv = nullptr;
-        a.in_w = P + L.enc[i].sa.in_w;
-        a.in_b = P + L.enc[i].sa.in_b;
-        a.out_w = P + L.enc[i].sa.out_w;
-        a.out_b = P + L.enc[i].sa.out_b;
-        a.wimg = wimg_attn(ws, W, blk_enc_attn(i));
-        a.qkv = (save_qkv && grid.wide) ? ws + W.qkv[blk_enc_attn(i)] : nullptr;
-        const int sa = slot_enc(i, 0);
-        a.out_pre = ws + W.act[sa];
-        a.out_stats = ws + W.stats[sa];
-        a.site_prob = site_enc(i, 0);
-        a.site_post = site_enc(i, 1);
+        const auto& pl = c.L.enc[i];
+        const int sa = slot_enc(i, 0), sf = slot_enc(i, 1);
+        AttnArgs a = attn_args(c, pl.sa, blk_enc_attn(i), prev, norm, nullptr, sa, site_enc(i, 0));
+        if (!save_qkv) a.qkv = nullptr;
         chain.attn(a);
-        FfnArgs f;
-        memset(&f, 0, sizeof(f));
-        f.dims = d;
-        f.xin = ws + W.act[sa];
-        f.ln = DvsLN{ws + W.stats[sa], P + L.enc[i].n1.w, P + L.enc[i].n1.b};
-        f.l1_w = P + L.enc[i].ff.l1_w;
-        f.l1_b = P + L.enc[i].ff.l1_b;
-        f.l2_w = P + L.enc[i].ff.l2_w;
-        f.l2_b = P + L.enc[i].ff.l2_b;
-        f.wimg = wimg_ffn(ws, W, blk_enc_ffn(i));
-        const int sf = slot_enc(i, 1);
-        f.out_pre = ws + W.act[sf];
-        f.out_stats = ws + W.stats[sf];
-        f.site_hidden = site_enc(i, 2);
-        f.site_post = site_enc(i, 3);
+        FfnArgs f = ffn_args(c, pl.ff, blk_enc_ffn(i), sa, pl.n1, sf, site_enc(i, 2));
         if (i == DVS_LAYERS - 1) {
-            f.out_norm = ws + W.enc_out;
-            f.ng = P + L.enc[i].n2.w;
-            f.nb = P + L.enc[i].n2.b;
+            f.out_norm = c.ws + c.W.enc_out;
+            f.ng = c.P + pl.n2.w;
+            f.nb = c.P + pl.n2.b;
         }
         chain.ffn(f);
-        ln = DvsLN{ws + W.stats[sf], P + L.enc[i].n2.w, P + L.enc[i].n2.b};
+        norm = &pl.n2;
         prev = sf;
     }
     const bool fused = chain.latent(lat);
     chain.flush();
-    if (!fused) dvs_launch_latent_fwd(lat, st);
-}
-
-static LatentArgs latent_args(const DvsDims& d, const DvsLayout& L, const DvsWorkspace& W, const float* P, float* ws,
-                              const float* eps, bool with_mem) {
-    LatentArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dims = d;
-    a.xenc = ws + W.enc_out;
-    a.fc1_w = P + L.fc1_w;
-    a.fc1_b = P + L.fc1_b;
-    a.fc2_w = P + L.fc2_w;
-    a.fc2_b = P + L.fc2_b;
-    a.fc3_w = P + L.fc3_w;
-    a.fc3_b = P + L.fc3_b;
-    a.limg = ws + W.limg;
-    a.eps_in = eps;
-    a.mu = ws + W.mu;
-    a.logvar = ws + W.logvar;
-    a.z = ws + W.z;
-    a.epsv = ws + W.epsv;
-    a.mem = with_mem ? ws + W.mem : nullptr;
-    a.dag_loss = ws + W.dag_loss;
-    return a;
-}
-
-LossArgs dvs_loss_args(const DvsDims& d, const DvsLayout& L, const DvsWorkspace& W, const DvsRecord* rec, const float* P,
-                       float* ws) {
-    LossArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dims = d;
-    a.rec = rec;
-    const int last = slot_dec(DVS_LAYERS - 1, 2);
-    a.xin = ws + W.act[last];
-    a.ln = DvsLN{ws + W.stats[last], P + L.dec[DVS_LAYERS - 1].n3.w, P + L.dec[DVS_LAYERS - 1].n3.b};
-    a.node0_w = P + L.node0_w;
-    a.node0_b = P + L.node0_b;
-    a.node2_w = P + L.node2_w;
-    a.node2_b = P + L.node2_b;
-    a.edge0_w = P + L.edge0_w;
-    a.edge0_b = P + L.edge0_b;
-    a.edge2_w = P + L.edge2_w;
-    a.edge2_b = P + L.edge2_b;
-    a.wimg = (const dvs_bf16*)(ws + W.wimg) + DVS_WIMG_LOSS;
-    a.dag_loss = ws + W.dag_loss;
-    return a;
+    if (!fused) dvs_launch_latent_fwd(lat, c.st);
 }
 
 // TransformerDecoder forward (pace.py:163-182) from the embedding in slot `dec_in`; memory = W.mem.
-static void decoder_forward(const DvsDims& d, const DvsLayout& L, const DvsWorkspace& W, const DvsRecord* rec,
-                            const float* params, float* ws, const FwdGrids& grid, int dec_in, dvs_stream_t st) {
-    FwdChain chain(grid, 1, st);
-    DvsLN ln = {nullptr, nullptr, nullptr};
+static void decoder_forward(const Step& c, int dec_in) {
+    FwdChain chain(c, 1);
+    const DvsNormP* norm = nullptr;
     int prev = dec_in;
     for (int i = 0; i < DVS_LAYERS; ++i) {
-        const auto& pl = L.dec[i];
-        AttnArgs a;
-        memset(&a, 0, sizeof(a));
-        a.dims = d;
-        a.rec = rec;
-        a.xin = ws + W.act[prev];
-        a.ln = ln;
-        a.in_w = params + pl.sa.in_w;
-        a.in_b = params + pl.sa.in_b;
-        a.out_w = params + pl.sa.out_w;
-        a.out_b = params + pl.sa.out_b;
-        a.wimg = wimg_attn(ws, W, blk_dec_self(i));
-        a.qkv = grid.wide ? ws + W.qkv[blk_dec_self(i)] : nullptr;
-        const int s0 = slot_dec(i, 0);
-        a.out_pre = ws + W.act[s0];
-        a.out_stats = ws + W.stats[s0];
-        a.site_prob = site_dec(i, 0);
-        a.site_post = site_dec(i, 1);
-        chain.attn(a);
-
-        AttnArgs c;
-        memset(&c, 0, sizeof(c));
-        c.dims = d;
-        c.rec = rec;
-        c.xin = ws + W.act[s0];
-        c.ln = DvsLN{ws + W.stats[s0], params + pl.n1.w, params + pl.n1.b};
-        c.kv = ws + W.mem;
-        c.in_w = params + pl.ca.in_w;
-        c.in_b = params + pl.ca.in_b;
-        c.out_w = params + pl.ca.out_w;
-        c.out_b = params + pl.ca.out_b;
-        c.wimg = wimg_attn(ws, W, blk_dec_cross(i));
-        c.qkv = grid.wide ? ws + W.qkv[blk_dec_cross(i)] : nullptr;
-        const int s1 = slot_dec(i, 1);
-        c.out_pre = ws + W.act[s1];
-        c.out_stats = ws + W.stats[s1];
-        c.site_prob = site_dec(i, 2);
-        c.site_post = site_dec(i, 3);
-        chain.attn(c);
-
-        FfnArgs f;
-        memset(&f, 0, sizeof(f));
-        f.dims = d;
-        f.xin = ws + W.act[s1];
-        f.ln = DvsLN{ws + W.stats[s1], params + pl.n2.w, params + pl.n2.b};
-        f.l1_w = params + pl.ff.l1_w;
-        f.l1_b = params + pl.ff.l1_b;
-        f.l2_w = params + pl.ff.l2_w;
-        f.l2_b = params + pl.ff.l2_b;
-        f.wimg = wimg_ffn(ws, W, blk_dec_ffn(i));
-        const int s2 = slot_dec(i, 2);
-        f.out_pre = ws + W.act[s2];
-        f.out_stats = ws + W.stats[s2];
-        f.site_hidden = site_dec(i, 4);
-        f.site_post = site_dec(i, 5);
-        chain.ffn(f);
-        ln = DvsLN{ws + W.stats[s2], params + pl.n3.w, params + pl.n3.b};
+        const auto& pl = c.L.dec[i];
+        const int s0 = slot_dec(i, 0), s1 = slot_dec(i, 1), s2 = slot_dec(i, 2);
+        chain.attn(attn_args(c, pl.sa, blk_dec_self(i), prev, norm, nullptr, s0, site_dec(i, 0)));
+        chain.attn(attn_args(c, pl.ca, blk_dec_cross(i), s0, &pl.n1, c.ws + c.W.mem, s1, site_dec(i, 2)));
+        chain.ffn(ffn_args(c, pl.ff, blk_dec_ffn(i), s1, pl.n2, s2, site_dec(i, 4)));
+        norm = &pl.n3;
         prev = s2;
     }
     chain.flush();
@@ -811,59 +829,27 @@ extern "C" int dvs_loss_forward_notify(const dvs_shape* s, const void* records, 
                                        uint32_t host_seq, void* stream) {
     if (int e = check_shape(s)) return e;
     if (!records || !params || !workspace || !losses) return fail(10, "dvs_loss_forward: null pointer");
-    if (int e = check_buffers(s, "dvs_loss_forward", true, records_bytes, true, n_params, true, workspace_bytes)) return e;
+    const Step c = make_step(s, records, params, workspace, stream);
+    if (int e = check_buffers(c, "dvs_loss_forward", records_bytes, n_params, workspace_bytes)) return e;
     call_begin();
-    const DvsDims d = make_dims(s);
-    const DvsLayout L = dvs_make_layout(d.N, d.C, nullptr, 0, nullptr);
-    const DvsWorkspace W = dvs_make_workspace(d.B, d.NT, L.total, dvs_num_slabs(), is_wide(s));
-    float* ws = (float*)workspace;
-    const DvsRecord* rec = (const DvsRecord*)records;
-    dvs_stream_t st = (dvs_stream_t)stream;
-    const FwdGrids grid = fwd_grids(d, is_wide(s));
-
-    prepare_images(L, d.N, d.C, grid.wide, params, ws, W, st);
-    const bool fused_dec_embed = d.drop.on;
-    encoder_forward(d, L, W, rec, params, ws, grid, st, latent_args(d, L, W, params, ws, eps, true), fused_dec_embed, true);
-
-    // decoder input embedding: identical to the encoder's in eval mode / dropout 0 (pace.py:2000-2012 recomputes it
-    // only to redraw the dropout masks)
-    int dec_in = fused_dec_embed ? 7 : 0;
-    if (d.drop.on && !fused_dec_embed) {
-        EmbedArgs e;
-        memset(&e, 0, sizeof(e));
-        e.dims = d;
-        e.rec = rec;
-        e.W1 = params + L.W1;
-        e.W2 = params + L.W2;
-        e.lab_w = params + L.lab_w;
-        e.lab_b = params + L.lab_b;
-        e.embimg = (const float*)((const dvs_bf16*)(ws + W.wimg) + DVS_WIMG_EMB);
-        e.out = ws + W.act[7];
-        e.site = 2;
-        launch_embed_fwd(e, grid, st);
-        dec_in = 7;
-    }
-    decoder_forward(d, L, W, rec, params, ws, grid, dec_in, st);
-    if (grid.wide) dvs_launch_loss_fwd_w(dvs_loss_args(d, L, W, rec, params, ws), grid.dags2, st);
-    else if (grid.nw == 4) dvs_launch_loss_fwd(dvs_loss_args(d, L, W, rec, params, ws), grid.chain, 4, st);
-    else dvs_launch_loss_fwd(dvs_loss_args(d, L, W, rec, params, ws), grid.tiles8, 8, st);
+    prepare_images(c);
+    // decoder input embedding: identical to the encoder's in eval mode / dropout 0 (pace.py:2000-2012 recomputes it only to
+    // redraw the dropout masks); under dropout the encoder's embedding launch writes it as well (slot 7)
+    encoder_forward(c, latent_args(c, eps, true), c.d.drop.on, true);
+    decoder_forward(c, c.d.drop.on ? 7 : 0);
+    launch_loss_fwd(c, loss_args(c));
     FinalizeArgs fa;
-    fa.B = d.B;
-    fa.beta = d.beta;
-    fa.dag_loss = ws + W.dag_loss;
+    fa.B = c.d.B;
+    fa.beta = c.d.beta;
+    fa.dag_loss = c.ws + c.W.dag_loss;
     fa.status = status;
     fa.losses = losses;
     fa.host_tail = (float*)host_tail;
     fa.host_seq = host_seq;
-    dvs_launch_finalize(fa, st);
-    const size_t nb = (size_t)d.B * 32 * sizeof(float);
-#ifdef DVS_EMU
-    if (mu) memcpy(mu, ws + W.mu, nb);
-    if (logvar) memcpy(logvar, ws + W.logvar, nb);
-#else
-    if (mu) DVS_HIP_CALL(hipMemcpyAsync(mu, ws + W.mu, nb, hipMemcpyDeviceToDevice, st));
-    if (logvar) DVS_HIP_CALL(hipMemcpyAsync(logvar, ws + W.logvar, nb, hipMemcpyDeviceToDevice, st));
-#endif
+    dvs_launch_finalize(fa, c.st);
+    const size_t nb = (size_t)c.d.B * 32 * sizeof(float);
+    if (mu) copy_out(mu, c.ws + c.W.mu, nb, c.st);
+    if (logvar) copy_out(logvar, c.ws + c.W.logvar, nb, c.st);
     return call_end("dvs_loss_forward");
 }
 
@@ -872,87 +858,49 @@ extern "C" int dvs_encode(const dvs_shape* s, const void* records, size_t record
                           void* stream) {
     if (int e = check_shape(s)) return e;
     if (!records || !params || !workspace || !mu || !logvar) return fail(10, "dvs_encode: null pointer");
-    if (int e = check_buffers(s, "dvs_encode", true, records_bytes, true, n_params, true, workspace_bytes)) return e;
+    const Step c = make_step(s, records, params, workspace, stream);
+    if (int e = check_buffers(c, "dvs_encode", records_bytes, n_params, workspace_bytes)) return e;
     call_begin();
-    const DvsDims d = make_dims(s);
-    const DvsLayout L = dvs_make_layout(d.N, d.C, nullptr, 0, nullptr);
-    const DvsWorkspace W = dvs_make_workspace(d.B, d.NT, L.total, dvs_num_slabs(), is_wide(s));
-    float* ws = (float*)workspace;
-    dvs_stream_t st = (dvs_stream_t)stream;
-    prepare_images(L, d.N, d.C, is_wide(s), params, ws, W, st);
-    LatentArgs la = latent_args(d, L, W, params, ws, nullptr, false);
+    prepare_images(c);
+    LatentArgs la = latent_args(c, nullptr, false);
     la.dims.training = 0;
-    encoder_forward(d, L, W, (const DvsRecord*)records, params, ws, fwd_grids(d, is_wide(s)), st, la);
-    const size_t nb = (size_t)d.B * 32 * sizeof(float);
-#ifdef DVS_EMU
-    memcpy(mu, ws + W.mu, nb);
-    memcpy(logvar, ws + W.logvar, nb);
-#else
-    DVS_HIP_CALL(hipMemcpyAsync(mu, ws + W.mu, nb, hipMemcpyDeviceToDevice, st));
-    DVS_HIP_CALL(hipMemcpyAsync(logvar, ws + W.logvar, nb, hipMemcpyDeviceToDevice, st));
-#endif
+    encoder_forward(c, la);
+    const size_t nb = (size_t)c.d.B * 32 * sizeof(float);
+    copy_out(mu, c.ws + c.W.mu, nb, c.st);
+    copy_out(logvar, c.ws + c.W.logvar, nb, c.st);
     return call_end("dvs_encode");
 }
 
 // ---- generation (k_decode.hip) -------------------------------------------------------------------------------------
-#include "dvs_decode.h"
-
 extern "C" int dvs_decode(const dvs_shape* s, const float* params, int64_t n_params, void* workspace,
                           size_t workspace_bytes, void* records, size_t records_bytes, const float* z,
                           const float* uniforms, void* state_out, size_t state_bytes, void* stream) {
     if (int e = check_shape(s)) return e;
     if (!params || !workspace || !records || !z || !state_out) return fail(10, "dvs_decode: null pointer");
     if (s->training) return fail(13, "dvs_decode: generation runs in eval mode (shape.training must be 0)");
-    if (int e = check_buffers(s, "dvs_decode", true, records_bytes, true, n_params, true, workspace_bytes)) return e;
+    const Step c = make_step(s, records, params, workspace, stream);
+    if (int e = check_buffers(c, "dvs_decode", records_bytes, n_params, workspace_bytes)) return e;
     if (state_bytes < (size_t)s->batch * sizeof(dvs_decode_state))
         return fail(14, "dvs_decode: state_bytes < batch * sizeof(dvs_decode_state)");
     call_begin();
-    const DvsDims d = make_dims(s);
-    const DvsLayout L = dvs_make_layout(d.N, d.C, nullptr, 0, nullptr);
-    const DvsWorkspace W = dvs_make_workspace(d.B, d.NT, L.total, dvs_num_slabs(), is_wide(s));
-    float* ws = (float*)workspace;
-    dvs_stream_t st = (dvs_stream_t)stream;
-    const bool wide = is_wide(s);
-    const FwdGrids grid = fwd_grids(d, wide);
-    const DvsRecord* rec = (const DvsRecord*)records;
-
-    prepare_images(L, d.N, d.C, wide, params, ws, W, st);
-    dvs_launch_decode_memory(d, z, params + L.fc3_w, params + L.fc3_b, ws + W.mem, st);
+    prepare_images(c);
+    dvs_launch_decode_memory(c.d, z, c.P + c.L.fc3_w, c.P + c.L.fc3_b, c.ws + c.W.mem, c.st);
     DecodeArgs a;
     memset(&a, 0, sizeof(a));
-    a.dims = d;
-    a.wide = wide ? 1 : 0;
+    a.dims = c.d;
+    a.wide = c.wide ? 1 : 0;
     a.rec = records;
     a.state = (DvsDecodeState*)state_out;
-    const int last = slot_dec(DVS_LAYERS - 1, 2);
-    a.xin = ws + W.act[last];
-    a.ln = DvsLN{ws + W.stats[last], params + L.dec[DVS_LAYERS - 1].n3.w, params + L.dec[DVS_LAYERS - 1].n3.b};
-    a.node0_w = params + L.node0_w;
-    a.node0_b = params + L.node0_b;
-    a.node2_w = params + L.node2_w;
-    a.node2_b = params + L.node2_b;
-    a.edge0_w = params + L.edge0_w;
-    a.edge0_b = params + L.edge0_b;
-    a.edge2_w = params + L.edge2_w;
-    a.edge2_b = params + L.edge2_b;
+    head_input(c, a);
     a.uniforms = uniforms;
-    dvs_launch_decode_init(a, st);
-    for (int idx = 2; idx < d.N; ++idx) {
-        EmbedArgs e;
-        memset(&e, 0, sizeof(e));
-        e.dims = d;
-        e.rec = rec;
-        e.W1 = params + L.W1;
-        e.W2 = params + L.W2;
-        e.lab_w = params + L.lab_w;
-        e.lab_b = params + L.lab_b;
-        e.embimg = (const float*)((const dvs_bf16*)(ws + W.wimg) + DVS_WIMG_EMB);
-        e.out = ws + W.act[7];
-        e.site = 2;
-        launch_embed_fwd(e, grid, st);
-        decoder_forward(d, L, W, rec, params, ws, grid, 7, st);
+    dvs_launch_decode_init(a, c.st);
+    EmbedArgs e = embed_args(c, 2);
+    e.out = c.ws + c.W.act[7];
+    for (int idx = 2; idx < c.d.N; ++idx) {
+        launch_embed_fwd(c, e);
+        decoder_forward(c, 7);
         a.idx = idx;
-        dvs_launch_decode_step(a, grid_for(d.B, 4), st);
+        dvs_launch_decode_step(a, c.g.dec4, c.st);
     }
     return call_end("dvs_decode");
 }
@@ -1168,9 +1116,9 @@ extern "C" int dvs_gp_acquire(int32_t batch, int32_t n_inducing, int32_t dim, in
 
 extern "C" int dvs_debug_activation(const dvs_shape* s, const void* workspace, int slot, float* out, void* stream) {
     if (int e = check_shape(s)) return e;
-    const int64_t P = dvs_make_layout(s->n_tokens, s->n_classes, nullptr, 0, nullptr).total;
-    const DvsWorkspace W = dvs_make_workspace(s->batch, tiles_of(s), P, dvs_num_slabs(), is_wide(s));
-    const float* ws = (const float*)workspace;
+    const Step c = make_step(s, nullptr, nullptr, (void*)workspace, stream);
+    const float* ws = c.ws;
+    const DvsWorkspace& W = c.W;
     const float* src = nullptr;
     if (slot >= 0 && slot < DVS_NSLOTS) src = ws + W.act[slot];
     else if (slot == 100) src = ws + W.enc_out;
@@ -1181,7 +1129,7 @@ extern "C" int dvs_debug_activation(const dvs_shape* s, const void* workspace, i
     else if (slot == 105) src = ws + W.genc;
     else return fail(11, "dvs_debug_activation: bad slot");
     call_begin();
-    dvs_launch_unfrag(src, out, s->batch * tiles_of(s), (dvs_stream_t)stream);
+    dvs_launch_unfrag(src, out, c.d.B * c.d.NT, c.st);
     return call_end("dvs_debug_activation");
 }
 

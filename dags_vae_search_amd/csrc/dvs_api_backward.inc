@@ -1,84 +1,85 @@
 // Backward + optimizer entry points (included by dvs_api.hip).
 
-static AttnBwdArgs attn_bwd_args(const DvsDims& d, const DvsRecord* rec, const float* P, float* ws, const DvsWorkspace& W,
-                                 const DvsAttnP& ap, int block, const float* xin, const DvsLN& ln, const float* kv,
-                                 const float* gpre, int site_prob, int site_post, int64_t Ptot) {
+// Argument blocks of the backward phases, from the call context (dvs_api.hip: Step) plus what varies.  in: activation slot
+// of the sublayer's input; norm: LayerNorm of the producer of `in` (null: an embedding), whose weight gradients the phase
+// also owns; gpre: d(pre-sum) of this sublayer; site0: first of its two consecutive dropout sites.
+static AttnBwdArgs attn_bwd_args(const Step& c, const DvsAttnP& ap, int block, int in, const DvsNormP* norm, const float* kv,
+                                 const float* gpre, int site0) {
     AttnBwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.wimg = wimg_attn(ws, W, block);
-    a.dims = d;
-    a.rec = rec;
-    a.xin = xin;
-    a.ln = ln;
+    a.wimg = wimg_attn(c, block);
+    a.dims = c.d;
+    a.rec = c.rec;
+    a.xin = c.ws + c.W.act[in];
+    a.ln = ln_of(c, in, norm);
     a.kv = kv;
-    a.in_w = P + ap.in_w;
-    a.in_b = P + ap.in_b;
-    a.out_w = P + ap.out_w;
-    a.out_b = P + ap.out_b;
+    a.in_w = c.P + ap.in_w;
+    a.in_b = c.P + ap.in_b;
+    a.out_w = c.P + ap.out_w;
+    a.out_b = c.P + ap.out_b;
     a.gpre = gpre;
-    a.gq = ws + W.gq;
-    a.gk = ws + W.gk;
-    a.gv = ws + W.gv;
-    a.site_prob = site_prob;
-    a.site_post = site_post;
-    a.slab = ws + W.slabs;
-    a.P = Ptot;
+    a.gq = c.ws + c.W.gq;
+    a.gk = c.ws + c.W.gk;
+    a.gv = c.ws + c.W.gv;
+    a.site_prob = site0;
+    a.site_post = site0 + 1;
+    a.slab = c.ws + c.W.slabs;
+    a.P = c.L.total;
     a.o_out_w = ap.out_w;
     a.o_out_b = ap.out_b;
-    a.qkv = W.qkv[8] > W.qkv[0] ? ws + W.qkv[block] : nullptr;      // (regions of size 0 on the one-tile path)
+    a.qkv = c.wide ? c.ws + c.W.qkv[block] : nullptr;      // as the forward parked them
     return a;
 }
 
-// block / p0: attention image block and first projection (0 q, 1 k, 2 v) of the stacked weights at w_off
-static ProjBwdArgs proj_bwd_args(const DvsDims& d, const float* P, float* ws, const DvsWorkspace& W, int block, int p0,
-                                 const float* xin, const DvsLN& ln, int64_t w_off, int64_t b_off, int nproj, const float* const* gy,
-                                 const float* gres, float* gout, int accumulate, int64_t o_ln_g, int64_t o_ln_b, int64_t Ptot) {
+// the q, k, v in-projections of attention block `block` behind k_attn_bwd: gy = (gq, gk, gv), d input = gres + ... -> gout
+static ProjBwdArgs proj_bwd_args(const Step& c, const DvsAttnP& ap, int block, int in, const DvsNormP* norm, const float* gres,
+                                 float* gout) {
     ProjBwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.dims = d;
-    a.xin = xin;
-    a.ln = ln;
-    a.w = P + w_off;
-    a.wimg = (const dvs_bf16*)wimg_attn(ws, W, block) + DvsAttnImg::WinT + (size_t)p0 * 2 * DVS_IMG64;
-    for (int i = 0; i < nproj; ++i) a.gy[i] = gy[i];
+    a.dims = c.d;
+    a.xin = c.ws + c.W.act[in];
+    a.ln = ln_of(c, in, norm);
+    a.w = c.P + ap.in_w;
+    a.wimg = (const dvs_bf16*)wimg_attn(c, block) + DvsAttnImg::WinT;
+    a.gy[0] = c.ws + c.W.gq;
+    a.gy[1] = c.ws + c.W.gk;
+    a.gy[2] = c.ws + c.W.gv;
     a.gres = gres;
     a.gout = gout;
-    a.accumulate_out = accumulate;
-    a.slot_order = 1;            // every use is an attention in-projection
-    a.slab = ws + W.slabs;
-    a.P = Ptot;
-    a.o_w = w_off;
-    a.o_b = b_off;
-    a.o_ln_g = o_ln_g;
-    a.o_ln_b = o_ln_b;
+    a.slot_order = c.wide ? 0 : 1;      // the wide attention kernels keep q/k/v in parameter order; the one-tile ones in head-aligned slot order
+    a.slab = c.ws + c.W.slabs;
+    a.P = c.L.total;
+    a.o_w = ap.in_w;
+    a.o_b = ap.in_b;
+    a.o_ln_g = norm ? norm->w : -1;
+    a.o_ln_b = norm ? norm->b : -1;
     return a;
 }
 
-static FfnBwdArgs ffn_bwd_args(const DvsDims& d, const float* P, float* ws, const DvsWorkspace& W, const DvsFfnP& fp,
-                               int block, const float* xin, const DvsLN& ln, const DvsNormP& lnp, const float* gpre, float* gout,
-                               int site_hidden, int site_post, int64_t Ptot) {
+static FfnBwdArgs ffn_bwd_args(const Step& c, const DvsFfnP& fp, int block, int in, const DvsNormP& norm, const float* gpre,
+                               float* gout, int site0) {
     FfnBwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.dims = d;
-    a.xin = xin;
-    a.ln = ln;
-    a.l1_w = P + fp.l1_w;
-    a.l1_b = P + fp.l1_b;
-    a.l2_w = P + fp.l2_w;
-    a.l2_b = P + fp.l2_b;
-    a.wimg = wimg_ffn(ws, W, block);
+    a.dims = c.d;
+    a.xin = c.ws + c.W.act[in];
+    a.ln = ln_of(c, in, &norm);
+    a.l1_w = c.P + fp.l1_w;
+    a.l1_b = c.P + fp.l1_b;
+    a.l2_w = c.P + fp.l2_w;
+    a.l2_b = c.P + fp.l2_b;
+    a.wimg = wimg_ffn(c, block);
     a.gpre = gpre;
     a.gout = gout;
-    a.site_hidden = site_hidden;
-    a.site_post = site_post;
-    a.slab = ws + W.slabs;
-    a.P = Ptot;
+    a.site_hidden = site0;
+    a.site_post = site0 + 1;
+    a.slab = c.ws + c.W.slabs;
+    a.P = c.L.total;
     a.o_l1_w = fp.l1_w;
     a.o_l1_b = fp.l1_b;
     a.o_l2_w = fp.l2_w;
     a.o_l2_b = fp.l2_b;
-    a.o_ln_g = lnp.w;
-    a.o_ln_b = lnp.b;
+    a.o_ln_g = norm.w;
+    a.o_ln_b = norm.b;
     a.o_own_g = -1;
     a.o_own_b = -1;
     return a;
@@ -96,29 +97,24 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
                                     float* grads, float* clip_scratch, void* stream) {
     if (int e = check_shape(s)) return e;
     if (!records || !params || !workspace || !gcoef || !grads) return fail(10, "dvs_loss_backward: null pointer");
-    if (int e = check_buffers(s, "dvs_loss_backward", true, records_bytes, true, n_params, true, workspace_bytes)) return e;
-    if (clip_scratch && 2 + dvs_sq_parts(param_floats(s)) > DVS_CLIP_SCRATCH_FLOATS)
+    const Step c = make_step(s, records, params, workspace, stream);
+    if (int e = check_buffers(c, "dvs_loss_backward", records_bytes, n_params, workspace_bytes)) return e;
+    if (clip_scratch && 2 + dvs_sq_parts(c.L.total) > DVS_CLIP_SCRATCH_FLOATS)
         return fail(14, "dvs_loss_backward_sq: clip_scratch (DVS_CLIP_SCRATCH_FLOATS) is too small for this parameter count");
     call_begin();
-    const DvsDims d = make_dims(s);
-    const DvsLayout L = dvs_make_layout(d.N, d.C, nullptr, 0, nullptr);
-    const int nslab = dvs_num_slabs();
-    const DvsWorkspace W = dvs_make_workspace(d.B, d.NT, L.total, nslab, is_wide(s));
-    float* ws = (float*)workspace;
-    const DvsRecord* rec = (const DvsRecord*)records;
-    const float* P = params;
-    dvs_stream_t st = (dvs_stream_t)stream;
-    const int64_t PT = L.total;
-    const bool wide = is_wide(s);
-    const int grid = active_slabs(d, wide);      // workgroups of every backward kernel = slabs written and reduced this step
-    const int nw = waves_per_wg(d, wide);
+    const DvsLayout& L = c.L;
+    const DvsWorkspace& W = c.W;
+    float* ws = c.ws;
+    dvs_stream_t st = c.st;
+    const bool wide = c.wide;
+    const int grid = c.slabs;      // workgroups of every backward kernel = slabs written and reduced this step
+    const int nw = c.nw;
     // One-tile path: the stack's phases are chained into launches of up to DVS_STACK_PHASES (k_bwd_stack); the wide path
-    // and DVS_SPLIT_STACK=1 (per-phase profiling) launch every phase on its own.
-    static const bool split_env = getenv("DVS_SPLIT_STACK") && atoi(getenv("DVS_SPLIT_STACK")) != 0;
-    const bool chain = !wide && !split_env;
+    // and DVS_SPLIT_STACK=1 launch every phase on its own.
+    const bool chain = !wide && !split_stack();
     // wide path: the token-local phases BETWEEN two attention launches (a layer's q / k / v projections and the FFN of the layer
     // below) still travel as one chained launch; k_attn_bwd_w flushes what has gathered
-    const bool chain_local = wide && !split_env;
+    const bool chain_local = wide && !split_stack();
     BwdStackArgs stack;
     memset(&stack, 0, sizeof(stack));
     int stack_tag = 0;
@@ -147,22 +143,20 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
             dvs_launch_attn_bwd(a, grid, nw, st);
         }
     };
-    // the wide attention kernels keep q/k/v in parameter order; the one-tile ones in head-aligned slot order
-    auto launch_proj_bwd = [&](ProjBwdArgs a, int nproj) {
-        a.slot_order = wide ? 0 : 1;
-        if (chain || chain_local) next_phase(DVS_PH_PROJ1 + nproj - 1).u.p = a;
-        else dvs_launch_proj_bwd(a, nproj, grid, nw, st);
+    auto launch_proj_bwd = [&](const ProjBwdArgs& a) {      // all three projections
+        if (chain || chain_local) next_phase(DVS_PH_PROJ1 + 2).u.p = a;
+        else dvs_launch_proj_bwd(a, 3, grid, nw, st);
     };
 
     // ---- loss head (+ last decoder LayerNorm) -------------------------------------------------------------------
     float* cur = ws + W.gA;
     float* oth = ws + W.gB;
     {
-        LossArgs la = dvs_loss_args(d, L, W, rec, P, ws);
+        LossArgs la = loss_args(c);
         la.gcoef = gcoef;
         la.gout = cur;
         la.slab = ws + W.slabs;
-        la.P = PT;
+        la.P = L.total;
         la.o_node0_w = L.node0_w;
         la.o_node0_b = L.node0_b;
         la.o_node2_w = L.node2_w;
@@ -176,56 +170,31 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
         if (wide) dvs_launch_loss_bwd_w(la, grid, st);
         else dvs_launch_loss_bwd(la, grid, st);
     }
-    const int dec_in = d.drop.on ? 7 : 0;
+    const int dec_in = c.d.drop.on ? 7 : 0;
     // ---- decoder, last layer first --------------------------------------------------------------------------------
     for (int i = DVS_LAYERS - 1; i >= 0; --i) {
         const auto& pl = L.dec[i];
         const int s0 = slot_dec(i, 0), s1 = slot_dec(i, 1);
         // FFN sublayer: input = LN2(pre s1)
-        {
-            const DvsLN ln = {ws + W.stats[s1], P + pl.n2.w, P + pl.n2.b};
-            FfnBwdArgs f = ffn_bwd_args(d, P, ws, W, pl.ff, blk_dec_ffn(i), ws + W.act[s1], ln, pl.n2, cur, oth, site_dec(i, 4),
-                                        site_dec(i, 5), PT);
-            launch_ffn_bwd(f);
-            float* t = cur; cur = oth; oth = t;
-        }
+        launch_ffn_bwd(ffn_bwd_args(c, pl.ff, blk_dec_ffn(i), s1, pl.n2, cur, oth, site_dec(i, 4)));
+        std::swap(cur, oth);
         // cross-attention sublayer: query input = LN1(pre s0), keys/values = memory
-        {
-            const DvsLN ln = {ws + W.stats[s0], P + pl.n1.w, P + pl.n1.b};
-            AttnBwdArgs a = attn_bwd_args(d, rec, P, ws, W, pl.ca, blk_dec_cross(i), ws + W.act[s0], ln, ws + W.mem, cur, site_dec(i, 2),
-                                          site_dec(i, 3), PT);
-            launch_attn_bwd(a);
-            // q projection (input LN1(pre s0), residual gradient, LayerNorm backward) and k / v projections (input = the decoder
-            // memory, gradient accumulated over the layers into gmem) as ONE split phase: the two were short phases of their own
-            // in rounds 1-2, and a phase's fixed cost (tail + cold start, ~20 k cycles) is as large as one of their DAG rounds
-            const float* gy[3] = {ws + W.gq, ws + W.gk, ws + W.gv};
-            ProjBwdArgs pq = proj_bwd_args(d, P, ws, W, blk_dec_cross(i), 0, ws + W.act[s0], ln, pl.ca.in_w, pl.ca.in_b, 3, gy, cur, oth, 0,
-                                           pl.n1.w, pl.n1.b, PT);
-            pq.xin2 = ws + W.mem;
-            pq.gout2 = ws + W.gmem;
-            pq.accumulate_out2 = i != DVS_LAYERS - 1;
-            launch_proj_bwd(pq, 3);
-            float* t = cur; cur = oth; oth = t;
-        }
+        launch_attn_bwd(attn_bwd_args(c, pl.ca, blk_dec_cross(i), s0, &pl.n1, ws + W.mem, cur, site_dec(i, 2)));
+        // q projection (input LN1(pre s0), residual gradient, LayerNorm backward) and k / v projections (input = the decoder
+        // memory, gradient accumulated over the layers into gmem) as ONE split phase: a phase's fixed cost (tail + cold
+        // start, ~20 k cycles) is as large as one DAG round of either
+        ProjBwdArgs pq = proj_bwd_args(c, pl.ca, blk_dec_cross(i), s0, &pl.n1, cur, oth);
+        pq.xin2 = ws + W.mem;
+        pq.gout2 = ws + W.gmem;
+        pq.accumulate_out2 = i != DVS_LAYERS - 1;
+        launch_proj_bwd(pq);
+        std::swap(cur, oth);
         // self-attention sublayer: input = LN3 of the previous layer (or the decoder embedding)
-        {
-            const int sp = i > 0 ? slot_dec(i - 1, 2) : dec_in;
-            DvsLN ln = {nullptr, nullptr, nullptr};
-            int64_t og = -1, ob = -1;
-            if (i > 0) {
-                ln = DvsLN{ws + W.stats[sp], P + L.dec[i - 1].n3.w, P + L.dec[i - 1].n3.b};
-                og = L.dec[i - 1].n3.w;
-                ob = L.dec[i - 1].n3.b;
-            }
-            AttnBwdArgs a = attn_bwd_args(d, rec, P, ws, W, pl.sa, blk_dec_self(i), ws + W.act[sp], ln, nullptr, cur, site_dec(i, 0),
-                                          site_dec(i, 1), PT);
-            launch_attn_bwd(a);
-            const float* gy[3] = {ws + W.gq, ws + W.gk, ws + W.gv};
-            ProjBwdArgs pp = proj_bwd_args(d, P, ws, W, blk_dec_self(i), 0, ws + W.act[sp], ln, pl.sa.in_w, pl.sa.in_b, 3, gy, cur, oth, 0, og, ob,
-                                           PT);
-            launch_proj_bwd(pp, 3);
-            float* t = cur; cur = oth; oth = t;
-        }
+        const int sp = i > 0 ? slot_dec(i - 1, 2) : dec_in;
+        const DvsNormP* np = i > 0 ? &L.dec[i - 1].n3 : nullptr;
+        launch_attn_bwd(attn_bwd_args(c, pl.sa, blk_dec_self(i), sp, np, nullptr, cur, site_dec(i, 0)));
+        launch_proj_bwd(proj_bwd_args(c, pl.sa, blk_dec_self(i), sp, np, cur, oth));
+        std::swap(cur, oth);
     }
     flush_stack();
     stack_tag = 1;
@@ -233,12 +202,14 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
     float* freebuf = oth;
 
     // ---- latent block ----------------------------------------------------------------------------------------------
+    // inside the encoder chain when there is one (k_bwd_stack<1>, ahead of the chain's first phase): k_fc_dw then follows
+    // the chain's LAST launch.  Decided HERE: flush_stack() clears has_latent, also when it runs mid-chain.
+    const bool fc_deferred = latent_in_chain(chain, nw);
     FcDwArgs fcdw;
-    bool fc_deferred = false;        // the latent block runs inside the encoder chain: k_fc_dw follows the chain's LAST launch
     {
         LatentBwdArgs a;
         memset(&a, 0, sizeof(a));
-        a.dims = d;
+        a.dims = c.d;
         a.gmem = ws + W.gmem;
         a.mu = ws + W.mu;
         a.logvar = ws + W.logvar;
@@ -247,23 +218,21 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
         a.gcoef = gcoef;
         a.gz = ws + W.gz;
         a.genc = ws + W.genc;
-        static const bool lat_off = getenv("DVS_LATENT_KERNELS") && atoi(getenv("DVS_LATENT_KERNELS")) != 0;
-        if (chain && !lat_off && nw == 8) {     // ahead of the encoder chain's first phase, in the same launch (k_bwd_stack<1>)
+        if (fc_deferred) {
             stack.has_latent = 1;
             stack.lat = a;
-            fc_deferred = true;      // decided HERE: flush_stack() clears has_latent, also when it runs mid-chain
         } else {
             dvs_launch_latent_bwd(a, st);
         }
         FcDwArgs& f = fcdw;
         memset(&f, 0, sizeof(f));
-        f.dims = d;
+        f.dims = c.d;
         f.gz = ws + W.gz;
         f.xenc = ws + W.enc_out;
         f.gmem = ws + W.gmem;
         f.z = ws + W.z;
         f.fcpart = ws + W.fcpart;
-        f.P = PT;
+        f.P = L.total;
         f.o_fc1_w = L.fc1_w;
         f.o_fc1_b = L.fc1_b;
         f.o_fc2_w = L.fc2_w;
@@ -278,55 +247,29 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
     for (int i = DVS_LAYERS - 1; i >= 0; --i) {
         const auto& pl = L.enc[i];
         const int s0 = slot_enc(i, 0), s1 = slot_enc(i, 1);
-        {
-            const DvsLN ln = {ws + W.stats[s0], P + pl.n1.w, P + pl.n1.b};
-            FfnBwdArgs f = ffn_bwd_args(d, P, ws, W, pl.ff, blk_enc_ffn(i), ws + W.act[s0], ln, pl.n1, cur, oth, site_enc(i, 2),
-                                        site_enc(i, 3), PT);
-            if (i == DVS_LAYERS - 1) {   // d enc_out is w.r.t. LN2(pre s1): pull back through it first
-                f.own_pre = ws + W.act[s1];
-                f.own = DvsLN{ws + W.stats[s1], P + pl.n2.w, P + pl.n2.b};
-                f.o_own_g = pl.n2.w;
-                f.o_own_b = pl.n2.b;
-            }
-            launch_ffn_bwd(f);
-            float* t = cur; cur = oth; oth = t;
+        FfnBwdArgs f = ffn_bwd_args(c, pl.ff, blk_enc_ffn(i), s0, pl.n1, cur, oth, site_enc(i, 2));
+        if (i == DVS_LAYERS - 1) {   // d enc_out is w.r.t. LN2(pre s1): pull back through it first
+            f.own_pre = ws + W.act[s1];
+            f.own = ln_of(c, s1, &pl.n2);
+            f.o_own_g = pl.n2.w;
+            f.o_own_b = pl.n2.b;
         }
-        {
-            const int sp = i > 0 ? slot_enc(i - 1, 1) : 0;
-            DvsLN ln = {nullptr, nullptr, nullptr};
-            int64_t og = -1, ob = -1;
-            if (i > 0) {
-                ln = DvsLN{ws + W.stats[sp], P + L.enc[i - 1].n2.w, P + L.enc[i - 1].n2.b};
-                og = L.enc[i - 1].n2.w;
-                ob = L.enc[i - 1].n2.b;
-            }
-            AttnBwdArgs a = attn_bwd_args(d, rec, P, ws, W, pl.sa, blk_enc_attn(i), ws + W.act[sp], ln, nullptr, cur, site_enc(i, 0),
-                                          site_enc(i, 1), PT);
-            launch_attn_bwd(a);
-            const float* gy[3] = {ws + W.gq, ws + W.gk, ws + W.gv};
-            ProjBwdArgs pp = proj_bwd_args(d, P, ws, W, blk_enc_attn(i), 0, ws + W.act[sp], ln, pl.sa.in_w, pl.sa.in_b, 3, gy, cur, oth, 0, og, ob,
-                                           PT);
-            launch_proj_bwd(pp, 3);
-            float* t = cur; cur = oth; oth = t;
-        }
+        launch_ffn_bwd(f);
+        std::swap(cur, oth);
+        const int sp = i > 0 ? slot_enc(i - 1, 1) : 0;
+        const DvsNormP* np = i > 0 ? &L.enc[i - 1].n2 : nullptr;
+        launch_attn_bwd(attn_bwd_args(c, pl.sa, blk_enc_attn(i), sp, np, nullptr, cur, site_enc(i, 0)));
+        launch_proj_bwd(proj_bwd_args(c, pl.sa, blk_enc_attn(i), sp, np, cur, oth));
+        std::swap(cur, oth);
     }
     flush_stack();
     if (fc_deferred) dvs_launch_fc_dw(fcdw, st);
     // ---- embeddings (encoder-side and decoder-side gradients; same weights) --------------------------------------------
     {
-        EmbedArgs e;
-        memset(&e, 0, sizeof(e));
-        e.dims = d;
-        e.rec = rec;
-        e.W1 = P + L.W1;
-        e.W2 = P + L.W2;
-        e.lab_w = P + L.lab_w;
-        e.lab_b = P + L.lab_b;
-        e.embimg = (const float*)((const dvs_bf16*)(ws + W.wimg) + DVS_WIMG_EMB);
-        e.site = 0;
+        EmbedArgs e = embed_args(c, 0);
         e.gout = cur;
         e.slab = ws + W.slabs;
-        e.P = PT;
+        e.P = L.total;
         e.oW1 = L.W1;
         e.oW2 = L.W2;
         e.olab_w = L.lab_w;
@@ -338,12 +281,12 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
     r.slab = ws + W.slabs;
     r.fcpart = ws + W.fcpart;
     r.grads = grads;
-    r.P = PT;
+    r.P = L.total;
     r.nslab = grid;
     r.fc_lo1 = L.fc1_w;
     r.fc_hi1 = L.dec[0].sa.in_w;     // fc1.weight .. fc2.bias are contiguous, the decoder follows
     r.fc_lo2 = L.fc3_w;
-    r.fc_hi2 = PT;
+    r.fc_hi2 = L.total;
     r.sqpart = clip_scratch ? clip_scratch + 2 : nullptr;
     dvs_launch_reduce_slabs(r, st);
     return call_end("dvs_loss_backward");
