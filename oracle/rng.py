@@ -88,3 +88,15 @@ class DeviceMasks:
         u2 = (h2 >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
         n = np.sqrt(np.float32(-2.0) * np.log(u1)) * np.cos(np.float32(6.283185307179586) * u2)
         return (n * self.eps_scale).astype(np.float32)
+
+
+def decode_uniforms(seed: int, B: int, N: int, dag_offset: int = 0):
+    """float32 [B, N, N]: the draws dvs_decode makes itself when no uniforms are passed (csrc/k_decode.hip:
+    decode_uniform): site 200, keyed by the global DAG index dag_offset + b; step idx draws element idx * 64 + k (k = 0 the
+    node type, k = 1 + vi edge candidate vi) and keeps its top 24 bits."""
+    dag = np.arange(B, dtype=np.uint64) + np.uint64(dag_offset)
+    key = site_key(int(seed), 200, dag)[:, None, None]
+    idx = np.arange(N, dtype=np.uint64)[None, :, None]
+    k = np.arange(N, dtype=np.uint64)[None, None, :]
+    h = draw(key, idx * np.uint64(64) + k)
+    return (h >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
