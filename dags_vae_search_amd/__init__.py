@@ -15,3 +15,4 @@ from .datasets import LabeledDagDatasetInMemory, LabeledDagDatasetInMemoryTest  
 from .search import (SearchResult, StructureSet, decoded_structures, generation_metrics, latent_bo_search,  # noqa: F401
                      optimize_acquisition)
 from .recon import evaluate_reconstruction, match_decoded  # noqa: F401
+from .generate import DagStream, create_encoder_dataset, encoder_dag_train_schema, generate_dags  # noqa: F401

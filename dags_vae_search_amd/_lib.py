@@ -23,6 +23,7 @@ LOSS_FLOATS = 5           # DVS_LOSS_FLOATS: total, recon, kld, non-finite flag,
 ABI_VERSION = 202         # DVS_VERSION of include/dvs.h this binding was written against
 GP_ACQ_MAX_INDUCING = 1023  # DVS_GP_ACQ_MAX_INDUCING
 STRUCT_HASH_INVALID = 0x7FFFFFFFFFFFFFFF  # DVS_STRUCT_HASH_INVALID
+GEN_LABELS_CHOICE, GEN_ACCEPT_ISOLATES, GEN_ACCEPT_NO_CONNECTIVITY, GEN_GROUP_SHIFT = 1, 2, 4, 8   # DVS_GEN_* flags
 SCORE_TYPES = {"loglik": 0, "aic": 1, "bic": 2, "bde": 3, "bds": 4, "k2": 5, "bdj": 6}   # dvs_score_type, by bnlearn's name
 
 
@@ -94,6 +95,14 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     #  out, stream)
     lib.dvs_structset_filter.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32,
                                          c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_generate_dags.restype = c_int
+    # (batch, n_vars, card, preds_are_u64, num_edges, seed, dag_offset, try_limit, flags, labels, preds, preds_bytes, attempts,
+    #  stream)
+    lib.dvs_generate_dags.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_int64, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_generate_edge_counts.restype = c_int
+    # (batch, n_entries, edge_counts, cum_weights, seed, dag_offset, num_edges, stream)
+    lib.dvs_generate_edge_counts.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p]
     lib.dvs_debug_launch.restype = c_int
     lib.dvs_debug_launch.argtypes = [c_size_t, c_void_p]
     lib.dvs_bic_scores.restype = c_int
@@ -134,7 +143,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_bic_scores", "dvs_bn_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

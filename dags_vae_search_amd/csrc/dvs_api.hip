@@ -982,6 +982,61 @@ extern "C" int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_
     return call_end("dvs_structset_filter");
 }
 
+// k_generate_dags lives in k_decode.hip (csrc/dvs_generate.h)
+extern "C" int dvs_generate_dags_impl(int B, int n, int card, int wide, const int* num_edges, uint64_t seed, uint32_t dag_offset,
+                                      int try_limit, int flags, int gshift, uint8_t* labels, void* preds, int* attempts,
+                                      void* stream);
+extern "C" int dvs_generate_dags(int32_t batch, int32_t n_vars, int32_t card, int32_t preds_are_u64, const int32_t* num_edges,
+                                 uint64_t seed, int64_t dag_offset, int32_t try_limit, int32_t flags, uint8_t* labels,
+                                 void* preds, size_t preds_bytes, int32_t* attempts, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_generate_dags: batch must be > 0");
+    if (batch > 1 << 30) return fail(2, "dvs_generate_dags: batch must be <= 2^30");
+    if (n_vars < 2 || n_vars > 45) return fail(3, "dvs_generate_dags: n_vars must be in [2, 45]");
+    if (card < 1 || card > 45) return fail(3, "dvs_generate_dags: card must be in [1, 45]");
+    const int group = (flags >> DVS_GEN_GROUP_SHIFT) & 15;
+    if ((flags & ~(7 | 15 << DVS_GEN_GROUP_SHIFT)) || group > 7) return fail(12, "dvs_generate_dags: unknown bits in flags");
+    if (!(flags & DVS_GEN_LABELS_CHOICE) && card < n_vars)
+        return fail(12, "dvs_generate_dags: labels without replacement ('sample') need card >= n_vars");
+    if ((preds_are_u64 != 0) != (n_vars > 13))
+        return fail(12, "dvs_generate_dags: predecessor rows are u16 for n_vars <= 13 and u64 above (preds_are_u64 does not match)");
+    if (try_limit < 1 || try_limit > 4096) return fail(12, "dvs_generate_dags: try_limit must be in [1, 4096]");
+    if (dag_offset < 0) return fail(12, "dvs_generate_dags: dag_offset must be >= 0");
+    if (!num_edges || !labels || !preds || !attempts) return fail(10, "dvs_generate_dags: null pointer");
+    const size_t need = (size_t)batch * n_vars * (preds_are_u64 ? 8 : 2);
+    if (preds_bytes < need) return fail_size("dvs_generate_dags: preds_bytes < batch * n_vars * row bytes", need);
+    // Lanes per DAG: attempts k G .. k G + G - 1 run side by side.  Spare lanes cost little until the launch holds about 16
+    // waves per SIMD (measured, DESIGN.md §13: 64 lanes up to B = 4096, 16 at B = 65 536), and one lane is all an
+    // always-accepted attempt 0 needs.
+    int gshift = 0;
+    if (group) {
+        gshift = group - 1;
+    } else if (!(flags & DVS_GEN_ACCEPT_NO_CONNECTIVITY)) {
+        static const int cus = dvs_device_cus();
+        const int64_t lanes = (int64_t)cus * 4 * 64 * 16;
+        while (gshift < 6 && ((int64_t)batch << (gshift + 1)) <= lanes && (1 << gshift) < try_limit) ++gshift;
+    }
+    call_begin();
+    if (int e = dvs_generate_dags_impl(batch, n_vars, card, preds_are_u64 ? 1 : 0, num_edges, seed, (uint32_t)dag_offset, try_limit,
+                                       flags & 7, gshift, labels, preds, attempts, stream))
+        return e;
+    return call_end("dvs_generate_dags");
+}
+
+extern "C" int dvs_generate_edge_counts_impl(int B, int K, const int* counts, const int* cum, uint64_t seed, uint32_t dag_offset,
+                                             int* out, void* stream);
+extern "C" int dvs_generate_edge_counts(int32_t batch, int32_t n_entries, const int32_t* edge_counts, const int32_t* cum_weights,
+                                        uint64_t seed, int64_t dag_offset, int32_t* num_edges, void* stream) {
+    if (batch <= 0 || batch > 1 << 30) return fail(2, "dvs_generate_edge_counts: batch must be in [1, 2^30]");
+    if (n_entries < 1 || n_entries > 1024) return fail(12, "dvs_generate_edge_counts: n_entries must be in [1, 1024]");
+    if (dag_offset < 0) return fail(12, "dvs_generate_edge_counts: dag_offset must be >= 0");
+    if (!edge_counts || !cum_weights || !num_edges) return fail(10, "dvs_generate_edge_counts: null pointer");
+    call_begin();
+    if (int e = dvs_generate_edge_counts_impl(batch, n_entries, edge_counts, cum_weights, seed, (uint32_t)dag_offset, num_edges,
+                                              stream))
+        return e;
+    return call_end("dvs_generate_edge_counts");
+}
+
 extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
                                    double* local, double* out, int* status, void* stream);
 extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,

@@ -15,6 +15,7 @@
 #include "dvs_decode.h"
 #include "dvs_match.h"          // reconstruction judging of the decoded rows (k_match_decoded)
 #include "dvs_structs.h"        // search candidates: validity / codec / structure key of the decoded rows, seen-set filter
+#include "dvs_generate.h"       // training-graph generator: Erdos-Renyi DAGs into the compact row codec (k_generate_dags)
 
 // per-wave scratch for the record build (lane 0) and the sampling (all lanes)
 struct DecScratch {

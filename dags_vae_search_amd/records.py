@@ -85,6 +85,16 @@ class CompactDagDataset:
         self.n = n
         self.data = encode_graphs(graphs, n).to(device)
 
+    @classmethod
+    def from_compact(cls, batch: CompactBatch, n: int) -> "CompactDagDataset":
+        """Wrap rows that already are the codec (generate.create_encoder_dataset writes them on the device): no host pass."""
+        if batch.labels.dim() != 2 or batch.labels.shape[1] != n or batch.preds.shape != batch.labels.shape:
+            raise ValueError(f"Expected labels / preds of shape [B, {n}], got {tuple(batch.labels.shape)} / {tuple(batch.preds.shape)}")
+        self = cls.__new__(cls)
+        self.n = n
+        self.data = batch
+        return self
+
     def __len__(self) -> int:
         return len(self.data)
 

@@ -228,6 +228,43 @@ int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_t* sorted_h
                          const uint64_t* seen_hashes, const uint64_t* seen_keys, size_t seen_keys_bytes, uint8_t* out,
                          void* stream);
 
+/* Training graphs on the device: `batch` Erdos-Renyi DAGs (the reference's LabeledDag.generate_random_graph_erdos_renyi,
+ * src/toolkit/labeled.py:281-333) written as the row codec of dvs_build_records, one launch, no host pass.
+ * DAG b has n_vars vertices and m = num_edges[b] (device i32 [batch]) edges among the P = n_vars (n_vars - 1) / 2 slots;
+ * slot t = v (v - 1) / 2 + u is the edge u -> v, u < v (igraph's Erdos_Renyi(n, m) + to_directed("acyclic"): a uniform
+ * m-subset of the unordered pairs, oriented low -> high).  With the counter-based draws of the dropout masks
+ * (key = site_key(seed, site, dag_offset + b), sites 300 edges / 301 labels), attempt a = 0, 1, .. takes slot t, in slot
+ * order, iff (draw(key_e, a * 1024 + t) * (P - t)) >> 32 < m - (slots taken so far): selection sampling, exactly m edges.
+ * The result is the first attempt in attempt order that is weakly connected over all vertices (over the vertices of degree
+ * >= 1 with DVS_GEN_ACCEPT_ISOLATES; attempt 0 with DVS_GEN_ACCEPT_NO_CONNECTIVITY).  Labels, drawn once after acceptance:
+ * without replacement ('sample', needs card >= n_vars: r = (draw(key_l, v) * (card - v)) >> 32, the r-th lowest unused
+ * value) or, with DVS_GEN_LABELS_CHOICE, (draw(key_l, v) * card) >> 32.  Vertices are in generation order, which is
+ * topological.  labels: device u8 [batch][n_vars]; preds: device [batch][n_vars], u16 for n_vars <= 13 and u64 above
+ * (preds_are_u64 must say so), bit u of preds[b][v] <=> u -> v; attempts: device i32 [batch]: the 1-based accepted attempt,
+ * 0 when none of try_limit was accepted, -1 when m is outside [n_vars - 1, P]; for 0 and -1 the DAG's rows are zero.
+ * A pure function of (seed, dag_offset + b, m, n_vars, card, try_limit, flags & 7): two calls give equal bytes, a batch
+ * split over calls or ranks by dag_offset gives the bytes of the whole batch, and the lane mapping does not matter.
+ * Bits DVS_GEN_GROUP_SHIFT .. +3 of flags, tuning only: 0 lets the library choose how many lanes share a DAG (they try
+ * consecutive attempts side by side, the lowest accepted one wins), k = 1 .. 7 asks for 2^(k-1).
+ * 2 <= n_vars <= 45, 1 <= card <= 45, 1 <= try_limit <= 4096, batch <= 2^30; code 14 with the needed size for a short preds
+ * buffer.  (Added in ABI 202 as a pure addition: the version number stays.) */
+#define DVS_GEN_LABELS_CHOICE 1
+#define DVS_GEN_ACCEPT_ISOLATES 2
+#define DVS_GEN_ACCEPT_NO_CONNECTIVITY 4
+#define DVS_GEN_GROUP_SHIFT 8
+int dvs_generate_dags(int32_t batch, int32_t n_vars, int32_t card, int32_t preds_are_u64, const int32_t* num_edges,
+                      uint64_t seed, int64_t dag_offset, int32_t try_limit, int32_t flags, uint8_t* labels, void* preds,
+                      size_t preds_bytes, int32_t* attempts, void* stream);
+
+/* Per-DAG edge counts for dvs_generate_dags, drawn on the device: DAG b gets edge_counts[i] (device i32 [n_entries]) with
+ * probability weight_i / W, where cum_weights (device i32 [n_entries]) holds the running sums of the positive integer
+ * weights and W = cum_weights[n_entries - 1] < 2^31: i is the first entry with cum_weights[i] > (draw(key_m, 0) * W) >> 32,
+ * key_m = site_key(seed, 302, dag_offset + b).  num_edges: device i32 [batch].  The mixture of a shuffled curriculum data
+ * set (schema entry i weighs (i + 1)^2), sharded by dag_offset like the graphs themselves.  1 <= n_entries <= 1024.
+ * (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_generate_edge_counts(int32_t batch, int32_t n_entries, const int32_t* edge_counts, const int32_t* cum_weights,
+                             uint64_t seed, int64_t dag_offset, int32_t* num_edges, void* stream);
+
 /* BIC of B discrete Bayesian-network structures on one data set (replaces BNLearnWrapper.score,
  * src/problem/bn/bnlearn.py:27-61 = `Rscript bnlearn_score.R`: bnlearn::score(net, data, type = "bic")).
  * data: device u64 [n_samples][ceil(n_vars/16)], variable i's level code (0..15) in bits 4*(i%16).. of word i/16;
