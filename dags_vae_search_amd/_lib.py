@@ -111,6 +111,16 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.dvs_bn_scores.restype = c_int
     lib.dvs_bn_scores.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_double, c_void_p,
                                   c_void_p, c_void_p, c_void_p]
+    lib.dvs_bn_toggle_scores.restype = c_int
+    # (batch, n_vars, n_samples, data, card, parents, score_type, score_arg, worklist (nullable), local, local_bytes, toggles,
+    #  toggles_bytes, status, stream)
+    lib.dvs_bn_toggle_scores.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_double,
+                                         c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_hc_step.restype = c_int
+    # (batch, n_vars, parents, local, toggles, toggles_bytes, max_parents, min_delta, forbidden (nullable), step_cap, worklist,
+    #  steps, converged, flags, trace (nullable), trace_bytes, active, stream)
+    lib.dvs_hc_step.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, ctypes.c_double, c_void_p,
+                                c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.dvs_bic_parent_masks.restype = c_int
     lib.dvs_bic_parent_masks.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dvs_gp_predict.restype = c_int
@@ -143,7 +153,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

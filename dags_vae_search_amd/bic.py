@@ -113,11 +113,9 @@ class BNLearnWrapper:
                              "cells; sorted samples: 16 384 samples, 63 key bits)")
         return (out, scratch) if local else out
 
-    def score_compact(self, batch) -> torch.Tensor:
-        """Score of a ``CompactBatch`` (records.py) that lives on the device -> float64 [B] on the device: the relabelling
-        (dvs_bic_parent_masks) and the scoring (dvs_bic_scores / dvs_bn_scores) are both HIP launches, nothing touches
-        the host."""
-        labels = batch.labels.to(self.device).contiguous()
+    def _compact_parent_masks(self, batch):
+        """(parent masks, the relabelling's status word), both on the device and unchecked"""
+        labels =batch.labels.to(self.device).contiguous()
         preds = batch.preds.to(self.device).contiguous()
         B, n = labels.shape
         assert n == self.n_vars, f"Expected {self.n_vars} vertices, but got {n}"                             # bnlearn.py:34
@@ -128,10 +126,49 @@ class BNLearnWrapper:
                                                          p(parents), p(status),
                                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                  "dvs_bic_parent_masks")
+        return parents, status
+
+    def compact_parent_masks(self, batch) -> torch.Tensor:
+        """Parent masks (int64 [B, n_vars], data-set variable indices) of a ``CompactBatch`` that lives on the device: the
+        relabelling of bnlearn.py:34-45 as one HIP launch (dvs_bic_parent_masks).  What ``score_masks``, ``toggle_scores``
+        and ``hill_climb`` take."""
+        parents, status = self._compact_parent_masks(batch)
+        if int(status.item()) & 32:
+            raise AssertionError(f"Expected graph labels from 0 to {self.n_vars - 1}")                        # bnlearn.py:35
+        return parents
+
+    def score_compact(self, batch) -> torch.Tensor:
+        """Score of a ``CompactBatch`` (records.py) that lives on the device -> float64 [B] on the device: the relabelling
+        (dvs_bic_parent_masks) and the scoring (dvs_bic_scores / dvs_bn_scores) are both HIP launches, nothing touches
+        the host."""
+        parents, status = self._compact_parent_masks(batch)
         out = self.score_masks(parents)
         if int(status.item()) & 32:
-            raise AssertionError(f"Expected graph labels from 0 to {n - 1}")                                  # bnlearn.py:35
+            raise AssertionError(f"Expected graph labels from 0 to {self.n_vars - 1}")                        # bnlearn.py:35
         return out
+
+    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
+        """The single-edge neighbourhood of every structure (dvs_bn_toggle_scores) -> (L f64 [B, n_vars],
+        T f64 [B, n_vars, n_vars]) on the device: L the local scores as ``score_masks(local=True)`` gives them, T[b, v, u]
+        the local score of v with bit u of ``parents[b, v]`` flipped (NaN on the diagonal and where the family is refused:
+        that move is not available).  ``worklist`` (int32 [2 B], ``hill_climb``'s) with ``out=(L, T)`` recomputes only
+        the rows it names, in place.  ``return_status`` appends the status word (bit 4: some family was refused)."""
+        parents = parents.to(self.device).contiguous()
+        B, n = parents.shape
+        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
+        if out is None:
+            if worklist is not None:
+                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
+            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
+                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
+        L, T = out
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        dl.check(self.lib, self.lib.dvs_bn_toggle_scores(
+            B, n, self.n_samples, p(self._data), p(self._card), p(parents), dl.SCORE_TYPES[self.metric_name], self._score_arg,
+            None if worklist is None else p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status),
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_toggle_scores")
+        return (L, T, status) if return_status else (L, T)
 
     def score(self, labeled_graph, label_key: str = LABEL_KEY) -> float:
         return self.score_batch([labeled_graph], label_key)[0]

@@ -1049,6 +1049,43 @@ extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, 
     return call_end("dvs_bic_scores");
 }
 
+// score_type / score_arg of dvs_bn_scores and dvs_bn_toggle_scores -> the argument the kernels take (include/dvs.h)
+static int bn_score_arg(const char* fn, int score_type, double score_arg, double* arg) {
+    char msg[160];
+    const bool dflt = score_arg != score_arg;               // NaN: the type's default
+    *arg = score_arg;
+    switch (score_type) {
+        case DVS_SCORE_LOGLIK:
+        case DVS_SCORE_K2:
+        case DVS_SCORE_BDJ:
+            if (!dflt) {
+                snprintf(msg, sizeof(msg), "%s: loglik, k2 and bdj take no argument (score_arg must be NaN)", fn);
+                return fail(13, msg);
+            }
+            *arg = 0.0;                                     // loglik is the penalised likelihood at k = 0
+            return 0;
+        case DVS_SCORE_AIC:
+        case DVS_SCORE_BIC:
+            if (!dflt && !(score_arg >= 0.0 && isfinite(score_arg))) {
+                snprintf(msg, sizeof(msg), "%s: k must be finite and >= 0", fn);
+                return fail(13, msg);
+            }
+            if (dflt && score_type == DVS_SCORE_AIC) *arg = 1.0;     // bic's default, log(S) / 2, is taken on the device
+            return 0;
+        case DVS_SCORE_BDE:
+        case DVS_SCORE_BDS:
+            if (!dflt && !(score_arg > 0.0 && isfinite(score_arg))) {
+                snprintf(msg, sizeof(msg), "%s: iss must be finite and > 0", fn);
+                return fail(13, msg);
+            }
+            if (dflt) *arg = 1.0;
+            return 0;
+        default:
+            snprintf(msg, sizeof(msg), "%s: score_type is not a dvs_score_type", fn);
+            return fail(12, msg);
+    }
+}
+
 extern "C" int dvs_bn_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
                                   int type, double arg, double* local, double* out, int* status, void* stream);
 extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
@@ -1057,32 +1094,63 @@ extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, c
     if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores: batch and n_samples must be > 0");
     if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores: n_vars must be in [1, 48]");
     if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bn_scores: null pointer");
-    const bool dflt = score_arg != score_arg;               // NaN: the type's default
     double arg = score_arg;
-    switch (score_type) {
-        case DVS_SCORE_LOGLIK:
-        case DVS_SCORE_K2:
-        case DVS_SCORE_BDJ:
-            if (!dflt) return fail(13, "dvs_bn_scores: loglik, k2 and bdj take no argument (score_arg must be NaN)");
-            arg = 0.0;                                      // loglik is the penalised likelihood at k = 0
-            break;
-        case DVS_SCORE_AIC:
-        case DVS_SCORE_BIC:
-            if (!dflt && !(score_arg >= 0.0 && isfinite(score_arg))) return fail(13, "dvs_bn_scores: k must be finite and >= 0");
-            if (dflt && score_type == DVS_SCORE_AIC) arg = 1.0;      // bic's default, log(S) / 2, is taken on the device
-            break;
-        case DVS_SCORE_BDE:
-        case DVS_SCORE_BDS:
-            if (!dflt && !(score_arg > 0.0 && isfinite(score_arg))) return fail(13, "dvs_bn_scores: iss must be finite and > 0");
-            if (dflt) arg = 1.0;
-            break;
-        default:
-            return fail(12, "dvs_bn_scores: score_type is not a dvs_score_type");
-    }
+    if (int e = bn_score_arg("dvs_bn_scores", score_type, score_arg, &arg)) return e;
     call_begin();
     if (int e = dvs_bn_scores_impl(batch, n_vars, n_samples, data, card, parents, score_type, arg, scratch, out, status, stream))
         return e;
     return call_end("dvs_bn_scores");
+}
+
+// k_bn_toggle / k_hc_step live in k_bic.hip (csrc/dvs_hillclimb.h)
+extern "C" int dvs_bn_toggle_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
+                                         int type, double arg, const int* worklist, double* local, double* toggles, int* status,
+                                         void* stream);
+extern "C" int dvs_bn_toggle_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                                    const uint64_t* parents, int32_t score_type, double score_arg, const int32_t* worklist,
+                                    double* local, size_t local_bytes, double* toggles, size_t toggles_bytes, int32_t* status,
+                                    void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_toggle_scores: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_toggle_scores: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff)
+        return fail(2, "dvs_bn_toggle_scores: batch * n_vars^2 must be < 2^31");
+    if (!data || !card || !parents || !local || !toggles || !status) return fail(10, "dvs_bn_toggle_scores: null pointer");
+    double arg = score_arg;
+    if (int e = bn_score_arg("dvs_bn_toggle_scores", score_type, score_arg, &arg)) return e;
+    if (local_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_bn_toggle_scores: local_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    if (toggles_bytes < (size_t)batch * n_vars * n_vars * 8)
+        return fail_size("dvs_bn_toggle_scores: toggles_bytes < batch * n_vars^2 * 8", (size_t)batch * n_vars * n_vars * 8);
+    call_begin();
+    if (int e = dvs_bn_toggle_scores_impl(batch, n_vars, n_samples, data, card, parents, score_type, arg, worklist, local, toggles,
+                                          status, stream))
+        return e;
+    return call_end("dvs_bn_toggle_scores");
+}
+
+extern "C" int dvs_hc_step_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
+                                double min_delta, const uint64_t* forbidden, int step_cap, int* worklist, int* steps,
+                                int* converged, int* flags, int64_t* trace, int* active, void* stream);
+extern "C" int dvs_hc_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                           size_t toggles_bytes, int32_t max_parents, double min_delta, const uint64_t* forbidden,
+                           int32_t step_cap, int32_t* worklist, int32_t* steps, int32_t* converged, int32_t* flags,
+                           int64_t* trace, size_t trace_bytes, int32_t* active, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_hc_step: batch must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_hc_step: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return fail(2, "dvs_hc_step: batch * n_vars^2 must be < 2^31");
+    if (!parents || !local || !toggles || !worklist || !steps || !converged || !flags || !active)
+        return fail(10, "dvs_hc_step: null pointer");
+    if (min_delta != min_delta) return fail(13, "dvs_hc_step: min_delta must not be NaN");
+    if (step_cap < 1) return fail(13, "dvs_hc_step: step_cap must be >= 1");
+    if (toggles_bytes < (size_t)batch * n_vars * n_vars * 8)
+        return fail_size("dvs_hc_step: toggles_bytes < batch * n_vars^2 * 8", (size_t)batch * n_vars * n_vars * 8);
+    if (trace && trace_bytes < (size_t)batch * step_cap * 16)
+        return fail_size("dvs_hc_step: trace_bytes < batch * step_cap * 16", (size_t)batch * step_cap * 16);
+    call_begin();
+    if (int e = dvs_hc_step_impl(batch, n_vars, parents, local, toggles, max_parents, min_delta, forbidden, step_cap, worklist,
+                                 steps, converged, flags, trace, active, stream))
+        return e;
+    return call_end("dvs_hc_step");
 }
 
 extern "C" int dvs_bic_parent_masks_impl(int B, int n, int wide, const uint8_t* labels, const void* preds, uint64_t* parents,

@@ -1,0 +1,227 @@
+// Greedy hill climbing over single-edge moves in structure space, next to the scorer it uses.  Included by
+// k_bic.hip after bn_family_score.
+//
+//   k_bn_toggle<FAMILY>  T[b][v][u] = local score of variable v with parent set P[b][v] xor (1 << u), L[b][v] = the local
+//                        score as it stands.  One workgroup per cell, each a bn_family_score call: the bytes of k_bic_local
+//                        for that parent set.  One table prices all three moves on u -> v:
+//                            add / delete   T[v][u] - L[v]
+//                            reverse        (T[v][u] - L[v]) + (T[u][v] - L[u])
+//                        Full pass: all B n rows.  Incremental pass: the rows named in the worklist, whose slots 2b and
+//                        2b + 1 belong to structure b and hold a variable index or -1 (k_hc_step writes them: no atomics,
+//                        no order); workgroups of an empty slot exit at once.
+//   k_hc_step            one wave per structure, lane = variable, the lane's parent row one u64: ancestor closure by n
+//                        rounds of row broadcasts, legality and delta of every move, the best one across lanes (largest
+//                        fp64 delta, exact ties to the lowest code = op n^2 + v n + u), applied if delta > min_delta.
+#pragma once
+
+struct ToggleArgs {
+    BicArgs s;                   // s.local = L [B][n]; s.out unused
+    const int* worklist;         // null: full pass; else i32 [2 B]
+    double* toggles;             // T [B][n][n]
+};
+
+template <int FAMILY>
+__global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
+    DVS_DYN_LDS(smem);
+    const int n = t.s.n;
+    const int u = blockIdx.x % n, row = blockIdx.x / n;
+    int dag, v;
+    if (t.worklist != nullptr) {
+        v = t.worklist[row];
+        dag = row >> 1;
+        if (v < 0 || v >= n || u == v) return;       // empty slot; L of a moved row is the T cell of the move (k_hc_step)
+    } else {
+        v = row % n;
+        dag = row / n;
+    }
+    const size_t cell = (size_t)dag * n + v;
+    const double score = bn_family_score<FAMILY>(t.s, v, t.s.parents + cell, u == v ? 0ull : 1ull << u, smem);
+    if (threadIdx.x == 0) {
+        if (u == v) {
+            t.s.local[cell] = score;
+            t.toggles[cell * n + u] = __longlong_as_double(0x7ff8000000000000LL);
+        } else {
+            t.toggles[cell * n + u] = score;
+        }
+    }
+}
+
+void dvs_launch_bn_toggle(const ToggleArgs& t, dvs_stream_t st) {
+    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
+    const unsigned rows = t.worklist != nullptr ? 2u * (unsigned)t.s.B : (unsigned)t.s.B * (unsigned)t.s.n;
+    if (t.s.type <= DVS_SCORE_BIC) {
+        DVS_SET_LDS(k_bn_toggle<0>, lds);
+        DVS_LAUNCH_AS("k_bn_toggle", k_bn_toggle<0>, dim3(rows * (unsigned)t.s.n), dim3(256), lds, st, t);
+    } else {
+        DVS_SET_LDS(k_bn_toggle<1>, lds);
+        DVS_LAUNCH_AS("k_bn_toggle_dirichlet", k_bn_toggle<1>, dim3(rows * (unsigned)t.s.n), dim3(256), lds, st, t);
+    }
+}
+
+extern "C" int dvs_bn_toggle_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
+                                         int type, double arg, const int* worklist, double* local, double* toggles, int* status,
+                                         void* stream) {
+    ToggleArgs t;
+    t.s.type = type;
+    t.s.arg = arg;
+    t.s.B = B;
+    t.s.n = n;
+    t.s.S = S;
+    t.s.words = (n + 15) / 16;
+    t.s.data = data;
+    t.s.card = card;
+    t.s.parents = parents;
+    t.s.local = local;
+    t.s.out = nullptr;
+    t.s.status = status;
+    t.worklist = worklist;
+    t.toggles = toggles;
+    dvs_launch_bn_toggle(t, (dvs_stream_t)stream);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// One greedy step
+// ---------------------------------------------------------------------------------------------------------
+struct HcArgs {
+    int B, n, max_parents, step_cap;
+    double min_delta;
+    uint64_t* parents;           // [B][n], updated in place
+    double* local;               // L [B][n], the moved rows updated from T
+    const double* toggles;       // T [B][n][n]
+    const uint64_t* forbidden;   // [n] or null: bit u of forbidden[v] bars u -> v
+    int* worklist;               // [2 B]
+    int* steps;                  // [B]
+    int* converged;              // [B]
+    int* flags;                  // [B]: 1 the start has a cycle, 2 a local score of the start is NaN
+    int64_t* trace;              // null or [B][step_cap][2]: (code, delta bits)
+    int* active;                 // += structures that moved in this launch
+};
+constexpr int HC_NO_MOVE = 0x7fffffff;
+
+__device__ __forceinline__ uint64_t hc_bcast64(uint64_t x, int src) {
+    int lo = (int)(x & 0xffffffffull), hi = (int)(x >> 32);
+    lo = __shfl(lo, src);
+    hi = __shfl(hi, src);
+    return ((uint64_t)(unsigned)hi << 32) | (uint64_t)(unsigned)lo;
+}
+// (delta, code) beats (bd, bc): larger delta, exact ties to the lower code — a total order, so the reduction tree's shape
+// cannot change the winner
+__device__ __forceinline__ void hc_consider(double d, int c, double& bd, int& bc) {
+    if (d > bd || (d == bd && c < bc)) {
+        bd = d;
+        bc = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const int n = a.n;
+    const bool live = lane < n;
+    const int nsteps = a.steps[b];
+    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) {          // wave-uniform
+        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        return;
+    }
+    const size_t base = (size_t)b * n;
+    const uint64_t row = live ? a.parents[base + lane] : 0ull;
+    const double Lv = live ? a.local[base + lane] : 0.0;
+    const uint64_t self = 1ull << lane;
+    // reach[v]: the ancestors of v (bit-row Warshall: after round k every path through 0 .. k is in)
+    uint64_t reach = row;
+    for (int k = 0; k < n; ++k) {
+        const uint64_t rk = hc_bcast64(reach, k);
+        if ((reach >> k) & 1ull) reach |= rk;
+    }
+    int fl = 0;
+    if (__ballot(live && (reach & self) != 0)) fl |= 1;
+    if (__ballot(live && Lv != Lv)) fl |= 2;
+    if (fl) {
+        if (lane == 0) a.flags[b] = fl;
+        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        return;
+    }
+    const bool capped = a.max_parents > 0;
+    const int npar = __popcll(row);
+    const uint64_t forb_v = (a.forbidden != nullptr && live) ? a.forbidden[lane] : 0ull;
+    const double* T = a.toggles + base * n;
+    const int nn = n * n;
+    double best = -__builtin_inf();
+    int bcode = HC_NO_MOVE;
+    for (int u = 0; u < n; ++u) {
+        const uint64_t child_u = __ballot(live && ((row >> u) & 1ull) != 0);
+        const uint64_t row_u = hc_bcast64(row, u), reach_u = hc_bcast64(reach, u);
+        const double L_u = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(Lv), u));
+        if (!live || u == lane) continue;
+        const double t_vu = T[lane * n + u];
+        if (t_vu != t_vu) continue;                               // a refused family: the move is not available
+        const double d_v = t_vu - Lv;
+        const uint64_t ubit = 1ull << u;
+        if (!(row & ubit)) {
+            if (!((reach_u >> lane) & 1ull) && !(capped && npar >= a.max_parents) && !(forb_v & ubit))
+                hc_consider(d_v, lane * n + u, best, bcode);
+        } else {
+            hc_consider(d_v, nn + lane * n + u, best, bcode);
+            const double t_uv = T[u * n + lane];
+            const uint64_t forb_u = a.forbidden != nullptr ? a.forbidden[u] : 0ull;
+            if (t_uv == t_uv && !((child_u & ~self) & (reach | self)) && !(capped && __popcll(row_u) >= a.max_parents) &&
+                !(forb_u & self))
+                hc_consider(d_v + (t_uv - L_u), 2 * nn + lane * n + u, best, bcode);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const double od = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(best), lane ^ s));
+        const int oc = __shfl(bcode, lane ^ s);
+        hc_consider(od, oc, best, bcode);
+    }
+    if (bcode != HC_NO_MOVE && best > a.min_delta) {
+        const int op = bcode / nn, v = (bcode % nn) / n, u = bcode % n;
+        if (lane == v) {
+            a.parents[base + v] = row ^ (1ull << u);
+            a.local[base + v] = T[v * n + u];
+        }
+        if (op == 2 && lane == u) {
+            a.parents[base + u] = row | (1ull << v);
+            a.local[base + u] = T[u * n + v];
+        }
+        if (lane == 0) {
+            a.worklist[2 * b] = v;
+            a.worklist[2 * b + 1] = op == 2 ? u : -1;
+            a.steps[b] = nsteps + 1;
+            if (a.trace != nullptr) {
+                int64_t* t = a.trace + ((size_t)b * a.step_cap + nsteps) * 2;
+                t[0] = bcode;
+                t[1] = (int64_t)__double_as_longlong(best);
+            }
+            atomicAdd(a.active, 1);
+        }
+    } else {
+        if (lane == 0) a.converged[b] = 1;
+        if (lane < 2) a.worklist[2 * b + lane] = -1;
+    }
+}
+
+extern "C" int dvs_hc_step_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
+                                double min_delta, const uint64_t* forbidden, int step_cap, int* worklist, int* steps,
+                                int* converged, int* flags, int64_t* trace, int* active, void* stream) {
+    HcArgs a;
+    a.B = B;
+    a.n = n;
+    a.max_parents = max_parents;
+    a.step_cap = step_cap;
+    a.min_delta = min_delta;
+    a.parents = parents;
+    a.local = local;
+    a.toggles = toggles;
+    a.forbidden = forbidden;
+    a.worklist = worklist;
+    a.steps = steps;
+    a.converged = converged;
+    a.flags = flags;
+    a.trace = trace;
+    a.active = active;
+    DVS_LAUNCH(k_hc_step, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
+    return 0;
+}

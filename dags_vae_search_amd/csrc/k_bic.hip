@@ -91,19 +91,24 @@ __device__ __forceinline__ void bn_prior(const BicArgs& a, int r, double q, cons
 //   sort:      larger parent sets (sachs: >= 9 ternary parents) are sparse — at most S cells are occupied — so the
 //              bit-packed 64-bit (configuration, state) keys of the S samples are bitonic-sorted in LDS and the counts
 //              are run lengths found by binary search.
+//
+// bn_family_score is the whole of that for one (variable, parent set): the local score of variable v under the parent mask
+// (*pmask ^ flip) with v's own bit masked off.  Every thread of the workgroup calls it (it holds barriers); thread 0 gets
+// the score, NaN (and status bit 4) when the family is refused.  k_bic_local instantiates it with flip = 0 for the mask as
+// it stands, k_bn_toggle (dvs_hillclimb.h) with one bit flipped: the same instructions in the same order, so the two
+// kernels give equal bytes for equal parent sets.
 template <int FAMILY>
-__global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
-    DVS_DYN_LDS(smem);
+__device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v, const uint64_t* pmask, const uint64_t flip,
+                                                  char* smem) {
     __shared__ double red[256];
     __shared__ int par_id[48], par_stride[48], par_shift[48];
     __shared__ int s_np, s_mode, s_rbits;
     __shared__ double s_q;
     __shared__ int s_qobs;                                   // family 1, bds: parent configurations observed in the data
     __shared__ double s_aj, s_ajk, s_lg_aj, s_lg_ajk;        // family 1: the prior's a_j, a_jk and their lgamma
-    const int v = blockIdx.x % a.n, dag = blockIdx.x / a.n;
     const int r = a.card[v];
     if (threadIdx.x == 0) {
-        uint64_t pm = a.parents[(size_t)dag * a.n + v] & ~(1ull << v);
+        uint64_t pm = (*pmask ^ flip) & ~(1ull << v);
         double q = 1.0;
         long long qi = 1;
         int np = 0, bits = bic_bits(r), mode = 0;          // mode 0 histogram, 1 sort, -1 unsupported
@@ -131,11 +136,8 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
     __syncthreads();
     const int np = s_np, mode = s_mode;
     if (mode < 0) {
-        if (threadIdx.x == 0) {
-            atomicOr(a.status, 16);
-            a.local[(size_t)dag * a.n + v] = __longlong_as_double(0x7ff8000000000000LL);
-        }
-        return;
+        if (threadIdx.x == 0) atomicOr(a.status, 16);
+        return __longlong_as_double(0x7ff8000000000000LL);
     }
     double acc = 0.0;
     if (mode == 0) {
@@ -249,15 +251,28 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
+    double score = 0.0;
     if (threadIdx.x == 0) {
         if constexpr (FAMILY == 0) {
             const double k = a.arg != a.arg ? 0.5 * log((double)a.S) : a.arg;
-            a.local[(size_t)dag * a.n + v] = red[0] - k * (double)(r - 1) * s_q;
+            score = red[0] - k * (double)(r - 1) * s_q;
         } else {
-            a.local[(size_t)dag * a.n + v] = red[0];
+            score = red[0];
         }
     }
+    return score;
 }
+
+template <int FAMILY>
+__global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
+    DVS_DYN_LDS(smem);
+    const int v = blockIdx.x % a.n, dag = blockIdx.x / a.n;
+    const size_t cell = (size_t)dag * a.n + v;
+    const double score = bn_family_score<FAMILY>(a, v, a.parents + cell, 0ull, smem);
+    if (threadIdx.x == 0) a.local[cell] = score;
+}
+
+#include "dvs_hillclimb.h"
 
 __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
     const int dag = blockIdx.x * blockDim.x + threadIdx.x;

@@ -308,6 +308,46 @@ int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64
                   const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
                   int32_t* status, void* stream);
 
+/* Greedy hill climbing over single-edge moves, step 1 of 2: the neighbourhood's local scores.
+ *   toggles[b][v][u] (device f64 [B][n_vars][n_vars]) = the local score of variable v with parent set parents[b][v] xor
+ *   (1 << u), u != v (the diagonal is NaN); local[b][v] (device f64 [B][n_vars]) = the local score as it stands.
+ * One table prices every move on u -> v: add and delete are toggles[v][u] - local[v], a reversal is
+ * (toggles[v][u] - local[v]) + (toggles[u][v] - local[u]).  Every cell is, bit for bit, what dvs_bn_scores writes into
+ * scratch[.][v] for a row holding that parent set (same score_type / score_arg, data, card, limits); a refused family
+ * (table too large for both counting paths, a parent bit >= n_vars) is NaN in its cell alone and sets status bit 4 — it
+ * means "this move is not available", not an error.
+ * worklist null: all B * n_vars rows.  worklist device i32 [2 * batch] (written by dvs_hc_step): slots 2b and 2b + 1 name
+ * the rows of structure b to recompute, -1 = none; only those rows of toggles are written, local is left to dvs_hc_step.
+ * Checked before anything is enqueued: codes 12 / 13 as dvs_bn_scores, 14 with the needed size for local_bytes <
+ * batch * n_vars * 8 or toggles_bytes < batch * n_vars^2 * 8; batch * n_vars^2 < 2^31.  (Added in ABI 202 as a pure addition:
+ * the version number stays.) */
+int dvs_bn_toggle_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                         const uint64_t* parents, int32_t score_type, double score_arg, const int32_t* worklist,
+                         double* local, size_t local_bytes, double* toggles, size_t toggles_bytes, int32_t* status,
+                         void* stream);
+
+/* Step 2 of 2: one greedy move per structure, in place.  With reach[v] the ancestors of v in parents[b]:
+ *   add u -> v      u not in P[v], v not an ancestor of u, |P[v]| < max_parents, bit u not in forbidden[v]
+ *   delete u -> v   u in P[v]
+ *   reverse u -> v  u in P[v], no child of u other than v is v's ancestor, |P[u]| < max_parents, bit v not in forbidden[u]
+ * and every toggles cell the move's delta reads is not NaN.  The move with the largest fp64 delta (expressions above, in
+ * that operand order) wins, exact ties go to the lowest code = op * n_vars^2 + v * n_vars + u (op 0 add, 1 delete,
+ * 2 reverse).  If delta > min_delta: parents' rows are updated, local[v] (and local[u]) are copied from toggles, the
+ * changed rows go into worklist slots 2b, 2b + 1 (for dvs_bn_toggle_scores), steps[b] += 1 and, with trace (device i64
+ * [batch][step_cap][2], nullable), (code, the delta's bits) is stored at trace[b][steps[b] before the move].  Otherwise
+ * converged[b] = 1 and both slots are -1.  A structure with converged[b], flags[b] or steps[b] >= step_cap is left alone.
+ * flags[b] (device i32, zeroed by the caller): bit 0 the structure has a cycle, bit 1 one of its local scores is NaN;
+ * either freezes it at zero steps.  max_parents <= 0: no cap.  forbidden: device u64 [n_vars] shared by the batch, nullable.
+ * steps, converged: device i32 [batch], zeroed by the caller before the first step.  *active (device i32, zeroed by the
+ * caller) += the number of structures that moved in this call.  Nothing depends on the order in which structures are
+ * processed: two runs give equal bytes.  Codes: 13 for a NaN min_delta or step_cap < 1, 14 with the needed size for
+ * toggles_bytes < batch * n_vars^2 * 8 or trace_bytes < batch * step_cap * 16.  (Added in ABI 202 as a pure addition: the
+ * version number stays.) */
+int dvs_hc_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles, size_t toggles_bytes,
+                int32_t max_parents, double min_delta, const uint64_t* forbidden, int32_t step_cap, int32_t* worklist,
+                int32_t* steps, int32_t* converged, int32_t* flags, int64_t* trace, size_t trace_bytes, int32_t* active,
+                void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
