@@ -17,3 +17,4 @@ from .search import (SearchResult, StructureSet, decoded_structures, generation_
 from .recon import evaluate_reconstruction, match_decoded  # noqa: F401
 from .generate import DagStream, create_encoder_dataset, encoder_dag_train_schema, generate_dags  # noqa: F401
 from .hillclimb import HillClimbResult, decode_move, hill_climb  # noqa: F401
+from .tabu import TabuResult, tabu_search  # noqa: F401

@@ -1153,6 +1153,63 @@ extern "C" int dvs_hc_step(int32_t batch, int32_t n_vars, uint64_t* parents, dou
     return call_end("dvs_hc_step");
 }
 
+// k_tabu_step / k_hc_perturb live in k_bic.hip (csrc/dvs_tabu.h)
+extern "C" int dvs_tabu_step_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
+                                  double min_delta, const uint64_t* forbidden, int step_cap, int* worklist, int* steps,
+                                  int* converged, int* flags, int64_t* trace, int* active, int tabu_len, uint64_t* ring,
+                                  int* visited, int max_stall, int* stall, double* best_score, uint64_t* best_parents,
+                                  void* stream);
+extern "C" int dvs_tabu_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                             size_t toggles_bytes, int32_t max_parents, double min_delta, const uint64_t* forbidden,
+                             int32_t step_cap, int32_t* worklist, int32_t* steps, int32_t* converged, int32_t* flags,
+                             int64_t* trace, size_t trace_bytes, int32_t* active, int32_t tabu_len, uint64_t* ring,
+                             size_t ring_bytes, int32_t* visited, int32_t max_stall, int32_t* stall, double* best_score,
+                             uint64_t* best_parents, size_t best_bytes, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_tabu_step: batch must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_tabu_step: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return fail(2, "dvs_tabu_step: batch * n_vars^2 must be < 2^31");
+    if (!parents || !local || !toggles || !worklist || !steps || !converged || !flags || !active || !ring || !visited || !stall ||
+        !best_score || !best_parents)
+        return fail(10, "dvs_tabu_step: null pointer");
+    if (min_delta != min_delta) return fail(13, "dvs_tabu_step: min_delta must not be NaN");
+    if (step_cap < 1) return fail(13, "dvs_tabu_step: step_cap must be >= 1");
+    if (tabu_len < 1) return fail(13, "dvs_tabu_step: tabu_len must be >= 1");
+    if (max_stall < 1) return fail(13, "dvs_tabu_step: max_stall must be >= 1");
+    if (toggles_bytes < (size_t)batch * n_vars * n_vars * 8)
+        return fail_size("dvs_tabu_step: toggles_bytes < batch * n_vars^2 * 8", (size_t)batch * n_vars * n_vars * 8);
+    if (trace && trace_bytes < (size_t)batch * step_cap * 16)
+        return fail_size("dvs_tabu_step: trace_bytes < batch * step_cap * 16", (size_t)batch * step_cap * 16);
+    if (ring_bytes < (size_t)batch * tabu_len * n_vars * 8)
+        return fail_size("dvs_tabu_step: ring_bytes < batch * tabu_len * n_vars * 8", (size_t)batch * tabu_len * n_vars * 8);
+    if (best_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_tabu_step: best_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    call_begin();
+    if (int e = dvs_tabu_step_impl(batch, n_vars, parents, local, toggles, max_parents, min_delta, forbidden, step_cap, worklist,
+                                   steps, converged, flags, trace, active, tabu_len, ring, visited, max_stall, stall, best_score,
+                                   best_parents, stream))
+        return e;
+    return call_end("dvs_tabu_step");
+}
+
+extern "C" int dvs_hc_perturb_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
+                                   const uint64_t* forbidden, int* worklist, int* flags, uint64_t seed, uint32_t draw_index,
+                                   void* stream);
+extern "C" int dvs_hc_perturb(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                              size_t toggles_bytes, int32_t max_parents, const uint64_t* forbidden, int32_t* worklist,
+                              int32_t* flags, uint64_t seed, uint32_t draw_index, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_hc_perturb: batch must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_hc_perturb: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return fail(2, "dvs_hc_perturb: batch * n_vars^2 must be < 2^31");
+    if (!parents || !local || !toggles || !worklist || !flags) return fail(10, "dvs_hc_perturb: null pointer");
+    if (toggles_bytes < (size_t)batch * n_vars * n_vars * 8)
+        return fail_size("dvs_hc_perturb: toggles_bytes < batch * n_vars^2 * 8", (size_t)batch * n_vars * n_vars * 8);
+    call_begin();
+    if (int e = dvs_hc_perturb_impl(batch, n_vars, parents, local, toggles, max_parents, forbidden, worklist, flags, seed,
+                                    draw_index, stream))
+        return e;
+    return call_end("dvs_hc_perturb");
+}
+
 extern "C" int dvs_bic_parent_masks_impl(int B, int n, int wide, const uint8_t* labels, const void* preds, uint64_t* parents,
                                          int* status, void* stream);
 extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,

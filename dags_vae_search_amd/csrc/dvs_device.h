@@ -359,8 +359,10 @@ __device__ __forceinline__ void dvs_ln_stats(const f4 (&x)[4], float& mean, floa
 // regenerates them instead of storing 34 masks, and a batch sharded over ranks draws the same bits as the same
 // batch on one GPU.  oracle/rng.py restates these functions in numpy for the dropout-on parity tests.
 // Sites: 0-33 the step's dropout masks (dvs_api.hip: site_enc / site_dec), 100 the reparameterisation noise, 200 the decode
-// sampler (k_decode.hip), 300 / 301 / 302 the graph generator's edge slots, labels and per-DAG edge counts (dvs_generate.h).
+// sampler (k_decode.hip), 300 / 301 / 302 the graph generator's edge slots, labels and per-DAG edge counts (dvs_generate.h),
+// 400 the random moves of dvs_hc_perturb (dvs_tabu.h; keyed by the structure's index in the batch, element = draw_index).
 constexpr uint32_t DVS_SITE_GEN_EDGES = 300u, DVS_SITE_GEN_LABELS = 301u, DVS_SITE_GEN_COUNTS = 302u;
+constexpr uint32_t DVS_SITE_HC_PERTURB = 400u;
 __device__ __forceinline__ uint32_t dvs_fmix32(uint32_t x) {
     x ^= x >> 16;
     x *= 0x85EBCA6Bu;

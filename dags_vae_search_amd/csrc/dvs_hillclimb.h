@@ -12,6 +12,8 @@
 //   k_hc_step            one wave per structure, lane = variable, the lane's parent row one u64: ancestor closure by n
 //                        rounds of row broadcasts, legality and delta of every move, the best one across lanes (largest
 //                        fp64 delta, exact ties to the lowest code = op n^2 + v n + u), applied if delta > min_delta.
+//                        Closure, legality and pricing are device functions (hc_load, hc_moves, hc_apply) shared with
+//                        k_tabu_step and k_hc_perturb (dvs_tabu.h).
 #pragma once
 
 struct ToggleArgs {
@@ -114,81 +116,124 @@ __device__ __forceinline__ void hc_consider(double d, int c, double& bd, int& bc
     }
 }
 
-__global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= a.B) return;
-    const int n = a.n;
-    const bool live = lane < n;
-    const int nsteps = a.steps[b];
-    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) {          // wave-uniform
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
-    const size_t base = (size_t)b * n;
-    const uint64_t row = live ? a.parents[base + lane] : 0ull;
-    const double Lv = live ? a.local[base + lane] : 0.0;
-    const uint64_t self = 1ull << lane;
-    // reach[v]: the ancestors of v (bit-row Warshall: after round k every path through 0 .. k is in)
+// ---- what k_hc_step, k_tabu_step and k_hc_perturb (dvs_tabu.h) share: one wave per structure, lane = variable -----------
+struct HcLane {
+    int n, lane;
+    bool live;
+    uint64_t row, reach, self;   // the lane's parent row, its ancestors, its own bit
+    double Lv;                   // its local score
+};
+
+// reach[v]: the ancestors of v (bit-row Warshall: after round k every path through 0 .. k is in)
+__device__ __forceinline__ uint64_t hc_closure(uint64_t row, int n) {
     uint64_t reach = row;
     for (int k = 0; k < n; ++k) {
         const uint64_t rk = hc_bcast64(reach, k);
         if ((reach >> k) & 1ull) reach |= rk;
     }
+    return reach;
+}
+
+// loads the lane's row and local score and closes the structure -> the flags of include/dvs.h (1 cycle, 2 NaN local score)
+__device__ __forceinline__ int hc_load(HcLane& c, int n, int lane, const uint64_t* parents, const double* local, size_t base) {
+    c.n = n;
+    c.lane = lane;
+    c.live = lane < n;
+    c.row = c.live ? parents[base + lane] : 0ull;
+    c.Lv = c.live ? local[base + lane] : 0.0;
+    c.self = 1ull << lane;
+    c.reach = hc_closure(c.row, n);
     int fl = 0;
-    if (__ballot(live && (reach & self) != 0)) fl |= 1;
-    if (__ballot(live && Lv != Lv)) fl |= 2;
-    if (fl) {
-        if (lane == 0) a.flags[b] = fl;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
-    const bool capped = a.max_parents > 0;
-    const int npar = __popcll(row);
-    const uint64_t forb_v = (a.forbidden != nullptr && live) ? a.forbidden[lane] : 0ull;
-    const double* T = a.toggles + base * n;
-    const int nn = n * n;
-    double best = -__builtin_inf();
-    int bcode = HC_NO_MOVE;
+    if (__ballot(c.live && (c.reach & c.self) != 0)) fl |= 1;
+    if (__ballot(c.live && c.Lv != c.Lv)) fl |= 2;
+    return fl;
+}
+
+// Legality and pricing: f(op, u, delta) for every legal move on u -> v = lane (op 0 add, 1 delete, 2 reverse) whose delta
+// reads no NaN cell, u ascending.  The ballots and broadcasts sit outside every lane-dependent branch.
+template <class F>
+__device__ __forceinline__ void hc_moves(const HcLane& c, const double* T, int max_parents, const uint64_t* forbidden, F&& f) {
+    const int n = c.n, lane = c.lane;
+    const bool capped = max_parents > 0;
+    const int npar = __popcll(c.row);
+    const uint64_t forb_v = (forbidden != nullptr && c.live) ? forbidden[lane] : 0ull;
     for (int u = 0; u < n; ++u) {
-        const uint64_t child_u = __ballot(live && ((row >> u) & 1ull) != 0);
-        const uint64_t row_u = hc_bcast64(row, u), reach_u = hc_bcast64(reach, u);
-        const double L_u = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(Lv), u));
-        if (!live || u == lane) continue;
+        const uint64_t child_u = __ballot(c.live && ((c.row >> u) & 1ull) != 0);
+        const uint64_t row_u = hc_bcast64(c.row, u), reach_u = hc_bcast64(c.reach, u);
+        const double L_u = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(c.Lv), u));
+        if (!c.live || u == lane) continue;
         const double t_vu = T[lane * n + u];
         if (t_vu != t_vu) continue;                               // a refused family: the move is not available
-        const double d_v = t_vu - Lv;
+        const double d_v = t_vu - c.Lv;
         const uint64_t ubit = 1ull << u;
-        if (!(row & ubit)) {
-            if (!((reach_u >> lane) & 1ull) && !(capped && npar >= a.max_parents) && !(forb_v & ubit))
-                hc_consider(d_v, lane * n + u, best, bcode);
+        if (!(c.row & ubit)) {
+            if (!((reach_u >> lane) & 1ull) && !(capped && npar >= max_parents) && !(forb_v & ubit)) f(0, u, d_v);
         } else {
-            hc_consider(d_v, nn + lane * n + u, best, bcode);
+            f(1, u, d_v);
             const double t_uv = T[u * n + lane];
-            const uint64_t forb_u = a.forbidden != nullptr ? a.forbidden[u] : 0ull;
-            if (t_uv == t_uv && !((child_u & ~self) & (reach | self)) && !(capped && __popcll(row_u) >= a.max_parents) &&
-                !(forb_u & self))
-                hc_consider(d_v + (t_uv - L_u), 2 * nn + lane * n + u, best, bcode);
+            const uint64_t forb_u = forbidden != nullptr ? forbidden[u] : 0ull;
+            if (t_uv == t_uv && !((child_u & ~c.self) & (c.reach | c.self)) && !(capped && __popcll(row_u) >= max_parents) &&
+                !(forb_u & c.self))
+                f(2, u, d_v + (t_uv - L_u));
         }
     }
+}
+
+// the best (delta, code) of the wave, in every lane
+__device__ __forceinline__ void hc_reduce_best(double& best, int& bcode, int lane) {
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) {
         const double od = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(best), lane ^ s));
         const int oc = __shfl(bcode, lane ^ s);
         hc_consider(od, oc, best, bcode);
     }
+}
+
+// applies the move `code`: the rows, local from the toggle table, the two worklist slots
+__device__ __forceinline__ void hc_apply(const HcLane& c, int code, uint64_t* parents, double* local, const double* T, size_t base,
+                                         int* worklist, int b) {
+    const int n = c.n, nn = n * n;
+    const int op = code / nn, v = (code % nn) / n, u = code % n;
+    if (c.lane == v) {
+        parents[base + v] = c.row ^ (1ull << u);
+        local[base + v] = T[v * n + u];
+    }
+    if (op == 2 && c.lane == u) {
+        parents[base + u] = c.row | (1ull << v);
+        local[base + u] = T[u * n + v];
+    }
+    if (c.lane == 0) {
+        worklist[2 * b] = v;
+        worklist[2 * b + 1] = op == 2 ? u : -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const int n = a.n;
+    const int nsteps = a.steps[b];
+    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) {          // wave-uniform
+        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        return;
+    }
+    const size_t base = (size_t)b * n;
+    HcLane c;
+    const int fl = hc_load(c, n, lane, a.parents, a.local, base);
+    if (fl) {
+        if (lane == 0) a.flags[b] = fl;
+        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        return;
+    }
+    const double* T = a.toggles + base * n;
+    const int nn = n * n;
+    double best = -__builtin_inf();
+    int bcode = HC_NO_MOVE;
+    hc_moves(c, T, a.max_parents, a.forbidden, [&](int op, int u, double d) { hc_consider(d, op * nn + lane * n + u, best, bcode); });
+    hc_reduce_best(best, bcode, lane);
     if (bcode != HC_NO_MOVE && best > a.min_delta) {
-        const int op = bcode / nn, v = (bcode % nn) / n, u = bcode % n;
-        if (lane == v) {
-            a.parents[base + v] = row ^ (1ull << u);
-            a.local[base + v] = T[v * n + u];
-        }
-        if (op == 2 && lane == u) {
-            a.parents[base + u] = row | (1ull << v);
-            a.local[base + u] = T[u * n + v];
-        }
+        hc_apply(c, bcode, a.parents, a.local, T, base, a.worklist, b);
         if (lane == 0) {
-            a.worklist[2 * b] = v;
-            a.worklist[2 * b + 1] = op == 2 ? u : -1;
             a.steps[b] = nsteps + 1;
             if (a.trace != nullptr) {
                 int64_t* t = a.trace + ((size_t)b * a.step_cap + nsteps) * 2;

@@ -348,6 +348,51 @@ int dvs_hc_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local,
                 int32_t* steps, int32_t* converged, int32_t* flags, int64_t* trace, size_t trace_bytes, int32_t* active,
                 void* stream);
 
+/* Tabu search over the same moves: one move per structure, in place, whatever its sign.  Arguments, move
+ * codes, legality (the NaN-cell rule included), delta expressions, flags, worklist, steps, trace and *active are those of
+ * dvs_hc_step; in addition, all device buffers:
+ *   ring          u64 [batch][tabu_len][n_vars]: the structures recently stood on
+ *   visited       i32 [batch], zeroed by the caller: structures pushed so far; the push slot is visited % tabu_len and the
+ *                 valid entries are the first min(visited, tabu_len)
+ *   stall         i32 [batch], zeroed by the caller: consecutive moves that did not raise the best
+ *   best_score    f64 [batch], set to -inf by the caller; best_parents u64 [batch][n_vars]
+ * A structure with converged[b], flags[b] or steps[b] >= step_cap is left alone: both worklist slots -1, nothing else
+ * written.  A cycle or a NaN local score sets flags[b] as in dvs_hc_step and freezes the structure at zero steps, before
+ * anything below.  Otherwise, with S(P) = local[0] + local[1] + ... + local[n_vars - 1] added left to right in fp64 (the
+ * order in which dvs_bn_scores adds its total):
+ *   1. first call (visited[b] == 0): best_score[b] = S(start), best_parents[b] = the start.
+ *   2. push: the current structure is stored at slot visited[b] % tabu_len and visited[b] += 1.
+ *   3. a move is tabu iff the structure it produces equals, row for row, one of the valid ring entries (the current
+ *      structure is one of them).  Exact: no hashing.  Among the legal moves that are not tabu the largest fp64 delta wins,
+ *      exact ties go to the lowest code; the move is taken whatever its sign.  If there is none: converged[b] = 1, both
+ *      slots -1, the structure is not touched.
+ *   4. apply, as dvs_hc_step: rows, local from toggles, worklist slots, steps[b] += 1, trace (code, delta bits), *active += 1.
+ *   5. S' = S(new structure) from the updated local.  If S' - best_score[b] > min_delta (strict): best_score[b] = S',
+ *      best_parents[b] = the new rows, stall[b] = 0.  Otherwise stall[b] += 1, and at stall[b] >= max_stall converged[b] = 1;
+ *      the move stays applied and the worklist stays written, so the tables match parents after the toggle pass.
+ * Nothing depends on the order in which structures are processed: two runs give equal bytes.  Codes: 13 for tabu_len < 1,
+ * max_stall < 1, a NaN min_delta or step_cap < 1; 14 with the needed size for toggles_bytes, trace_bytes (as dvs_hc_step),
+ * ring_bytes < batch * tabu_len * n_vars * 8 or best_bytes < batch * n_vars * 8.  (Added in ABI 202 as a pure addition: the
+ * version number stays.) */
+int dvs_tabu_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles, size_t toggles_bytes,
+                  int32_t max_parents, double min_delta, const uint64_t* forbidden, int32_t step_cap, int32_t* worklist,
+                  int32_t* steps, int32_t* converged, int32_t* flags, int64_t* trace, size_t trace_bytes, int32_t* active,
+                  int32_t tabu_len, uint64_t* ring, size_t ring_bytes, int32_t* visited, int32_t max_stall, int32_t* stall,
+                  double* best_score, uint64_t* best_parents, size_t best_bytes, void* stream);
+
+/* One uniformly random legal move per structure, in place (the perturbation of a random restart).  Legality is that of
+ * dvs_hc_step, "every toggles cell the move's delta reads is not NaN" included, so local can be copied from toggles; the
+ * scores are not looked at otherwise.  With M legal moves in ascending code order the move taken is number
+ * (uint64(r) * M) >> 32, r = dvs_draw(dvs_site_key(seed_lo, seed_hi, 400, b), draw_index) of csrc/dvs_device.h (b the
+ * structure's index in the batch; oracle/rng.py restates both functions); move k is taken with probability within 2^-32 of
+ * 1 / M, a bias of at most M / 2^32 in all.  The rows, local and the worklist slots are written as by a step, so the
+ * incremental dvs_bn_toggle_scores pass follows; steps, trace and converged do not exist here.  M = 0, or flags[b] set on entry or
+ * by this call (cycle, NaN local score, as dvs_hc_step): the structure is untouched and both slots are -1.  Code 14 with the
+ * needed size for toggles_bytes < batch * n_vars^2 * 8.  (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_hc_perturb(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles, size_t toggles_bytes,
+                   int32_t max_parents, const uint64_t* forbidden, int32_t* worklist, int32_t* flags, uint64_t seed,
+                   uint32_t draw_index, void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
