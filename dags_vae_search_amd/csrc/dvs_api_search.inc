@@ -1,0 +1,506 @@
+// Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
+// BN scorers, hill climbing, tabu and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// field name and calls that block's launcher between call_begin() and call_end().
+
+static int failf(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+static int fail_size(const char* what, size_t need) { return failf(14, "%s = %zu", what, need); }
+
+// ---- reconstruction matching (dvs_match.h) ---------------------------------------------------------------------------
+extern "C" int dvs_match_decoded(int32_t batch, int32_t n_vars, int32_t card, int32_t repeats, int32_t preds_are_u64,
+                                 const uint8_t* labels, const void* preds, const void* states, size_t state_bytes,
+                                 int32_t budget, uint8_t* flags, void* stream) {
+    if (batch <= 0 || repeats <= 0) return fail(2, "dvs_match_decoded: batch and repeats must be > 0");
+    if ((int64_t)batch * repeats > (int64_t)1 << 30) return fail(2, "dvs_match_decoded: batch * repeats must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_match_decoded: n_vars must be in [1, 45]");
+    if (card < 1 || card > 45) return fail(3, "dvs_match_decoded: card must be in [1, 45]");
+    if (!preds_are_u64 && n_vars > 16) return fail(12, "dvs_match_decoded: 16-bit predecessor rows hold at most 16 vertices");
+    if (budget < 1) return fail(12, "dvs_match_decoded: budget must be >= 1");
+    if (!labels || !preds || !states || !flags) return fail(10, "dvs_match_decoded: null pointer");
+    const size_t need = (size_t)batch * repeats * sizeof(dvs_decode_state);
+    if (state_bytes < need) return fail_size("dvs_match_decoded: state_bytes < batch * repeats * DVS_DECODE_STATE_BYTES", need);
+    MatchArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.card = card;
+    a.R = repeats;
+    a.wide = preds_are_u64 ? 1 : 0;
+    a.budget = budget;
+    a.labels = labels;
+    a.preds = preds;
+    a.states = (const DvsDecodeState*)states;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_match_decoded(a, (dvs_stream_t)stream);
+    return call_end("dvs_match_decoded");
+}
+
+// ---- search candidates (dvs_structs.h) -------------------------------------------------------------------------------
+extern "C" int dvs_decoded_structures(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const void* states,
+                                      size_t state_bytes, uint64_t hash_mask, uint8_t* flags, uint8_t* labels, void* preds,
+                                      uint64_t* keys, size_t keys_bytes, uint64_t* hashes, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_decoded_structures: batch must be > 0");
+    if (batch > 1 << 30) return fail(2, "dvs_decoded_structures: batch must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_decoded_structures: n_vars must be in [1, 45]");
+    if (!preds_are_u64 && n_vars > 16) return fail(12, "dvs_decoded_structures: 16-bit predecessor rows hold at most 16 vertices");
+    if (!states || !flags || !labels || !preds || !keys || !hashes) return fail(10, "dvs_decoded_structures: null pointer");
+    if (state_bytes < (size_t)batch * sizeof(dvs_decode_state))
+        return fail_size("dvs_decoded_structures: state_bytes < batch * DVS_DECODE_STATE_BYTES", (size_t)batch * sizeof(dvs_decode_state));
+    if (keys_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_decoded_structures: keys_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    StructArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.wide = preds_are_u64 ? 1 : 0;
+    a.hash_mask = hash_mask;
+    a.states = (const DvsDecodeState*)states;
+    a.flags = flags;
+    a.labels = labels;
+    a.preds = preds;
+    a.keys = keys;
+    a.hashes = hashes;
+    call_begin();
+    dvs_launch_decoded_structures(a, (dvs_stream_t)stream);
+    return call_end("dvs_decoded_structures");
+}
+
+extern "C" int dvs_structset_filter(int32_t batch, int32_t n_vars, const uint64_t* sorted_hashes, const int64_t* order,
+                                    const uint64_t* keys, size_t keys_bytes, const uint8_t* flags, int32_t seen_count,
+                                    const uint64_t* seen_hashes, const uint64_t* seen_keys, size_t seen_keys_bytes,
+                                    uint8_t* out, void* stream) {
+    if (batch < 0 || seen_count < 0) return fail(2, "dvs_structset_filter: batch and seen_count must be >= 0");
+    if (batch > 1 << 30) return fail(2, "dvs_structset_filter: batch must be <= 2^30");
+    if (n_vars < 1 || n_vars > 45) return fail(3, "dvs_structset_filter: n_vars must be in [1, 45]");
+    if (batch == 0) return 0;                    // an empty batch: nothing to judge, nothing is enqueued
+    if (!sorted_hashes || !order || !keys || !flags || !out) return fail(10, "dvs_structset_filter: null pointer");
+    if (seen_count > 0 && (!seen_hashes || !seen_keys)) return fail(10, "dvs_structset_filter: null pointer (seen set)");
+    if (keys_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_structset_filter: keys_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    if (seen_keys_bytes < (size_t)seen_count * n_vars * 8)
+        return fail_size("dvs_structset_filter: seen_keys_bytes < seen_count * n_vars * 8", (size_t)seen_count * n_vars * 8);
+    FilterArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.S = seen_count;
+    a.sorted_hashes = sorted_hashes;
+    a.order = order;
+    a.keys = keys;
+    a.flags = flags;
+    a.seen_hashes = seen_hashes;
+    a.seen_keys = seen_keys;
+    a.out = out;
+    call_begin();
+    dvs_launch_structset_filter(a, (dvs_stream_t)stream);
+    return call_end("dvs_structset_filter");
+}
+
+// ---- graph generator (dvs_generate.h) --------------------------------------------------------------------------------
+extern "C" int dvs_generate_dags(int32_t batch, int32_t n_vars, int32_t card, int32_t preds_are_u64, const int32_t* num_edges,
+                                 uint64_t seed, int64_t dag_offset, int32_t try_limit, int32_t flags, uint8_t* labels,
+                                 void* preds, size_t preds_bytes, int32_t* attempts, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_generate_dags: batch must be > 0");
+    if (batch > 1 << 30) return fail(2, "dvs_generate_dags: batch must be <= 2^30");
+    if (n_vars < 2 || n_vars > 45) return fail(3, "dvs_generate_dags: n_vars must be in [2, 45]");
+    if (card < 1 || card > 45) return fail(3, "dvs_generate_dags: card must be in [1, 45]");
+    const int group = (flags >> DVS_GEN_GROUP_SHIFT) & 15;
+    if ((flags & ~(7 | 15 << DVS_GEN_GROUP_SHIFT)) || group > 7) return fail(12, "dvs_generate_dags: unknown bits in flags");
+    if (!(flags & DVS_GEN_LABELS_CHOICE) && card < n_vars)
+        return fail(12, "dvs_generate_dags: labels without replacement ('sample') need card >= n_vars");
+    if ((preds_are_u64 != 0) != (n_vars > 13))
+        return fail(12, "dvs_generate_dags: predecessor rows are u16 for n_vars <= 13 and u64 above (preds_are_u64 does not match)");
+    if (try_limit < 1 || try_limit > 4096) return fail(12, "dvs_generate_dags: try_limit must be in [1, 4096]");
+    if (dag_offset < 0) return fail(12, "dvs_generate_dags: dag_offset must be >= 0");
+    if (!num_edges || !labels || !preds || !attempts) return fail(10, "dvs_generate_dags: null pointer");
+    const size_t need = (size_t)batch * n_vars * (preds_are_u64 ? 8 : 2);
+    if (preds_bytes < need) return fail_size("dvs_generate_dags: preds_bytes < batch * n_vars * row bytes", need);
+    // Lanes per DAG: attempts k G .. k G + G - 1 run side by side.  Spare lanes cost little until the launch holds about 16
+    // waves per SIMD (measured, DESIGN.md §13: 64 lanes up to B = 4096, 16 at B = 65 536), and one lane is all an
+    // always-accepted attempt 0 needs.
+    int gshift = 0;
+    if (group) {
+        gshift = group - 1;
+    } else if (!(flags & DVS_GEN_ACCEPT_NO_CONNECTIVITY)) {
+        static const int cus = dvs_device_cus();
+        const int64_t lanes = (int64_t)cus * 4 * 64 * 16;
+        while (gshift < 6 && ((int64_t)batch << (gshift + 1)) <= lanes && (1 << gshift) < try_limit) ++gshift;
+    }
+    GenArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.card = card;
+    a.try_limit = try_limit;
+    a.flags = flags & 7;
+    a.gshift = gshift;
+    a.dag_offset = (uint32_t)dag_offset;
+    a.num_edges = num_edges;
+    a.labels = labels;
+    a.preds = preds;
+    a.attempts = attempts;
+    call_begin();
+    dvs_launch_generate_dags(a, seed, preds_are_u64 != 0, (dvs_stream_t)stream);
+    return call_end("dvs_generate_dags");
+}
+
+extern "C" int dvs_generate_edge_counts(int32_t batch, int32_t n_entries, const int32_t* edge_counts, const int32_t* cum_weights,
+                                        uint64_t seed, int64_t dag_offset, int32_t* num_edges, void* stream) {
+    if (batch <= 0 || batch > 1 << 30) return fail(2, "dvs_generate_edge_counts: batch must be in [1, 2^30]");
+    if (n_entries < 1 || n_entries > 1024) return fail(12, "dvs_generate_edge_counts: n_entries must be in [1, 1024]");
+    if (dag_offset < 0) return fail(12, "dvs_generate_edge_counts: dag_offset must be >= 0");
+    if (!edge_counts || !cum_weights || !num_edges) return fail(10, "dvs_generate_edge_counts: null pointer");
+    call_begin();
+    dvs_launch_generate_edge_counts(batch, n_entries, edge_counts, cum_weights, seed, (uint32_t)dag_offset, num_edges,
+                                    (dvs_stream_t)stream);
+    return call_end("dvs_generate_edge_counts");
+}
+
+// ---- BN scorers (k_bic.hip) ------------------------------------------------------------------------------------------
+extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                              const uint64_t* parents, double* scratch, double* out, int32_t* status, void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bic_scores: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bic_scores: n_vars must be in [1, 48]");
+    if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bic_scores: null pointer");
+    BicArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.S = n_samples;
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.local = scratch;
+    a.out = out;
+    a.status = status;
+    a.type = DVS_SCORE_BIC;
+    a.arg = __builtin_nan("");                  // k = log(S) / 2, taken on the device
+    call_begin();
+    dvs_launch_bic(a, (dvs_stream_t)stream);
+    return call_end("dvs_bic_scores");
+}
+
+// score_type / score_arg of dvs_bn_scores and dvs_bn_toggle_scores -> the argument the kernels take (include/dvs.h): the
+// resolved k (loglik 0, aic, bic; NaN = log(S) / 2 taken on the device) or iss (bde, bds)
+static int bn_score_arg(const char* fn, int score_type, double score_arg, double* arg) {
+    const bool dflt = score_arg != score_arg;               // NaN: the type's default
+    *arg = score_arg;
+    switch (score_type) {
+        case DVS_SCORE_LOGLIK:
+        case DVS_SCORE_K2:
+        case DVS_SCORE_BDJ:
+            if (!dflt) return failf(13, "%s: loglik, k2 and bdj take no argument (score_arg must be NaN)", fn);
+            *arg = 0.0;                                     // loglik is the penalised likelihood at k = 0
+            return 0;
+        case DVS_SCORE_AIC:
+        case DVS_SCORE_BIC:
+            if (!dflt && !(score_arg >= 0.0 && isfinite(score_arg))) return failf(13, "%s: k must be finite and >= 0", fn);
+            if (dflt && score_type == DVS_SCORE_AIC) *arg = 1.0;     // bic's default, log(S) / 2, is taken on the device
+            return 0;
+        case DVS_SCORE_BDE:
+        case DVS_SCORE_BDS:
+            if (!dflt && !(score_arg > 0.0 && isfinite(score_arg))) return failf(13, "%s: iss must be finite and > 0", fn);
+            if (dflt) *arg = 1.0;
+            return 0;
+        default:
+            return failf(12, "%s: score_type is not a dvs_score_type", fn);
+    }
+}
+
+extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                             const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                             int32_t* status, void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores: n_vars must be in [1, 48]");
+    if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bn_scores: null pointer");
+    BicArgs a = {};
+    if (int e = bn_score_arg("dvs_bn_scores", score_type, score_arg, &a.arg)) return e;
+    a.B = batch;
+    a.n = n_vars;
+    a.S = n_samples;
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.local = scratch;
+    a.out = out;
+    a.status = status;
+    a.type = score_type;
+    call_begin();
+    dvs_launch_bic(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_scores");
+}
+
+// ---- hill climbing, tabu, random restarts (dvs_hillclimb.h, dvs_tabu.h) ----------------------------------------------
+// What dvs_bn_toggle_scores, dvs_hc_step, dvs_tabu_step and dvs_hc_perturb check alike, each at its own place in the entry
+// point's order: the range of the toggle table's index and the caller's table and trace buffers (code 14 with the size).
+struct HcCheck {
+    const char* fn;
+    int batch, n_vars;
+    int dims() const {
+        if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+        if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: batch * n_vars^2 must be < 2^31", fn);
+        return 0;
+    }
+    int toggles(size_t toggles_bytes) const {
+        const size_t need = (size_t)batch * n_vars * n_vars * 8;
+        return toggles_bytes < need ? failf(14, "%s: toggles_bytes < batch * n_vars^2 * 8 = %zu", fn, need) : 0;
+    }
+    int trace(const int64_t* trace, size_t trace_bytes, int step_cap) const {
+        const size_t need = (size_t)batch * step_cap * 16;
+        return trace && trace_bytes < need ? failf(14, "%s: trace_bytes < batch * step_cap * 16 = %zu", fn, need) : 0;
+    }
+};
+
+extern "C" int dvs_bn_toggle_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                                    const uint64_t* parents, int32_t score_type, double score_arg, const int32_t* worklist,
+                                    double* local, size_t local_bytes, double* toggles, size_t toggles_bytes, int32_t* status,
+                                    void* stream) {
+    const HcCheck chk = {"dvs_bn_toggle_scores", batch, n_vars};
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_toggle_scores: batch and n_samples must be > 0");
+    if (int e = chk.dims()) return e;
+    if (!data || !card || !parents || !local || !toggles || !status) return fail(10, "dvs_bn_toggle_scores: null pointer");
+    ToggleArgs t = {};
+    if (int e = bn_score_arg("dvs_bn_toggle_scores", score_type, score_arg, &t.s.arg)) return e;
+    if (local_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_bn_toggle_scores: local_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    if (int e = chk.toggles(toggles_bytes)) return e;
+    t.s.B = batch;
+    t.s.n = n_vars;
+    t.s.S = n_samples;
+    t.s.data = data;
+    t.s.card = card;
+    t.s.parents = parents;
+    t.s.local = local;
+    t.s.out = nullptr;
+    t.s.status = status;
+    t.s.type = score_type;
+    t.worklist = worklist;
+    t.toggles = toggles;
+    call_begin();
+    dvs_launch_bn_toggle(t, (dvs_stream_t)stream);
+    return call_end("dvs_bn_toggle_scores");
+}
+
+extern "C" int dvs_hc_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                           size_t toggles_bytes, int32_t max_parents, double min_delta, const uint64_t* forbidden,
+                           int32_t step_cap, int32_t* worklist, int32_t* steps, int32_t* converged, int32_t* flags,
+                           int64_t* trace, size_t trace_bytes, int32_t* active, void* stream) {
+    const HcCheck chk = {"dvs_hc_step", batch, n_vars};
+    if (batch <= 0) return fail(2, "dvs_hc_step: batch must be > 0");
+    if (int e = chk.dims()) return e;
+    if (!parents || !local || !toggles || !worklist || !steps || !converged || !flags || !active)
+        return fail(10, "dvs_hc_step: null pointer");
+    if (min_delta != min_delta) return fail(13, "dvs_hc_step: min_delta must not be NaN");
+    if (step_cap < 1) return fail(13, "dvs_hc_step: step_cap must be >= 1");
+    if (int e = chk.toggles(toggles_bytes)) return e;
+    if (int e = chk.trace(trace, trace_bytes, step_cap)) return e;
+    HcArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.max_parents = max_parents;
+    a.step_cap = step_cap;
+    a.min_delta = min_delta;
+    a.parents = parents;
+    a.local = local;
+    a.toggles = toggles;
+    a.forbidden = forbidden;
+    a.worklist = worklist;
+    a.steps = steps;
+    a.converged = converged;
+    a.flags = flags;
+    a.trace = trace;
+    a.active = active;
+    call_begin();
+    dvs_launch_hc_step(a, (dvs_stream_t)stream);
+    return call_end("dvs_hc_step");
+}
+
+extern "C" int dvs_tabu_step(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                             size_t toggles_bytes, int32_t max_parents, double min_delta, const uint64_t* forbidden,
+                             int32_t step_cap, int32_t* worklist, int32_t* steps, int32_t* converged, int32_t* flags,
+                             int64_t* trace, size_t trace_bytes, int32_t* active, int32_t tabu_len, uint64_t* ring,
+                             size_t ring_bytes, int32_t* visited, int32_t max_stall, int32_t* stall, double* best_score,
+                             uint64_t* best_parents, size_t best_bytes, void* stream) {
+    const HcCheck chk = {"dvs_tabu_step", batch, n_vars};
+    if (batch <= 0) return fail(2, "dvs_tabu_step: batch must be > 0");
+    if (int e = chk.dims()) return e;
+    if (!parents || !local || !toggles || !worklist || !steps || !converged || !flags || !active || !ring || !visited || !stall ||
+        !best_score || !best_parents)
+        return fail(10, "dvs_tabu_step: null pointer");
+    if (min_delta != min_delta) return fail(13, "dvs_tabu_step: min_delta must not be NaN");
+    if (step_cap < 1) return fail(13, "dvs_tabu_step: step_cap must be >= 1");
+    if (tabu_len < 1) return fail(13, "dvs_tabu_step: tabu_len must be >= 1");
+    if (max_stall < 1) return fail(13, "dvs_tabu_step: max_stall must be >= 1");
+    if (int e = chk.toggles(toggles_bytes)) return e;
+    if (int e = chk.trace(trace, trace_bytes, step_cap)) return e;
+    if (ring_bytes < (size_t)batch * tabu_len * n_vars * 8)
+        return fail_size("dvs_tabu_step: ring_bytes < batch * tabu_len * n_vars * 8", (size_t)batch * tabu_len * n_vars * 8);
+    if (best_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_tabu_step: best_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    TabuArgs t;
+    t.h.B = batch;
+    t.h.n = n_vars;
+    t.h.max_parents = max_parents;
+    t.h.step_cap = step_cap;
+    t.h.min_delta = min_delta;
+    t.h.parents = parents;
+    t.h.local = local;
+    t.h.toggles = toggles;
+    t.h.forbidden = forbidden;
+    t.h.worklist = worklist;
+    t.h.steps = steps;
+    t.h.converged = converged;
+    t.h.flags = flags;
+    t.h.trace = trace;
+    t.h.active = active;
+    t.tabu_len = tabu_len;
+    t.max_stall = max_stall;
+    t.ring = ring;
+    t.visited = visited;
+    t.stall = stall;
+    t.best_score = best_score;
+    t.best_parents = best_parents;
+    call_begin();
+    dvs_launch_tabu_step(t, (dvs_stream_t)stream);
+    return call_end("dvs_tabu_step");
+}
+
+extern "C" int dvs_hc_perturb(int32_t batch, int32_t n_vars, uint64_t* parents, double* local, const double* toggles,
+                              size_t toggles_bytes, int32_t max_parents, const uint64_t* forbidden, int32_t* worklist,
+                              int32_t* flags, uint64_t seed, uint32_t draw_index, void* stream) {
+    const HcCheck chk = {"dvs_hc_perturb", batch, n_vars};
+    if (batch <= 0) return fail(2, "dvs_hc_perturb: batch must be > 0");
+    if (int e = chk.dims()) return e;
+    if (!parents || !local || !toggles || !worklist || !flags) return fail(10, "dvs_hc_perturb: null pointer");
+    if (int e = chk.toggles(toggles_bytes)) return e;
+    PerturbArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.max_parents = max_parents;
+    a.draw_index = draw_index;
+    a.parents = parents;
+    a.local = local;
+    a.toggles = toggles;
+    a.forbidden = forbidden;
+    a.worklist = worklist;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_hc_perturb(a, seed, (dvs_stream_t)stream);
+    return call_end("dvs_hc_perturb");
+}
+
+extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,
+                                    const void* preds, uint64_t* parents, int32_t* status, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_bic_parent_masks: batch must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bic_parent_masks: n_vars must be in [1, 48]");
+    if (!preds_are_u64 && n_vars > 16) return fail(12, "dvs_bic_parent_masks: 16-bit predecessor rows hold at most 16 vertices");
+    if (!labels || !preds || !parents || !status) return fail(10, "dvs_bic_parent_masks: null pointer");
+    BicMaskArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.wide = preds_are_u64 ? 1 : 0;
+    a.labels = labels;
+    a.preds = preds;
+    a.parents = parents;
+    a.status = status;
+    call_begin();
+    dvs_launch_bic_parent_masks(a, (dvs_stream_t)stream);
+    return call_end("dvs_bic_parent_masks");
+}
+
+// ---- GP predictor (k_bic.hip, k_gp_acq.hip) --------------------------------------------------------------------------
+extern "C" int dvs_gp_predict(int32_t batch, int32_t n_inducing, int32_t dim, const float* x, const float* inducing,
+                              const double* alpha, double outputscale, double lengthscale, double constant, double* out,
+                              void* stream) {
+    if (batch <= 0 || n_inducing <= 0 || dim <= 0) return fail(2, "dvs_gp_predict: sizes must be > 0");
+    if (!(lengthscale > 0.0)) return fail(5, "dvs_gp_predict: lengthscale must be > 0");
+    if (!x || !inducing || !alpha || !out) return fail(10, "dvs_gp_predict: null pointer");
+    GpArgs a = {};
+    a.B = batch;
+    a.M = n_inducing;
+    a.D = dim;
+    a.x = x;
+    a.z = inducing;
+    a.alpha = alpha;
+    a.outputscale = outputscale;
+    a.constant = constant;
+    a.out = out;
+    call_begin();
+    dvs_launch_gp_predict(a, lengthscale, (dvs_stream_t)stream);
+    return call_end("dvs_gp_predict");
+}
+
+static int gp_check(const char* fn, int na, int nb, int dim, double outputscale, double lengthscale) {
+    if (na <= 0 || nb <= 0 || dim <= 0 || dim > 32) return failf(2, "%s: sizes must be > 0 and dim <= 32", fn);
+    if (!(lengthscale > 0.0) || !(outputscale > 0.0)) return failf(5, "%s: lengthscale and outputscale must be > 0", fn);
+    return 0;
+}
+extern "C" int dvs_gp_kernel(int32_t na, int32_t nb, int32_t dim, const float* xa, const float* xb, double outputscale,
+                             double lengthscale, double* K, void* stream) {
+    if (int e = gp_check("dvs_gp_kernel", na, nb, dim, outputscale, lengthscale)) return e;
+    if (!xa || !xb || !K) return fail(10, "dvs_gp_kernel: null pointer");
+    GpKernArgs a = {};
+    a.na = na;
+    a.nb = nb;
+    a.D = dim;
+    a.xa = xa;
+    a.xb = xb;
+    a.outputscale = outputscale;
+    a.K = K;
+    call_begin();
+    dvs_launch_gp_kernel(a, lengthscale, (dvs_stream_t)stream);
+    return call_end("dvs_gp_kernel");
+}
+extern "C" int dvs_gp_kernel_backward(int32_t na, int32_t nb, int32_t dim, int32_t symmetric, const float* xa, const float* xb,
+                                      double outputscale, double lengthscale, const double* G, double* dxa, double* row_sums,
+                                      void* stream) {
+    if (int e = gp_check("dvs_gp_kernel_backward", na, nb, dim, outputscale, lengthscale)) return e;
+    if (!xa || !xb || !G || !dxa || !row_sums) return fail(10, "dvs_gp_kernel_backward: null pointer");
+    if (symmetric && na != nb) return fail(12, "dvs_gp_kernel_backward: symmetric needs na == nb");
+    GpKernArgs a = {};
+    a.na = na;
+    a.nb = nb;
+    a.D = dim;
+    a.symmetric = symmetric;
+    a.xa = xa;
+    a.xb = xb;
+    a.outputscale = outputscale;
+    a.G = G;
+    a.dxa = dxa;
+    a.rows = row_sums;
+    call_begin();
+    dvs_launch_gp_kernel_bwd(a, lengthscale, (dvs_stream_t)stream);
+    return call_end("dvs_gp_kernel_backward");
+}
+
+extern "C" int dvs_gp_acquire(int32_t batch, int32_t n_inducing, int32_t dim, int32_t ld, const float* x, const float* inducing,
+                              const double* weights, double c0, double outputscale, double lengthscale, double constant,
+                              double best, double xi, double* mean, double* var, double* ei, float* grad, void* stream) {
+    if (int e = gp_check("dvs_gp_acquire", batch, n_inducing, dim, outputscale, lengthscale)) return e;
+    if (n_inducing > DVS_GP_ACQ_MAX_INDUCING) return fail(2, "dvs_gp_acquire: n_inducing must be <= 1023");
+    if (ld < n_inducing + 1) return fail(12, "dvs_gp_acquire: ld must be >= n_inducing + 1 (P | alpha)");
+    if (!(c0 >= 0.0)) return fail(12, "dvs_gp_acquire: c0 must be >= 0");
+    if (!x || !inducing || !weights || !mean || !var || !ei) return fail(10, "dvs_gp_acquire: null pointer");
+    if (!dvs_launch_gp_acquire) return fail(20, "dvs_gp_acquire: k_gp_acq.hip is not part of this build");   // weak: dvs_search_args.h
+    GpAcqArgs a = {};
+    a.Q = batch;
+    a.M = n_inducing;
+    a.D = dim;
+    a.ld = ld;
+    a.x = x;
+    a.z = inducing;
+    a.W = weights;
+    a.c0 = c0;
+    a.outputscale = outputscale;
+    a.constant = constant;
+    a.best = best;
+    a.xi = xi;
+    a.mean = mean;
+    a.var = var;
+    a.ei = ei;
+    a.grad = grad;
+    call_begin();
+    dvs_launch_gp_acquire(a, lengthscale, (dvs_stream_t)stream);
+    return call_end("dvs_gp_acquire");
+}

@@ -2,7 +2,7 @@
 //
 // Replaces LabeledDag.generate_random_graph_erdos_renyi (src/toolkit/labeled.py:281-333: igraph Erdos_Renyi(n, m),
 // to_directed("acyclic"), a connectivity test and up to try_limit retries, one igraph object at a time) and the Python
-// loop of synthetic.py.  Included by k_decode.hip only (the kernel and its _impl are defined here, once).
+// loop of synthetic.py.  Included by k_decode.hip only (the kernels and their launchers are defined here, once).
 //
 // Semantics (pinned bit for bit by tests/generate_corpus.py).  DAG b, n vertices, m = num_edges[b] edges,
 // P = n (n - 1) / 2 slots; slot t = v (v - 1) / 2 + u is the edge u -> v (u < v), walked v = 1 .. n-1 outer, u = 0 .. v-1
@@ -20,17 +20,9 @@
 // Control flow around the two ballots is wave-uniform.
 #pragma once
 #include "dvs_decode.h"
+#include "dvs_search_args.h"
 
 constexpr int GEN_LABELS_CHOICE = 1, GEN_ACCEPT_ISOLATES = 2, GEN_ACCEPT_NO_CONNECTIVITY = 4;
-
-struct GenArgs {
-    int B, n, card, try_limit, flags, gshift;
-    uint32_t seed_lo, seed_hi, dag_offset;
-    const int* num_edges;        // [B]
-    uint8_t* labels;             // [B][n]
-    void* preds;                 // [B][n] u16 / u64
-    int* attempts;               // [B]
-};
 
 // one attempt of this lane: rows into col[v * 64]; true iff accepted
 template <class Acc>
@@ -146,33 +138,18 @@ __global__ __launch_bounds__(256) void k_generate_edge_counts(int B, int K, cons
     out[b] = counts[i];
 }
 
-extern "C" int dvs_generate_edge_counts_impl(int B, int K, const int* counts, const int* cum, uint64_t seed, uint32_t dag_offset,
-                                             int* out, void* stream) {
-    DVS_LAUNCH(k_generate_edge_counts, dim3((unsigned)(((size_t)B + 255) / 256)), dim3(256), 0, (dvs_stream_t)stream, B, K, counts,
-               cum, (uint32_t)seed, (uint32_t)(seed >> 32), dag_offset, out);
-    return 0;
+void dvs_launch_generate_edge_counts(int B, int K, const int* counts, const int* cum, uint64_t seed, uint32_t dag_offset, int* out,
+                                     dvs_stream_t st) {
+    DVS_LAUNCH(k_generate_edge_counts, dim3((unsigned)(((size_t)B + 255) / 256)), dim3(256), 0, st, B, K, counts, cum, (uint32_t)seed,
+               (uint32_t)(seed >> 32), dag_offset, out);
 }
 
-extern "C" int dvs_generate_dags_impl(int B, int n, int card, int wide, const int* num_edges, uint64_t seed, uint32_t dag_offset,
-                                      int try_limit, int flags, int gshift, uint8_t* labels, void* preds, int* attempts,
-                                      void* stream) {
-    GenArgs a;
-    a.B = B;
-    a.n = n;
-    a.card = card;
-    a.try_limit = try_limit;
-    a.flags = flags;
-    a.gshift = gshift;
+void dvs_launch_generate_dags(const GenArgs& in, uint64_t seed, bool wide, dvs_stream_t st) {
+    GenArgs a = in;
     a.seed_lo = (uint32_t)seed;
     a.seed_hi = (uint32_t)(seed >> 32);
-    a.dag_offset = dag_offset;
-    a.num_edges = num_edges;
-    a.labels = labels;
-    a.preds = preds;
-    a.attempts = attempts;
-    const int per = 64 >> gshift;
-    const dim3 grid((unsigned)(((size_t)B + per - 1) / per));
-    if (wide) DVS_LAUNCH_AS("k_generate_dags", (k_generate_dags<uint64_t, uint64_t>), grid, dim3(64), (size_t)n * 64 * 8, (dvs_stream_t)stream, a);
-    else DVS_LAUNCH_AS("k_generate_dags", (k_generate_dags<uint16_t, uint32_t>), grid, dim3(64), (size_t)n * 64 * 4, (dvs_stream_t)stream, a);
-    return 0;
+    const int per = 64 >> a.gshift;
+    const dim3 grid((unsigned)(((size_t)a.B + per - 1) / per));
+    if (wide) DVS_LAUNCH_AS("k_generate_dags", (k_generate_dags<uint64_t, uint64_t>), grid, dim3(64), (size_t)a.n * 64 * 8, st, a);
+    else DVS_LAUNCH_AS("k_generate_dags", (k_generate_dags<uint16_t, uint32_t>), grid, dim3(64), (size_t)a.n * 64 * 4, st, a);
 }

@@ -15,12 +15,7 @@
 //                        Closure, legality and pricing are device functions (hc_load, hc_moves, hc_apply) shared with
 //                        k_tabu_step and k_hc_perturb (dvs_tabu.h).
 #pragma once
-
-struct ToggleArgs {
-    BicArgs s;                   // s.local = L [B][n]; s.out unused
-    const int* worklist;         // null: full pass; else i32 [2 B]
-    double* toggles;             // T [B][n][n]
-};
+#include "dvs_search_args.h"
 
 template <int FAMILY>
 __global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
@@ -48,7 +43,9 @@ __global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
     }
 }
 
-void dvs_launch_bn_toggle(const ToggleArgs& t, dvs_stream_t st) {
+void dvs_launch_bn_toggle(const ToggleArgs& in, dvs_stream_t st) {
+    ToggleArgs t = in;
+    t.s.words = bic_words(t.s.n);
     const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
     const unsigned rows = t.worklist != nullptr ? 2u * (unsigned)t.s.B : (unsigned)t.s.B * (unsigned)t.s.n;
     if (t.s.type <= DVS_SCORE_BIC) {
@@ -60,45 +57,9 @@ void dvs_launch_bn_toggle(const ToggleArgs& t, dvs_stream_t st) {
     }
 }
 
-extern "C" int dvs_bn_toggle_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
-                                         int type, double arg, const int* worklist, double* local, double* toggles, int* status,
-                                         void* stream) {
-    ToggleArgs t;
-    t.s.type = type;
-    t.s.arg = arg;
-    t.s.B = B;
-    t.s.n = n;
-    t.s.S = S;
-    t.s.words = (n + 15) / 16;
-    t.s.data = data;
-    t.s.card = card;
-    t.s.parents = parents;
-    t.s.local = local;
-    t.s.out = nullptr;
-    t.s.status = status;
-    t.worklist = worklist;
-    t.toggles = toggles;
-    dvs_launch_bn_toggle(t, (dvs_stream_t)stream);
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // One greedy step
 // ---------------------------------------------------------------------------------------------------------
-struct HcArgs {
-    int B, n, max_parents, step_cap;
-    double min_delta;
-    uint64_t* parents;           // [B][n], updated in place
-    double* local;               // L [B][n], the moved rows updated from T
-    const double* toggles;       // T [B][n][n]
-    const uint64_t* forbidden;   // [n] or null: bit u of forbidden[v] bars u -> v
-    int* worklist;               // [2 B]
-    int* steps;                  // [B]
-    int* converged;              // [B]
-    int* flags;                  // [B]: 1 the start has a cycle, 2 a local score of the start is NaN
-    int64_t* trace;              // null or [B][step_cap][2]: (code, delta bits)
-    int* active;                 // += structures that moved in this launch
-};
 constexpr int HC_NO_MOVE = 0x7fffffff;
 
 __device__ __forceinline__ uint64_t hc_bcast64(uint64_t x, int src) {
@@ -248,25 +209,6 @@ __global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
     }
 }
 
-extern "C" int dvs_hc_step_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
-                                double min_delta, const uint64_t* forbidden, int step_cap, int* worklist, int* steps,
-                                int* converged, int* flags, int64_t* trace, int* active, void* stream) {
-    HcArgs a;
-    a.B = B;
-    a.n = n;
-    a.max_parents = max_parents;
-    a.step_cap = step_cap;
-    a.min_delta = min_delta;
-    a.parents = parents;
-    a.local = local;
-    a.toggles = toggles;
-    a.forbidden = forbidden;
-    a.worklist = worklist;
-    a.steps = steps;
-    a.converged = converged;
-    a.flags = flags;
-    a.trace = trace;
-    a.active = active;
-    DVS_LAUNCH(k_hc_step, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_hc_step(const HcArgs& a, dvs_stream_t st) {
+    DVS_LAUNCH(k_hc_step, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
 }

@@ -2,7 +2,7 @@
 //
 // Replaces the host loop of batch_test (experiments/03_synthetic_12/main.py:200-217: toolkit.is_valid_graph /
 // graph_equals per decoded graph, networkx VF2 when labels repeat).  One wave64 per (target, decoded row) pair, one lane
-// per vertex (n <= 45); no LDS.  Included by k_decode.hip only (the kernel and its _impl are defined here, once).
+// per vertex (n <= 45); no LDS.  Included by k_decode.hip only (the kernel and its launcher are defined here, once).
 //
 // Flags of decoded row k (target k / R):  bit 0 valid (nv == n_tokens, every label in [0, card)), bit 1 same structure
 // (isomorphic, labels ignored), bit 2 same labelled graph, bit 3 undecided (a search ran out of `budget` nodes; bits 1
@@ -21,17 +21,10 @@
 // shuffle or the pair index), so every ballot and shuffle runs with the full EXEC mask.
 #pragma once
 #include "dvs_decode.h"
+#include "dvs_search_args.h"
 
 constexpr int MATCH_MAX_N = 45;
 constexpr int MATCH_VALID = 1, MATCH_STRUCT = 2, MATCH_LABELLED = 4, MATCH_UNDECIDED = 8;
-
-struct MatchArgs {
-    int B, n, card, R, wide, budget;
-    const uint8_t* labels;       // targets: u8 [B][n]
-    const void* preds;           // targets: u16 / u64 [B][n], bit u of preds[v] <=> u -> v
-    const DvsDecodeState* states;    // [B * R]
-    uint8_t* flags;              // [B * R]
-};
 
 // one vertex (lane) of both graphs: target (1) and decoded row (2)
 struct MatchLane {
@@ -235,20 +228,7 @@ __global__ __launch_bounds__(256) void k_match_decoded(MatchArgs a) {
     if (lane == 0) a.flags[k] = (uint8_t)f;
 }
 
-extern "C" int dvs_match_decoded_impl(int B, int n, int card, int R, int wide, const uint8_t* labels, const void* preds,
-                                      const void* states, int budget, uint8_t* flags, void* stream) {
-    MatchArgs a;
-    a.B = B;
-    a.n = n;
-    a.card = card;
-    a.R = R;
-    a.wide = wide;
-    a.budget = budget;
-    a.labels = labels;
-    a.preds = preds;
-    a.states = (const DvsDecodeState*)states;
-    a.flags = flags;
-    const size_t pairs = (size_t)B * R;
-    DVS_LAUNCH(k_match_decoded, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_match_decoded(const MatchArgs& a, dvs_stream_t st) {
+    const size_t pairs = (size_t)a.B * a.R;
+    DVS_LAUNCH(k_match_decoded, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a);
 }

@@ -2,7 +2,7 @@
 // (k_decoded_structures), and the exact "is this structure new" filter against a device-resident set
 // (k_structset_filter).  Together they replace the host stage between decode and BIC of latent_bo_search
 // (dags_vae_search_amd/search.py: graphs_from_states -> is_search_valid -> structure_key -> Python set -> encode_graphs),
-// which is the specification both kernels are pinned to.  Included by k_decode.hip only (kernels and _impl functions are
+// which is the specification both kernels are pinned to.  Included by k_decode.hip only (kernels and launchers are
 // defined here, once), next to dvs_match.h.
 //
 // k_decoded_structures — one wave64 per decoded row, one lane per user vertex (n <= 45), no LDS, no atomics.
@@ -42,32 +42,11 @@
 // row index or values every lane loads from the same address), so every ballot and shuffle runs with the full EXEC mask.
 #pragma once
 #include "dvs_decode.h"
+#include "dvs_search_args.h"
 
 constexpr int STRUCT_VALID = 1, STRUCT_SHORT = 2, STRUCT_LABEL_RANGE = 4, STRUCT_LABEL_REPEAT = 8;
 constexpr int FILTER_NEW = 1, FILTER_SEEN = 2, FILTER_DUPLICATE = 4;
 constexpr uint64_t STRUCT_HASH_INVALID = 0x7fffffffffffffffull;     // DVS_STRUCT_HASH_INVALID (include/dvs.h)
-
-struct StructArgs {
-    int B, n, wide;
-    uint64_t hash_mask;
-    const DvsDecodeState* states;    // [B]
-    uint8_t* flags;                  // [B]
-    uint8_t* labels;                 // [B][n]
-    void* preds;                     // u16 / u64 [B][n]
-    uint64_t* keys;                  // [B][n]
-    uint64_t* hashes;                // [B]
-};
-
-struct FilterArgs {
-    int B, n, S;
-    const uint64_t* sorted_hashes;   // [B] ascending
-    const int64_t* order;            // [B] row index of sorted position p
-    const uint64_t* keys;            // [B][n], row order
-    const uint8_t* flags;            // [B], row order
-    const uint64_t* seen_hashes;     // [S] ascending
-    const uint64_t* seen_keys;       // [S][n]
-    uint8_t* out;                    // [B], row order
-};
 
 // splitmix64's finaliser
 __device__ __forceinline__ uint64_t structs_mix64(uint64_t x) {
@@ -179,37 +158,9 @@ __global__ __launch_bounds__(256) void k_structset_filter(FilterArgs a) {
     if (lane == 0) a.out[r] = FILTER_NEW;
 }
 
-extern "C" int dvs_decoded_structures_impl(int B, int n, int wide, const void* states, uint64_t hash_mask, uint8_t* flags,
-                                           uint8_t* labels, void* preds, uint64_t* keys, uint64_t* hashes, void* stream) {
-    StructArgs a;
-    a.B = B;
-    a.n = n;
-    a.wide = wide;
-    a.hash_mask = hash_mask;
-    a.states = (const DvsDecodeState*)states;
-    a.flags = flags;
-    a.labels = labels;
-    a.preds = preds;
-    a.keys = keys;
-    a.hashes = hashes;
-    DVS_LAUNCH(k_decoded_structures, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_decoded_structures(const StructArgs& a, dvs_stream_t st) {
+    DVS_LAUNCH(k_decoded_structures, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
 }
-
-extern "C" int dvs_structset_filter_impl(int B, int n, const uint64_t* sorted_hashes, const int64_t* order,
-                                         const uint64_t* keys, const uint8_t* flags, int S, const uint64_t* seen_hashes,
-                                         const uint64_t* seen_keys, uint8_t* out, void* stream) {
-    FilterArgs a;
-    a.B = B;
-    a.n = n;
-    a.S = S;
-    a.sorted_hashes = sorted_hashes;
-    a.order = order;
-    a.keys = keys;
-    a.flags = flags;
-    a.seen_hashes = seen_hashes;
-    a.seen_keys = seen_keys;
-    a.out = out;
-    DVS_LAUNCH(k_structset_filter, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_structset_filter(const FilterArgs& a, dvs_stream_t st) {
+    DVS_LAUNCH(k_structset_filter, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
 }

@@ -10,16 +10,7 @@
 //   k_hc_perturb   one uniformly random legal move per structure: per-lane bit rows of the legal adds, deletes and reversals,
 //                  a shuffle prefix over lanes per op, the draw of site DVS_SITE_HC_PERTURB scaled to the count.
 #pragma once
-
-struct TabuArgs {
-    HcArgs h;
-    int tabu_len, max_stall;
-    uint64_t* ring;              // [B][tabu_len][n]
-    int* visited;                // [B]: structures pushed so far; the push slot is visited % tabu_len
-    int* stall;                  // [B]: consecutive moves that did not raise the best
-    double* best_score;          // [B]
-    uint64_t* best_parents;      // [B][n]
-};
+#include "dvs_search_args.h"
 
 __device__ __forceinline__ int hc_ctz64(uint64_t x) { return __popcll((x & (0ull - x)) - 1ull); }
 
@@ -127,52 +118,13 @@ __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
     }
 }
 
-extern "C" int dvs_tabu_step_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
-                                  double min_delta, const uint64_t* forbidden, int step_cap, int* worklist, int* steps,
-                                  int* converged, int* flags, int64_t* trace, int* active, int tabu_len, uint64_t* ring,
-                                  int* visited, int max_stall, int* stall, double* best_score, uint64_t* best_parents,
-                                  void* stream) {
-    TabuArgs t;
-    t.h.B = B;
-    t.h.n = n;
-    t.h.max_parents = max_parents;
-    t.h.step_cap = step_cap;
-    t.h.min_delta = min_delta;
-    t.h.parents = parents;
-    t.h.local = local;
-    t.h.toggles = toggles;
-    t.h.forbidden = forbidden;
-    t.h.worklist = worklist;
-    t.h.steps = steps;
-    t.h.converged = converged;
-    t.h.flags = flags;
-    t.h.trace = trace;
-    t.h.active = active;
-    t.tabu_len = tabu_len;
-    t.max_stall = max_stall;
-    t.ring = ring;
-    t.visited = visited;
-    t.stall = stall;
-    t.best_score = best_score;
-    t.best_parents = best_parents;
-    DVS_LAUNCH(k_tabu_step, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, t);
-    return 0;
+void dvs_launch_tabu_step(const TabuArgs& t, dvs_stream_t st) {
+    DVS_LAUNCH(k_tabu_step, dim3((unsigned)((t.h.B + 3) / 4)), dim3(256), 0, st, t);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // One random legal move
 // ---------------------------------------------------------------------------------------------------------
-struct PerturbArgs {
-    int B, n, max_parents;
-    uint32_t seed_lo, seed_hi, draw_index;
-    uint64_t* parents;
-    double* local;
-    const double* toggles;
-    const uint64_t* forbidden;
-    int* worklist;
-    int* flags;
-};
-
 // inclusive prefix sum over the lanes of a wave
 __device__ __forceinline__ int hc_scan(int x, int lane) {
 #pragma unroll
@@ -240,22 +192,9 @@ __global__ __launch_bounds__(256) void k_hc_perturb(PerturbArgs a) {
     hc_apply(c, op * n * n + v * n + u, a.parents, a.local, T, base, a.worklist, b);
 }
 
-extern "C" int dvs_hc_perturb_impl(int B, int n, uint64_t* parents, double* local, const double* toggles, int max_parents,
-                                   const uint64_t* forbidden, int* worklist, int* flags, uint64_t seed, uint32_t draw_index,
-                                   void* stream) {
-    PerturbArgs a;
-    a.B = B;
-    a.n = n;
-    a.max_parents = max_parents;
+void dvs_launch_hc_perturb(const PerturbArgs& in, uint64_t seed, dvs_stream_t st) {
+    PerturbArgs a = in;
     a.seed_lo = (uint32_t)(seed & 0xffffffffull);
     a.seed_hi = (uint32_t)(seed >> 32);
-    a.draw_index = draw_index;
-    a.parents = parents;
-    a.local = local;
-    a.toggles = toggles;
-    a.forbidden = forbidden;
-    a.worklist = worklist;
-    a.flags = flags;
-    DVS_LAUNCH(k_hc_perturb, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+    DVS_LAUNCH(k_hc_perturb, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
 }

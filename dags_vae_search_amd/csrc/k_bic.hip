@@ -19,21 +19,11 @@
 // before the sum: one more pass over the table rows (dense) or over the sorted keys (sort), an integer count.  lgamma is
 // the device math library's, in fp64; its two arguments that do not depend on the cell, lgamma(a_j) and lgamma(a_jk), are
 // taken once per workgroup.  Family 1 is VALU-bound by lgamma (two per occupied cell and row) — no MFMA there either.
-#include "dvs_kernels.h"
+#include "dvs_search_args.h"
 
 constexpr int BIC_MAX_BINS = 36864;          // q_v * r_v histogram bins that fit LDS (144 KB of u32 counters)
 
-struct BicArgs {
-    int B, n, S, words;
-    const uint64_t* data;        // [S][words]
-    const uint8_t* card;         // [n] levels of each variable (2..16)
-    const uint64_t* parents;     // [B][n]: bit u of parents[b][v] <=> edge u -> v (dataset variable indices)
-    double* local;               // [B][n] scratch: local scores
-    double* out;                 // [B]
-    int* status;
-    int type;                    // dvs_score_type; family 1 reads it for the prior
-    double arg;                  // family 0: k (NaN: log(S) / 2, taken on the device as dvs_bic_scores always has); family 1: iss
-};
+static inline int bic_words(int n) { return (n + 15) / 16; }       // 4-bit level codes, 16 variables per 64-bit word
 
 __device__ __forceinline__ double bn_lgamma(double x) {
 #ifdef DVS_EMU
@@ -283,7 +273,9 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
     a.out[dag] = s;
 }
 
-void dvs_launch_bic(const BicArgs& a, dvs_stream_t st) {
+void dvs_launch_bic(const BicArgs& in, dvs_stream_t st) {
+    BicArgs a = in;
+    a.words = bic_words(a.n);
     const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
     if (a.type <= DVS_SCORE_BIC) {
         DVS_SET_LDS(k_bic_local<0>, lds);
@@ -295,30 +287,6 @@ void dvs_launch_bic(const BicArgs& a, dvs_stream_t st) {
     DVS_LAUNCH(k_bic_sum, dim3((a.B + 255) / 256), dim3(256), 0, st, a);
 }
 
-// type: dvs_score_type; arg: the resolved k (loglik 0, aic, bic; NaN = log(S) / 2 taken on the device) or iss (bde, bds)
-extern "C" int dvs_bn_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
-                                  int type, double arg, double* local, double* out, int* status, void* stream) {
-    BicArgs a;
-    a.type = type;
-    a.arg = arg;
-    a.B = B;
-    a.n = n;
-    a.S = S;
-    a.words = (n + 15) / 16;
-    a.data = data;
-    a.card = card;
-    a.parents = parents;
-    a.local = local;
-    a.out = out;
-    a.status = status;
-    dvs_launch_bic(a, (dvs_stream_t)stream);
-    return 0;
-}
-extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, const uint8_t* card, const uint64_t* parents,
-                                   double* local, double* out, int* status, void* stream) {
-    return dvs_bn_scores_impl(B, n, S, data, card, parents, DVS_SCORE_BIC, __builtin_nan(""), local, out, status, stream);
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // GP predictor, predictive mean: mean(x*) = c + sum_m o exp(-|x* - z_m|^2 / (2 l^2)) alpha_m for the
 // reference's SGPR model (src/predictors/gp.py:13-32: ConstantMean + InducingPointKernel(ScaleKernel(RBF))), with alpha
@@ -327,14 +295,6 @@ extern "C" int dvs_bic_scores_impl(int B, int n, int S, const uint64_t* data, co
 // orders of magnitude larger than the result.  B x M x 32 MACs — tiny; the kernel exists so that the encode -> predict
 // -> decode loop of latent-space search never leaves the device.
 // ---------------------------------------------------------------------------------------------------------
-struct GpArgs {
-    int B, M, D;
-    const float* x;              // [B][D] queries
-    const float* z;              // [M][D] inducing points
-    const double* alpha;         // [M]
-    double outputscale, inv2l2, constant;
-    double* out;                 // [B]
-};
 __global__ __launch_bounds__(256) void k_gp_predict(GpArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = blockIdx.x * 4 + wave;
@@ -363,21 +323,10 @@ __global__ __launch_bounds__(256) void k_gp_predict(GpArgs a) {
     if (lane == 0) a.out[q] = a.constant + a.outputscale * acc;
 }
 
-extern "C" int dvs_gp_predict_impl(int B, int M, int D, const float* x, const float* z, const double* alpha,
-                                   double outputscale, double lengthscale, double constant, double* out, void* stream) {
-    GpArgs a;
-    a.B = B;
-    a.M = M;
-    a.D = D;
-    a.x = x;
-    a.z = z;
-    a.alpha = alpha;
-    a.outputscale = outputscale;
-    a.inv2l2 = 0.5 / (lengthscale * lengthscale);
-    a.constant = constant;
-    a.out = out;
-    DVS_LAUNCH(k_gp_predict, dim3((B + 3) / 4), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_gp_predict(const GpArgs& in, double lengthscale, dvs_stream_t st) {
+    GpArgs a = in;
+    a.inv2l2 = dvs_gp_inv2l2(lengthscale);
+    DVS_LAUNCH(k_gp_predict, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -392,16 +341,6 @@ extern "C" int dvs_gp_predict_impl(int B, int M, int D, const float* x, const fl
 //                    dF/do = sum G K / o.  One wave per row a, lanes stride over b, fixed-order reduction: bitwise
 //                    reproducible.  K is recomputed from the points (a 32-dim distance) instead of read.
 // ---------------------------------------------------------------------------------------------------------
-struct GpKernArgs {
-    int na, nb, D, symmetric;
-    const float* xa;
-    const float* xb;
-    double outputscale, inv2l2, inv_l2, inv_l3, inv_o;
-    double* K;                   // forward: [na][nb]
-    const double* G;             // backward: [na][nb]
-    double* dxa;                 // backward: [na][D]
-    double* rows;                // backward: [na][2]: d/dl, d/do partials
-};
 constexpr int DVS_GP_MAXD = 32;
 __global__ __launch_bounds__(256) void k_gp_kernel(GpKernArgs a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -469,38 +408,22 @@ __global__ __launch_bounds__(256) void k_gp_kernel_bwd(GpKernArgs a) {
     }
 }
 
-static GpKernArgs gp_kern_args(int na, int nb, int D, const float* xa, const float* xb, double outputscale, double lengthscale) {
-    GpKernArgs a = {};
-    a.na = na;
-    a.nb = nb;
-    a.D = D;
-    a.xa = xa;
-    a.xb = xb;
-    a.outputscale = outputscale;
-    a.inv2l2 = 0.5 / (lengthscale * lengthscale);
-    a.inv_l2 = 1.0 / (lengthscale * lengthscale);
+static GpKernArgs gp_kern_derived(const GpKernArgs& in, double lengthscale) {
+    GpKernArgs a = in;
+    a.inv2l2 = dvs_gp_inv2l2(lengthscale);
+    a.inv_l2 = dvs_gp_inv_l2(lengthscale);
     a.inv_l3 = 1.0 / (lengthscale * lengthscale * lengthscale);
-    a.inv_o = 1.0 / outputscale;
+    a.inv_o = 1.0 / a.outputscale;
     return a;
 }
-extern "C" int dvs_gp_kernel_impl(int na, int nb, int D, const float* xa, const float* xb, double outputscale, double lengthscale,
-                                  double* K, void* stream) {
-    GpKernArgs a = gp_kern_args(na, nb, D, xa, xb, outputscale, lengthscale);
-    a.K = K;
-    const size_t n = (size_t)na * nb;
-    DVS_LAUNCH(k_gp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_gp_kernel(const GpKernArgs& in, double lengthscale, dvs_stream_t st) {
+    const GpKernArgs a = gp_kern_derived(in, lengthscale);
+    const size_t n = (size_t)a.na * a.nb;
+    DVS_LAUNCH(k_gp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
 }
-extern "C" int dvs_gp_kernel_backward_impl(int na, int nb, int D, int symmetric, const float* xa, const float* xb,
-                                           double outputscale, double lengthscale, const double* G, double* dxa, double* rows,
-                                           void* stream) {
-    GpKernArgs a = gp_kern_args(na, nb, D, xa, xb, outputscale, lengthscale);
-    a.symmetric = symmetric;
-    a.G = G;
-    a.dxa = dxa;
-    a.rows = rows;
-    DVS_LAUNCH(k_gp_kernel_bwd, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_gp_kernel_bwd(const GpKernArgs& in, double lengthscale, dvs_stream_t st) {
+    const GpKernArgs a = gp_kern_derived(in, lengthscale);
+    DVS_LAUNCH(k_gp_kernel_bwd, dim3((unsigned)((a.na + 3) / 4)), dim3(256), 0, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -509,13 +432,6 @@ extern "C" int dvs_gp_kernel_backward_impl(int na, int nb, int D, int symmetric,
 // One thread per (DAG, vertex).  status bit 5: the labels of a DAG are not a permutation of 0..n-1 (the reference asserts,
 // bnlearn.py:35) — that DAG's masks are zeroed.
 // ---------------------------------------------------------------------------------------------------------
-struct BicMaskArgs {
-    int B, n, wide;
-    const uint8_t* labels;       // [B][n]
-    const void* preds;           // [B][n] u16 (wide == 0) or u64
-    uint64_t* parents;           // [B][n]
-    int* status;
-};
 __global__ __launch_bounds__(256) void k_bic_parent_masks(BicMaskArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B * a.n) return;
@@ -539,16 +455,6 @@ __global__ __launch_bounds__(256) void k_bic_parent_masks(BicMaskArgs a) {
     }
     a.parents[(size_t)b * a.n + lab[v]] = m;
 }
-extern "C" int dvs_bic_parent_masks_impl(int B, int n, int wide, const uint8_t* labels, const void* preds, uint64_t* parents,
-                                         int* status, void* stream) {
-    BicMaskArgs a;
-    a.B = B;
-    a.n = n;
-    a.wide = wide;
-    a.labels = labels;
-    a.preds = preds;
-    a.parents = parents;
-    a.status = status;
-    DVS_LAUNCH(k_bic_parent_masks, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, (dvs_stream_t)stream, a);
-    return 0;
+void dvs_launch_bic_parent_masks(const BicMaskArgs& a, dvs_stream_t st) {
+    DVS_LAUNCH(k_bic_parent_masks, dim3((unsigned)((a.B * a.n + 255) / 256)), dim3(256), 0, st, a);
 }

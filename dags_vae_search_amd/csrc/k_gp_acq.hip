@@ -20,7 +20,7 @@
 //      then waves 0 .. ceil(D/16)-1 each contract one 16-wide slice of the dimensions: G = (w o K) Z on the same MFMA,
 //      grad = (G - x s) / l^2 with s = sum_m w_m k_m = Phi (mean - c) + phi / sigma k^T P k.
 // sigma <= 1e-12 o: EI = max(imp, 0) and the gradient is d mean / dx where imp > 0, else 0.
-#include "dvs_kernels.h"
+#include "dvs_search_args.h"
 
 typedef double dvs_d4 __attribute__((ext_vector_type(4)));
 
@@ -44,18 +44,6 @@ constexpr int GPA_VGPR_ARRAYS = GPA_TPW * 4 * 2 + 2 * GPA_TPW * 2;
 static_assert(GPA_VGPR_ARRAYS + 32 <= GPA_VGPR_BUDGET, "accumulators + B fragments must leave room at 4 waves per SIMD");
 static_assert(GPA_MAXD <= 2 * 16, "gradient: one wave per 16 dimensions, at most 2 slices");
 static_assert(GPA_MAXD / 16 <= GPA_WAVES, "gradient slices need a wave each");
-
-struct GpAcqArgs {
-    int Q, M, D, ld, Mp, NT;
-    const float* x;              // [Q][D]
-    const float* z;              // [M][D]
-    const double* W;             // [M][ld]: P in columns 0..M-1, alpha in column M
-    double c0, outputscale, inv2l2, inv_l2, constant, best, xi, sig_floor;
-    double* mean;                // [Q]
-    double* var;                 // [Q]
-    double* ei;                  // [Q]
-    float* grad;                 // [Q][D] or null
-};
 
 __device__ __forceinline__ double gpa_shfl_xor(double v, int s) {
     const long long bits = __double_as_longlong(v);
@@ -229,33 +217,14 @@ __global__ __launch_bounds__(GPA_THREADS, 2) void k_gp_acquire(GpAcqArgs a) {
     }
 }
 
-extern "C" int dvs_gp_acquire_impl(int Q, int M, int D, int ld, const float* x, const float* z, const double* W, double c0,
-                                   double outputscale, double lengthscale, double constant, double best, double xi,
-                                   double* mean, double* var, double* ei, float* grad, void* stream) {
-    GpAcqArgs a = {};
-    a.Q = Q;
-    a.M = M;
-    a.D = D;
-    a.ld = ld;
-    a.Mp = (M + 3) / 4 * 4;
-    a.NT = (M + 1 + 15) / 16;
-    a.x = x;
-    a.z = z;
-    a.W = W;
-    a.c0 = c0;
-    a.outputscale = outputscale;
-    a.inv2l2 = 0.5 / (lengthscale * lengthscale);
-    a.inv_l2 = 1.0 / (lengthscale * lengthscale);
-    a.constant = constant;
-    a.best = best;
-    a.xi = xi;
-    a.sig_floor = 1e-12 * outputscale;
-    a.mean = mean;
-    a.var = var;
-    a.ei = ei;
-    a.grad = grad;
+void dvs_launch_gp_acquire(const GpAcqArgs& in, double lengthscale, dvs_stream_t st) {
+    GpAcqArgs a = in;
+    a.Mp = (a.M + 3) / 4 * 4;
+    a.NT = (a.M + 1 + 15) / 16;
+    a.inv2l2 = dvs_gp_inv2l2(lengthscale);
+    a.inv_l2 = dvs_gp_inv_l2(lengthscale);
+    a.sig_floor = 1e-12 * a.outputscale;
     const size_t lds = gpa_lds_doubles(a.Mp) * sizeof(double);
     DVS_SET_LDS(k_gp_acquire, lds);
-    DVS_LAUNCH(k_gp_acquire, dim3((unsigned)((Q + GPA_Q - 1) / GPA_Q)), dim3(GPA_THREADS), lds, (dvs_stream_t)stream, a);
-    return 0;
+    DVS_LAUNCH(k_gp_acquire, dim3((unsigned)((a.Q + GPA_Q - 1) / GPA_Q)), dim3(GPA_THREADS), lds, st, a);
 }
