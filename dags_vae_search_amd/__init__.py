@@ -18,3 +18,4 @@ from .recon import evaluate_reconstruction, match_decoded  # noqa: F401
 from .generate import DagStream, create_encoder_dataset, encoder_dag_train_schema, generate_dags  # noqa: F401
 from .hillclimb import HillClimbResult, decode_move, hill_climb  # noqa: F401
 from .tabu import TabuResult, tabu_search  # noqa: F401
+from .compare import StructureComparison, compare_structures, cpdag, equivalence_classes, shd  # noqa: F401

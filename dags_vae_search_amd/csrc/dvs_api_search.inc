@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -388,6 +388,49 @@ extern "C" int dvs_hc_perturb(int32_t batch, int32_t n_vars, uint64_t* parents, 
     call_begin();
     dvs_launch_hc_perturb(a, seed, (dvs_stream_t)stream);
     return call_end("dvs_hc_perturb");
+}
+
+// ---- structure comparison (dvs_cpdag.h) ------------------------------------------------------------------------------
+// What dvs_cpdag and dvs_pdag_compare check alike, first: the batch, n_vars and the range of the row index.
+static int pdag_dims(const char* fn, int batch, int n_vars) {
+    if (batch <= 0) return failf(2, "%s: batch must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if ((int64_t)batch * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: batch * n_vars must be < 2^31", fn);
+    return 0;
+}
+
+extern "C" int dvs_cpdag(int32_t batch, int32_t n_vars, const uint64_t* parents, uint64_t* pdag, size_t pdag_bytes,
+                         int32_t* flags, void* stream) {
+    if (int e = pdag_dims("dvs_cpdag", batch, n_vars)) return e;
+    if (!parents || !pdag || !flags) return fail(10, "dvs_cpdag: null pointer");
+    if (pdag_bytes < (size_t)batch * n_vars * 8) return fail_size("dvs_cpdag: pdag_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    CpdagArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.parents = parents;
+    a.pdag = pdag;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_cpdag(a, (dvs_stream_t)stream);
+    return call_end("dvs_cpdag");
+}
+
+extern "C" int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a, const uint64_t* b, int32_t b_rows,
+                                int32_t* counts, size_t counts_bytes, void* stream) {
+    if (int e = pdag_dims("dvs_pdag_compare", batch, n_vars)) return e;
+    if (!a || !b || !counts) return fail(10, "dvs_pdag_compare: null pointer");
+    if (b_rows != 1 && b_rows != batch) return fail(12, "dvs_pdag_compare: b_rows must be 1 or batch");
+    if (counts_bytes < (size_t)batch * 20) return fail_size("dvs_pdag_compare: counts_bytes < batch * 20", (size_t)batch * 20);
+    PdagCompareArgs c;
+    c.B = batch;
+    c.n = n_vars;
+    c.b_rows = b_rows;
+    c.a = a;
+    c.b = b;
+    c.counts = counts;
+    call_begin();
+    dvs_launch_pdag_compare(c, (dvs_stream_t)stream);
+    return call_end("dvs_pdag_compare");
 }
 
 extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,

@@ -1,6 +1,7 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
-// climbing, tabu and the GP predictor (k_bic.hip with dvs_hillclimb.h / dvs_tabu.h; k_gp_acq.hip).  Plain C++, no device
+// climbing, tabu, structure comparison and the GP predictor (k_bic.hip with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h;
+// k_gp_acq.hip).  Plain C++, no device
 // code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -119,6 +120,23 @@ struct PerturbArgs {
     int* flags;
 };
 void dvs_launch_hc_perturb(const PerturbArgs& a, uint64_t seed, dvs_stream_t st);
+
+// ---- structure comparison (dvs_cpdag.h) ------------------------------------------------------------------------------
+struct CpdagArgs {
+    int B, n;
+    const uint64_t* parents;     // [B][n]
+    uint64_t* pdag;              // [B][n]: bit u of pdag[b][v] <=> u -> v or u - v (an undirected edge has both bits)
+    int* flags;                  // [B], written: 0, 1 a directed cycle, 2 a parent bit >= n or a self-loop
+};
+void dvs_launch_cpdag(const CpdagArgs& a, dvs_stream_t st);
+
+struct PdagCompareArgs {
+    int B, n, b_rows;            // b_rows: 1 (one target for the batch) or B
+    const uint64_t* a;           // [B][n]
+    const uint64_t* b;           // [b_rows][n]
+    int* counts;                 // [B][5]: shd, tp, fp, fn, hamming
+};
+void dvs_launch_pdag_compare(const PdagCompareArgs& a, dvs_stream_t st);
 
 // ---- row codec -> BIC parent masks (k_bic.hip) -----------------------------------------------------------------------
 struct BicMaskArgs {

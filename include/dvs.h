@@ -393,6 +393,43 @@ int dvs_hc_perturb(int32_t batch, int32_t n_vars, uint64_t* parents, double* loc
                    int32_t max_parents, const uint64_t* forbidden, int32_t* worklist, int32_t* flags, uint64_t seed,
                    uint32_t draw_index, void* stream);
 
+/* Structure comparison.  A PDAG is stored like a parent-mask batch, device u64 [B][n_vars]: bit u of row v is
+ * set iff u -> v or u - v; an undirected edge u - v has bit u of row v and bit v of row u, a directed one u -> v only bit u of
+ * row v (bnlearn's amat).  A DAG's parent masks are a PDAG in this form.
+ *
+ * dvs_cpdag: parents (device u64 [batch][n_vars], any variable order) -> pdag (device u64 [batch][n_vars]), the completed
+ * PDAG of each DAG's Markov equivalence class: the skeleton, the v-structures (u -> v is compelled if v has a parent that is
+ * neither u nor adjacent to u), then Meek's rules to a fixpoint, each for an undirected u - v, with all orientations of a
+ * round found first and applied together:
+ *   R1  u -> v if some w -> u is not adjacent to v
+ *   R2  u -> v if u -> w -> v for some w
+ *   R3  u -> v if u - w1 -> v and u - w2 -> v for two non-adjacent w1, w2
+ * (R4 cannot fire when the start is a DAG's own v-structures.)  An edge is directed in pdag iff it has that direction in
+ * every DAG of the class.  flags (device i32 [batch], written for every structure): 0, or 2 = a parent bit >= n_vars or a
+ * self-loop, or else 1 = the rows have a directed cycle; a flagged structure gets all-zero pdag rows and does not affect the
+ * others.  Integers only: two runs give equal bytes.  Checked before anything is enqueued, in this order: batch > 0 (2),
+ * n_vars in [1, 48] (3), batch * n_vars < 2^31 (2), null pointers (10), pdag_bytes < batch * n_vars * 8 (14 with the needed
+ * size).  (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_cpdag(int32_t batch, int32_t n_vars, const uint64_t* parents, uint64_t* pdag, size_t pdag_bytes, int32_t* flags,
+              void* stream);
+
+/* Counts over the unordered pairs {u, v}, u != v, of two PDAG batches: a (device u64 [batch][n_vars], the learned side)
+ * against b (device u64 [b_rows][n_vars], the target; b_rows = 1: one target for the whole batch, else b_rows = batch).  The
+ * state of a pair in a mask is none, u -> v, v -> u or undirected; a pair is present when its state is not none.  Bits >=
+ * n_vars and the diagonal of either side are ignored.  counts (device i32 [batch][5]):
+ *   [0] shd      pairs whose states differ
+ *   [1] tp       pairs present in a with the same state in b
+ *   [2] fp       pairs present in a whose state differs in b
+ *   [3] fn       pairs present in b whose state differs in a
+ *   [4] hamming  pairs present in exactly one of the two
+ * so a reversed arc, or a directed against an undirected edge, is shd 1, fp 1, fn 1; tp + fp is the number of edges of a and
+ * tp + fn that of b.  On two outputs of dvs_cpdag, shd is the structural Hamming distance of Tsamardinos et al. (2006); on
+ * DAG masks as they are, the counts are those of the DAGs.  Checked before anything is enqueued, in this order: batch > 0
+ * (2), n_vars in [1, 48] (3), batch * n_vars < 2^31 (2), null pointers (10), b_rows not 1 or batch (12), counts_bytes <
+ * batch * 20 (14 with the needed size).  (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a, const uint64_t* b, int32_t b_rows, int32_t* counts,
+                     size_t counts_bytes, void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
