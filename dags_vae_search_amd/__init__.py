@@ -19,3 +19,4 @@ from .generate import DagStream, create_encoder_dataset, encoder_dag_train_schem
 from .hillclimb import HillClimbResult, decode_move, hill_climb  # noqa: F401
 from .tabu import TabuResult, tabu_search  # noqa: F401
 from .compare import StructureComparison, compare_structures, cpdag, equivalence_classes, shd  # noqa: F401
+from .exact import ExactResult, exact_from_tables, exact_search, local_score_table  # noqa: F401

@@ -137,6 +137,13 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.dvs_pdag_compare.restype = c_int
     # (batch, n_vars, a, b, b_rows, counts, counts_bytes, stream)
     lib.dvs_pdag_compare.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]
+    lib.dvs_exact_workspace_bytes.restype = c_size_t
+    lib.dvs_exact_workspace_bytes.argtypes = [c_int32, c_int32]
+    lib.dvs_exact_search.restype = c_int
+    # (batch, n_vars, table, table_bytes, max_parents, forbidden (nullable), workspace, workspace_bytes, parents, order, score,
+    #  flags, stream)
+    lib.dvs_exact_search.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p, c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dvs_bic_parent_masks.restype = c_int
     lib.dvs_bic_parent_masks.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dvs_gp_predict.restype = c_int
@@ -169,7 +176,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

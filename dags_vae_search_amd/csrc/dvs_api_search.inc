@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -431,6 +431,47 @@ extern "C" int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a
     call_begin();
     dvs_launch_pdag_compare(c, (dvs_stream_t)stream);
     return call_end("dvs_pdag_compare");
+}
+
+// ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
+static int exact_dims(const char* fn, int batch, int n_vars) {
+    if (batch <= 0) return failf(2, "%s: batch must be > 0", fn);
+    if (n_vars < 1 || n_vars > 20) return failf(3, "%s: n_vars must be in [1, 20]", fn);
+    if (((int64_t)batch << n_vars) * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: batch * 2^n_vars * n_vars must be < 2^31", fn);
+    return 0;
+}
+
+extern "C" size_t dvs_exact_workspace_bytes(int32_t batch, int32_t n_vars) {
+    if (exact_dims("dvs_exact_workspace_bytes", batch, n_vars)) return 0;
+    return dvs_exact_layout(batch, n_vars).total;
+}
+
+extern "C" int dvs_exact_search(int32_t batch, int32_t n_vars, const double* table, size_t table_bytes, int32_t max_parents,
+                                const uint64_t* forbidden, void* workspace, size_t workspace_bytes, uint64_t* parents,
+                                int32_t* order, double* score, int32_t* flags, void* stream) {
+    if (int e = exact_dims("dvs_exact_search", batch, n_vars)) return e;
+    if (!table || !workspace || !parents || !order || !score || !flags) return fail(10, "dvs_exact_search: null pointer");
+    const size_t cells = ((size_t)batch << n_vars) * n_vars;
+    if (table_bytes < cells * 8) return fail_size("dvs_exact_search: table_bytes < batch * 2^n_vars * n_vars * 8", cells * 8);
+    const ExactLayout l = dvs_exact_layout(batch, n_vars);
+    if (workspace_bytes < l.total) return fail_size("dvs_exact_search: workspace_bytes < dvs_exact_workspace_bytes", l.total);
+    ExactArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.max_parents = max_parents;
+    a.table = table;
+    a.forbidden = forbidden;
+    a.best = (double*)((char*)workspace + l.best);
+    a.arg = (uint32_t*)((char*)workspace + l.arg);
+    a.R = (double*)((char*)workspace + l.R);
+    a.sink = (int*)((char*)workspace + l.sink);
+    a.parents = parents;
+    a.order = order;
+    a.score = score;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_exact(a, (dvs_stream_t)stream);
+    return call_end("dvs_exact_search");
 }
 
 extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,

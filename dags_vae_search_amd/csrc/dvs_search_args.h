@@ -1,7 +1,7 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
-// climbing, tabu, structure comparison and the GP predictor (k_bic.hip with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h;
-// k_gp_acq.hip).  Plain C++, no device
+// climbing, tabu, structure comparison, exact search and the GP predictor (k_bic.hip with dvs_hillclimb.h / dvs_tabu.h /
+// dvs_cpdag.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
 // code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -137,6 +137,37 @@ struct PdagCompareArgs {
     int* counts;                 // [B][5]: shd, tp, fp, fn, hamming
 };
 void dvs_launch_pdag_compare(const PdagCompareArgs& a, dvs_stream_t st);
+
+// ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
+// The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.
+struct ExactLayout {
+    size_t best, arg, R, sink, total;            // byte offsets, and the size of the whole
+};
+inline ExactLayout dvs_exact_layout(int batch, int n_vars) {
+    const size_t subsets = (size_t)batch << n_vars, cells = subsets * n_vars;
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    ExactLayout l;
+    l.best = 0;
+    l.arg = up(cells * 8);
+    l.R = l.arg + up(cells * 4);
+    l.sink = l.R + up(subsets * 8);
+    l.total = l.sink + up(subsets * 4);
+    return l;
+}
+struct ExactArgs {
+    int B, n, max_parents;
+    const double* table;         // [B][2^n][n]: cell [S][v] = local score of v with parents S & ~(1 << v), NaN = not available
+    const uint64_t* forbidden;   // [n] or null
+    double* best;                // workspace [B][2^n][n]
+    uint32_t* arg;               // workspace [B][2^n][n]
+    double* R;                   // workspace [B][2^n]
+    int* sink;                   // workspace [B][2^n]
+    uint64_t* parents;           // [B][n]
+    int* order;                  // [B][n]
+    double* score;               // [B]
+    int* flags;                  // [B], written: 1 no admissible DAG (score -inf)
+};
+void dvs_launch_exact(const ExactArgs& a, dvs_stream_t st);
 
 // ---- row codec -> BIC parent masks (k_bic.hip) -----------------------------------------------------------------------
 struct BicMaskArgs {

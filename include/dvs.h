@@ -430,6 +430,36 @@ int dvs_cpdag(int32_t batch, int32_t n_vars, const uint64_t* parents, uint64_t* 
 int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a, const uint64_t* b, int32_t b_rows, int32_t* counts,
                      size_t counts_bytes, void* stream);
 
+/* Exact structure search: the DAG with the largest decomposable score, by the subset dynamic programme of
+ * Silander and Myllymaki (2006).  table (device f64 [batch][2^n_vars][n_vars]): cell [t][S][v] is the local score of
+ * variable v with parent set S & ~(1 << v) — what dvs_bn_scores writes into scratch for a batch whose row S holds
+ * parents[v] = S & ~(1 << v); a NaN cell means "this family is not available" (refused, or never scored).  The batch is
+ * batch independent tables.  fp64 throughout, every result defined by a total order: two runs give equal bytes.
+ *   admissible   P is admissible for v when bit v is not in P, popcount(P) <= max_parents (max_parents <= 0: no cap),
+ *                P & forbidden[v] == 0 (forbidden: device u64 [n_vars], nullable, shared by the batch, as in dvs_hc_step)
+ *                and table[P][v] is not NaN.
+ *   best, arg    for every S and every v not in S: best[S][v] is the largest table[P][v] over the admissible P that are
+ *                subsets of S and arg[S][v] (u32) that P; exact fp64 ties go to the numerically smallest P.  No admissible P
+ *                (only when table[0][v] is NaN): best = -inf, arg = 0xFFFFFFFF.  Cells with v in S are unspecified.
+ *   R, sink      R[0] = +0.0 (sink[0] = -1).  For non-empty W: R[W] is the largest R[W ^ (1 << s)] + best[W ^ (1 << s)][s]
+ *                over s in W, the operands in that order, one fp64 addition; sink[W] (i32) is that s, ties to the lowest s.
+ *   backtrack    W = all ones; for k = n_vars - 1 down to 0: s = sink[W], order[k] = s, parents[s] = arg[W ^ (1 << s)][s],
+ *                W ^= 1 << s.  score = R[all ones].  score == -inf: flags[t] = 1, parents all zero, order all -1; otherwise
+ *                flags[t] = 0.  order is a topological order: parents[order[k]] has bits only among order[0 .. k-1].
+ * Outputs: parents u64 [batch][n_vars] (bit u of parents[v] <=> u -> v), order i32 [batch][n_vars], score f64 [batch], flags
+ * i32 [batch] (all written for every table).  workspace (dvs_exact_workspace_bytes bytes) holds the stages for callers and
+ * tests to read, each array starting at the next multiple of 256 bytes: best f64 [batch][2^n_vars][n_vars], then arg u32
+ * [batch][2^n_vars][n_vars], then R f64 [batch][2^n_vars], then sink i32 [batch][2^n_vars].  Checked before anything is
+ * enqueued, in this order: batch > 0 (2), n_vars in [1, 20] (3), batch * 2^n_vars * n_vars < 2^31 (2), null pointers (10;
+ * forbidden may be null), table_bytes < batch * 2^n_vars * n_vars * 8, then workspace_bytes < dvs_exact_workspace_bytes (14
+ * with the needed size).  dvs_exact_workspace_bytes returns 0 (and sets dvs_last_error) when the first three fail.  Parity
+ * with an external exact solver is unpinned: the result rests on these definitions and on brute force over all DAGs of up to
+ * five vertices.  (Added in ABI 202 as a pure addition: the version number stays.) */
+size_t dvs_exact_workspace_bytes(int32_t batch, int32_t n_vars);
+int dvs_exact_search(int32_t batch, int32_t n_vars, const double* table, size_t table_bytes, int32_t max_parents,
+                     const uint64_t* forbidden, void* workspace, size_t workspace_bytes, uint64_t* parents, int32_t* order,
+                     double* score, int32_t* flags, void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
