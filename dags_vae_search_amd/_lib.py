@@ -24,6 +24,8 @@ ABI_VERSION = 202         # DVS_VERSION of include/dvs.h this binding was writte
 GP_ACQ_MAX_INDUCING = 1023  # DVS_GP_ACQ_MAX_INDUCING
 STRUCT_HASH_INVALID = 0x7FFFFFFFFFFFFFFF  # DVS_STRUCT_HASH_INVALID
 GEN_LABELS_CHOICE, GEN_ACCEPT_ISOLATES, GEN_ACCEPT_NO_CONNECTIVITY, GEN_GROUP_SHIFT = 1, 2, 4, 8   # DVS_GEN_* flags
+CI_TYPES = {"mi": 0, "x2": 1, "mi-adf": 2, "x2-adf": 3}   # dvs_ci_type, by bnlearn's name
+CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
 SCORE_TYPES = {"loglik": 0, "aic": 1, "bic": 2, "bde": 3, "bds": 4, "k2": 5, "bdj": 6}   # dvs_score_type, by bnlearn's name
 
 
@@ -137,6 +139,23 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.dvs_pdag_compare.restype = c_int
     # (batch, n_vars, a, b, b_rows, counts, counts_bytes, stream)
     lib.dvs_pdag_compare.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]
+    lib.dvs_ci_tests.restype = c_int
+    # (n_tests, n_vars, n_samples, data, card, pairs, cond, test_type, max_cells, out, out_bytes, status, stream)
+    lib.dvs_ci_tests.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                 c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_pc_expand.restype = c_int
+    # (n_pairs, n_vars, level, adj, pair_xy, offsets, n_tests, pairs, cond, tests_bytes, stream)
+    lib.dvs_pc_expand.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]
+    lib.dvs_pc_reduce.restype = c_int
+    # (n_pairs, n_vars, pair_xy, offsets, n_tests, cond, out, alpha, adj, adj_next, sepset, sepset_bytes, result,
+    #  result_bytes, refused, stream)
+    lib.dvs_pc_reduce.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_double,
+                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_pc_orient.restype = c_int
+    # (batch, n_vars, skeleton, sepsets, sepsets_bytes, pdag, pdag_bytes, conflicts, flags, stream)
+    lib.dvs_pc_orient.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                  c_void_p]
     lib.dvs_exact_workspace_bytes.restype = c_size_t
     lib.dvs_exact_workspace_bytes.argtypes = [c_int32, c_int32]
     lib.dvs_exact_search.restype = c_int
@@ -176,7 +195,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

@@ -74,6 +74,7 @@ class BNLearnWrapper:
         self.lib = dl.load()
         self.device = torch.device(device)
         self._data = torch.from_numpy(packed.view(np.int64)).to(self.device)
+        self._card_host = [int(c) for c in arr.max(0) + 1]                 # pc.py sizes the CI tables' LDS from it
         self._card = torch.from_numpy((arr.max(0) + 1).astype(np.uint8)).to(self.device)
 
     def _parent_masks(self, graphs: Sequence, label_key: str) -> np.ndarray:

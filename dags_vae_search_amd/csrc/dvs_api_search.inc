@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -431,6 +431,116 @@ extern "C" int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a
     call_begin();
     dvs_launch_pdag_compare(c, (dvs_stream_t)stream);
     return call_end("dvs_pdag_compare");
+}
+
+// ---- conditional-independence tests and PC-stable (dvs_citest.h) -----------------------------------------------------
+extern "C" int dvs_ci_tests(int32_t n_tests, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                            const int32_t* pairs, const uint64_t* cond, int32_t test_type, int32_t max_cells, double* out,
+                            size_t out_bytes, int32_t* status, void* stream) {
+    if (n_tests <= 0 || n_samples <= 0) return fail(2, "dvs_ci_tests: n_tests and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_ci_tests: n_vars must be in [1, 48]");
+    if (test_type < DVS_CI_MI || test_type > DVS_CI_X2_ADF) return fail(12, "dvs_ci_tests: test_type is not a dvs_ci_type");
+    if (max_cells < 1 || max_cells > DVS_CI_MAX_CELLS) return fail(13, "dvs_ci_tests: max_cells must be in [1, 36864]");
+    if (!data || !card || !pairs || !cond || !out || !status) return fail(10, "dvs_ci_tests: null pointer");
+    if (out_bytes < (size_t)n_tests * 24) return fail_size("dvs_ci_tests: out_bytes < n_tests * 24", (size_t)n_tests * 24);
+    CiArgs a = {};
+    a.T = n_tests;
+    a.n = n_vars;
+    a.S = n_samples;
+    a.type = test_type;
+    a.max_cells = max_cells;
+    a.data = data;
+    a.card = card;
+    a.pairs = pairs;
+    a.cond = cond;
+    a.out = out;
+    a.status = status;
+    call_begin();
+    dvs_launch_ci_tests(a, (dvs_stream_t)stream);
+    return call_end("dvs_ci_tests");
+}
+
+// What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
+static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
+    if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (n_tests < 1 || n_tests > (int64_t)0x7fffffff) return failf(2, "%s: n_tests must be in [1, 2^31 - 1]", fn);
+    return 0;
+}
+
+extern "C" int dvs_pc_expand(int32_t n_pairs, int32_t n_vars, int32_t level, const uint64_t* adj, const int32_t* pair_xy,
+                             const int64_t* offsets, int64_t n_tests, int32_t* pairs, uint64_t* cond, size_t tests_bytes,
+                             void* stream) {
+    if (int e = pc_dims("dvs_pc_expand", n_pairs, n_vars, n_tests)) return e;
+    if (level < 0 || level > DVS_WTOK - 2) return fail(13, "dvs_pc_expand: level must be in [0, 46]");
+    if (!adj || !pair_xy || !offsets || !pairs || !cond) return fail(10, "dvs_pc_expand: null pointer");
+    if (tests_bytes < (size_t)n_tests * 8) return fail_size("dvs_pc_expand: tests_bytes < n_tests * 8", (size_t)n_tests * 8);
+    PcExpandArgs a = {};
+    a.P = n_pairs;
+    a.n = n_vars;
+    a.level = level;
+    a.T = n_tests;
+    a.adj = adj;
+    a.pair_xy = pair_xy;
+    a.offsets = (const long long*)offsets;
+    a.pairs = pairs;
+    a.cond = cond;
+    call_begin();
+    dvs_launch_pc_expand(a, (dvs_stream_t)stream);
+    return call_end("dvs_pc_expand");
+}
+
+extern "C" int dvs_pc_reduce(int32_t n_pairs, int32_t n_vars, const int32_t* pair_xy, const int64_t* offsets, int64_t n_tests,
+                             const uint64_t* cond, const double* out, double alpha, const uint64_t* adj, uint64_t* adj_next,
+                             uint64_t* sepset, size_t sepset_bytes, int64_t* result, size_t result_bytes, int32_t* refused,
+                             void* stream) {
+    if (int e = pc_dims("dvs_pc_reduce", n_pairs, n_vars, n_tests)) return e;
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(13, "dvs_pc_reduce: alpha must be in [0, 1]");
+    if (!pair_xy || !offsets || !cond || !out || !adj || !adj_next || !sepset || !result || !refused)
+        return fail(10, "dvs_pc_reduce: null pointer");
+    if (sepset_bytes < (size_t)n_vars * n_vars * 8)
+        return fail_size("dvs_pc_reduce: sepset_bytes < n_vars^2 * 8", (size_t)n_vars * n_vars * 8);
+    if (result_bytes < (size_t)n_pairs * 16) return fail_size("dvs_pc_reduce: result_bytes < n_pairs * 16", (size_t)n_pairs * 16);
+    PcReduceArgs a = {};
+    a.P = n_pairs;
+    a.n = n_vars;
+    a.T = n_tests;
+    a.alpha = alpha;
+    a.pair_xy = pair_xy;
+    a.offsets = (const long long*)offsets;
+    a.cond = cond;
+    a.out = out;
+    a.adj = adj;
+    a.adj_next = adj_next;
+    a.sepset = sepset;
+    a.result = (long long*)result;
+    a.refused = refused;
+    call_begin();
+    dvs_launch_pc_reduce(a, (dvs_stream_t)stream);
+    return call_end("dvs_pc_reduce");
+}
+
+extern "C" int dvs_pc_orient(int32_t batch, int32_t n_vars, const uint64_t* skeleton, const uint64_t* sepsets,
+                             size_t sepsets_bytes, uint64_t* pdag, size_t pdag_bytes, int32_t* conflicts, int32_t* flags,
+                             void* stream) {
+    if (batch <= 0) return fail(2, "dvs_pc_orient: batch must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_pc_orient: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return fail(2, "dvs_pc_orient: batch * n_vars^2 must be < 2^31");
+    if (!skeleton || !sepsets || !pdag || !conflicts || !flags) return fail(10, "dvs_pc_orient: null pointer");
+    const size_t rows = (size_t)batch * n_vars * 8;
+    if (sepsets_bytes < rows * n_vars) return fail_size("dvs_pc_orient: sepsets_bytes < batch * n_vars^2 * 8", rows * n_vars);
+    if (pdag_bytes < rows) return fail_size("dvs_pc_orient: pdag_bytes < batch * n_vars * 8", rows);
+    PcOrientArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.skeleton = skeleton;
+    a.sepsets = sepsets;
+    a.pdag = pdag;
+    a.conflicts = conflicts;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_pc_orient(a, (dvs_stream_t)stream);
+    return call_end("dvs_pc_orient");
 }
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------

@@ -23,6 +23,36 @@ __device__ __forceinline__ uint64_t pd_transpose(uint64_t x, int n, int lane) {
     return t;
 }
 
+// Meek's rules R1 - R3 to a fixpoint on one wave's PDAG, for k_cpdag and k_pc_orient (dvs_citest.h).  D: directed in
+// (u -> lane), U: undirected (u - lane), adj: the lane's skeleton row, s_adj: the wave's skeleton rows in LDS, written and
+// synchronised by the caller.  Every lane of the wave calls it.
+__device__ __forceinline__ void pd_meek(uint64_t& D, uint64_t& U, const uint64_t adj, const uint64_t* s_adj, const int n,
+                                        const int lane) {
+    const uint64_t self = 1ull << lane;
+    const int max_rounds = n * (n - 1) / 2 + 1;
+    for (int round = 0; round < max_rounds; ++round) {
+        uint64_t O = 0ull, via = 0ull;                       // O: u -> lane found this round; via: the parents of lane's parents
+        for (int u = 0; u < n; ++u) {
+            const uint64_t D_u = hc_bcast64(D, u), U_u = hc_bcast64(U, u);
+            const uint64_t ubit = 1ull << u;
+            if (D & ubit) via |= D_u;
+            if (!(U & ubit)) continue;
+            bool hit = (D_u & ~adj & ~self) != 0ull;                             // R1: w -> u - lane, w not adjacent to lane
+            const uint64_t S = U_u & D;                                          // R3: u - w -> lane for two non-adjacent w
+            for (uint64_t rest = S; !hit && rest; rest &= rest - 1ull) {
+                const int w = hc_ctz64(rest);
+                hit = (S & ~s_adj[w] & ~(1ull << w)) != 0ull;
+            }
+            if (hit) O |= ubit;
+        }
+        O |= U & via;                                                            // R2: u -> w -> lane, u - lane
+        if (!__ballot(O != 0ull)) break;                                         // wave-uniform: nothing oriented
+        const uint64_t O_out = pd_transpose(O, n, lane);                         // lane -> w found this round
+        D |= O;
+        U &= ~O & ~O_out;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_cpdag(CpdagArgs a) {
     __shared__ uint64_t s_adj[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x * 4 + wave;
@@ -52,28 +82,7 @@ __global__ __launch_bounds__(256) void k_cpdag(CpdagArgs a) {
     }
     uint64_t U = adj & ~D & ~pd_transpose(D, n, lane);                           // undirected: u - lane
     dvs_wave_sync();                                                             // s_adj is read by the other lanes below
-    const int max_rounds = n * (n - 1) / 2 + 1;
-    for (int round = 0; round < max_rounds; ++round) {
-        uint64_t O = 0ull, via = 0ull;                       // O: u -> lane found this round; via: the parents of lane's parents
-        for (int u = 0; u < n; ++u) {
-            const uint64_t D_u = hc_bcast64(D, u), U_u = hc_bcast64(U, u);
-            const uint64_t ubit = 1ull << u;
-            if (D & ubit) via |= D_u;
-            if (!(U & ubit)) continue;
-            bool hit = (D_u & ~adj & ~self) != 0ull;                             // R1: w -> u - lane, w not adjacent to lane
-            const uint64_t S = U_u & D;                                          // R3: u - w -> lane for two non-adjacent w
-            for (uint64_t rest = S; !hit && rest; rest &= rest - 1ull) {
-                const int w = hc_ctz64(rest);
-                hit = (S & ~s_adj[wave][w] & ~(1ull << w)) != 0ull;
-            }
-            if (hit) O |= ubit;
-        }
-        O |= U & via;                                                            // R2: u -> w -> lane, u - lane
-        if (!__ballot(O != 0ull)) break;                                         // wave-uniform: nothing oriented
-        const uint64_t O_out = pd_transpose(O, n, lane);                         // lane -> w found this round
-        D |= O;
-        U &= ~O & ~O_out;
-    }
+    pd_meek(D, U, adj, s_adj[wave], n, lane);
     if (live) a.pdag[base + lane] = D | U;
 }
 

@@ -1,7 +1,7 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
-// climbing, tabu, structure comparison, exact search and the GP predictor (k_bic.hip with dvs_hillclimb.h / dvs_tabu.h /
-// dvs_cpdag.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
+// climbing, tabu, structure comparison, CI tests and PC-stable, exact search and the GP predictor (k_bic.hip with
+// dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
 // code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -137,6 +137,56 @@ struct PdagCompareArgs {
     int* counts;                 // [B][5]: shd, tp, fp, fn, hamming
 };
 void dvs_launch_pdag_compare(const PdagCompareArgs& a, dvs_stream_t st);
+
+// ---- conditional-independence tests and PC-stable (dvs_citest.h) -----------------------------------------------------
+constexpr int DVS_CI_MAX_CELLS = 36864;          // = BIC_MAX_BINS of k_bic.hip: the dense table that fits LDS
+struct CiArgs {
+    int T, n, S, words, type, max_cells;         // words: launcher
+    const uint64_t* data;        // [S][words]
+    const uint8_t* card;         // [n]
+    const int* pairs;            // [T][2]: x, y
+    const uint64_t* cond;        // [T]: bit z <=> z is in the conditioning set
+    double* out;                 // [T][3]: statistic, df, p-value
+    int* status;
+};
+void dvs_launch_ci_tests(const CiArgs& a, dvs_stream_t st);
+
+struct PcExpandArgs {
+    int P, n, level;
+    long long T;
+    const uint64_t* adj;         // [n]: the level's frozen adjacency rows
+    const int* pair_xy;          // [P][2]
+    const long long* offsets;    // [P + 1]: tests of pair p are offsets[p] .. offsets[p + 1] - 1
+    int* pairs;                  // [T][2]
+    uint64_t* cond;              // [T]
+};
+void dvs_launch_pc_expand(const PcExpandArgs& a, dvs_stream_t st);
+
+struct PcReduceArgs {
+    int P, n;
+    long long T;
+    double alpha;
+    const int* pair_xy;          // [P][2]
+    const long long* offsets;    // [P + 1]
+    const uint64_t* cond;        // [T]
+    const double* out;           // [T][3]
+    const uint64_t* adj;         // [n]
+    uint64_t* adj_next;          // [n]
+    uint64_t* sepset;            // [n][n], the separated pairs' cells written
+    long long* result;           // [P][2]: (index of the separating test or -1, refused tests of the pair)
+    int* refused;                // [1], written
+};
+void dvs_launch_pc_reduce(const PcReduceArgs& a, dvs_stream_t st);
+
+struct PcOrientArgs {
+    int B, n;
+    const uint64_t* skeleton;    // [B][n]
+    const uint64_t* sepsets;     // [B][n][n]
+    uint64_t* pdag;              // [B][n], the layout of CpdagArgs::pdag
+    int* conflicts;              // [B]
+    int* flags;                  // [B]
+};
+void dvs_launch_pc_orient(const PcOrientArgs& a, dvs_stream_t st);
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 // The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.

@@ -265,6 +265,7 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
 #include "dvs_hillclimb.h"
 #include "dvs_tabu.h"
 #include "dvs_cpdag.h"
+#include "dvs_citest.h"
 #include "dvs_exact.h"
 
 __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {

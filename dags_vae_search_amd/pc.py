@@ -1,0 +1,212 @@
+"""Constraint-based structure learning on the device (csrc/dvs_citest.h): bnlearn's ``ci.test`` and
+``pc.stable`` for discrete data, next to the score-based searches.
+
+``ci_tests`` evaluates a batch of conditional-independence tests (G^2 ``mi``, Pearson ``x2`` and their ``-adf`` variants) on the
+evaluator's packed data set; ``pc_stable`` runs the order-independent PC skeleton search level by level (one read-back of the
+48 adjacency words per level) and orients the result into a PDAG; ``skeleton_blacklist`` turns a learned skeleton into the
+``forbidden`` rows that ``hill_climb``, ``tabu_search`` and ``exact_search`` accept — the restrict-then-maximise hybrid.
+
+The definitions are those of include/dvs.h (dvs_ci_tests, dvs_pc_expand, dvs_pc_reduce, dvs_pc_orient).  Parity with
+bnlearn's ``ci.test`` / ``pc.stable`` rests on them and is not pinned against an R run.
+"""
+from __future__ import annotations
+
+import ctypes
+from math import comb
+from typing import List, NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib as dl
+
+MAX_VARS = 48
+INDEX_RANGE = (1 << 31) - 1                # tests of one level: dvs_pc_expand's n_tests
+
+
+class PCResult(NamedTuple):
+    pdag: torch.Tensor                     # int64 [n]: bit u of row v <=> u -> v or u - v (the layout of ``cpdag``)
+    skeleton: torch.Tensor                 # int64 [n]: symmetric adjacency rows
+    sepsets: torch.Tensor                  # int64 [n, n]: the separating set of every separated pair, as a bit mask
+    tests_per_level: List[int]             # tests evaluated at level 0, 1, ...
+    refused: int                           # tests that were refused (table too large): never counted as independence
+    conflicts: int                         # edges that colliders claimed in both directions (left undirected)
+    flags: int                             # 0, or 1 when the directed part of ``pdag`` has a cycle
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _evaluator(what, evaluator):
+    if evaluator.device.type != "cuda":
+        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {evaluator.device}); this package has no CPU path")
+    return evaluator._card_host
+
+
+def _test_type(test):
+    if test not in dl.CI_TYPES:
+        raise ValueError(f"test must be one of {sorted(dl.CI_TYPES)} (got {test!r})")
+    return dl.CI_TYPES[test]
+
+
+def _max_cells(card, level):
+    """the largest (z, x, y) table a test with `level` conditioning variables can have, capped at what LDS holds"""
+    cells = 1
+    for c in sorted(card, reverse=True)[:level + 2]:
+        cells *= c
+    return max(1, min(cells, dl.CI_MAX_CELLS))
+
+
+def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk):
+    lib, T = evaluator.lib, cond.numel()
+    for t0 in range(0, T, chunk):
+        m = min(chunk, T - t0)
+        dl.check(lib, lib.dvs_ci_tests(m, evaluator.n_vars, evaluator.n_samples, _p(evaluator._data), _p(evaluator._card),
+                                       _p(pairs[t0:]), _p(cond[t0:]), typ, max_cells, _p(out[t0:]), m * 24, _p(status), _stream()),
+                 "dvs_ci_tests")
+
+
+def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = False, chunk: int = 65536):
+    """``pairs`` int32 [T, 2] (x, y) and ``cond`` int64 [T] (bit z: z is conditioned on), both on the evaluator's device ->
+    float64 [T, 3] on the device: (statistic, df, p-value) of ``test`` in {"mi", "x2", "mi-adf", "x2-adf"}.  A test whose
+    table exceeds 36 864 cells, with x = y, with x or y in its conditioning set or with an index outside the data set comes
+    back as three NaNs (``return_status=True`` also returns the status word: bit 4 says that some test was refused)."""
+    what = "ci_tests"
+    card = _evaluator(what, evaluator)
+    typ = _test_type(test)
+    for name, t in (("pairs", pairs), ("cond", cond)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a torch tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got {name} on {t.device}); this package has no CPU path")
+    if pairs.dtype != torch.int32 or pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+        raise ValueError(f"{what}: pairs must be int32 [T >= 1, 2]")
+    if cond.dtype != torch.int64 or cond.shape != (pairs.shape[0],):
+        raise ValueError(f"{what}: cond must be int64 [{pairs.shape[0]}] bit masks")
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    dev = evaluator.device
+    with torch.cuda.device(dev):
+        pairs, cond = pairs.contiguous(), cond.contiguous()
+        # the largest conditioning set sizes the LDS table: a popcount of the bits below n_vars (a higher bit is refused anyway)
+        x = cond & ((1 << evaluator.n_vars) - 1)
+        x = x - ((x >> 1) & 0x5555555555555555)
+        x = (x & 0x3333333333333333) + ((x >> 2) & 0x3333333333333333)
+        x = (x + (x >> 4)) & 0x0F0F0F0F0F0F0F0F
+        level = int(((x * 0x0101010101010101) >> 56).max())
+        out = torch.empty(cond.numel(), 3, dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk)
+    return (out, status) if return_status else out
+
+
+def ci_test(evaluator, x: int, y: int, cond=(), test: str = "mi") -> torch.Tensor:
+    """one test of x against y given the variables in ``cond`` -> float64 [3] on the device: (statistic, df, p-value)"""
+    _evaluator("ci_test", evaluator)
+    mask = 0
+    for z in cond:
+        if not 0 <= int(z) < 63:
+            raise ValueError(f"ci_test: conditioning variable {z} out of range")
+        mask |= 1 << int(z)
+    dev = evaluator.device
+    pairs = torch.tensor([[int(x), int(y)]], dtype=torch.int32, device=dev)
+    return ci_tests(evaluator, pairs, torch.tensor([mask], dtype=torch.int64, device=dev), test)[0]
+
+
+def level_tests(adj: List[int], level: int):
+    """The pairs of a PC-stable level and where their tests start: (pair_xy [[x, y], ...] with x < y adjacent and at least one
+    test, offsets [P + 1]) for the adjacency rows ``adj`` (Python ints) — the host half of dvs_pc_expand."""
+    n = len(adj)
+    pair_xy, offsets = [], [0]
+    for x in range(n):
+        for y in range(x + 1, n):
+            if not (adj[x] >> y) & 1:
+                continue
+            kx, ky = bin(adj[x] & ~(1 << y)).count("1"), bin(adj[y] & ~(1 << x)).count("1")
+            count = 1 if level == 0 else comb(kx, level) + comb(ky, level)
+            if count:
+                pair_xy.append([x, y])
+                offsets.append(offsets[-1] + count)
+    return pair_xy, offsets
+
+
+def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Optional[int] = None, chunk: int = 65536) -> PCResult:
+    """The PC-stable algorithm (Colombo and Maathuis 2014) on the evaluator's data set: the skeleton by levels of conditional
+    independence tests of growing conditioning-set size, every level working on the adjacency rows frozen at its start, then
+    colliders from the separating sets and Meek's rules.  ``max_cond`` caps the size of the conditioning sets (None: no cap,
+    the search stops at the first level where no adjacent pair has enough neighbours left).  ``chunk``: tests per launch."""
+    what = "pc_stable"
+    card = _evaluator(what, evaluator)
+    typ = _test_type(test)
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha must be in [0, 1]")
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    if max_cond is not None and int(max_cond) < 0:
+        raise ValueError("max_cond must be >= 0 or None")
+    dev, n, lib = evaluator.device, evaluator.n_vars, evaluator.lib
+    full = (1 << n) - 1
+    adj = [full & ~(1 << v) for v in range(n)]
+    tests_per_level, refused_total = [], 0
+
+    def dev_u64(values):
+        return torch.from_numpy(np.array(values, np.uint64).view(np.int64)).to(dev)
+
+    with torch.cuda.device(dev):
+        sepsets = torch.zeros(n, n, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        refused = torch.zeros(1, dtype=torch.int32, device=dev)
+        level = 0
+        while max_cond is None or level <= int(max_cond):
+            pair_xy, offsets = level_tests(adj, level)
+            T = offsets[-1]
+            if T == 0:
+                break
+            if T > INDEX_RANGE:
+                raise ValueError(f"{what}: level {level} has {T:,} tests, beyond the index range of one level ({INDEX_RANGE:,}): "
+                                 f"set max_cond below {level}")
+            P = len(pair_xy)
+            d_adj, d_next = dev_u64(adj), torch.empty(n, dtype=torch.int64, device=dev)
+            d_xy = torch.tensor(pair_xy, dtype=torch.int32, device=dev)
+            d_off = torch.tensor(offsets, dtype=torch.int64, device=dev)
+            pairs = torch.empty(T, 2, dtype=torch.int32, device=dev)
+            cond = torch.empty(T, dtype=torch.int64, device=dev)
+            out = torch.empty(T, 3, dtype=torch.float64, device=dev)
+            result = torch.empty(P, 2, dtype=torch.int64, device=dev)
+            dl.check(lib, lib.dvs_pc_expand(P, n, level, _p(d_adj), _p(d_xy), _p(d_off), T, _p(pairs), _p(cond), T * 8, _stream()),
+                     "dvs_pc_expand")
+            _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk)
+            dl.check(lib, lib.dvs_pc_reduce(P, n, _p(d_xy), _p(d_off), T, _p(cond), _p(out), float(alpha), _p(d_adj), _p(d_next),
+                                            _p(sepsets), n * n * 8, _p(result), P * 16, _p(refused), _stream()), "dvs_pc_reduce")
+            adj = [int(a) for a in d_next.cpu().numpy().view(np.uint64)]        # the level's one read-back
+            refused_total += int(refused.cpu()[0])
+            tests_per_level.append(T)
+            level += 1
+        skeleton = dev_u64(adj)
+        pdag = torch.empty(n, dtype=torch.int64, device=dev)
+        conflicts = torch.empty(1, dtype=torch.int32, device=dev)
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+        dl.check(lib, lib.dvs_pc_orient(1, n, _p(skeleton), _p(sepsets), n * n * 8, _p(pdag), n * 8, _p(conflicts), _p(flags),
+                                        _stream()), "dvs_pc_orient")
+        conflicts, flags = int(conflicts.cpu()[0]), int(flags.cpu()[0])
+    return PCResult(pdag, skeleton, sepsets, tests_per_level, refused_total, conflicts, flags)
+
+
+def skeleton_blacklist(skeleton: torch.Tensor) -> torch.Tensor:
+    """int64 [n] adjacency rows on the device -> the ``forbidden`` rows of ``hill_climb``, ``tabu_search`` and
+    ``exact_search``: bit u of row v is set for every u != v that is not adjacent to v, so a search keeps to the skeleton."""
+    what = "skeleton_blacklist"
+    if not torch.is_tensor(skeleton):
+        raise TypeError(f"{what}: skeleton must be a torch tensor of adjacency rows")
+    if skeleton.device.type != "cuda":
+        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {skeleton.device}); this package has no CPU path")
+    if skeleton.dtype != torch.int64 or skeleton.ndim != 1 or not 1 <= skeleton.shape[0] <= MAX_VARS:
+        raise ValueError(f"{what}: skeleton must be int64 [n <= 48] adjacency rows")
+    n = skeleton.shape[0]
+    own = torch.ones(n, dtype=torch.int64, device=skeleton.device) << torch.arange(n, dtype=torch.int64, device=skeleton.device)
+    return (~skeleton & ((1 << n) - 1) & ~own).contiguous()

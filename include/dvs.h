@@ -430,6 +430,70 @@ int dvs_cpdag(int32_t batch, int32_t n_vars, const uint64_t* parents, uint64_t* 
 int dvs_pdag_compare(int32_t batch, int32_t n_vars, const uint64_t* a, const uint64_t* b, int32_t b_rows, int32_t* counts,
                      size_t counts_bytes, void* stream);
 
+/* Constraint-based structure learning: bnlearn's ci.test and pc.stable for discrete data.
+ *
+ * dvs_ci_tests: n_tests conditional-independence tests on one data set.  data, card, n_vars <= 48, n_samples as for
+ * dvs_bn_scores; pairs (device i32 [n_tests][2]) names x and y of test t, cond (device u64 [n_tests]) its conditioning set Z as
+ * a bit mask; out (device f64 [n_tests][3]) gets (statistic, df, p-value).  With n the counts over the samples of the
+ * (z, x, y) table, n_xz, n_yz, n_z its marginals, r the level counts of card, sums over occupied cells, natural logarithms:
+ *   DVS_CI_MI       statistic G^2 = 2 sum n_xyz log(n_xyz n_z / (n_xz n_yz));       df = (r_x - 1)(r_y - 1) prod r_z
+ *   DVS_CI_X2       statistic X^2 = sum (n_xyz - e)^2 / e, e = n_xz n_yz / n_z, over the cells with e > 0;   df as MI
+ *   DVS_CI_MI_ADF, DVS_CI_X2_ADF    the same statistics with df = sum_z max(rows_z - 1, 0) max(cols_z - 1, 0), rows_z (cols_z)
+ *                   the number of x (y) levels with a non-zero marginal in configuration z; configurations with n_z = 0 add 0
+ * The statistic is clamped at 0 (and written so); p = Q(df / 2, statistic / 2), the regularised upper incomplete gamma function
+ * (its series below a + 1, a Lentz continued fraction above), and p = 1 for df = 0.  A test is refused — three NaNs and bit 4
+ * of status (device int32, zeroed by the caller) — when r_x r_y prod r_z > max_cells, x = y, x or y is a member of Z, or any
+ * index is < 0 or >= n_vars.  max_cells in [1, 36 864] also sizes the launch's LDS (max_cells * 4 bytes): pass the largest
+ * table of the batch, not the limit.  Integer counts, fp64 arithmetic, fixed summation order: two calls give equal bytes.
+ * Checked before anything is enqueued, in this order: n_tests, n_samples > 0 (2), n_vars in [1, 48] (3), test_type (12),
+ * max_cells (13), null pointers (10), out_bytes < n_tests * 24 (14 with the needed size).  Parity with bnlearn's ci.test is
+ * unpinned: the result rests on these definitions.  (Added in ABI 202 as a pure addition: the version number stays.) */
+typedef enum dvs_ci_type {
+    DVS_CI_MI = 0,
+    DVS_CI_X2 = 1,
+    DVS_CI_MI_ADF = 2,
+    DVS_CI_X2_ADF = 3
+} dvs_ci_type;
+int dvs_ci_tests(int32_t n_tests, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                 const int32_t* pairs, const uint64_t* cond, int32_t test_type, int32_t max_cells, double* out,
+                 size_t out_bytes, int32_t* status, void* stream);
+
+/* One level of the PC-stable skeleton search, in two calls around dvs_ci_tests.  adj (device u64 [n_vars]) holds the adjacency
+ * rows frozen at the start of the level; pair_xy (device i32 [n_pairs][2]) lists adjacent pairs x < y and offsets (device i64
+ * [n_pairs + 1], offsets[0] = 0, offsets[n_pairs] = n_tests) where each pair's tests start (a pair may have none).  The tests of
+ * a pair at level l are, in this order: the l-subsets of adj[x] \ {y} in ascending numeric order of their masks, then the
+ * l-subsets of adj[y] \ {x} in the same order; a side with fewer than l members has none, and level 0 has the single empty
+ * set.  dvs_pc_expand writes test t's (x, y) into pairs (device i32 [n_tests][2]) and its set into cond (device u64 [n_tests]),
+ * each buffer tests_bytes >= n_tests * 8 bytes; a t that the offsets place outside its pair's tests gets (-1, -1), which
+ * dvs_ci_tests refuses.  Checked in this order: n_pairs in [1, 1128] (2), n_vars in [1, 48] (3), n_tests in [1, 2^31 - 1] (2),
+ * level in [0, 46] (13), null pointers (10), tests_bytes (14 with the needed size).
+ *
+ * dvs_pc_reduce reads cond and out (device f64 [n_tests][3], dvs_ci_tests' output over the whole level).  Pair p is separated
+ * when some test of it has p-value > alpha; a NaN (refused) test never separates.  result (device i64 [n_pairs][2]) gets the
+ * index of the lowest such test, or -1, and the pair's number of NaN tests.  For a separated pair sepset[x][y] = sepset[y][x]
+ * = that test's cond (sepset: device u64 [n_vars][n_vars]; other cells are left as they are) and both adjacency bits are
+ * clear in adj_next (device u64 [n_vars], written whole; may not alias adj); *refused (device i32, written) is the level's
+ * NaN tests.  Checked in this order: n_pairs, n_vars, n_tests as above, alpha in [0, 1] (13), null pointers (10), sepset_bytes
+ * < n_vars^2 * 8, then result_bytes < n_pairs * 16 (14 with the needed size).  Integers and comparisons only: two runs give
+ * equal bytes.  (Added in ABI 202 as pure additions: the version number stays.) */
+int dvs_pc_expand(int32_t n_pairs, int32_t n_vars, int32_t level, const uint64_t* adj, const int32_t* pair_xy,
+                  const int64_t* offsets, int64_t n_tests, int32_t* pairs, uint64_t* cond, size_t tests_bytes, void* stream);
+int dvs_pc_reduce(int32_t n_pairs, int32_t n_vars, const int32_t* pair_xy, const int64_t* offsets, int64_t n_tests,
+                  const uint64_t* cond, const double* out, double alpha, const uint64_t* adj, uint64_t* adj_next,
+                  uint64_t* sepset, size_t sepset_bytes, int64_t* result, size_t result_bytes, int32_t* refused, void* stream);
+
+/* PC's orientation step on a batch: skeleton (device u64 [batch][n_vars], symmetric adjacency rows) and sepsets (device u64
+ * [batch][n_vars][n_vars]) -> pdag (device u64 [batch][n_vars]) in the layout dvs_cpdag writes.  For every unshielded triple
+ * x - z - y (x, y not adjacent) with z not in sepset[x][y], x -> z and y -> z are claimed; an edge claimed in both directions
+ * stays undirected and is counted once in conflicts (device i32 [batch]).  Then Meek's rules R1 - R3 to a fixpoint exactly as
+ * dvs_cpdag applies them.  flags (device i32 [batch]): 2 = illegal rows (an asymmetric skeleton, a bit >= n_vars, a self-loop;
+ * pdag rows zero, conflicts 0), else 1 = the directed part of the result has a cycle (the rows are kept), else 0.  Checked in
+ * this order: batch > 0 (2), n_vars in [1, 48] (3), batch * n_vars^2 < 2^31 (2), null pointers (10), sepsets_bytes < batch *
+ * n_vars^2 * 8, then pdag_bytes < batch * n_vars * 8 (14 with the needed size).  Integers only: two runs give equal bytes.
+ * (Added in ABI 202 as a pure addition: the version number stays.) */
+int dvs_pc_orient(int32_t batch, int32_t n_vars, const uint64_t* skeleton, const uint64_t* sepsets, size_t sepsets_bytes,
+                  uint64_t* pdag, size_t pdag_bytes, int32_t* conflicts, int32_t* flags, void* stream);
+
 /* Exact structure search: the DAG with the largest decomposable score, by the subset dynamic programme of
  * Silander and Myllymaki (2006).  table (device f64 [batch][2^n_vars][n_vars]): cell [t][S][v] is the local score of
  * variable v with parent set S & ~(1 << v) — what dvs_bn_scores writes into scratch for a batch whose row S holds
