@@ -76,6 +76,14 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, gcoef, grads, clip_scratch, stream)
     lib.dvs_loss_backward_sq.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
                                          c_void_p, c_void_p, c_void_p]
+    lib.dvs_loss_forward_defer.restype = c_int
+    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, eps, mu, logvar, stream)
+    lib.dvs_loss_forward_defer.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]
+    lib.dvs_loss_backward_emit.restype = c_int
+    # (... as dvs_loss_backward_sq ..., clip_scratch, status, losses, host_tail (pinned), host_seq, stream)
+    lib.dvs_loss_backward_emit.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
     lib.dvs_encode.restype = c_int
     # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, mu, logvar, stream)
     lib.dvs_encode.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
@@ -191,12 +199,14 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.dvs_profile_collect.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int]
     lib.dvs_debug_activation.restype = c_int
     lib.dvs_debug_activation.argtypes = [P(DvsShape), c_void_p, c_int, c_void_p, c_void_p]
+    lib.dvs_debug_dag_losses.restype = c_int
+    lib.dvs_debug_dag_losses.argtypes = [P(DvsShape), c_void_p, c_void_p, c_void_p]
     return lib
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
-           "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_dag_losses", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 
 def profile_collect(lib):

@@ -818,6 +818,31 @@ static void decoder_forward(const Step& c, int dec_in) {
     chain.flush();
 }
 
+// images, encoder (+ latent block), decoder: the forward up to the loss head; then the optional mu / logvar copies
+static void forward_to_decoder(const Step& c, const float* eps) {
+    prepare_images(c);
+    // decoder input embedding: identical to the encoder's in eval mode / dropout 0 (pace.py:2000-2012 recomputes it only to
+    // redraw the dropout masks); under dropout the encoder's embedding launch writes it as well (slot 7)
+    encoder_forward(c, latent_args(c, eps, true), c.d.drop.on, true);
+    decoder_forward(c, c.d.drop.on ? 7 : 0);
+}
+static void copy_out_latent(const Step& c, float* mu, float* logvar) {
+    const size_t nb = (size_t)c.d.B * 32 * sizeof(float);
+    if (mu) copy_out(mu, c.ws + c.W.mu, nb, c.st);
+    if (logvar) copy_out(logvar, c.ws + c.W.logvar, nb, c.st);
+}
+static FinalizeArgs finalize_args(const Step& c, int32_t* status, float* losses, void* host_tail, uint32_t host_seq) {
+    FinalizeArgs fa;
+    fa.B = c.d.B;
+    fa.beta = c.d.beta;
+    fa.dag_loss = c.ws + c.W.dag_loss;
+    fa.status = status;
+    fa.losses = losses;
+    fa.host_tail = (float*)host_tail;
+    fa.host_seq = host_seq;
+    return fa;
+}
+
 extern "C" int dvs_loss_forward(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
                                 int64_t n_params, void* workspace, size_t workspace_bytes, const float* eps,
                                 const int32_t* status, float* losses, float* mu, float* logvar, void* stream) {
@@ -834,25 +859,25 @@ extern "C" int dvs_loss_forward_notify(const dvs_shape* s, const void* records, 
     const Step c = make_step(s, records, params, workspace, stream);
     if (int e = check_buffers(c, "dvs_loss_forward", records_bytes, n_params, workspace_bytes)) return e;
     call_begin();
-    prepare_images(c);
-    // decoder input embedding: identical to the encoder's in eval mode / dropout 0 (pace.py:2000-2012 recomputes it only to
-    // redraw the dropout masks); under dropout the encoder's embedding launch writes it as well (slot 7)
-    encoder_forward(c, latent_args(c, eps, true), c.d.drop.on, true);
-    decoder_forward(c, c.d.drop.on ? 7 : 0);
+    forward_to_decoder(c, eps);
     launch_loss_fwd(c, loss_args(c));
-    FinalizeArgs fa;
-    fa.B = c.d.B;
-    fa.beta = c.d.beta;
-    fa.dag_loss = c.ws + c.W.dag_loss;
-    fa.status = status;
-    fa.losses = losses;
-    fa.host_tail = (float*)host_tail;
-    fa.host_seq = host_seq;
-    dvs_launch_finalize(fa, c.st);
-    const size_t nb = (size_t)c.d.B * 32 * sizeof(float);
-    if (mu) copy_out(mu, c.ws + c.W.mu, nb, c.st);
-    if (logvar) copy_out(logvar, c.ws + c.W.logvar, nb, c.st);
+    dvs_launch_finalize(finalize_args(c, status, losses, host_tail, host_seq), c.st);
+    copy_out_latent(c, mu, logvar);
     return call_end("dvs_loss_forward");
+}
+
+extern "C" int dvs_loss_forward_defer(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
+                                      int64_t n_params, void* workspace, size_t workspace_bytes, const float* eps, float* mu,
+                                      float* logvar, void* stream) {
+    if (int e = check_shape(s)) return e;
+    if (!records || !params || !workspace) return fail(10, "dvs_loss_forward_defer: null pointer");
+    const Step c = make_step(s, records, params, workspace, stream);
+    if (int e = check_buffers(c, "dvs_loss_forward_defer", records_bytes, n_params, workspace_bytes)) return e;
+    if (c.wide) return fail(13, "dvs_loss_forward_defer: one-tile path only (n_tokens, n_classes <= 16)");
+    call_begin();
+    forward_to_decoder(c, eps);
+    copy_out_latent(c, mu, logvar);
+    return call_end("dvs_loss_forward_defer");
 }
 
 extern "C" int dvs_encode(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
@@ -924,6 +949,15 @@ extern "C" int dvs_debug_activation(const dvs_shape* s, const void* workspace, i
     call_begin();
     dvs_launch_unfrag(src, out, c.d.B * c.d.NT, c.st);
     return call_end("dvs_debug_activation");
+}
+
+extern "C" int dvs_debug_dag_losses(const dvs_shape* s, const void* workspace, float* out, void* stream) {
+    if (int e = check_shape(s)) return e;
+    if (!workspace || !out) return fail(10, "dvs_debug_dag_losses: null pointer");
+    const Step c = make_step(s, nullptr, nullptr, (void*)workspace, stream);
+    call_begin();
+    copy_out(out, c.ws + c.W.dag_loss, (size_t)c.d.B * 2 * sizeof(float), c.st);
+    return call_end("dvs_debug_dag_losses");
 }
 
 // Error-path test hook (include/dvs.h): an empty kernel through the product's launch macro.

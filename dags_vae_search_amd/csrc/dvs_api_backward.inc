@@ -95,10 +95,20 @@ extern "C" int dvs_loss_backward(const dvs_shape* s, const void* records, size_t
 extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
                                     int64_t n_params, void* workspace, size_t workspace_bytes, const float* gcoef,
                                     float* grads, float* clip_scratch, void* stream) {
+    return dvs_loss_backward_emit(s, records, records_bytes, params, n_params, workspace, workspace_bytes, gcoef, grads,
+                                  clip_scratch, nullptr, nullptr, nullptr, 0u, stream);      // no losses: the plain loss-head backward
+}
+
+extern "C" int dvs_loss_backward_emit(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
+                                      int64_t n_params, void* workspace, size_t workspace_bytes, const float* gcoef,
+                                      float* grads, float* clip_scratch, int32_t* status, float* losses, void* host_tail,
+                                      uint32_t host_seq, void* stream) {
     if (int e = check_shape(s)) return e;
     if (!records || !params || !workspace || !gcoef || !grads) return fail(10, "dvs_loss_backward: null pointer");
     const Step c = make_step(s, records, params, workspace, stream);
     if (int e = check_buffers(c, "dvs_loss_backward", records_bytes, n_params, workspace_bytes)) return e;
+    const bool emit_loss = losses != nullptr;      // behind dvs_loss_forward_defer: the loss head runs once, here
+    if (emit_loss && c.wide) return fail(13, "dvs_loss_backward_emit: one-tile path only (n_tokens, n_classes <= 16)");
     if (clip_scratch && 2 + dvs_sq_parts(c.L.total) > DVS_CLIP_SCRATCH_FLOATS)
         return fail(14, "dvs_loss_backward_sq: clip_scratch (DVS_CLIP_SCRATCH_FLOATS) is too small for this parameter count");
     call_begin();
@@ -168,7 +178,9 @@ extern "C" int dvs_loss_backward_sq(const dvs_shape* s, const void* records, siz
         la.o_ln_g = L.dec[DVS_LAYERS - 1].n3.w;
         la.o_ln_b = L.dec[DVS_LAYERS - 1].n3.b;
         if (wide) dvs_launch_loss_bwd_w(la, grid, st);
-        else dvs_launch_loss_bwd(la, grid, st);
+        else dvs_launch_loss_bwd(la, grid, emit_loss, st);
+        // the per-DAG losses are complete (KL: the latent block of the forward; reconstruction: the launch above)
+        if (emit_loss) dvs_launch_finalize(finalize_args(c, status, losses, host_tail, host_seq), st);
     }
     const int dec_in = c.d.drop.on ? 7 : 0;
     // ---- decoder, last layer first --------------------------------------------------------------------------------

@@ -13,6 +13,10 @@ __device__ unsigned long long dvs_stamps_lossb[256 * 4 * 12];
 DVS_STAMP_READER(lossb)
 #endif
 #define LBSTAMP(k) DVS_ACC_STAMP_AT(dvs_stamps_lossb, lst_, 4, 12, k)      // 4 waves, ids 0-9
+// EMIT (the fused train step, dvs_loss_backward_emit): the kernel also writes the per-DAG reconstruction loss k_loss_fwd would
+// have written, dag_loss[2 dag] — logits, max, sum of exponentials and pair logits are all live here anyway.  The gradient's
+// arithmetic is the same in both instances; the plain one is instruction for instruction the kernel without the switch.
+template <bool EMIT>
 __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan) {
 #ifdef DVS_STAMPS
     unsigned long long lst_ = __builtin_amdgcn_s_memtime();
@@ -65,7 +69,9 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
         float rstd;
         dvs_load_x<true>(h, xhat, rstd, a.xin, a.ln, l.lg, l.lb, dag, N, L);
         // touch the wave's NEXT tile (one dword per 64-byte piece: one load instruction): this kernel runs one wave per SIMD,
-        // nothing else hides the ~4 k cycles a cold tile load + LayerNorm statistics cost at the top of every round
+        // nothing else hides the ~4 k cycles a cold tile load + LayerNorm statistics cost at the top of every round.  (Loading
+        // that tile into registers a round ahead instead, record words included, took 2.5 us off this kernel's 72 at B = 4096
+        // and 0.16 % off the step: under three times the run-to-run spread)
         const int nxt = dag + gridDim.x * L.nwaves;
         const float touch = a.xin[(size_t)(nxt < a.dims.B ? nxt : dag) * DVS_TILE + L.lane * 16];
         const DvsRecord* rec = a.rec + dag;
@@ -73,6 +79,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
         dvs_t2n<4>(hN, h, scrV, L);
         LBSTAMP(1);              // tile load + LayerNorm + transpose
         f4 dh[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
+        float nll = 0.f, enll = 0.f;          // EMIT: this lane's share of the node NLL and of the edge BCE, as k_loss_fwd splits them
         // ---- node head ----------------------------------------------------------------------------------
         {
             f4 t1p[2], t1[2];
@@ -100,6 +107,12 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
             const float rse = dvs_rcp(se);
             const int target = rec->label[(L.r + 1) & 15];
             const bool vt = L.r < N - 1;
+            if constexpr (EMIT) {              // k_loss_fwd's node term from the same logits, maximum and sum
+                const float lse = mx + __logf(se);
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg)
+                    nll -= (4 * L.g + reg == target && L.r < N - 1) ? (lgt[0][reg] - lse) : 0.f;
+            }
             f4 dlg[1];
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
@@ -177,6 +190,11 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
                 const float truth = (float)((par >> (jj[u] + 1)) & 1u);
                 const float sg = dvs_rcp(1.0f + __expf(-logit));
                 dl[u] = pv ? gr * (sg - truth) : 0.f;
+                if constexpr (EMIT) {          // k_loss_fwd's BCE term; lane g keeps the pairs j = g, g + 4, ... of its row, as there
+                    const float x = logit;
+                    const float bce = fmaxf(x, 0.f) - x * truth + __logf(1.0f + __expf(-fabsf(x)));
+                    enll += (pv && (jj[u] & 3) == L.g) ? bce : 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -229,6 +247,11 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
         dvs_matb_T<4>(dh, dvs_split_T(dV), l.WbT, l.WbT + DVS_IMG64, 0, L);
         dvs_ln_bwd(dh, xhat, rstd, l.lg, dgam, dbet, L);
         dvs_store_tile(a.gout, dag, dh, L);
+        if constexpr (EMIT) {
+            nll += enll;                       // every lane holds distinct pairs
+            nll = dvs_sum_wave(nll);
+            if (L.lane == 0) a.dag_loss[(size_t)dag * 2] = nll;
+        }
 #ifndef DVS_EMU
         asm volatile("" ::"v"(touch));         // keeps the touch load alive without using its value
 #else
@@ -279,12 +302,17 @@ __global__ __launch_bounds__(256) void k_loss_bwd(LossArgs a, DvsStagePlan plan)
     LBSTAMP(9);                  // slab epilogue
 }
 
-void dvs_launch_loss_bwd(const LossArgs& a, int grid, dvs_stream_t st) {
+void dvs_launch_loss_bwd(const LossArgs& a, int grid, bool emit_loss, dvs_stream_t st) {
     const size_t lds = loss_lds_bytes(4, 3);       // (the epilogue's staging areas are smaller than the DAG loop's layout)
     DvsStagePlan plan;
     loss_plan(plan, a);
-    DVS_SET_LDS(k_loss_bwd, lds);
-    DVS_LAUNCH(k_loss_bwd, dim3(grid), dim3(256), lds, st, a, plan);
+    if (emit_loss) {
+        DVS_SET_LDS(k_loss_bwd<true>, lds);
+        DVS_LAUNCH_AS("k_loss_bwd", k_loss_bwd<true>, dim3(grid), dim3(256), lds, st, a, plan);
+    } else {
+        DVS_SET_LDS(k_loss_bwd<false>, lds);
+        DVS_LAUNCH_AS("k_loss_bwd", k_loss_bwd<false>, dim3(grid), dim3(256), lds, st, a, plan);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -189,6 +189,37 @@ class PaceEngine:
                                                       _ptr(params), params.numel(), _ptr(ws), _nbytes(ws), _ptr(gcoef),
                                                       _ptr(grads), _stream()), "dvs_loss_backward")
 
+    def loss_forward_defer(self, shape, params: torch.Tensor, eps: Optional[torch.Tensor],
+                           mu: Optional[torch.Tensor] = None, logvar: Optional[torch.Tensor] = None):
+        """dvs_loss_forward_defer: the forward up to the decoder, without the loss head; loss_backward_emit must follow."""
+        _require_cuda(params, "parameters")
+        if self.wide:
+            raise ValueError("loss_forward_defer: one-tile path only")
+        ws = self.workspace(shape.batch, params.device)
+        dl.check(self.lib, self.lib.dvs_loss_forward_defer(
+            ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
+            _ptr(eps), _ptr(mu), _ptr(logvar), _stream()), "dvs_loss_forward_defer")
+
+    def loss_backward_emit(self, shape, params: torch.Tensor, gcoef: torch.Tensor, grads: torch.Tensor, losses: torch.Tensor,
+                           clip_scratch: Optional[torch.Tensor] = None, host_tail: Optional[torch.Tensor] = None,
+                           host_seq: int = 0):
+        """dvs_loss_backward_emit: the backward whose loss-head kernel also writes the per-DAG reconstruction loss; `losses`
+        and the optional pinned `host_tail` packet are what loss_forward would have written, one kernel later."""
+        ws = self.workspace(shape.batch, params.device)
+        if grads.numel() < params.numel():
+            raise ValueError("gradient buffer is smaller than the parameter buffer")
+        if losses.numel() < dl.LOSS_FLOATS:
+            raise ValueError(f"losses must hold {dl.LOSS_FLOATS} floats")
+        if clip_scratch is not None and (clip_scratch.numel() < dl.CLIP_SCRATCH_FLOATS or clip_scratch.dtype != torch.float32):
+            raise ValueError(f"clip_scratch must hold {dl.CLIP_SCRATCH_FLOATS} float32 words")
+        if host_tail is not None and (not host_tail.is_pinned() or host_tail.numel() < 4 or host_tail.dtype != torch.float32
+                                      or host_tail.data_ptr() % 16):
+            raise ValueError("host_tail must be at least 4 pinned float32 words, 16-byte aligned")
+        dl.check(self.lib, self.lib.dvs_loss_backward_emit(
+            ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
+            _ptr(gcoef), _ptr(grads), _ptr(clip_scratch), _ptr(self._status), _ptr(losses),
+            None if host_tail is None else host_tail.data_ptr(), int(host_seq) & 0xFFFFFF, _stream()), "dvs_loss_backward_emit")
+
     def encode(self, shape, params: torch.Tensor, mu: torch.Tensor, logvar: torch.Tensor):
         ws = self.workspace(shape.batch, params.device)
         dl.check(self.lib, self.lib.dvs_encode(ctypes.byref(shape), _ptr(self._records), _nbytes(self._records),
@@ -223,6 +254,14 @@ class PaceEngine:
         shape = self.shape(batch)
         dl.check(self.lib, self.lib.dvs_debug_activation(ctypes.byref(shape), _ptr(self._ws), slot, _ptr(out), _stream()),
                  "dvs_debug_activation")
+        return out
+
+    def dag_losses(self, batch: int) -> torch.Tensor:
+        """[batch, 2] = per-DAG {reconstruction loss, KL term} of the last step (debug / test access)."""
+        out = torch.empty(batch, 2, dtype=torch.float32, device=self._ws.device)
+        shape = self.shape(batch)
+        dl.check(self.lib, self.lib.dvs_debug_dag_losses(ctypes.byref(shape), _ptr(self._ws), _ptr(out), _stream()),
+                 "dvs_debug_dag_losses")
         return out
 
     def flatten(self, params: Dict[str, torch.Tensor], device) -> torch.Tensor:

@@ -180,6 +180,7 @@ class PaceVaeV3(nn.Module):
         self._step = 0
         self.dag_offset = 0            # global index of the first DAG of the next batch (data-parallel shards)
         self.nan_check = True          # raise ValueError on non-finite loss (pace.py:97-98), costs one host sync
+        self._loss_once = True         # test hook: False makes the fused step take the two-kernel loss head (the reference sequence)
         self._flatten()
 
     # ---- properties (pace.py:1217-1243) ------------------------------------------------------------------------
@@ -369,7 +370,7 @@ class PaceVaeV3(nn.Module):
                 if spins > 2_000_000:                               # ~0.3-0.5 s of polling: then fall back to a stream synchronise
                     torch.cuda.current_stream().synchronize()
                     if int(words[3]) >> 8 != seq:
-                        raise RuntimeError("the device never signalled the end of the forward (dvs_loss_forward_notify)")
+                        raise RuntimeError("the device never signalled the loss scalars (dvs_loss_forward_notify / dvs_loss_backward_emit)")
             # ONE 16-byte store on the device side, but the host reads four separate words: take the payload, then check that
             # the sequence word still says the same (include/dvs.h states the coherence requirement on this buffer; nothing
             # else writes it before the NEXT step's forward, which this thread has not enqueued yet — the re-read is the cheap
@@ -497,6 +498,7 @@ class PaceVaeV3(nn.Module):
         # Data-parallel steps (``exchange``) always take the event + side-stream variant — their scalars pass through the
         # all-reduce first — whatever DVS_EARLY_READ says, so every rank issues the same collectives.
         notify = early_read and exchange is None and self._host_tail.is_pinned() and _EARLY_READ_MODE != "event"
+        loss_once = False
         if notify:
             self._host_seq = (getattr(self, "_host_seq", 0) + 1) & 0xFFFFFF or 1
             # this step's scalars get a device tensor of their own: train_batch hands 0-d views of it to the caller (the
@@ -504,7 +506,14 @@ class PaceVaeV3(nn.Module):
             # a host-side free-list pop, no device work)
             losses = self._notify_losses = torch.empty(8, dtype=torch.float32, device=grads.device)[:dl.LOSS_FLOATS]
             self._step_guard = losses[3:5]
-            eng.loss_forward(shape, self.flat_params, eps, losses, host_tail=self._host_tail, host_seq=self._host_seq)
+            # the fused single-process step on the one-tile path runs the loss head ONCE: the loss-head backward recomputes
+            # all of the forward's and needs no loss value, so it writes the per-DAG losses and the reduction + notification
+            # follow IT (include/dvs.h: dvs_loss_forward_defer / dvs_loss_backward_emit; the host reads one kernel later)
+            loss_once = self._loss_once and clip_scratch is not None and not eng.wide
+            if loss_once:
+                eng.loss_forward_defer(shape, self.flat_params, eps)
+            else:
+                eng.loss_forward(shape, self.flat_params, eps, losses, host_tail=self._host_tail, host_seq=self._host_seq)
             self._early_pending = "poll"
         else:
             eng.loss_forward(shape, self.flat_params, eps, losses)
@@ -514,7 +523,11 @@ class PaceVaeV3(nn.Module):
         if not hasattr(self, "_gcoef") or self._gcoef.device != grads.device or self._gcoef_beta != beta:
             self._gcoef = torch.tensor([1.0, beta], dtype=torch.float32, device=grads.device)
             self._gcoef_beta = beta
-        eng.loss_backward(shape, self.flat_params, self._gcoef, grads, clip_scratch=clip_scratch)
+        if loss_once:
+            eng.loss_backward_emit(shape, self.flat_params, self._gcoef, grads, losses, clip_scratch=clip_scratch,
+                                   host_tail=self._host_tail, host_seq=self._host_seq)
+        else:
+            eng.loss_backward(shape, self.flat_params, self._gcoef, grads, clip_scratch=clip_scratch)
         self.bind_flat_grads()            # host-only (re-points .grad views if an optimiser cleared them); GPU is busy
         return losses
 

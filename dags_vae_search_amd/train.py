@@ -39,7 +39,8 @@ def train_batch(batch, model, optimizer, max_grad_norm=1.0, group=None):
     (``dags_vae_search_amd.optim.Adam``) the step runs without an autograd graph: forward+backward kernels write the
     flat gradient, ``group`` (a torch.distributed process group, or True for the default one) SUM-all-reduces it over
     RCCL, and one fused kernel pair clips and applies Adam.  Either way the call returns once the step's FORWARD is done
-    (where the reference's ``loss.item()`` returns) with the global loss; backward, all-reduce and optimiser are queued.  With any other optimiser the reference sequence runs on
+    (where the reference's ``loss.item()`` returns; single process on the one-tile path: one kernel later, behind the loss-head
+    backward, which writes the loss there) with the global loss; backward, all-reduce and optimiser are queued.  With any other optimiser the reference sequence runs on
     top of the autograd-wrapped kernels (parameters are ordinary leaf tensors with .grad)."""
     if not model.training:
         model.train()
@@ -74,7 +75,7 @@ def train_batch(batch, model, optimizer, max_grad_norm=1.0, group=None):
         # enqueued when the host learns about it, so they carry the two flags as a device-side guard and skip the update
         # (data-parallel: the flags were all-reduced with the losses, every rank skips and raises alike).
         optimizer.step(max_grad_norm=max_grad_norm, guard=guard, from_partials=not dp)
-        host, status = model.read_step()                            # waits for the forward's notification / the side stream's copy only
+        host, status = model.read_step()                            # waits for the loss notification / the side stream's copy only
         scalars = model._early_scalars                              # 0-d views of a device tensor owned by this step
         recon, kld = scalars[1], scalars[2]
         try:

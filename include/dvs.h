@@ -138,6 +138,28 @@ int dvs_loss_backward_sq(const dvs_shape* s, const void* records, size_t records
                          void* workspace, size_t workspace_bytes, const float* gcoef, float* grads, float* clip_scratch,
                          void* stream);
 
+/* The fused single-process train step with the loss head run ONCE (one-tile path, n_tokens and n_classes <= 16; 13 otherwise).
+ * The loss-head backward recomputes every quantity of the loss-head forward — logits, their maximum and sum of exponentials,
+ * all pair logits — and needs no loss value (its only coefficient is gcoef), so the pair below leaves the forward's loss-head
+ * launch out and lets the backward's write the per-DAG reconstruction loss.  Additions to ABI 202; the version number stays.
+ *   dvs_loss_forward_defer: dvs_loss_forward up to and including the decoder (per-DAG KL terms, saved activations, weight
+ *     images, optional mu / logvar); it writes NO loss scalars.
+ *   dvs_loss_backward_emit: dvs_loss_backward_sq whose first kernel also writes the per-DAG reconstruction loss, followed at
+ *     once by the reduction to `losses` (as dvs_loss_forward defines them; the guard of the dvs_clip_adam* call behind it may
+ *     point at &losses[3]) and, with host_tail, by the host notification of dvs_loss_forward_notify — same packet, same
+ *     coherence requirement, same re-arming of *status —, which the host now sees one kernel later than behind a forward.
+ *     losses == NULL: exactly dvs_loss_backward_sq (status, host_tail, host_seq unused; must then follow dvs_loss_forward*).
+ * Gradients are bit-identical to dvs_loss_forward + dvs_loss_backward_sq.  The reconstruction loss is the same sum of the same
+ * terms with the pair logits taken from the backward's recompute, whose 64-term inner sum is associated differently: it
+ * agrees with dvs_loss_forward's to fp32 rounding, not bit for bit; kld, mu, logvar are bit-identical. */
+int dvs_loss_forward_defer(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
+                           int64_t n_params, void* workspace, size_t workspace_bytes, const float* eps, float* mu,
+                           float* logvar, void* stream);
+int dvs_loss_backward_emit(const dvs_shape* s, const void* records, size_t records_bytes, const float* params,
+                           int64_t n_params, void* workspace, size_t workspace_bytes, const float* gcoef, float* grads,
+                           float* clip_scratch, int32_t* status, float* losses, void* host_tail, uint32_t host_seq,
+                           void* stream);
+
 /* PaceVaeV3.encode_direct (pace.py:1613-1641): mu, logvar device [B,32]. */
 int dvs_encode(const dvs_shape* s, const void* records, size_t records_bytes, const float* params, int64_t n_params,
                void* workspace, size_t workspace_bytes, float* mu, float* logvar, void* stream);
@@ -589,6 +611,10 @@ int dvs_debug_launch(size_t dynamic_lds_bytes, void* stream);
 
 /* Debug/test access: copy saved activation `slot` (natural [B, 16*ceil(n_tokens/16), 64] layout) out of the workspace. */
 int dvs_debug_activation(const dvs_shape* s, const void* workspace, int slot, float* out, void* stream);
+
+/* Debug/test access: copy the per-DAG loss terms of the last step out of the workspace: out (device f32 [B][2]) =
+ * {reconstruction loss, KL term} of every DAG, the addends of losses[1] and losses[2]. */
+int dvs_debug_dag_losses(const dvs_shape* s, const void* workspace, float* out, void* stream);
 
 #ifdef __cplusplus
 }
