@@ -21,3 +21,4 @@ from .tabu import TabuResult, tabu_search  # noqa: F401
 from .compare import StructureComparison, compare_structures, cpdag, equivalence_classes, shd  # noqa: F401
 from .exact import ExactResult, exact_from_tables, exact_search, local_score_table  # noqa: F401
 from .pc import PCResult, ci_test, ci_tests, pc_stable, skeleton_blacklist  # noqa: F401
+from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, sample  # noqa: F401

@@ -77,6 +77,38 @@ class BNLearnWrapper:
         self._card_host = [int(c) for c in arr.max(0) + 1]                 # pc.py sizes the CI tables' LDS from it
         self._card = torch.from_numpy((arr.max(0) + 1).astype(np.uint8)).to(self.device)
 
+    @classmethod
+    def from_packed(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, card, *, iss=None, k=None):
+        """An evaluator around rows that are already packed on the device (int64 [S, ceil(n / 16)], 4-bit level codes:
+        what ``sample`` returns and ``_data`` holds), with no host round trip.  ``card`` (n level counts, 1..16) is taken as
+        given, not read off the rows: a sample may miss a level.  ``metric_name``, ``iss`` and ``k`` as in ``__init__``."""
+        if metric_name not in dl.SCORE_TYPES:
+            raise NotImplementedError(f"built scores: {', '.join(sorted(dl.SCORE_TYPES))} (got {metric_name!r})")
+        if iss is not None and not (metric_name in DIRICHLET_SCORES and math.isfinite(iss) and iss > 0):
+            raise ValueError(f"iss is the argument of {' / '.join(DIRICHLET_SCORES)}, finite and > 0 (got {iss!r} for {metric_name!r})")
+        if k is not None and not (metric_name in PENALISED_SCORES and math.isfinite(k) and k >= 0):
+            raise ValueError(f"k is the argument of {' / '.join(PENALISED_SCORES)}, finite and >= 0 (got {k!r} for {metric_name!r})")
+        card = [int(c) for c in card]
+        n = len(card)
+        if not torch.is_tensor(packed) or packed.device.type != "cuda":
+            raise RuntimeError("dags_vae_search_amd: from_packed takes rows on the GPU; this package has no CPU path")
+        if not 1 <= n <= dl.MAX_TOKENS or any(not 1 <= c <= 16 for c in card):
+            raise ValueError("card must hold 1..48 level counts in 1..16")
+        if packed.dtype != torch.int64 or packed.ndim != 2 or packed.shape[0] < 1 or packed.shape[1] != (n + 15) // 16:
+            raise ValueError(f"packed must be int64 [S >= 1, {(n + 15) // 16}] for {n} variables")
+        self = cls.__new__(cls)
+        self.dataset_name, self.metric_name = dataset_name, metric_name
+        self.iss, self.k = iss, k
+        arg = iss if iss is not None else k
+        self._score_arg = float("nan") if arg is None else float(arg)
+        self.n_samples, self.n_vars = int(packed.shape[0]), n
+        self.lib = dl.load()
+        self.device = packed.device
+        self._data = packed.contiguous()
+        self._card_host = card
+        self._card = torch.tensor(card, dtype=torch.uint8, device=self.device)
+        return self
+
     def _parent_masks(self, graphs: Sequence, label_key: str) -> np.ndarray:
         n = self.n_vars
         masks = np.zeros((len(graphs), n), np.uint64)

@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -541,6 +541,113 @@ extern "C" int dvs_pc_orient(int32_t batch, int32_t n_vars, const uint64_t* skel
     call_begin();
     dvs_launch_pc_orient(a, (dvs_stream_t)stream);
     return call_end("dvs_pc_orient");
+}
+
+// ---- BN parameters: fit, forward sampling, held-out log-likelihood (dvs_params.h) -------------------------------------
+extern "C" int dvs_bn_fit(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                          const uint64_t* parents, int32_t method, double iss, int32_t unobserved, const int64_t* offsets,
+                          double* cpt, size_t cpt_bytes, int32_t* status, void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_fit: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_fit: n_vars must be in [1, 48]");
+    if ((int64_t)batch * n_vars > (int64_t)0x7fffffff) return fail(2, "dvs_bn_fit: batch * n_vars must be < 2^31");
+    if (method != DVS_FIT_MLE && method != DVS_FIT_BAYES) return fail(12, "dvs_bn_fit: method is not a dvs_fit_method");
+    if (method == DVS_FIT_BAYES && !(iss > 0.0 && isfinite(iss))) return fail(13, "dvs_bn_fit: iss must be finite and > 0");
+    if (unobserved != 0 && unobserved != 1) return fail(12, "dvs_bn_fit: unobserved must be 0 (NaN) or 1 (uniform)");
+    if (!data || !card || !parents || !offsets || !cpt || !status) return fail(10, "dvs_bn_fit: null pointer");
+    const size_t need = (size_t)batch * n_vars * 8;          // every family has a cell; the slots themselves are on the device
+    if (cpt_bytes < need) return fail_size("dvs_bn_fit: cpt_bytes < batch * n_vars * 8", need);
+    BnFitArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.S = n_samples;
+    a.method = method;
+    a.unobserved = unobserved;
+    a.iss = iss;
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.cpt_cells = (long long)(cpt_bytes / 8);
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_fit(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_fit");
+}
+
+static int bn_sample_dims(const char* fn, int64_t n_cells, int n_vars) {
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (n_cells < n_vars || n_cells > (int64_t)0x7fffffff) return failf(2, "%s: n_cells must be in [n_vars, 2^31 - 1]", fn);
+    return 0;
+}
+
+extern "C" size_t dvs_bn_sample_workspace_bytes(int64_t n_cells, int32_t n_vars) {
+    if (bn_sample_dims("dvs_bn_sample_workspace_bytes", n_cells, n_vars)) return 0;
+    return dvs_bn_sample_layout(n_cells).total;
+}
+
+extern "C" int dvs_bn_sample(int32_t n_vars, int64_t n_rows, const uint8_t* card, const uint64_t* parents, const int64_t* offsets,
+                             const double* cpt, int64_t n_cells, uint64_t seed, int64_t row_offset, void* workspace,
+                             size_t workspace_bytes, uint64_t* data_out, int32_t* status, void* stream) {
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return fail(2, "dvs_bn_sample: n_rows must be in [1, 2^31 - 1]");
+    if (int e = bn_sample_dims("dvs_bn_sample", n_cells, n_vars)) return e;
+    if (row_offset < 0) return fail(12, "dvs_bn_sample: row_offset must be >= 0");
+    if (!card || !parents || !offsets || !cpt || !workspace || !data_out || !status) return fail(10, "dvs_bn_sample: null pointer");
+    const BnSampleLayout l = dvs_bn_sample_layout(n_cells);
+    if (workspace_bytes < l.total) return fail_size("dvs_bn_sample: workspace_bytes < dvs_bn_sample_workspace_bytes", l.total);
+    BnSampleArgs a = {};
+    a.n = n_vars;
+    a.rows = n_rows;
+    a.n_cells = n_cells;
+    a.row_offset = (uint32_t)row_offset;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.header = (int*)((char*)workspace + l.order);
+    a.thr = (uint32_t*)((char*)workspace + l.thr);
+    a.out = data_out;
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_sample(a, seed, (dvs_stream_t)stream);
+    return call_end("dvs_bn_sample");
+}
+
+extern "C" int dvs_bn_loglik(int32_t batch, int32_t n_vars, int64_t n_rows, const uint64_t* data, const uint8_t* card,
+                             const uint64_t* parents, const int64_t* offsets, const double* cpt, double* per_row, double* out,
+                             void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    if (batch <= 0) return fail(2, "dvs_bn_loglik: batch must be > 0");
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return fail(2, "dvs_bn_loglik: n_rows must be in [1, 2^31 - 1]");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_loglik: n_vars must be in [1, 48]");
+    const int64_t chunks = (n_rows + 255) / 256;
+    if ((int64_t)batch * n_vars > (int64_t)0x7fffffff || (int64_t)batch * chunks > (int64_t)0x7fffffff)
+        return fail(2, "dvs_bn_loglik: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31");
+    if (!data || !card || !parents || !offsets || !cpt || !out || !workspace || !status)
+        return fail(10, "dvs_bn_loglik: null pointer");
+    const BnLoglikLayout l = dvs_bn_loglik_layout(batch, n_vars, n_rows);
+    const size_t need = l.logs + (size_t)batch * n_vars * 8;
+    if (workspace_bytes < need) return fail_size("dvs_bn_loglik: workspace_bytes < partials + flags + batch * n_vars * 8", need);
+    BnLoglikArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.chunks = (int)chunks;
+    a.rows = n_rows;
+    const size_t room = (workspace_bytes - l.logs) / 8;
+    a.log_cells = room > (size_t)0x7fffffff ? 0x7fffffffLL : (long long)room;
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.per_row = per_row;
+    a.out = out;
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.fam_ok = (int*)((char*)workspace + l.fam_ok);
+    a.logs = (double*)((char*)workspace + l.logs);
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_loglik(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_loglik");
 }
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
-// climbing, tabu, structure comparison, CI tests and PC-stable, exact search and the GP predictor (k_bic.hip with
-// dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
+// climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor (k_bic.hip
+// with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
 // code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -187,6 +187,80 @@ struct PcOrientArgs {
     int* flags;                  // [B]
 };
 void dvs_launch_pc_orient(const PcOrientArgs& a, dvs_stream_t st);
+
+// ---- BN parameters: fit, forward sampling, held-out log-likelihood (dvs_params.h) -------------------------------------
+// CPT layout (include/dvs.h): cpt[offsets[b * n + v] + key * r + k], key the mixed-radix parent configuration.
+constexpr int DVS_BN_SAMPLE_LDS_CELLS = 8192;    // thresholds staged in LDS up to here (32 KiB: five workgroups per CU)
+struct BnFitArgs {
+    int B, n, S, words, method, unobserved;      // words: launcher
+    double iss;
+    const uint64_t* data;        // [S][words]
+    const uint8_t* card;         // [n]
+    const uint64_t* parents;     // [B][n]
+    const long long* offsets;    // [B * n + 1]
+    double* cpt;
+    long long cpt_cells;         // cpt_bytes / 8: a slot that ends beyond it is refused
+    int* status;
+};
+void dvs_launch_bn_fit(const BnFitArgs& a, dvs_stream_t st);
+
+// The workspace of dvs_bn_sample: a header of 64 i32 (order [48], then the "drawable" word at index 48), then the u32
+// thresholds, cell for cell as the network's tables lie behind offsets[0].
+struct BnSampleLayout {
+    size_t order, thr, total;
+};
+inline BnSampleLayout dvs_bn_sample_layout(long long n_cells) {
+    BnSampleLayout l;
+    l.order = 0;
+    l.thr = 256;
+    l.total = l.thr + (((size_t)n_cells * 4 + 255) & ~(size_t)255);
+    return l;
+}
+struct BnSampleArgs {
+    int n, words;                // words: launcher
+    long long rows, n_cells;
+    uint32_t seed_lo, seed_hi, row_offset;       // seed_lo / seed_hi: launcher, from `seed`
+    const uint8_t* card;         // [n]
+    const uint64_t* parents;     // [n]
+    const long long* offsets;    // [n + 1]
+    const double* cpt;
+    int* header;                 // workspace: order [48], drawable at [48]
+    uint32_t* thr;               // workspace: [n_cells]
+    uint64_t* out;               // [rows][words]
+    int* status;
+};
+void dvs_launch_bn_sample(const BnSampleArgs& a, uint64_t seed, dvs_stream_t st);
+
+// The workspace of dvs_bn_loglik: the chunk partials f64 [B][chunks], the family flags i32 [B][n], then log(theta), cell for
+// cell as the tables lie behind offsets[0]; each array starts at a multiple of 256 bytes.
+struct BnLoglikLayout {
+    size_t partials, fam_ok, logs, chunks;       // logs: also the least workspace (a table of no cells)
+};
+inline BnLoglikLayout dvs_bn_loglik_layout(int batch, int n_vars, long long rows) {
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    BnLoglikLayout l;
+    l.chunks = (size_t)((rows + 255) / 256);
+    l.partials = 0;
+    l.fam_ok = up((size_t)batch * l.chunks * 8);
+    l.logs = l.fam_ok + up((size_t)batch * n_vars * 4);
+    return l;
+}
+struct BnLoglikArgs {
+    int B, n, words, chunks;     // words: launcher
+    long long rows, log_cells;   // log_cells: doubles the workspace holds behind `logs`
+    const uint64_t* data;        // [rows][words]
+    const uint8_t* card;
+    const uint64_t* parents;     // [B][n]
+    const long long* offsets;    // [B * n + 1]
+    const double* cpt;
+    double* per_row;             // null or [B][rows]
+    double* out;                 // [B]
+    double* partials;            // workspace [B][chunks]
+    int* fam_ok;                 // workspace [B][n]
+    double* logs;                // workspace [log_cells]
+    int* status;
+};
+void dvs_launch_bn_loglik(const BnLoglikArgs& a, dvs_stream_t st);
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 // The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.

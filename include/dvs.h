@@ -516,6 +516,87 @@ int dvs_pc_reduce(int32_t n_pairs, int32_t n_vars, const int32_t* pair_xy, const
 int dvs_pc_orient(int32_t batch, int32_t n_vars, const uint64_t* skeleton, const uint64_t* sepsets, size_t sepsets_bytes,
                   uint64_t* pdag, size_t pdag_bytes, int32_t* conflicts, int32_t* flags, void* stream);
 
+/* Parameters of a discrete Bayesian network: bnlearn's bn.fit, rbn and logLik(fitted, newdata) on the device.
+ *
+ * Layout of the conditional probability tables, shared by the three calls.  For variable v of structure b, r is its level count
+ * card[v], q the product of its parents' level counts (1 without parents) and key the mixed-radix parent configuration with
+ * the lowest variable id fastest: key = sum_i level(p_i) * prod_{i' < i} card[p_i'] over the parents p_0 < p_1 < ... (the
+ * histogram index of dvs_bn_scores).  theta(v, key, k) = P(v = k | configuration key) is
+ *   cpt[offsets[b * n_vars + v] + key * r + k]                                   (device f64)
+ * with offsets device i64 [batch * n_vars + 1], non-decreasing, offsets[i + 1] - offsets[i] == q * r for every family i.  The
+ * self bit of a parent row is ignored, as in dvs_bn_scores.  A family is malformed when a parent bit is >= n_vars, card[v] is
+ * 0 or its slot in offsets does not have q * r cells.
+ *
+ * dvs_bn_fit: the tables of batch structures from one data set (data, card, n_vars <= 48, n_samples as for dvs_bn_scores).
+ * With N_jk the count of configuration j and level k and N_j = sum_k N_jk:
+ *   DVS_FIT_MLE    theta = N_jk / N_j, one fp64 division.  An unobserved configuration (N_j = 0) gets NaN in every cell with
+ *                  unobserved = 0 (bnlearn's default) and 1 / r with unobserved = 1 (replace.unidentifiable = TRUE).
+ *   DVS_FIT_BAYES  theta = (N_jk + a) / (N_j + r * a), a = iss / (r * q): bnlearn's method = "bayes".  fp64, the operations
+ *                  in exactly that order and none fused; iss finite and > 0 (ignored by DVS_FIT_MLE, as unobserved is here).
+ * A family is refused — its cells left unwritten, bit 4 of status (device int32, zeroed by the caller) set, the other
+ * families of the launch written as usual — when it is malformed, when its slot ends beyond cpt_bytes, or when q * r > 36 864:
+ * the counts live in the dense LDS table of dvs_bn_scores and no sorted-samples path exists here.  A data level >= card[v]
+ * is not counted.  Integer counts, one rounding per operation: two calls give equal bytes.  Checked before anything is
+ * enqueued, in this order: batch, n_samples > 0 (2), n_vars in [1, 48] (3), batch * n_vars < 2^31 (2), method (12), iss (13),
+ * unobserved not 0 or 1 (12), null pointers (10), cpt_bytes < batch * n_vars * 8 (14 with that size: every family has a cell;
+ * the slots themselves are device data and are checked there).
+ *
+ * dvs_bn_sample: n_rows rows drawn from ONE network by forward sampling: card, parents (device u64 [n_vars]) and offsets
+ * (device i64 [n_vars + 1]) are those of the network — for structure b of a fitted batch pass parents + b * n_vars and
+ * offsets + b * n_vars with the same cpt.  n_cells = offsets[n_vars] - offsets[0], which the caller knows from building
+ * offsets.  data_out (device u64 [n_rows][ceil(n_vars / 16)]) gets the rows in the layout dvs_bic_scores reads, every word
+ * written.  workspace: dvs_bn_sample_workspace_bytes(n_cells, n_vars) bytes of device memory (0 and dvs_last_error for
+ * arguments out of range).  Two launches:
+ *   prep   a topological order of parents (the lowest variable whose parents are all placed, repeatedly); u32 thresholds for
+ *          every row (v, key) of the tables: with c_k = theta_0 + ... + theta_k added sequentially in fp64,
+ *          T_k = min(floor(c_k * 2^31), 2^31), and T_k = 2^31 for every k at or beyond the last level with theta > 0.
+ *          Status bits, each of which leaves data_out untouched: bit 0 a cycle; bit 4 a malformed
+ *          family, card[v] > 16 or offsets[n_vars] - offsets[0] != n_cells; bit 6 a cell that is not finite or is negative, or a
+ *          row with |c_{r-1} - 1| > 1e-9.
+ *   draw   row i has the global index g = (row_offset + i) mod 2^32 and key = dvs_site_key(seed_lo, seed_hi, 500, g) of
+ *          csrc/dvs_device.h (oracle/rng.py restates it).  Variable v draws h = dvs_draw(key, v); its level is the number of
+ *          k < r - 1 with (h >> 1) >= T_k, its parents' levels being known by then.
+ * So a level with theta = 0 is never drawn (a cumulative sum that has reached its last positive level has T = 2^31, above
+ * every 31-bit draw, and a level of probability zero adds nothing to the count below it), and the bytes depend on (seed, g,
+ * v) and the tables only: not on the order chosen, the launch geometry, whether the thresholds were staged in LDS (tables of
+ * up to 8192 cells) or read from memory, or how a request is cut into calls with consecutive row_offset.  P(level = k) is
+ * theta_k to within 2^-31 absolute.  Checked before anything is enqueued, in this order: n_rows in [1, 2^31 - 1] (2), n_vars
+ * in [1, 48] (3), n_cells in [n_vars, 2^31 - 1] (2), row_offset >= 0 (12), null pointers (10), workspace_bytes (14 with the
+ * needed size).
+ *
+ * dvs_bn_loglik: the log-likelihood of n_rows rows (data: device u64 [n_rows][ceil(n_vars / 16)], any rows, not the fit's)
+ * under each of batch networks.  The term of a row is sum_v log theta(v, key_v, x_v), natural logarithm, added in ascending
+ * v in fp64 starting from +0; per_row (device f64 [batch][n_rows], nullable) gets it.  out[b] (device f64 [batch]) is the sum
+ * of the row terms in this order: rows 256 c .. 256 c + 255 (absent rows count +0) are added by the tree x[i] += x[i + s] for
+ * s = 128, 64, ..., 1 over 256 slots; slot t of a second such array then adds the chunk sums c = t, t + 256, t + 512, ... in ascending c
+ * starting from +0, and the same tree over those 256 slots gives out[b].  No floating-point atomics:
+ * two calls give equal bytes, and per_row given or null gives the same out.  Nothing is special-cased: a row that meets
+ * theta = 0 contributes -inf and one that meets NaN (or a negative cell) NaN, by IEEE arithmetic.  log theta is taken once per
+ * cell into the workspace.  A malformed family, or a table that does not fit the workspace, makes out[b] and every row term of
+ * that structure NaN and sets bit 4 of status; a row with a level >= card[v] for some v gets a NaN term (so out[b] is NaN) and
+ * sets bit 4 too.  workspace (device): with chunks = ceil(n_rows / 256) and each array starting at the next multiple of 256
+ * bytes: f64 [batch][chunks], i32 [batch][n_vars], then f64 [offsets[batch * n_vars] - offsets[0]].  Checked before anything is
+ * enqueued, in this order: batch > 0 (2), n_rows in [1, 2^31 - 1] (2), n_vars in [1, 48] (3), batch * n_vars and batch * chunks
+ * < 2^31 (2), null pointers (10; per_row may be null), workspace_bytes below the first two arrays plus batch * n_vars * 8 (14
+ * with that size; the tables' own size is device data and is checked there).
+ *
+ * Parity with bnlearn's bn.fit, rbn, logLik and bn.cv is unpinned against an R run: the results rest on these definitions.
+ * (Added in ABI 202 as pure additions: the version number stays.) */
+typedef enum dvs_fit_method {
+    DVS_FIT_MLE = 0,
+    DVS_FIT_BAYES = 1
+} dvs_fit_method;
+int dvs_bn_fit(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+               const uint64_t* parents, int32_t method, double iss, int32_t unobserved, const int64_t* offsets, double* cpt,
+               size_t cpt_bytes, int32_t* status, void* stream);
+size_t dvs_bn_sample_workspace_bytes(int64_t n_cells, int32_t n_vars);
+int dvs_bn_sample(int32_t n_vars, int64_t n_rows, const uint8_t* card, const uint64_t* parents, const int64_t* offsets,
+                  const double* cpt, int64_t n_cells, uint64_t seed, int64_t row_offset, void* workspace, size_t workspace_bytes,
+                  uint64_t* data_out, int32_t* status, void* stream);
+int dvs_bn_loglik(int32_t batch, int32_t n_vars, int64_t n_rows, const uint64_t* data, const uint8_t* card,
+                  const uint64_t* parents, const int64_t* offsets, const double* cpt, double* per_row, double* out,
+                  void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
 /* Exact structure search: the DAG with the largest decomposable score, by the subset dynamic programme of
  * Silander and Myllymaki (2006).  table (device f64 [batch][2^n_vars][n_vars]): cell [t][S][v] is the local score of
  * variable v with parent set S & ~(1 << v) — what dvs_bn_scores writes into scratch for a batch whose row S holds
