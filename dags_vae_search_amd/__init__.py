@@ -22,3 +22,4 @@ from .compare import StructureComparison, compare_structures, cpdag, equivalence
 from .exact import ExactResult, exact_from_tables, exact_search, local_score_table  # noqa: F401
 from .pc import PCResult, ci_test, ci_tests, pc_stable, skeleton_blacklist  # noqa: F401
 from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, sample  # noqa: F401
+from .infer import cpdist, cpquery, posterior, predict  # noqa: F401

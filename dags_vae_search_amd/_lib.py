@@ -28,6 +28,7 @@ CI_TYPES = {"mi": 0, "x2": 1, "mi-adf": 2, "x2-adf": 3}   # dvs_ci_type, by bnle
 CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
 FIT_METHODS = {"mle": 0, "bayes": 1}   # dvs_fit_method, by bnlearn's name
 FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
+LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
 SCORE_TYPES = {"loglik": 0, "aic": 1, "bic": 2, "bde": 3, "bds": 4, "k2": 5, "bdj": 6}   # dvs_score_type, by bnlearn's name
 
 
@@ -182,6 +183,20 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     #  stream)
     lib.dvs_bn_loglik.argtypes = [c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_bn_lw_workspace_bytes.restype = c_size_t
+    lib.dvs_bn_lw_workspace_bytes.argtypes = [c_int64, c_int32, c_int64, c_int64, c_uint64]
+    lib.dvs_bn_lw.restype = c_int
+    # (n_vars, n_queries, n_particles, card, parents, offsets, cpt, n_cells, evidence, observed, event (nullable), targets, seed,
+    #  query_offset, workspace, workspace_bytes, sums, marginals (nullable), particles (nullable), particle_weights (nullable),
+    #  status, stream)
+    lib.dvs_bn_lw.argtypes = [c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                              c_void_p, c_uint64, c_uint64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p]
+    lib.dvs_bn_blanket_posterior.restype = c_int
+    # (batch, n_vars, n_rows, data, card, parents, offsets, cpt, cpt_bytes, target, use_children, posterior (nullable), pred,
+    #  status, stream)
+    lib.dvs_bn_blanket_posterior.argtypes = [c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.dvs_exact_workspace_bytes.restype = c_size_t
     lib.dvs_exact_workspace_bytes.argtypes = [c_int32, c_int32]
     lib.dvs_exact_search.restype = c_int
@@ -223,7 +238,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_bn_fit", "dvs_bn_sample_workspace_bytes", "dvs_bn_sample", "dvs_bn_loglik", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_bn_fit", "dvs_bn_sample_workspace_bytes", "dvs_bn_sample", "dvs_bn_loglik", "dvs_bn_lw_workspace_bytes", "dvs_bn_lw", "dvs_bn_blanket_posterior", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_dag_losses", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

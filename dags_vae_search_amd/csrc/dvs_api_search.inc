@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -648,6 +648,105 @@ extern "C" int dvs_bn_loglik(int32_t batch, int32_t n_vars, int64_t n_rows, cons
     call_begin();
     dvs_launch_bn_loglik(a, (dvs_stream_t)stream);
     return call_end("dvs_bn_loglik");
+}
+
+// ---- inference on a fitted network: likelihood weighting, exact blanket posterior (dvs_infer.h) ------------------------
+static int bn_lw_dims(const char* fn, int64_t n_cells, int n_vars, int64_t n_queries, int64_t n_particles, uint64_t targets) {
+    if (n_queries < 1 || n_queries > (int64_t)0x7fffffff || n_particles < 1 || n_particles > (int64_t)0x7fffffff)
+        return failf(2, "%s: n_queries and n_particles must be in [1, 2^31 - 1]", fn);
+    if (int e = bn_sample_dims(fn, n_cells, n_vars)) return e;
+    if (n_queries * ((n_particles + 255) / 256) > (int64_t)0x7fffffff)
+        return failf(2, "%s: n_queries * ceil(n_particles / 256) must be < 2^31", fn);
+    if (targets >> n_vars) return failf(12, "%s: targets has a bit at or above n_vars", fn);
+    return 0;
+}
+
+extern "C" size_t dvs_bn_lw_workspace_bytes(int64_t n_cells, int32_t n_vars, int64_t n_queries, int64_t n_particles,
+                                            uint64_t targets) {
+    if (bn_lw_dims("dvs_bn_lw_workspace_bytes", n_cells, n_vars, n_queries, n_particles, targets)) return 0;
+    return dvs_bn_lw_layout(n_cells, n_queries, n_particles, targets).total;
+}
+
+extern "C" int dvs_bn_lw(int32_t n_vars, int64_t n_queries, int64_t n_particles, const uint8_t* card, const uint64_t* parents,
+                         const int64_t* offsets, const double* cpt, int64_t n_cells, const uint64_t* evidence,
+                         const uint64_t* observed, const uint16_t* event, uint64_t targets, uint64_t seed, int64_t query_offset,
+                         void* workspace, size_t workspace_bytes, double* sums, double* marginals, uint64_t* particles,
+                         double* particle_weights, int32_t* status, void* stream) {
+    if (int e = bn_lw_dims("dvs_bn_lw", n_cells, n_vars, n_queries, n_particles, targets)) return e;
+    if (query_offset < 0) return fail(12, "dvs_bn_lw: query_offset must be >= 0");
+    if (!card || !parents || !offsets || !cpt || !evidence || !observed || !workspace || !sums || !status)
+        return fail(10, "dvs_bn_lw: null pointer");
+    if ((targets != 0) != (marginals != nullptr)) return fail(12, "dvs_bn_lw: marginals goes with targets != 0, and only with it");
+    if ((particles != nullptr) != (particle_weights != nullptr))
+        return fail(12, "dvs_bn_lw: particles and particle_weights are both null or both given");
+    const BnLwLayout l = dvs_bn_lw_layout(n_cells, n_queries, n_particles, targets);
+    if (workspace_bytes < l.total) return fail_size("dvs_bn_lw: workspace_bytes < dvs_bn_lw_workspace_bytes", l.total);
+    BnLwArgs a = {};
+    a.n = n_vars;
+    a.Q = (int)n_queries;
+    static const int cus = dvs_device_cus();
+    a.cus = cus;
+    a.chunks = (int)l.chunks;
+    a.M = n_particles;
+    a.n_cells = n_cells;
+    a.query_offset = (uint32_t)query_offset;
+    a.targets = targets;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.evidence = evidence;
+    a.observed = observed;
+    a.event = event;
+    a.header = (int*)((char*)workspace + l.order);
+    a.thr = (uint32_t*)((char*)workspace + l.thr);
+    a.qbad = (int*)((char*)workspace + l.qbad);
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.sums = sums;
+    a.marginals = marginals;
+    a.particles = particles;
+    a.pweights = particle_weights;
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_lw(a, seed, (dvs_stream_t)stream);
+    return call_end("dvs_bn_lw");
+}
+
+extern "C" int dvs_bn_blanket_posterior(int32_t batch, int32_t n_vars, int64_t n_rows, const uint64_t* data, const uint8_t* card,
+                                        const uint64_t* parents, const int64_t* offsets, const double* cpt, size_t cpt_bytes,
+                                        int32_t target, int32_t use_children, double* posterior, uint8_t* pred, int32_t* status,
+                                        void* stream) {
+    if (batch <= 0) return fail(2, "dvs_bn_blanket_posterior: batch must be > 0");
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return fail(2, "dvs_bn_blanket_posterior: n_rows must be in [1, 2^31 - 1]");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_blanket_posterior: n_vars must be in [1, 48]");
+    const int64_t chunks = (n_rows + 255) / 256;
+    if ((int64_t)batch * n_vars > (int64_t)0x7fffffff || (int64_t)batch * chunks > (int64_t)0x7fffffff)
+        return fail(2, "dvs_bn_blanket_posterior: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31");
+    if (target < 0 || target >= n_vars) return fail(12, "dvs_bn_blanket_posterior: target must be in [0, n_vars)");
+    if (use_children != 0 && use_children != 1) return fail(12, "dvs_bn_blanket_posterior: use_children must be 0 or 1");
+    if (!data || !card || !parents || !offsets || !cpt || !pred || !status)
+        return fail(10, "dvs_bn_blanket_posterior: null pointer");
+    const size_t need = (size_t)batch * n_vars * 8;          // every family has a cell; the slots themselves are on the device
+    if (cpt_bytes < need) return fail_size("dvs_bn_blanket_posterior: cpt_bytes < batch * n_vars * 8", need);
+    BnBlanketArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.chunks = (int)chunks;
+    a.target = target;
+    a.use_children = use_children;
+    a.rows = n_rows;
+    a.cpt_cells = (long long)(cpt_bytes / 8);
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.posterior = posterior;
+    a.pred = pred;
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_blanket(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_blanket_posterior");
 }
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------

@@ -361,10 +361,13 @@ __device__ __forceinline__ void dvs_ln_stats(const f4 (&x)[4], float& mean, floa
 // Sites: 0-33 the step's dropout masks (dvs_api.hip: site_enc / site_dec), 100 the reparameterisation noise, 200 the decode
 // sampler (k_decode.hip), 300 / 301 / 302 the graph generator's edge slots, labels and per-DAG edge counts (dvs_generate.h),
 // 400 the random moves of dvs_hc_perturb (dvs_tabu.h; keyed by the structure's index in the batch, element = draw_index),
-// 500 the forward sampler of dvs_bn_sample (dvs_params.h; keyed by the global row index, element = variable).
+// 500 the forward sampler of dvs_bn_sample (dvs_params.h; keyed by the global row index, element = variable),
+// 501 the likelihood-weighting sampler of dvs_bn_lw (dvs_infer.h; keyed by the global query index; variable v of particle p
+// draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw).
 constexpr uint32_t DVS_SITE_GEN_EDGES = 300u, DVS_SITE_GEN_LABELS = 301u, DVS_SITE_GEN_COUNTS = 302u;
 constexpr uint32_t DVS_SITE_HC_PERTURB = 400u;
 constexpr uint32_t DVS_SITE_BN_SAMPLE = 500u;
+constexpr uint32_t DVS_SITE_BN_LW = 501u;
 __device__ __forceinline__ uint32_t dvs_fmix32(uint32_t x) {
     x ^= x >> 16;
     x *= 0x85EBCA6Bu;

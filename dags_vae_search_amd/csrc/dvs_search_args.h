@@ -262,6 +262,65 @@ struct BnLoglikArgs {
 };
 void dvs_launch_bn_loglik(const BnLoglikArgs& a, dvs_stream_t st);
 
+// ---- inference on a fitted network: likelihood weighting, exact blanket posterior (dvs_infer.h) ------------------------
+// The workspace of dvs_bn_lw: the sampler's workspace (header, thresholds), then the per-query "evidence level >= card" flags
+// i32 [Q], then the chunk partials f64 [Q][chunks][3 + 16 T]; each array starts at a multiple of 256 bytes.
+struct BnLwLayout {
+    size_t order, thr, qbad, partials, total, chunks, cells;
+};
+inline BnLwLayout dvs_bn_lw_layout(long long n_cells, long long n_queries, long long n_particles, uint64_t targets) {
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const BnSampleLayout s = dvs_bn_sample_layout(n_cells);
+    BnLwLayout l;
+    int T = 0;
+    for (uint64_t tm = targets; tm; tm &= tm - 1ull) ++T;
+    l.order = s.order;
+    l.thr = s.thr;
+    l.qbad = s.total;
+    l.chunks = (size_t)((n_particles + 255) / 256);
+    l.cells = (size_t)(3 + 16 * T);
+    l.partials = l.qbad + up((size_t)n_queries * 4);
+    l.total = l.partials + up((size_t)n_queries * l.chunks * l.cells * 8);
+    return l;
+}
+struct BnLwArgs {
+    int n, words, Q, chunks, T, cells, cus;      // words, T, cells: launcher; cus: dvs_device_cus(), sizes the grid
+    long long M, n_cells;
+    uint32_t seed_lo, seed_hi, query_offset;     // seed_lo / seed_hi: launcher, from `seed`
+    uint64_t targets;
+    const uint8_t* card;         // [n]
+    const uint64_t* parents;     // [n]
+    const long long* offsets;    // [n + 1]
+    const double* cpt;
+    const uint64_t* evidence;    // [Q][words]
+    const uint64_t* observed;    // [Q]
+    const uint16_t* event;       // [n] or null
+    int* header;                 // workspace: order [48], drawable at [48]
+    uint32_t* thr;               // workspace: [n_cells]
+    int* qbad;                   // workspace: [Q]
+    double* partials;            // workspace: [Q][chunks][cells]
+    double* sums;                // [Q][3]
+    double* marginals;           // [Q][T][16] or null (then targets == 0)
+    uint64_t* particles;         // [Q][M][words] or null
+    double* pweights;            // [Q][M] or null, with particles
+    int* status;
+};
+void dvs_launch_bn_lw(const BnLwArgs& a, uint64_t seed, dvs_stream_t st);
+
+struct BnBlanketArgs {
+    int B, n, words, chunks, target, use_children;       // words: launcher
+    long long rows, cpt_cells;   // cpt_cells: cpt_bytes / 8: a slot that ends beyond it is malformed
+    const uint64_t* data;        // [rows][words]
+    const uint8_t* card;
+    const uint64_t* parents;     // [B][n]
+    const long long* offsets;    // [B * n + 1]
+    const double* cpt;
+    double* posterior;           // null or [B][rows][card[target]]
+    uint8_t* pred;               // [B][rows]
+    int* status;
+};
+void dvs_launch_bn_blanket(const BnBlanketArgs& a, dvs_stream_t st);
+
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 // The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.
 struct ExactLayout {

@@ -267,6 +267,7 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
 #include "dvs_cpdag.h"
 #include "dvs_citest.h"
 #include "dvs_params.h"
+#include "dvs_infer.h"
 #include "dvs_exact.h"
 
 __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {

@@ -1,5 +1,5 @@
 """Parameters of a discrete Bayesian network on the device (csrc/dvs_params.h): bnlearn's ``bn.fit``, ``rbn``,
-``logLik(fitted, newdata)`` and ``bn.cv(loss = "logl")`` next to the structure searches.
+``logLik(fitted, newdata)`` and ``bn.cv`` next to the structure searches.
 
 ``bn_fit`` turns parent masks into conditional probability tables on the evaluator's data set, ``sample`` draws packed rows
 from one fitted network, ``log_likelihood`` scores rows the tables were not fitted on, and ``cross_validate`` composes the three
@@ -232,26 +232,65 @@ def cv_folds(n_rows: int, folds: int, seed: int) -> List[np.ndarray]:
     return [perm[f * n_rows // folds:(f + 1) * n_rows // folds] for f in range(folds)]
 
 
-def cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 0, method: str = "mle", iss=None) -> torch.Tensor:
-    """bnlearn's ``bn.cv(loss = "logl")`` for fixed structures: the rows are permuted (``cv_folds``), each part is held out in
-    turn, the tables are fitted on the rest (``bn_fit``) and the part is scored (``log_likelihood``).  -> float64 [B] on the
-    device: minus the held-out log-likelihood per row, summed over the parts and divided by the number of rows.  Under "mle" a
-    held-out row whose configuration the rest never showed makes the loss NaN, and one whose level the rest never showed under
-    its configuration +inf, as with bnlearn's defaults; "bayes" keeps it finite."""
+CV_LOSSES = {"logl": None, "pred": "parents", "pred-exact": "exact", "pred-lw": "bayes-lw"}   # loss -> predict's method
+
+
+def cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 0, method: str = "mle", iss=None, loss: str = "logl",
+                   target=None, n=None) -> torch.Tensor:
+    """bnlearn's ``bn.cv`` for fixed structures: the rows are permuted (``cv_folds``), each part is held out in turn, the tables
+    are fitted on the rest (``bn_fit``) and the part is scored.  -> float64 [B] on the device.
+
+    ``loss="logl"`` (the default): minus the held-out log-likelihood (``log_likelihood``) per row, summed over the parts and
+    divided by the number of rows.  Under "mle" a held-out row whose configuration the rest never showed makes the loss NaN,
+    and one whose level the rest never showed under its configuration +inf, as with bnlearn's defaults; "bayes" keeps it finite.
+
+    ``loss="pred" | "pred-exact" | "pred-lw"``: the share of held-out rows whose level of variable ``target`` is predicted
+    wrongly (``infer.predict`` with method "parents", "exact" or "bayes-lw" with ``n`` particles per row, 500 by default, and ``seed``; ``n``
+    is the argument of "pred-lw" alone; a row that predicts 255 counts as wrong).  "pred-lw" runs one likelihood-weighting call
+    per structure and part; the other two take the whole batch of structures in one call per part.  bnlearn has "pred" and "pred-lw"; "pred-exact" is what "pred-lw" approximates."""
     what = "cross_validate"
     _need_cuda(what, evaluator.device)
     S = evaluator.n_samples
     if not 2 <= int(folds) <= S:
         raise ValueError(f"{what}: folds must be in [2, {S}]")
+    if loss not in CV_LOSSES:
+        raise ValueError(f"{what}: loss must be one of {sorted(CV_LOSSES)} (got {loss!r})")
+    if (loss == "logl") != (target is None):
+        raise ValueError(f"{what}: target is the argument of the prediction losses, and they need it")
+    if n is not None and (loss != "pred-lw" or int(n) < 1):
+        raise ValueError(f"{what}: n (>= 1) is the argument of loss='pred-lw'")
+    n = 500 if n is None else int(n)
+    if target is not None and not 0 <= int(target) < evaluator.n_vars:
+        raise ValueError(f"{what}: target must be in [0, {evaluator.n_vars})")
     dev = evaluator.device
     with torch.cuda.device(dev):
         parts = [torch.from_numpy(p).to(dev) for p in cv_folds(S, int(folds), seed)]
         total = None
+        done = 0
         for f, part in enumerate(parts):
             rest = torch.cat([p for g, p in enumerate(parts) if g != f])
             train = BNLearnWrapper.from_packed(evaluator.dataset_name, evaluator.metric_name, evaluator._data[rest],
                                                evaluator._card_host, iss=evaluator.iss, k=evaluator.k)
             fitted = bn_fit(train, parents, method=method, iss=iss)
-            ll = log_likelihood(fitted, evaluator._data[part])
+            held = evaluator._data[part]
+            if loss == "logl":
+                ll = log_likelihood(fitted, held)
+            else:
+                ll = _wrong_predictions(fitted, held, int(target), CV_LOSSES[loss], n, seed, done)
+            done += held.shape[0]
             total = ll if total is None else total + ll
-    return -total / S
+    if loss == "logl":
+        return -total / S
+    return total / torch.full_like(total, float(S))          # tensor by tensor: one correctly rounded division of the count
+
+
+def _wrong_predictions(fitted, held, target, method, n, seed, query_offset):
+    """float64 [B]: the held-out rows whose level of `target` structure b predicts wrongly"""
+    from . import infer
+    truth = ((held[:, target // 16] >> (4 * (target % 16))) & 15).to(torch.uint8)
+    if method != "bayes-lw":
+        pred, _ = infer._blanket(fitted, held.contiguous(), target, method == "exact", False, None, "cross_validate")
+    else:
+        pred = torch.stack([infer.predict(fitted, target, held, method=method, n=n, seed=seed, index=b, query_offset=query_offset)
+                            for b in range(fitted.batch)])
+    return (pred != truth[None, :]).sum(1).to(torch.float64)

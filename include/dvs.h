@@ -597,6 +597,74 @@ int dvs_bn_loglik(int32_t batch, int32_t n_vars, int64_t n_rows, const uint64_t*
                   const uint64_t* parents, const int64_t* offsets, const double* cpt, double* per_row, double* out,
                   void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
+/* Inference on a fitted network: bnlearn's cpquery, cpdist and predict on the device.  The CPT layout is the
+ * one above.
+ *
+ * dvs_bn_lw: likelihood weighting on ONE network (card, parents, offsets, cpt, n_cells as for dvs_bn_sample), n_queries (Q)
+ * queries of n_particles (M) particles each.  evidence: device u64 [Q][ceil(n_vars / 16)], rows in the layout of
+ * dvs_bic_scores; observed: device u64 [Q], bit v set <=> variable v of query q is clamped to its level in evidence[q] (the
+ * other nibbles of the row are not read); event: device u16 [n_vars], nullable: bit k of event[v] set <=> level k of v is
+ * allowed, and a particle satisfies the event when the level of every variable is allowed (a conjunction of level sets); null
+ * allows everything.  targets: a mask of the variables whose weighted marginals are wanted.  The preparation is that of
+ * dvs_bn_sample (order, thresholds T_k, status bits 0 / 4 / 6, each of which leaves every output untouched).  Query q has the
+ * global index g = (query_offset + q) mod 2^32 and key = dvs_site_key(seed_lo, seed_hi, 501, g).  Particle p of query q
+ * starts with the weight w = 1.0 and takes the variables in the preparation's order:
+ *   unobserved v   draws h = dvs_draw(dvs_draw(key, v), p); its level is the number of k < r - 1 with (h >> 1) >= T_k, as
+ *                  in dvs_bn_sample.
+ *   observed v     takes its evidence level x and w = w * theta, theta the cell of level x under the parent configuration of v
+ *                  (the CPT layout above; the parents' levels are known by then), one fp64 multiplication; theta = 0 gives
+ *                  exactly 0.
+ * The particle index enters the last mixing step, next to the variable's: for a fixed (query, variable) p -> h is a bijection
+ * of the 32-bit words, so two particles of one query never share a draw of any variable, however many there are — a derived
+ * 32-bit per-particle key would make about M^2 / 2^33 pairs of particles of one query share all of theirs.
+ * Outputs (device f64), cell by cell the sum over the particles of one value per particle:
+ *   sums [Q][3]            w, w * w, and w if the particle satisfies the event else +0 (so [2] equals [0] for event null)
+ *   marginals [Q][T][16]   given exactly when targets != 0; T = popcount(targets), targets in ascending id; cell k: w if the
+ *                          target's level is k else +0; cells k >= card are +0.
+ *   particles u64 [Q][M][ceil(n_vars / 16)], particle_weights f64 [Q][M]   both null or both given: bnlearn's cpdist.
+ * Every sum is taken in this order, the one of dvs_bn_loglik: particles 256 c .. 256 c + 255 (absent ones count +0) are added
+ * by the tree x[i] += x[i + s] for s = 128, 64, ..., 1 over 256 slots; slot t of a second such array then adds the chunk sums
+ * c = t, t + 256, ... in ascending c starting from +0, and the same tree over those 256 slots gives the cell.  It does not
+ * depend on the launch geometry, on whether the thresholds were staged in LDS, on which optional outputs are requested or on
+ * how the queries are cut into calls with consecutive query_offset.  No floating-point atomics: two calls give equal bytes.
+ * Status: a query with an observed bit >= n_vars or an evidence level >= card[v] sets bit 4 and gets NaN in every cell of
+ * sums, marginals and particle_weights (its particle rows are zero words); the other queries are written as usual.  A query
+ * whose weights sum to 0 (evidence of probability zero) is no error: its sums are plain zeros and bit 7 is set as
+ * information.  workspace: dvs_bn_lw_workspace_bytes bytes (0 and dvs_last_error for arguments out of range).  Checked before
+ * anything is enqueued, in this order: n_queries, n_particles in [1, 2^31 - 1] (2), n_vars in [1, 48] (3), n_cells in [n_vars,
+ * 2^31 - 1] (2), n_queries * ceil(n_particles / 256) < 2^31 (2), a targets bit >= n_vars (12), query_offset >= 0 (12), null
+ * pointers (10; event, marginals, particles and particle_weights may be null), marginals given exactly when targets != 0 (12),
+ * particles and particle_weights both or neither (12), workspace_bytes (14 with the needed size).
+ *
+ * dvs_bn_blanket_posterior: the posterior of variable `target` given all the others, for n_rows rows (data as for
+ * dvs_bn_loglik; the target's own column is ignored) under each of batch networks.  For level k of the target
+ *   use_children = 0   p_k = theta_t(k | pa_t): bnlearn's predict(method = "parents");
+ *   use_children = 1   p_k = theta_t(k | pa_t) * prod_c theta_c(x_c | pa_c with target = k), the children c of the target in
+ *                      ascending id, one fp64 multiplication each in that order: the exact posterior, which
+ *                      predict(method = "bayes-lw") with every other variable observed approximates.
+ * posterior (device f64 [batch][n_rows][card[target]], nullable) gets p_k / (p_0 + p_1 + ... added in ascending k starting
+ * from +0), one division per cell.  Up to 48 factors can underflow for extreme tables; a row whose products are all zero
+ * gives NaN (0 / 0), as does one that meets a NaN cell.  pred (device u8 [batch][n_rows]) is the lowest level among the
+ * largest posterior cells — bnlearn breaks such ties at random — and 255 for a row with a NaN cell.  A malformed family
+ * (as for dvs_bn_loglik; also card[v] > 16 or a slot that ends beyond cpt_bytes) makes every row of that structure NaN / 255
+ * and sets bit 4 of status; a row with a level >= card[v] for some v other than the target gets NaN / 255 and sets bit 4 too.
+ * Checked before anything is enqueued, in this order: batch > 0 (2), n_rows in [1, 2^31 - 1] (2), n_vars in [1, 48] (3),
+ * batch * n_vars and batch * ceil(n_rows / 256) < 2^31 (2), target in [0, n_vars) (12), use_children 0 or 1 (12), null
+ * pointers (10; posterior may be null), cpt_bytes < batch * n_vars * 8 (14 with that size).
+ *
+ * Parity with bnlearn's cpquery, cpdist, predict and bn.cv(loss = "pred" / "pred-lw") is unpinned against an R run: the
+ * results rest on these definitions.  (Added in ABI 202 as pure additions: the version number stays.) */
+size_t dvs_bn_lw_workspace_bytes(int64_t n_cells, int32_t n_vars, int64_t n_queries, int64_t n_particles, uint64_t targets);
+int dvs_bn_lw(int32_t n_vars, int64_t n_queries, int64_t n_particles, const uint8_t* card, const uint64_t* parents,
+              const int64_t* offsets, const double* cpt, int64_t n_cells, const uint64_t* evidence, const uint64_t* observed,
+              const uint16_t* event, uint64_t targets, uint64_t seed, int64_t query_offset, void* workspace,
+              size_t workspace_bytes, double* sums, double* marginals, uint64_t* particles, double* particle_weights,
+              int32_t* status, void* stream);
+int dvs_bn_blanket_posterior(int32_t batch, int32_t n_vars, int64_t n_rows, const uint64_t* data, const uint8_t* card,
+                             const uint64_t* parents, const int64_t* offsets, const double* cpt, size_t cpt_bytes,
+                             int32_t target, int32_t use_children, double* posterior, uint8_t* pred, int32_t* status,
+                             void* stream);
+
 /* Exact structure search: the DAG with the largest decomposable score, by the subset dynamic programme of
  * Silander and Myllymaki (2006).  table (device f64 [batch][2^n_vars][n_vars]): cell [t][S][v] is the local score of
  * variable v with parent set S & ~(1 << v) — what dvs_bn_scores writes into scratch for a batch whose row S holds
