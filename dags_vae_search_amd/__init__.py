@@ -23,3 +23,5 @@ from .exact import ExactResult, exact_from_tables, exact_search, local_score_tab
 from .pc import PCResult, ci_test, ci_tests, pc_stable, skeleton_blacklist  # noqa: F401
 from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, sample  # noqa: F401
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
+from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
+                       inclusion_threshold)

@@ -203,5 +203,91 @@ class BNLearnWrapper:
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_toggle_scores")
         return (L, T, status) if return_status else (L, T)
 
+    def with_rows(self, rows: torch.Tensor, set_of=None) -> "RowSetEvaluator":
+        """A view of this evaluator in which every structure of a batch is scored on its own multiset of rows
+        (dvs_bn_scores_rows / dvs_bn_toggle_scores_rows): ``rows`` int32 [n_sets, set_size] indices into this data set,
+        ``set_of`` int32 [B] the set of each structure (None: structure b uses set b).  What ``hill_climb`` and
+        ``tabu_search`` take to climb one bootstrap replicate per structure (strength.py)."""
+        return RowSetEvaluator(self, rows, set_of)
+
     def score(self, labeled_graph, label_key: str = LABEL_KEY) -> float:
         return self.score_batch([labeled_graph], label_key)[0]
+
+
+class RowSetEvaluator:
+    """``BNLearnWrapper.with_rows``: the base evaluator's data, score and device, with structure b counted over the rows
+    ``rows[set_of[b]]``.  ``n_samples`` is the set size: every score is, bit for bit, the base score type on the gathered
+    data set (bic's default penalty is log(set_size) / 2).  The indices are checked here, once: the device does not."""
+
+    def __init__(self, base: BNLearnWrapper, rows, set_of=None):
+        self.base = base
+        self.lib, self.device, self.n_vars, self.metric_name = base.lib, base.device, base.n_vars, base.metric_name
+        self.dataset_name, self.iss, self.k = base.dataset_name, base.iss, base.k
+        if not torch.is_tensor(rows) or rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1 or \
+                rows.dtype not in (torch.int32, torch.int64):
+            raise ValueError("rows must be an integer tensor [n_sets >= 1, set_size >= 1]")
+        rows = rows.to(self.device)
+        if int(torch.amin(rows)) < 0 or int(torch.amax(rows)) >= base.n_samples:
+            raise ValueError(f"rows must lie in [0, {base.n_samples})")
+        self.rows = rows.to(torch.int32).contiguous()
+        self.n_sets, self.n_samples = int(rows.shape[0]), int(rows.shape[1])
+        self.set_of = None
+        if set_of is not None:
+            set_of = torch.as_tensor(set_of).to(self.device)
+            if set_of.ndim != 1 or set_of.numel() < 1 or set_of.dtype not in (torch.int32, torch.int64):
+                raise ValueError("set_of must be an integer tensor [B]")
+            if int(torch.amin(set_of)) < 0 or int(torch.amax(set_of)) >= self.n_sets:
+                raise ValueError(f"set_of must lie in [0, {self.n_sets})")
+            self.set_of = set_of.to(torch.int32).contiguous()
+
+    def compact_parent_masks(self, batch) -> torch.Tensor:
+        return self.base.compact_parent_masks(batch)
+
+    def _row_args(self, B):
+        if self.set_of is None:
+            if B > self.n_sets:
+                raise ValueError(f"{B} structures but {self.n_sets} row sets: pass set_of")
+        elif self.set_of.numel() != B:
+            raise ValueError(f"{B} structures but set_of names {self.set_of.numel()}")
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        return p(self.rows), self.n_samples, self.n_sets, p(self.set_of)
+
+    def score_masks(self, parents: torch.Tensor, local: bool = False):
+        """``BNLearnWrapper.score_masks`` with structure b on its own rows"""
+        base = self.base
+        parents = parents.to(self.device).contiguous()
+        B = parents.shape[0]
+        row_args = self._row_args(B)
+        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        dl.check(self.lib, self.lib.dvs_bn_scores_rows(
+            B, self.n_vars, base.n_samples, p(base._data), p(base._card), p(parents), dl.SCORE_TYPES[self.metric_name],
+            base._score_arg, p(scratch), p(out), p(status), *row_args,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_scores_rows")
+        if int(status.item()) & 16:
+            raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
+                             "cells; sorted samples: 16 384 samples, 63 key bits)")
+        return (out, scratch) if local else out
+
+    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
+        """``BNLearnWrapper.toggle_scores`` with structure b on its own rows"""
+        base = self.base
+        parents = parents.to(self.device).contiguous()
+        B, n = parents.shape
+        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
+        row_args = self._row_args(B)
+        if out is None:
+            if worklist is not None:
+                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
+            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
+                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
+        L, T = out
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        dl.check(self.lib, self.lib.dvs_bn_toggle_scores_rows(
+            B, n, base.n_samples, p(base._data), p(base._card), p(parents), dl.SCORE_TYPES[self.metric_name], base._score_arg,
+            None if worklist is None else p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), *row_args,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_toggle_scores_rows")
+        return (L, T, status) if return_status else (L, T)

@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -788,6 +788,137 @@ extern "C" int dvs_exact_search(int32_t batch, int32_t n_vars, const double* tab
     call_begin();
     dvs_launch_exact(a, (dvs_stream_t)stream);
     return call_end("dvs_exact_search");
+}
+
+// ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------
+// What the two *_rows entry points check alike, after the score argument: the row-set arguments (code 13).
+static int row_set_check(const char* fn, int batch, int set_size, int n_sets, const int32_t* set_of) {
+    if (set_size < 1 || n_sets < 1) return failf(13, "%s: set_size and n_sets must be >= 1", fn);
+    if (!set_of && n_sets < batch) return failf(13, "%s: set_of is null (structure b uses set b), so n_sets must be >= batch", fn);
+    return 0;
+}
+
+extern "C" int dvs_bn_scores_rows(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                                  const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                                  int32_t* status, const int32_t* rows, int32_t set_size, int32_t n_sets, const int32_t* set_of,
+                                  void* stream) {
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores_rows: batch and n_samples must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores_rows: n_vars must be in [1, 48]");
+    if (!data || !card || !parents || !scratch || !out || !status || !rows) return fail(10, "dvs_bn_scores_rows: null pointer");
+    BicRowsArgs a = {};
+    if (int e = bn_score_arg("dvs_bn_scores_rows", score_type, score_arg, &a.s.arg)) return e;
+    if (int e = row_set_check("dvs_bn_scores_rows", batch, set_size, n_sets, set_of)) return e;
+    a.s.B = batch;
+    a.s.n = n_vars;
+    a.s.S = set_size;
+    a.s.data = data;
+    a.s.card = card;
+    a.s.parents = parents;
+    a.s.local = scratch;
+    a.s.out = out;
+    a.s.status = status;
+    a.s.type = score_type;
+    a.r.rows = rows;
+    a.r.set_of = set_of;
+    a.r.set_size = set_size;
+    a.r.n_sets = n_sets;
+    call_begin();
+    dvs_launch_bic_rows(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_scores_rows");
+}
+
+extern "C" int dvs_bn_toggle_scores_rows(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data,
+                                         const uint8_t* card, const uint64_t* parents, int32_t score_type, double score_arg,
+                                         const int32_t* worklist, double* local, size_t local_bytes, double* toggles,
+                                         size_t toggles_bytes, int32_t* status, const int32_t* rows, int32_t set_size,
+                                         int32_t n_sets, const int32_t* set_of, void* stream) {
+    const HcCheck chk = {"dvs_bn_toggle_scores_rows", batch, n_vars};
+    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_toggle_scores_rows: batch and n_samples must be > 0");
+    if (int e = chk.dims()) return e;
+    if (!data || !card || !parents || !local || !toggles || !status || !rows)
+        return fail(10, "dvs_bn_toggle_scores_rows: null pointer");
+    ToggleRowsArgs a = {};
+    if (int e = bn_score_arg("dvs_bn_toggle_scores_rows", score_type, score_arg, &a.t.s.arg)) return e;
+    if (int e = row_set_check("dvs_bn_toggle_scores_rows", batch, set_size, n_sets, set_of)) return e;
+    if (local_bytes < (size_t)batch * n_vars * 8)
+        return fail_size("dvs_bn_toggle_scores_rows: local_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
+    if (int e = chk.toggles(toggles_bytes)) return e;
+    a.t.s.B = batch;
+    a.t.s.n = n_vars;
+    a.t.s.S = set_size;
+    a.t.s.data = data;
+    a.t.s.card = card;
+    a.t.s.parents = parents;
+    a.t.s.local = local;
+    a.t.s.out = nullptr;
+    a.t.s.status = status;
+    a.t.s.type = score_type;
+    a.t.worklist = worklist;
+    a.t.toggles = toggles;
+    a.r.rows = rows;
+    a.r.set_of = set_of;
+    a.r.set_size = set_size;
+    a.r.n_sets = n_sets;
+    call_begin();
+    dvs_launch_bn_toggle_rows(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_toggle_scores_rows");
+}
+
+extern "C" int dvs_bootstrap_rows(int32_t n_sets, int32_t set_size, int32_t n_samples, uint64_t seed, int64_t set_offset,
+                                  int32_t* rows, void* stream) {
+    if (n_sets <= 0) return fail(2, "dvs_bootstrap_rows: n_sets must be > 0");
+    if (set_size < 1 || n_samples < 1) return fail(13, "dvs_bootstrap_rows: set_size and n_samples must be >= 1");
+    if ((int64_t)n_sets * set_size > (int64_t)0x7fffffff) return fail(2, "dvs_bootstrap_rows: n_sets * set_size must be < 2^31");
+    if (set_offset < 0) return fail(12, "dvs_bootstrap_rows: set_offset must be >= 0");
+    if (!rows) return fail(10, "dvs_bootstrap_rows: null pointer");
+    BootRowsArgs a = {};
+    a.n_sets = n_sets;
+    a.set_size = set_size;
+    a.n_samples = n_samples;
+    a.set_offset = (uint32_t)set_offset;         // the global set index is taken mod 2^32
+    a.rows = rows;
+    call_begin();
+    dvs_launch_bootstrap_rows(a, seed, (dvs_stream_t)stream);
+    return call_end("dvs_bootstrap_rows");
+}
+
+extern "C" int dvs_arc_strength(int32_t batch, int32_t n_vars, const uint64_t* pdag, int32_t* counts, size_t counts_bytes,
+                                void* stream) {
+    if (int e = pdag_dims("dvs_arc_strength", batch, n_vars)) return e;
+    if (!pdag || !counts) return fail(10, "dvs_arc_strength: null pointer");
+    if (counts_bytes < (size_t)n_vars * n_vars * 8)
+        return fail_size("dvs_arc_strength: counts_bytes < n_vars^2 * 8", (size_t)n_vars * n_vars * 8);
+    ArcStrengthArgs a;
+    a.B = batch;
+    a.n = n_vars;
+    a.pdag = pdag;
+    a.counts = counts;
+    call_begin();
+    dvs_launch_arc_strength(a, (dvs_stream_t)stream);
+    return call_end("dvs_arc_strength");
+}
+
+extern "C" int dvs_averaged_network(int32_t groups, int32_t n_vars, const int32_t* counts, const int32_t* n_networks,
+                                    const int32_t* min_any, uint64_t* parents, size_t parents_bytes, int32_t* info,
+                                    void* stream) {
+    if (groups <= 0) return fail(2, "dvs_averaged_network: groups must be > 0");
+    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_averaged_network: n_vars must be in [1, 48]");
+    if ((int64_t)groups * n_vars * n_vars * 2 > (int64_t)0x7fffffff)
+        return fail(2, "dvs_averaged_network: groups * n_vars^2 * 2 must be < 2^31");
+    if (!counts || !n_networks || !min_any || !parents || !info) return fail(10, "dvs_averaged_network: null pointer");
+    if (parents_bytes < (size_t)groups * n_vars * 8)
+        return fail_size("dvs_averaged_network: parents_bytes < groups * n_vars * 8", (size_t)groups * n_vars * 8);
+    AvgNetArgs a;
+    a.G = groups;
+    a.n = n_vars;
+    a.counts = counts;
+    a.n_networks = n_networks;
+    a.min_any = min_any;
+    a.parents = parents;
+    a.info = info;
+    call_begin();
+    dvs_launch_averaged_network(a, (dvs_stream_t)stream);
+    return call_end("dvs_averaged_network");
 }
 
 extern "C" int dvs_bic_parent_masks(int32_t batch, int32_t n_vars, int32_t preds_are_u64, const uint8_t* labels,

@@ -363,11 +363,13 @@ __device__ __forceinline__ void dvs_ln_stats(const f4 (&x)[4], float& mean, floa
 // 400 the random moves of dvs_hc_perturb (dvs_tabu.h; keyed by the structure's index in the batch, element = draw_index),
 // 500 the forward sampler of dvs_bn_sample (dvs_params.h; keyed by the global row index, element = variable),
 // 501 the likelihood-weighting sampler of dvs_bn_lw (dvs_infer.h; keyed by the global query index; variable v of particle p
-// draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw).
+// draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw),
+// 600 the bootstrap row sets of dvs_bootstrap_rows (dvs_strength.h; keyed by the global set index, element = position).
 constexpr uint32_t DVS_SITE_GEN_EDGES = 300u, DVS_SITE_GEN_LABELS = 301u, DVS_SITE_GEN_COUNTS = 302u;
 constexpr uint32_t DVS_SITE_HC_PERTURB = 400u;
 constexpr uint32_t DVS_SITE_BN_SAMPLE = 500u;
 constexpr uint32_t DVS_SITE_BN_LW = 501u;
+constexpr uint32_t DVS_SITE_BOOTSTRAP = 600u;
 __device__ __forceinline__ uint32_t dvs_fmix32(uint32_t x) {
     x ^= x >> 16;
     x *= 0x85EBCA6Bu;

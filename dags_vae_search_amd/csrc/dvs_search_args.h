@@ -1,7 +1,7 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor (k_bic.hip
-// with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_exact.h; k_gp_acq.hip).  Plain C++, no device
+// with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_exact.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device
 // code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -351,6 +351,49 @@ struct ExactArgs {
     int* flags;                  // [B], written: 1 no admissible DAG (score -inf)
 };
 void dvs_launch_exact(const ExactArgs& a, dvs_stream_t st);
+
+// ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------
+// The row-set fields live beside BicArgs / ToggleArgs, not inside them: the kernels of the plain entry points take the
+// argument blocks they always took.
+struct RowSetArgs {
+    const int* rows;             // [n_sets][set_size], each in [0, n_samples): not range-checked on the device
+    const int* set_of;           // [B] or null: structure b counts over set set_of[b] (null: set b)
+    int set_size, n_sets;
+};
+struct BicRowsArgs {
+    BicArgs s;                   // s.S = set_size
+    RowSetArgs r;
+};
+void dvs_launch_bic_rows(const BicRowsArgs& a, dvs_stream_t st);
+struct ToggleRowsArgs {
+    ToggleArgs t;                // t.s.S = set_size
+    RowSetArgs r;
+};
+void dvs_launch_bn_toggle_rows(const ToggleRowsArgs& a, dvs_stream_t st);
+
+struct BootRowsArgs {
+    int n_sets, set_size, n_samples;
+    uint32_t seed_lo, seed_hi, set_offset;       // seed_lo / seed_hi: launcher, from `seed`
+    int* rows;                   // [n_sets][set_size]
+};
+void dvs_launch_bootstrap_rows(const BootRowsArgs& a, uint64_t seed, dvs_stream_t st);
+
+struct ArcStrengthArgs {
+    int B, n;
+    const uint64_t* pdag;        // [B][n], the layout of CpdagArgs::pdag
+    int* counts;                 // [n][n][2], accumulated into
+};
+void dvs_launch_arc_strength(const ArcStrengthArgs& a, dvs_stream_t st);
+
+struct AvgNetArgs {
+    int G, n;
+    const int* counts;           // [G][n][n][2]
+    const int* n_networks;       // [G]
+    const int* min_any;          // [G]: < 0 asks for the estimated threshold
+    uint64_t* parents;           // [G][n]
+    int* info;                   // [G][4]: min_any used, arcs placed, pairs dropped for a cycle, ties
+};
+void dvs_launch_averaged_network(const AvgNetArgs& a, dvs_stream_t st);
 
 // ---- row codec -> BIC parent masks (k_bic.hip) -----------------------------------------------------------------------
 struct BicMaskArgs {

@@ -87,9 +87,13 @@ __device__ __forceinline__ void bn_prior(const BicArgs& a, int r, double q, cons
 // the score, NaN (and status bit 4) when the family is refused.  k_bic_local instantiates it with flip = 0 for the mask as
 // it stands, k_bn_toggle (dvs_hillclimb.h) with one bit flipped: the same instructions in the same order, so the two
 // kernels give equal bytes for equal parent sets.
-template <int FAMILY>
+//
+// ROWS (dvs_strength.h: k_bic_local_rows, k_bn_toggle_rows): sample s of the workgroup's data set is row rows[s] of a.data and
+// a.S is the set's size; nothing else changes, and the counts do not depend on the order of the rows, so the score is, bit
+// for bit, that of the gathered data set.  The instantiations without ROWS never read `rows`.
+template <int FAMILY, bool ROWS = false>
 __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v, const uint64_t* pmask, const uint64_t flip,
-                                                  char* smem) {
+                                                  char* smem, const int* rows = nullptr) {
     __shared__ double red[256];
     __shared__ int par_id[48], par_stride[48], par_shift[48];
     __shared__ int s_np, s_mode, s_rbits;
@@ -136,7 +140,7 @@ __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v,
         for (int i = threadIdx.x; i < bins; i += blockDim.x) hist[i] = 0u;
         __syncthreads();
         for (int s = threadIdx.x; s < a.S; s += blockDim.x) {
-            const uint64_t* row = a.data + (size_t)s * a.words;
+            const uint64_t* row = a.data + (size_t)(ROWS ? rows[s] : s) * a.words;
             int key = 0;
             for (int i = 0; i < np; ++i) key += bic_level(row, par_id[i]) * par_stride[i];
             atomicAdd(&hist[key * r + bic_level(row, v)], 1u);
@@ -184,7 +188,7 @@ __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v,
         for (int s = threadIdx.x; s < spad; s += blockDim.x) {
             uint64_t key = ~0ull;
             if (s < S) {
-                const uint64_t* row = a.data + (size_t)s * a.words;
+                const uint64_t* row = a.data + (size_t)(ROWS ? rows[s] : s) * a.words;
                 key = (uint64_t)bic_level(row, v);
                 for (int i = 0; i < np; ++i) key |= (uint64_t)bic_level(row, par_id[i]) << par_shift[i];
             }
@@ -269,6 +273,7 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
 #include "dvs_params.h"
 #include "dvs_infer.h"
 #include "dvs_exact.h"
+#include "dvs_strength.h"
 
 __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
     const int dag = blockIdx.x * blockDim.x + threadIdx.x;

@@ -695,6 +695,80 @@ int dvs_exact_search(int32_t batch, int32_t n_vars, const double* table, size_t 
                      const uint64_t* forbidden, void* workspace, size_t workspace_bytes, uint64_t* parents, int32_t* order,
                      double* score, int32_t* flags, void* stream);
 
+/* Model averaging: bnlearn's boot.strength, custom.strength, inclusion.threshold and averaged.network as
+ * five building blocks.  All are pure additions to ABI 202: the version number stays.
+ *
+ * Row sets in the scorer.  dvs_bn_scores_rows and dvs_bn_toggle_scores_rows take the arguments of dvs_bn_scores and
+ * dvs_bn_toggle_scores (the worklist included) and, after status, four more:
+ *   rows      device i32 [n_sets][set_size], each entry in [0, n_samples)
+ *   set_size, n_sets
+ *   set_of    device i32 [batch], each in [0, n_sets); nullable: null means structure b uses set b (n_sets >= batch).
+ * Structure b is scored on the data set of S = set_size samples whose sample i is data[rows[set_of[b]][i]].  Everything the
+ * call writes for that structure — out, scratch, local, toggles, the NaN cells and status bit 4 — is, bit for bit, what the
+ * plain entry point writes for it on that gathered data set: both counting paths are independent of the order of the
+ * samples (integer atomics; sorted keys).  So bic's default k is log(set_size) / 2, the sorted-samples path holds
+ * set_size <= 16 384, and set_size may be larger or smaller than n_samples.  PRECONDITION: the entries of rows and set_of
+ * are NOT range-checked on the device; an index outside its range reads memory the call was not given.  Callers that take
+ * indices from outside check them first (BNLearnWrapper.with_rows does).  Checked before anything is enqueued: the plain
+ * entry point's checks in its order (rows counts among the null pointers, code 10), then after the score argument code 13
+ * for set_size < 1, n_sets < 1 or a null set_of with n_sets < batch, then (toggle) the size checks, code 14. */
+int dvs_bn_scores_rows(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                       const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                       int32_t* status, const int32_t* rows, int32_t set_size, int32_t n_sets, const int32_t* set_of,
+                       void* stream);
+int dvs_bn_toggle_scores_rows(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                              const uint64_t* parents, int32_t score_type, double score_arg, const int32_t* worklist,
+                              double* local, size_t local_bytes, double* toggles, size_t toggles_bytes, int32_t* status,
+                              const int32_t* rows, int32_t set_size, int32_t n_sets, const int32_t* set_of, void* stream);
+
+/* Bootstrap draw: rows (device i32 [n_sets][set_size]) with replacement from 0 .. n_samples - 1.  Set r has the global index
+ * g = (set_offset + r) mod 2^32 and the key dvs_site_key(seed_lo, seed_hi, 600, g) of csrc/dvs_device.h;
+ *   rows[r][i] = (uint64(dvs_draw(key, i)) * n_samples) >> 32
+ * (oracle/rng.py restates both functions).  Index k is drawn with probability within 2^-32 of 1 / n_samples, a bias of at
+ * most n_samples / 2^32 in all.  A set is a function of (seed, g) only: a request may be cut into calls or shards with
+ * set_offset.  Checked in this order: n_sets > 0 (2), set_size >= 1 and n_samples >= 1 (13), n_sets * set_size < 2^31 (2),
+ * set_offset >= 0 (12), null pointer (10). */
+int dvs_bootstrap_rows(int32_t n_sets, int32_t set_size, int32_t n_samples, uint64_t seed, int64_t set_offset, int32_t* rows,
+                       void* stream);
+
+/* Arc counts over a batch of networks (bnlearn's custom.strength with the direction doubled, so that everything stays an
+ * integer).  pdag: device u64 [batch][n_vars] in the PDAG form of dvs_cpdag (a DAG's parent masks are one); u and v are
+ * adjacent in a network iff bit u of row v or bit v of row u is set.  counts: device i32 [n_vars][n_vars][2], ACCUMULATED into
+ * (the caller zeroes it first; chunks and ranks add up).  For every ordered pair u != v and every network in which u and v
+ * are adjacent:
+ *   counts[u][v][0] += 1
+ *   counts[u][v][1] += 2 if the network has u -> v only, 1 if it has u - v, 0 if it has v -> u only
+ * so counts[u][v][0] == counts[v][u][0] and counts[u][v][1] + counts[v][u][1] == 2 counts[u][v][0].  Bits on the diagonal or
+ * at positions >= n_vars are ignored; the diagonal cells are not written.  Integer adds only: the result does not depend
+ * on the order of processing and two runs give equal bytes.  Checked in this order: batch > 0 (2), n_vars in [1, 48] (3),
+ * batch * n_vars < 2^31 (2), null pointers (10), counts_bytes < n_vars^2 * 8 (14 with the needed size). */
+int dvs_arc_strength(int32_t batch, int32_t n_vars, const uint64_t* pdag, int32_t* counts, size_t counts_bytes, void* stream);
+
+/* Significance threshold and averaged network, one per group.  counts: device i32 [groups][n_vars][n_vars][2] in the layout
+ * of dvs_arc_strength; n_networks, min_any: device i32 [groups].  A batch of groups is a threshold sweep over one count matrix
+ * (the caller repeats it) or several matrices.  For a pair u < v let A = counts[u][v][0], D = counts[u][v][1] and
+ * D' = counts[v][u][1] (counts[v][u][0] is not read).
+ *   significance  the pair is significant iff A >= min_any[g].  min_any[g] < 0 asks for the estimated threshold: with
+ *                 R = n_networks[g], T = the largest A over the pairs with 2 A <= R, or, when no pair has 2 A <= R, the
+ *                 smallest A over all pairs (T = 0 when n_vars = 1: there are no pairs); min_any = T + 1.  This is the L1
+ *                 estimator of Scutari and Nagarajan (2013) in closed form: the p minimising the L1 distance between the
+ *                 empirical CDF F of the strengths A / R and the step at p is F(1/2), whose type-1 quantile is the largest
+ *                 observed strength <= 1/2, or the smallest observed strength when none is.
+ *   order         the significant pairs are processed by A descending, then |D - D'| descending, then u n_vars + v ascending.
+ *   orientation   u -> v if D > D', v -> u if D < D'; on a tie u -> v is tried first, then v -> u (in an acyclic graph one
+ *                 of the two closes no cycle).
+ *   insertion     an arc whose head is already an ancestor of its tail would close a cycle and is not added; a pair that
+ *                 is not a tie is then dropped.
+ * parents: device u64 [groups][n_vars], always acyclic.  info: device i32 [groups][4] = (the min_any used, arcs placed,
+ * pairs dropped for a cycle, significant pairs with D == D').  Two differences from bnlearn's averaged.network, on purpose:
+ * bnlearn leaves a tie undirected (the result is then a PDAG) where this orients it, and bnlearn finds the threshold with a
+ * numerical optimiser (optimize, fuzzy in the last digits) where this takes the closed form; parity with an R run is
+ * unpinned and rests on these definitions.  Integers only: two runs give equal bytes.  Checked in this order: groups > 0
+ * (2), n_vars in [1, 48] (3), groups * n_vars^2 * 2 < 2^31 (2), null pointers (10), parents_bytes < groups * n_vars * 8 (14
+ * with the needed size). */
+int dvs_averaged_network(int32_t groups, int32_t n_vars, const int32_t* counts, const int32_t* n_networks,
+                         const int32_t* min_any, uint64_t* parents, size_t parents_bytes, int32_t* info, void* stream);
+
 /* The relabelling step of BNLearnWrapper.score (src/problem/bn/bnlearn.py:34-45: graph vertex v stands for data-set variable
  * labels[v]) on the device, from the row codec of dvs_build_records: labels device u8 [B][n_vars], preds device [B][n_vars]
  * (u16, or u64 when preds_are_u64) -> parents device u64 [B][n_vars] in data-set variable indices, ready for dvs_bic_scores.
