@@ -159,28 +159,6 @@ extern "C" int dvs_generate_edge_counts(int32_t batch, int32_t n_entries, const 
 }
 
 // ---- BN scorers (k_bic.hip) ------------------------------------------------------------------------------------------
-extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
-                              const uint64_t* parents, double* scratch, double* out, int32_t* status, void* stream) {
-    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bic_scores: batch and n_samples must be > 0");
-    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bic_scores: n_vars must be in [1, 48]");
-    if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bic_scores: null pointer");
-    BicArgs a = {};
-    a.B = batch;
-    a.n = n_vars;
-    a.S = n_samples;
-    a.data = data;
-    a.card = card;
-    a.parents = parents;
-    a.local = scratch;
-    a.out = out;
-    a.status = status;
-    a.type = DVS_SCORE_BIC;
-    a.arg = __builtin_nan("");                  // k = log(S) / 2, taken on the device
-    call_begin();
-    dvs_launch_bic(a, (dvs_stream_t)stream);
-    return call_end("dvs_bic_scores");
-}
-
 // score_type / score_arg of dvs_bn_scores and dvs_bn_toggle_scores -> the argument the kernels take (include/dvs.h): the
 // resolved k (loglik 0, aic, bic; NaN = log(S) / 2 taken on the device) or iss (bde, bds)
 static int bn_score_arg(const char* fn, int score_type, double score_arg, double* arg) {
@@ -208,29 +186,6 @@ static int bn_score_arg(const char* fn, int score_type, double score_arg, double
     }
 }
 
-extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
-                             const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
-                             int32_t* status, void* stream) {
-    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores: batch and n_samples must be > 0");
-    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores: n_vars must be in [1, 48]");
-    if (!data || !card || !parents || !scratch || !out || !status) return fail(10, "dvs_bn_scores: null pointer");
-    BicArgs a = {};
-    if (int e = bn_score_arg("dvs_bn_scores", score_type, score_arg, &a.arg)) return e;
-    a.B = batch;
-    a.n = n_vars;
-    a.S = n_samples;
-    a.data = data;
-    a.card = card;
-    a.parents = parents;
-    a.local = scratch;
-    a.out = out;
-    a.status = status;
-    a.type = score_type;
-    call_begin();
-    dvs_launch_bic(a, (dvs_stream_t)stream);
-    return call_end("dvs_bn_scores");
-}
-
 // ---- hill climbing, tabu, random restarts (dvs_hillclimb.h, dvs_tabu.h) ----------------------------------------------
 // What dvs_bn_toggle_scores, dvs_hc_step, dvs_tabu_step and dvs_hc_perturb check alike, each at its own place in the entry
 // point's order: the range of the toggle table's index and the caller's table and trace buffers (code 14 with the size).
@@ -252,29 +207,74 @@ struct HcCheck {
     }
 };
 
+// The five scorer entry points (dvs_bic_scores, dvs_bn_scores[_rows], dvs_bn_toggle_scores[_rows]) open with the same checks
+// in the same order: sizes (2), n_vars (3; the toggle table's index range with it), pointers (10).
+static int scorer_check(const char* fn, int batch, int n_vars, int n_samples, bool toggle_table, bool any_null) {
+    if (batch <= 0 || n_samples <= 0) return failf(2, "%s: batch and n_samples must be > 0", fn);
+    const HcCheck chk = {fn, batch, n_vars};
+    if (toggle_table) {
+        if (int e = chk.dims()) return e;
+    } else if (n_vars < 1 || n_vars > DVS_WTOK) {
+        return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    }
+    return any_null ? failf(10, "%s: null pointer", fn) : 0;
+}
+// ... and fill one BicArgs; n_counted is the size of the data set a structure counts over (n_samples, or a row set's size).
+// Fails as bn_score_arg does.
+static int scorer_args(const char* fn, BicArgs& a, int batch, int n_vars, int n_counted, const uint64_t* data, const uint8_t* card,
+                       const uint64_t* parents, int score_type, double score_arg, double* local, double* out, int32_t* status) {
+    if (int e = bn_score_arg(fn, score_type, score_arg, &a.arg)) return e;
+    a.B = batch;
+    a.n = n_vars;
+    a.S = n_counted;
+    a.data = data;
+    a.card = card;
+    a.parents = parents;
+    a.local = local;
+    a.out = out;
+    a.status = status;
+    a.type = score_type;
+    return 0;
+}
+// the caller's L and T buffers of the two toggle entry points (code 14 with the size)
+static int toggle_buffers(const HcCheck& chk, size_t local_bytes, size_t toggles_bytes) {
+    const size_t need = (size_t)chk.batch * chk.n_vars * 8;
+    if (local_bytes < need) return failf(14, "%s: local_bytes < batch * n_vars * 8 = %zu", chk.fn, need);
+    return chk.toggles(toggles_bytes);
+}
+
+static int bn_scores_call(const char* fn, int batch, int n_vars, int n_samples, const uint64_t* data, const uint8_t* card,
+                          const uint64_t* parents, int score_type, double score_arg, double* scratch, double* out, int32_t* status,
+                          void* stream) {
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, false, !data || !card || !parents || !scratch || !out || !status)) return e;
+    BicArgs a = {};
+    if (int e = scorer_args(fn, a, batch, n_vars, n_samples, data, card, parents, score_type, score_arg, scratch, out, status)) return e;
+    call_begin();
+    dvs_launch_bic(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+extern "C" int dvs_bic_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                              const uint64_t* parents, double* scratch, double* out, int32_t* status, void* stream) {
+    // bic with its default k: NaN stands for log(S) / 2, taken on the device
+    return bn_scores_call("dvs_bic_scores", batch, n_vars, n_samples, data, card, parents, DVS_SCORE_BIC, __builtin_nan(""), scratch,
+                          out, status, stream);
+}
+extern "C" int dvs_bn_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                             const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
+                             int32_t* status, void* stream) {
+    return bn_scores_call("dvs_bn_scores", batch, n_vars, n_samples, data, card, parents, score_type, score_arg, scratch, out, status,
+                          stream);
+}
+
 extern "C" int dvs_bn_toggle_scores(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
                                     const uint64_t* parents, int32_t score_type, double score_arg, const int32_t* worklist,
                                     double* local, size_t local_bytes, double* toggles, size_t toggles_bytes, int32_t* status,
                                     void* stream) {
-    const HcCheck chk = {"dvs_bn_toggle_scores", batch, n_vars};
-    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_toggle_scores: batch and n_samples must be > 0");
-    if (int e = chk.dims()) return e;
-    if (!data || !card || !parents || !local || !toggles || !status) return fail(10, "dvs_bn_toggle_scores: null pointer");
+    const char* fn = "dvs_bn_toggle_scores";
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, true, !data || !card || !parents || !local || !toggles || !status)) return e;
     ToggleArgs t = {};
-    if (int e = bn_score_arg("dvs_bn_toggle_scores", score_type, score_arg, &t.s.arg)) return e;
-    if (local_bytes < (size_t)batch * n_vars * 8)
-        return fail_size("dvs_bn_toggle_scores: local_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
-    if (int e = chk.toggles(toggles_bytes)) return e;
-    t.s.B = batch;
-    t.s.n = n_vars;
-    t.s.S = n_samples;
-    t.s.data = data;
-    t.s.card = card;
-    t.s.parents = parents;
-    t.s.local = local;
-    t.s.out = nullptr;
-    t.s.status = status;
-    t.s.type = score_type;
+    if (int e = scorer_args(fn, t.s, batch, n_vars, n_samples, data, card, parents, score_type, score_arg, local, nullptr, status)) return e;
+    if (int e = toggle_buffers({fn, batch, n_vars}, local_bytes, toggles_bytes)) return e;
     t.worklist = worklist;
     t.toggles = toggles;
     call_begin();
@@ -791,10 +791,14 @@ extern "C" int dvs_exact_search(int32_t batch, int32_t n_vars, const double* tab
 }
 
 // ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------
-// What the two *_rows entry points check alike, after the score argument: the row-set arguments (code 13).
-static int row_set_check(const char* fn, int batch, int set_size, int n_sets, const int32_t* set_of) {
+// What the two *_rows entry points check alike, after the score argument: the row-set arguments (code 13), into their block.
+static int row_set_args(const char* fn, RowSetArgs& r, int batch, const int32_t* rows, int set_size, int n_sets, const int32_t* set_of) {
     if (set_size < 1 || n_sets < 1) return failf(13, "%s: set_size and n_sets must be >= 1", fn);
     if (!set_of && n_sets < batch) return failf(13, "%s: set_of is null (structure b uses set b), so n_sets must be >= batch", fn);
+    r.rows = rows;
+    r.set_of = set_of;
+    r.set_size = set_size;
+    r.n_sets = n_sets;
     return 0;
 }
 
@@ -802,26 +806,12 @@ extern "C" int dvs_bn_scores_rows(int32_t batch, int32_t n_vars, int32_t n_sampl
                                   const uint64_t* parents, int32_t score_type, double score_arg, double* scratch, double* out,
                                   int32_t* status, const int32_t* rows, int32_t set_size, int32_t n_sets, const int32_t* set_of,
                                   void* stream) {
-    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_scores_rows: batch and n_samples must be > 0");
-    if (n_vars < 1 || n_vars > DVS_WTOK) return fail(3, "dvs_bn_scores_rows: n_vars must be in [1, 48]");
-    if (!data || !card || !parents || !scratch || !out || !status || !rows) return fail(10, "dvs_bn_scores_rows: null pointer");
+    const char* fn = "dvs_bn_scores_rows";
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, false, !data || !card || !parents || !scratch || !out || !status || !rows))
+        return e;
     BicRowsArgs a = {};
-    if (int e = bn_score_arg("dvs_bn_scores_rows", score_type, score_arg, &a.s.arg)) return e;
-    if (int e = row_set_check("dvs_bn_scores_rows", batch, set_size, n_sets, set_of)) return e;
-    a.s.B = batch;
-    a.s.n = n_vars;
-    a.s.S = set_size;
-    a.s.data = data;
-    a.s.card = card;
-    a.s.parents = parents;
-    a.s.local = scratch;
-    a.s.out = out;
-    a.s.status = status;
-    a.s.type = score_type;
-    a.r.rows = rows;
-    a.r.set_of = set_of;
-    a.r.set_size = set_size;
-    a.r.n_sets = n_sets;
+    if (int e = scorer_args(fn, a.s, batch, n_vars, set_size, data, card, parents, score_type, score_arg, scratch, out, status)) return e;
+    if (int e = row_set_args(fn, a.r, batch, rows, set_size, n_sets, set_of)) return e;
     call_begin();
     dvs_launch_bic_rows(a, (dvs_stream_t)stream);
     return call_end("dvs_bn_scores_rows");
@@ -832,33 +822,16 @@ extern "C" int dvs_bn_toggle_scores_rows(int32_t batch, int32_t n_vars, int32_t 
                                          const int32_t* worklist, double* local, size_t local_bytes, double* toggles,
                                          size_t toggles_bytes, int32_t* status, const int32_t* rows, int32_t set_size,
                                          int32_t n_sets, const int32_t* set_of, void* stream) {
-    const HcCheck chk = {"dvs_bn_toggle_scores_rows", batch, n_vars};
-    if (batch <= 0 || n_samples <= 0) return fail(2, "dvs_bn_toggle_scores_rows: batch and n_samples must be > 0");
-    if (int e = chk.dims()) return e;
-    if (!data || !card || !parents || !local || !toggles || !status || !rows)
-        return fail(10, "dvs_bn_toggle_scores_rows: null pointer");
+    const char* fn = "dvs_bn_toggle_scores_rows";
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, true, !data || !card || !parents || !local || !toggles || !status || !rows))
+        return e;
     ToggleRowsArgs a = {};
-    if (int e = bn_score_arg("dvs_bn_toggle_scores_rows", score_type, score_arg, &a.t.s.arg)) return e;
-    if (int e = row_set_check("dvs_bn_toggle_scores_rows", batch, set_size, n_sets, set_of)) return e;
-    if (local_bytes < (size_t)batch * n_vars * 8)
-        return fail_size("dvs_bn_toggle_scores_rows: local_bytes < batch * n_vars * 8", (size_t)batch * n_vars * 8);
-    if (int e = chk.toggles(toggles_bytes)) return e;
-    a.t.s.B = batch;
-    a.t.s.n = n_vars;
-    a.t.s.S = set_size;
-    a.t.s.data = data;
-    a.t.s.card = card;
-    a.t.s.parents = parents;
-    a.t.s.local = local;
-    a.t.s.out = nullptr;
-    a.t.s.status = status;
-    a.t.s.type = score_type;
+    if (int e = scorer_args(fn, a.t.s, batch, n_vars, set_size, data, card, parents, score_type, score_arg, local, nullptr, status))
+        return e;
+    if (int e = row_set_args(fn, a.r, batch, rows, set_size, n_sets, set_of)) return e;
+    if (int e = toggle_buffers({fn, batch, n_vars}, local_bytes, toggles_bytes)) return e;
     a.t.worklist = worklist;
     a.t.toggles = toggles;
-    a.r.rows = rows;
-    a.r.set_of = set_of;
-    a.r.set_size = set_size;
-    a.r.n_sets = n_sets;
     call_begin();
     dvs_launch_bn_toggle_rows(a, (dvs_stream_t)stream);
     return call_end("dvs_bn_toggle_scores_rows");

@@ -3,8 +3,9 @@
 // histogram adds and the status atomicOr: two runs give equal bytes.
 //
 //   k_ci_tests       one workgroup per test (x, y | Z): the dense (z, x, y) table in dynamic LDS (max_cells * 4 bytes, sized
-//                    per launch), filled by integer atomics; the thread that owns configuration z forms its marginals and its
-//                    partial sums; a fixed-order tree; thread 0 takes the p-value, Q(df / 2, statistic / 2).
+//                    per launch), laid out by bn_family_layout with Z for the parents and filled by bn_dense_count; the thread
+//                    that owns configuration z forms its marginals and its partial sums; a fixed-order tree; thread 0 takes
+//                    the p-value, Q(df / 2, statistic / 2).
 //   k_pc_expand      one thread per test of a PC-stable level: its pair by binary search in the prefix offsets, its
 //                    conditioning set by unranking in the combinatorial number system (u64 binomials, integers only).
 //   k_pc_reduce_*    one wave per pair finds the lowest-index test with p > alpha and counts the refused ones; one workgroup
@@ -12,13 +13,12 @@
 //   k_pc_orient      one wave per structure, lane = variable: colliders from the separating sets, conflicts left undirected
 //                    and counted, then pd_meek (dvs_cpdag.h), then the cycle check of the directed part.
 #pragma once
-#include "dvs_search_args.h"
+#include "dvs_cpdag.h"               // pd_transpose, pd_meek
 
 // ---------------------------------------------------------------------------------------------------------
 // Q(a, x), the regularised upper incomplete gamma function: the series for P below a + 1, a modified Lentz continued
 // fraction for Q above.  Both share the factor x^a e^-x / Gamma(a), taken through bn_lgamma.
 // ---------------------------------------------------------------------------------------------------------
-static_assert(DVS_CI_MAX_CELLS == BIC_MAX_BINS, "the CI table shares the scorer's LDS budget");
 constexpr int CI_GAMMA_ITER = 20000;        // sqrt(a) terms are needed near x = a: a few hundred at a = 18 432
 
 __device__ inline double ci_gamma_q(const double a, const double x) {
@@ -64,53 +64,34 @@ __global__ __launch_bounds__(256) void k_ci_tests(CiArgs a) {
     const int tid = threadIdx.x;
     const int x = a.pairs[2 * t], y = a.pairs[2 * t + 1];
     if (tid == 0) {
-        uint64_t zm = a.cond[t];
-        const uint64_t below_n = a.n >= 64 ? ~0ull : (1ull << a.n) - 1ull;
-        bool ok = x >= 0 && y >= 0 && x < a.n && y < a.n && x != y && !(zm & ~below_n);
-        ok = ok && !((zm >> x) & 1ull) && !((zm >> y) & 1ull);
-        long long cells = 1;
-        int nz = 0;
+        const uint64_t zm = a.cond[t];
+        bool ok = x >= 0 && y >= 0 && x < a.n && y < a.n && x != y && !((zm >> x) & 1ull) && !((zm >> y) & 1ull);
         if (ok) {
-            cells = (long long)a.card[x] * a.card[y];
-            long long q = 1;
-            for (; zm; zm &= zm - 1ull) {
-                const int z = __popcll((zm & (0ull - zm)) - 1ull);
-                z_id[nz] = z;
-                z_stride[nz] = (int)q;                     // mixed radix, lowest variable id fastest
-                q *= a.card[z];
-                cells *= a.card[z];
-                ++nz;
-                if (cells > a.max_cells) break;
-            }
-            ok = cells <= a.max_cells && cells >= 1;
+            const long long plane = (long long)a.card[x] * a.card[y];
+            long long q = 0;
+            const int nz = bn_family_layout(zm, a.n, a.card, plane, a.max_cells, z_id, z_stride, &q);
+            ok = nz >= 0 && q * plane >= 1;                // a variable of no levels has no table
+            s_nz = nz;
             s_q = (int)q;
         }
-        s_nz = nz;
         s_ok = ok ? 1 : 0;
     }
     __syncthreads();
     if (!s_ok) {
         if (tid == 0) {
             atomicOr(a.status, 16);
-            const double nan = __longlong_as_double(0x7ff8000000000000LL);
-            a.out[3 * t] = nan;
-            a.out[3 * t + 1] = nan;
-            a.out[3 * t + 2] = nan;
+            a.out[3 * t] = bn_nan();
+            a.out[3 * t + 1] = bn_nan();
+            a.out[3 * t + 2] = bn_nan();
         }
         return;
     }
     const int nz = s_nz, q = s_q, rx = a.card[x], ry = a.card[y], plane = rx * ry, cells = q * plane;
     unsigned* hist = (unsigned*)smem;
-    for (int i = tid; i < cells; i += blockDim.x) hist[i] = 0u;
-    __syncthreads();
-    for (int s = tid; s < a.S; s += blockDim.x) {
-        const uint64_t* row = a.data + (size_t)s * a.words;
-        int key = 0;
-        for (int i = 0; i < nz; ++i) key += bic_level(row, z_id[i]) * z_stride[i];
-        const int idx = (key * rx + bic_level(row, x)) * ry + bic_level(row, y);
-        if (idx < cells) atomicAdd(&hist[idx], 1u);        // a level code >= card is not counted, never written out of the table
-    }
-    __syncthreads();
+    // guarded: a level code >= card is not counted, never written out of the table
+    bn_dense_count<false, true>(hist, cells, a.data, a.words, a.S, nullptr, nz, z_id, z_stride, [&](const uint64_t* row, int key) {
+        return (key * rx + bic_level(row, x)) * ry + bic_level(row, y);
+    });
     const bool g2 = a.type == DVS_CI_MI || a.type == DVS_CI_MI_ADF;
     double acc = 0.0;
     int adf = 0;
@@ -157,13 +138,7 @@ __global__ __launch_bounds__(256) void k_ci_tests(CiArgs a) {
     red[tid] = acc;
     redi[tid] = adf;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[tid] += red[tid + s];
-            redi[tid] += redi[tid + s];
-        }
-        __syncthreads();
-    }
+    dvs_block_sum256(tid, red, redi);
     if (tid == 0) {
         double stat = g2 ? 2.0 * red[0] : red[0];
         if (!(stat > 0.0)) stat = 0.0;
@@ -274,9 +249,9 @@ __global__ __launch_bounds__(256) void k_pc_reduce_pairs(PcReduceArgs a) {
         else if (pv > a.alpha && first == none) first = i;
     }
 #pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const long long of = (long long)hc_bcast64((uint64_t)first, lane ^ s);
-        refused += (long long)hc_bcast64((uint64_t)refused, lane ^ s);
+    for (int s = 32; s > 0; s >>= 1) {                       // min and sum in one butterfly
+        const long long of = dvs_shfl_xor(first, lane, s);
+        refused += dvs_shfl_xor(refused, lane, s);
         if (of < first) first = of;
     }
     if (lane == 0) {
@@ -360,21 +335,20 @@ __global__ __launch_bounds__(256) void k_pc_orient(PcOrientArgs a) {
     uint64_t C = 0ull;                                                           // claimed in: u -> lane
     const uint64_t* sep = a.sepsets + base * n;
     for (uint64_t xs = adj; xs; xs &= xs - 1ull) {
-        const int x = hc_ctz64(xs);
+        const int x = dvs_ctz64(xs);
         for (uint64_t ys = adj & ~s_adj[wave][x] & ~(1ull << x); ys; ys &= ys - 1ull) {
-            const int y = hc_ctz64(ys);
+            const int y = dvs_ctz64(ys);
             if (!((sep[(size_t)x * n + y] >> lane) & 1ull)) C |= 1ull << x;
         }
     }
     const uint64_t C_out = pd_transpose(C, n, lane);                             // claimed out: lane -> w
     const uint64_t both = C & C_out;                                             // claimed both ways: stays undirected
     int conf = __popcll(both & (self - 1ull));
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) conf += __shfl_xor(conf, s);
+    conf = dvs_wave_sum(conf, lane);
     uint64_t D = C & ~both;
     uint64_t U = adj & ~D & ~pd_transpose(D, n, lane);
     pd_meek(D, U, adj, s_adj[wave], n, lane);
-    const uint64_t reach = hc_closure(D, n);
+    const uint64_t reach = bn_closure(D, n);
     const bool cyclic = __ballot(live && (reach & self) != 0ull) != 0ull;
     if (lane == 0) {
         a.flags[b] = cyclic ? 1 : 0;

@@ -11,7 +11,7 @@
 //   k_pdag_compare   per unordered pair {u, v} the state (none, u -> v, v -> u, undirected) in two masks: lane v owns the
 //                    pairs with u < v, reads its row and, transposed by ballots, its column; popcounts, one packed butterfly.
 #pragma once
-#include "dvs_search_args.h"
+#include "dvs_bn_common.h"
 
 // t[v] bit u = x[u] bit v over the lanes below n (the rows of lanes >= n are zero on entry)
 __device__ __forceinline__ uint64_t pd_transpose(uint64_t x, int n, int lane) {
@@ -33,14 +33,14 @@ __device__ __forceinline__ void pd_meek(uint64_t& D, uint64_t& U, const uint64_t
     for (int round = 0; round < max_rounds; ++round) {
         uint64_t O = 0ull, via = 0ull;                       // O: u -> lane found this round; via: the parents of lane's parents
         for (int u = 0; u < n; ++u) {
-            const uint64_t D_u = hc_bcast64(D, u), U_u = hc_bcast64(U, u);
+            const uint64_t D_u = dvs_bcast64(D, u), U_u = dvs_bcast64(U, u);
             const uint64_t ubit = 1ull << u;
             if (D & ubit) via |= D_u;
             if (!(U & ubit)) continue;
             bool hit = (D_u & ~adj & ~self) != 0ull;                             // R1: w -> u - lane, w not adjacent to lane
             const uint64_t S = U_u & D;                                          // R3: u - w -> lane for two non-adjacent w
             for (uint64_t rest = S; !hit && rest; rest &= rest - 1ull) {
-                const int w = hc_ctz64(rest);
+                const int w = dvs_ctz64(rest);
                 hit = (S & ~s_adj[w] & ~(1ull << w)) != 0ull;
             }
             if (hit) O |= ubit;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_cpdag(CpdagArgs a) {
     const bool live = lane < n;
     const uint64_t row = live ? a.parents[base + lane] : 0ull;
     const uint64_t self = 1ull << lane, below_n = (1ull << n) - 1ull;           // n <= 48
-    const uint64_t reach = hc_closure(row, n);
+    const uint64_t reach = bn_closure(row, n);
     const bool illegal = __ballot(live && (row & (~below_n | self)) != 0ull) != 0ull;
     const bool cyclic = __ballot(live && (reach & self) != 0ull) != 0ull;
     const int fl = illegal ? 2 : (cyclic ? 1 : 0);                               // a self-loop is an illegal bit, not a cycle
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_cpdag(CpdagArgs a) {
     // v-structures: u -> v is compelled if v has a parent that is neither u nor adjacent to u
     uint64_t D = 0ull;                                                           // directed in: u -> lane
     for (int u = 0; u < n; ++u) {
-        const uint64_t adj_u = hc_bcast64(adj, u);
+        const uint64_t adj_u = dvs_bcast64(adj, u);
         const uint64_t ubit = 1ull << u;
         if ((row & ubit) && (row & ~adj_u & ~ubit)) D |= ubit;
     }
@@ -107,8 +107,7 @@ __global__ __launch_bounds__(256) void k_pdag_compare(PdagCompareArgs a) {
     // shd, tp, fp, fn, hamming in 12-bit fields: each is at most 48 * 47 / 2 = 1128 over the whole wave
     uint64_t acc = (uint64_t)__popcll(differ) | (uint64_t)__popcll(in_a & ~differ) << 12 | (uint64_t)__popcll(in_a & differ) << 24 |
                    (uint64_t)__popcll(in_t & differ) << 36 | (uint64_t)__popcll(in_a ^ in_t) << 48;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) acc += hc_bcast64(acc, lane ^ s);
+    acc = dvs_wave_sum(acc, lane);
     if (lane < 5) a.counts[(size_t)b * 5 + lane] = (int)((acc >> (12 * lane)) & 0xfffull);
 }
 

@@ -354,6 +354,62 @@ __device__ __forceinline__ void dvs_ln_stats(const f4 (&x)[4], float& mean, floa
     rstd = 1.0f / sqrtf(dvs_sum_g(s) * (1.f / 64.f) + 1e-5f);
 }
 
+// ---- 64-bit values and whole-wave reductions of the search side (lane = variable / structure / sample) ---------------
+// A 64-bit value crosses lanes as two 32-bit halves.  dvs_shfl_xor(x, lane, mask) is x of lane `lane ^ mask`, the caller's
+// own lane index passed in: HIP's __shfl_xor carries a range clamp per call that the compiler does not fold, and
+// lane ^ mask never leaves the wave.  The reductions are xor butterflies from 32 down to 1 with the result in every lane:
+// sum (a fixed pairing, so a double sum is reproducible), max and min over int, 64-bit integers and double.
+// (dvs_sum_wave above is the train step's float sum; it pairs the other way round.)
+__device__ __forceinline__ int dvs_ctz64(uint64_t v) { return __builtin_ctzll(v); }     // v != 0
+__device__ __forceinline__ uint64_t dvs_bcast64(uint64_t x, int src) {                   // x of lane src
+    int lo = (int)(x & 0xffffffffull), hi = (int)(x >> 32);
+    lo = __shfl(lo, src);
+    hi = __shfl(hi, src);
+    return ((uint64_t)(unsigned)hi << 32) | (uint64_t)(unsigned)lo;
+}
+__device__ __forceinline__ double dvs_bcast_f64(double x, int src) {
+    return __longlong_as_double((long long)dvs_bcast64((uint64_t)__double_as_longlong(x), src));
+}
+__device__ __forceinline__ int dvs_shfl_xor(int x, int lane, int mask) { return __shfl(x, lane ^ mask); }
+__device__ __forceinline__ uint64_t dvs_shfl_xor(uint64_t x, int lane, int mask) { return dvs_bcast64(x, lane ^ mask); }
+__device__ __forceinline__ long long dvs_shfl_xor(long long x, int lane, int mask) { return (long long)dvs_bcast64((uint64_t)x, lane ^ mask); }
+__device__ __forceinline__ double dvs_shfl_xor(double x, int lane, int mask) { return dvs_bcast_f64(x, lane ^ mask); }
+template <class T>
+__device__ __forceinline__ T dvs_wave_sum(T x, int lane) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x += dvs_shfl_xor(x, lane, s);
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T dvs_wave_max(T x, int lane) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const T o = dvs_shfl_xor(x, lane, s);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T dvs_wave_min(T x, int lane) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const T o = dvs_shfl_xor(x, lane, s);
+        x = o < x ? o : x;
+    }
+    return x;
+}
+
+// Sum over the 256 threads of a workgroup, one or several 256-slot LDS arrays at once: x[i] += x[i + s] for s = 128, ..., 1,
+// a barrier after every step — a fixed pairing, so the sum in x[0] is reproducible.  The caller has written the slots and
+// passed a barrier; every thread calls it.
+template <class... T>
+__device__ __forceinline__ void dvs_block_sum256(const int tid, T*... x) {
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) ((x[tid] += x[tid + s]), ...);
+        __syncthreads();
+    }
+}
+
 // ---- counter-based dropout / noise ------------------------------------------------------------------------------
 // Stateless: mask bits are a pure function of (seed, site, global DAG index, element), so the backward pass
 // regenerates them instead of storing 34 masks, and a batch sharded over ranks draws the same bits as the same

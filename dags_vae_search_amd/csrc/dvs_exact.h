@@ -16,7 +16,7 @@
 //                      one launch per level (one workgroup takes 122 us at n = 11 and 238 us at n = 12, 13 launches 97 us).
 //   k_exact_backtrack  n serial steps, one thread per table.
 #pragma once
-#include "dvs_search_args.h"
+#include "dvs_bn_common.h"
 
 constexpr int EX_TILE_BITS = 8;              // bits of S per LDS pass
 constexpr int EX_ONE_WG_VARS = 9;            // k_exact_sinks: up to here one workgroup walks all levels of a table

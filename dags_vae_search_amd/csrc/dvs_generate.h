@@ -146,8 +146,7 @@ void dvs_launch_generate_edge_counts(int B, int K, const int* counts, const int*
 
 void dvs_launch_generate_dags(const GenArgs& in, uint64_t seed, bool wide, dvs_stream_t st) {
     GenArgs a = in;
-    a.seed_lo = (uint32_t)seed;
-    a.seed_hi = (uint32_t)(seed >> 32);
+    dvs_seed_split(a, seed);
     const int per = 64 >> a.gshift;
     const dim3 grid((unsigned)(((size_t)a.B + per - 1) / per));
     if (wide) DVS_LAUNCH_AS("k_generate_dags", (k_generate_dags<uint64_t, uint64_t>), grid, dim3(64), (size_t)a.n * 64 * 8, st, a);

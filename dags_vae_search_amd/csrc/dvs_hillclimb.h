@@ -3,7 +3,8 @@
 //
 //   k_bn_toggle<FAMILY>  T[b][v][u] = local score of variable v with parent set P[b][v] xor (1 << u), L[b][v] = the local
 //                        score as it stands.  One workgroup per cell, each a bn_family_score call: the bytes of k_bic_local
-//                        for that parent set.  One table prices all three moves on u -> v:
+//                        for that parent set.  bn_toggle_cell is its body and, with a row set, that of k_bn_toggle_rows
+//                        (dvs_strength.h).  One table prices all three moves on u -> v:
 //                            add / delete   T[v][u] - L[v]
 //                            reverse        (T[v][u] - L[v]) + (T[u][v] - L[u])
 //                        Full pass: all B n rows.  Incremental pass: the rows named in the worklist, whose slots 2b and
@@ -12,13 +13,13 @@
 //   k_hc_step            one wave per structure, lane = variable, the lane's parent row one u64: ancestor closure by n
 //                        rounds of row broadcasts, legality and delta of every move, the best one across lanes (largest
 //                        fp64 delta, exact ties to the lowest code = op n^2 + v n + u), applied if delta > min_delta.
-//                        Closure, legality and pricing are device functions (hc_load, hc_moves, hc_apply) shared with
-//                        k_tabu_step and k_hc_perturb (dvs_tabu.h).
+//                        How a step starts and ends, closure, legality and pricing are device functions (hc_sit_out,
+//                        hc_moves, hc_apply, hc_record) shared with k_tabu_step and k_hc_perturb (dvs_tabu.h).
 #pragma once
-#include "dvs_search_args.h"
+#include "dvs_bn_common.h"
 
-template <int FAMILY>
-__global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
+template <int FAMILY, bool ROWS>
+__device__ __forceinline__ void bn_toggle_cell(const ToggleArgs& t, const RowSetArgs* r) {      // r is read with ROWS only
     DVS_DYN_LDS(smem);
     const int n = t.s.n;
     const int u = blockIdx.x % n, row = blockIdx.x / n;
@@ -32,29 +33,31 @@ __global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
         dag = row / n;
     }
     const size_t cell = (size_t)dag * n + v;
-    const double score = bn_family_score<FAMILY>(t.s, v, t.s.parents + cell, u == v ? 0ull : 1ull << u, smem);
+    const double score = bn_family_score<FAMILY, ROWS>(t.s, v, t.s.parents + cell, u == v ? 0ull : 1ull << u, smem,
+                                                       ROWS ? rs_rows(*r, dag) : nullptr);
     if (threadIdx.x == 0) {
         if (u == v) {
             t.s.local[cell] = score;
-            t.toggles[cell * n + u] = __longlong_as_double(0x7ff8000000000000LL);
+            t.toggles[cell * n + u] = bn_nan();
         } else {
             t.toggles[cell * n + u] = score;
         }
     }
 }
+template <int FAMILY>
+__global__ __launch_bounds__(256) void k_bn_toggle(ToggleArgs t) {
+    bn_toggle_cell<FAMILY, false>(t, nullptr);
+}
 
+// one workgroup per cell of the rows a pass covers: the two worklist slots of every structure, or all its n rows
+static inline dim3 bn_toggle_grid(const ToggleArgs& t) {
+    const unsigned rows = t.worklist != nullptr ? 2u * (unsigned)t.s.B : (unsigned)t.s.B * (unsigned)t.s.n;
+    return dim3(rows * (unsigned)t.s.n);
+}
 void dvs_launch_bn_toggle(const ToggleArgs& in, dvs_stream_t st) {
     ToggleArgs t = in;
     t.s.words = bic_words(t.s.n);
-    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    const unsigned rows = t.worklist != nullptr ? 2u * (unsigned)t.s.B : (unsigned)t.s.B * (unsigned)t.s.n;
-    if (t.s.type <= DVS_SCORE_BIC) {
-        DVS_SET_LDS(k_bn_toggle<0>, lds);
-        DVS_LAUNCH_AS("k_bn_toggle", k_bn_toggle<0>, dim3(rows * (unsigned)t.s.n), dim3(256), lds, st, t);
-    } else {
-        DVS_SET_LDS(k_bn_toggle<1>, lds);
-        DVS_LAUNCH_AS("k_bn_toggle_dirichlet", k_bn_toggle<1>, dim3(rows * (unsigned)t.s.n), dim3(256), lds, st, t);
-    }
+    BN_LAUNCH_FAMILY(t.s.type, k_bn_toggle, "k_bn_toggle", "k_bn_toggle_dirichlet", bn_toggle_grid(t), st, t);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -62,12 +65,6 @@ void dvs_launch_bn_toggle(const ToggleArgs& in, dvs_stream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 constexpr int HC_NO_MOVE = 0x7fffffff;
 
-__device__ __forceinline__ uint64_t hc_bcast64(uint64_t x, int src) {
-    int lo = (int)(x & 0xffffffffull), hi = (int)(x >> 32);
-    lo = __shfl(lo, src);
-    hi = __shfl(hi, src);
-    return ((uint64_t)(unsigned)hi << 32) | (uint64_t)(unsigned)lo;
-}
 // (delta, code) beats (bd, bc): larger delta, exact ties to the lower code — a total order, so the reduction tree's shape
 // cannot change the winner
 __device__ __forceinline__ void hc_consider(double d, int c, double& bd, int& bc) {
@@ -85,16 +82,6 @@ struct HcLane {
     double Lv;                   // its local score
 };
 
-// reach[v]: the ancestors of v (bit-row Warshall: after round k every path through 0 .. k is in)
-__device__ __forceinline__ uint64_t hc_closure(uint64_t row, int n) {
-    uint64_t reach = row;
-    for (int k = 0; k < n; ++k) {
-        const uint64_t rk = hc_bcast64(reach, k);
-        if ((reach >> k) & 1ull) reach |= rk;
-    }
-    return reach;
-}
-
 // loads the lane's row and local score and closes the structure -> the flags of include/dvs.h (1 cycle, 2 NaN local score)
 __device__ __forceinline__ int hc_load(HcLane& c, int n, int lane, const uint64_t* parents, const double* local, size_t base) {
     c.n = n;
@@ -103,11 +90,31 @@ __device__ __forceinline__ int hc_load(HcLane& c, int n, int lane, const uint64_
     c.row = c.live ? parents[base + lane] : 0ull;
     c.Lv = c.live ? local[base + lane] : 0.0;
     c.self = 1ull << lane;
-    c.reach = hc_closure(c.row, n);
+    c.reach = bn_closure(c.row, n);
     int fl = 0;
     if (__ballot(c.live && (c.reach & c.self) != 0)) fl |= 1;
     if (__ballot(c.live && c.Lv != c.Lv)) fl |= 2;
     return fl;
+}
+
+// How a step kernel starts, in the three of them: a structure that is finished or was flagged before sits the launch out
+// (fl = 0); else hc_load, and a flag found now (fl != 0) is written and it sits out too.  Sitting out clears the structure's
+// two worklist slots, so the next toggle pass skips it.  The kernels keep the two wave-uniform branches themselves and
+// return hc_sit_out(...): a prologue that returned "go on" instead compiled to more registers in all three.
+__device__ __forceinline__ void hc_sit_out(int fl, int lane, int b, int* flags, int* worklist) {
+    if (fl && lane == 0) flags[b] = fl;
+    if (lane < 2) worklist[2 * b + lane] = -1;
+}
+
+// How a step that moved ends (lane 0): the step count, the trace entry, one more active structure.
+__device__ __forceinline__ void hc_record(const HcArgs& a, int b, int nsteps, int bcode, double best) {
+    a.steps[b] = nsteps + 1;
+    if (a.trace != nullptr) {
+        int64_t* t = a.trace + ((size_t)b * a.step_cap + nsteps) * 2;
+        t[0] = bcode;
+        t[1] = (int64_t)__double_as_longlong(best);
+    }
+    atomicAdd(a.active, 1);
 }
 
 // Legality and pricing: f(op, u, delta) for every legal move on u -> v = lane (op 0 add, 1 delete, 2 reverse) whose delta
@@ -120,8 +127,8 @@ __device__ __forceinline__ void hc_moves(const HcLane& c, const double* T, int m
     const uint64_t forb_v = (forbidden != nullptr && c.live) ? forbidden[lane] : 0ull;
     for (int u = 0; u < n; ++u) {
         const uint64_t child_u = __ballot(c.live && ((c.row >> u) & 1ull) != 0);
-        const uint64_t row_u = hc_bcast64(c.row, u), reach_u = hc_bcast64(c.reach, u);
-        const double L_u = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(c.Lv), u));
+        const uint64_t row_u = dvs_bcast64(c.row, u), reach_u = dvs_bcast64(c.reach, u);
+        const double L_u = dvs_bcast_f64(c.Lv, u);
         if (!c.live || u == lane) continue;
         const double t_vu = T[lane * n + u];
         if (t_vu != t_vu) continue;                               // a refused family: the move is not available
@@ -144,8 +151,8 @@ __device__ __forceinline__ void hc_moves(const HcLane& c, const double* T, int m
 __device__ __forceinline__ void hc_reduce_best(double& best, int& bcode, int lane) {
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) {
-        const double od = __longlong_as_double((long long)hc_bcast64((uint64_t)__double_as_longlong(best), lane ^ s));
-        const int oc = __shfl(bcode, lane ^ s);
+        const double od = dvs_shfl_xor(best, lane, s);
+        const int oc = dvs_shfl_xor(bcode, lane, s);
         hc_consider(od, oc, best, bcode);
     }
 }
@@ -174,18 +181,10 @@ __global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
     if (b >= a.B) return;
     const int n = a.n;
     const int nsteps = a.steps[b];
-    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) {          // wave-uniform
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
     const size_t base = (size_t)b * n;
     HcLane c;
-    const int fl = hc_load(c, n, lane, a.parents, a.local, base);
-    if (fl) {
-        if (lane == 0) a.flags[b] = fl;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
+    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) return hc_sit_out(0, lane, b, a.flags, a.worklist);
+    if (const int fl = hc_load(c, n, lane, a.parents, a.local, base)) return hc_sit_out(fl, lane, b, a.flags, a.worklist);
     const double* T = a.toggles + base * n;
     const int nn = n * n;
     double best = -__builtin_inf();
@@ -194,18 +193,10 @@ __global__ __launch_bounds__(256) void k_hc_step(HcArgs a) {
     hc_reduce_best(best, bcode, lane);
     if (bcode != HC_NO_MOVE && best > a.min_delta) {
         hc_apply(c, bcode, a.parents, a.local, T, base, a.worklist, b);
-        if (lane == 0) {
-            a.steps[b] = nsteps + 1;
-            if (a.trace != nullptr) {
-                int64_t* t = a.trace + ((size_t)b * a.step_cap + nsteps) * 2;
-                t[0] = bcode;
-                t[1] = (int64_t)__double_as_longlong(best);
-            }
-            atomicAdd(a.active, 1);
-        }
+        if (lane == 0) hc_record(a, b, nsteps, bcode, best);
     } else {
         if (lane == 0) a.converged[b] = 1;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        hc_sit_out(0, lane, b, a.flags, a.worklist);
     }
 }
 

@@ -7,7 +7,7 @@
 //   k_bn_lw_check        one thread per query: an observed variable whose evidence level is >= its level count (or an
 //                        observed bit >= n) marks the query (workspace) and sets bit 4.
 //   k_bn_lw              a 256-thread workgroup walks (query, 256-particle chunk) work items in a grid-stride loop, one
-//                        particle per thread: the variables in the prep's order, the levels in three u64 registers, an
+//                        particle per thread: the variables in the prep's order, the levels in registers (BnRow), an
 //                        observed variable clamped (weight *= theta), an unobserved one drawn as k_bn_sample draws.  The
 //                        thresholds are staged once per workgroup (LDS up to DVS_BN_SAMPLE_LDS_CELLS), not once per chunk.
 //                        Every cell of the chunk (sum w, sum w^2, sum w [event], then w [level = k] per target level) is
@@ -26,11 +26,6 @@ constexpr int BN_LW_BATCH = 8;                               // cells reduced pe
 #define BN_LW_GROUPS_PER_CU 3                                // workgroups launched per CU: what its LDS holds of the staged kernel
                                                              // (17 KiB + 32 KiB each); 8 and 16 measured no faster
 #endif
-
-__device__ __forceinline__ int bn_level(uint64_t w0, uint64_t w1, uint64_t w2, int v) {
-    const uint64_t w = v < 16 ? w0 : v < 32 ? w1 : w2;
-    return (int)((w >> (4 * (v & 15))) & 15ull);
-}
 
 // red: nb arrays of 256 slots; x[i] += x[i + s] for s = 128, ..., 1 in each, all threads sharing the additions of a step
 __device__ __forceinline__ void bn_lw_tree(double* red, const int nb, const int tid) {
@@ -52,7 +47,7 @@ __global__ __launch_bounds__(256) void k_bn_lw_check(BnLwArgs a) {
     const uint64_t* ev = a.evidence + (size_t)q * a.words;
     for (int v = 0; v < a.n; ++v)
         if ((obs >> v) & 1ull)
-            if ((int)((ev[v >> 4] >> (4 * (v & 15))) & 15ull) >= a.card[v]) bad = true;
+            if (bic_level(ev, v) >= a.card[v]) bad = true;
     a.qbad[q] = bad ? 1 : 0;
     if (bad) atomicOr(a.status, 16);
 }
@@ -69,14 +64,12 @@ __global__ __launch_bounds__(256) void k_bn_lw(BnLwArgs a) {
     if (!a.header[BN_HDR_DRAWABLE]) return;                  // uniform: the prep refused the network
     if (tid < n) {
         s_order[tid] = a.header[tid];
-        s_base[tid] = (int)(a.offsets[tid] - a.offsets[0]);
-        s_card[tid] = a.card[tid];
-        s_par[tid] = a.parents[tid] & ~(1ull << tid);
+        bn_stage_var(tid, tid, a.offsets, a.card, a.parents, s_base, s_card, s_par);
         s_event[tid] = a.event ? a.event[tid] : (unsigned short)0xffffu;
     }
     if (tid == 0) {
         int t = 0;
-        for (uint64_t tm = a.targets; tm; tm &= tm - 1ull) s_tgt[t++] = hc_ctz64(tm);
+        for (uint64_t tm = a.targets; tm; tm &= tm - 1ull) s_tgt[t++] = dvs_ctz64(tm);
     }
     const uint32_t* thr = a.thr;
     if (STAGED) {
@@ -100,44 +93,29 @@ __global__ __launch_bounds__(256) void k_bn_lw(BnLwArgs a) {
             continue;
         }
         const uint64_t obs = a.observed[q];
-        const uint64_t* ev = a.evidence + (size_t)q * a.words;
-        const uint64_t e0 = ev[0], e1 = a.words > 1 ? ev[1] : 0ull, e2 = a.words > 2 ? ev[2] : 0ull;
+        const BnRow ev = bn_row_load(a.evidence + (size_t)q * a.words, a.words);
         const uint32_t key = dvs_site_key(a.seed_lo, a.seed_hi, DVS_SITE_BN_LW, a.query_offset + (uint32_t)q);
-        uint64_t w0 = 0ull, w1 = 0ull, w2 = 0ull;
+        BnRow x = {0ull, 0ull, 0ull};
         double w = 1.0;
         bool in_event = true;
         {
 #pragma clang fp contract(off)
             for (int i = 0; i < n; ++i) {
                 const int v = s_order[i], r = s_card[v];
-                int cfg = 0, stride = 1;
-                for (uint64_t pm = s_par[v]; pm; pm &= pm - 1ull) {
-                    const int u = hc_ctz64(pm);
-                    cfg += bn_level(w0, w1, w2, u) * stride;
-                    stride *= s_card[u];
-                }
+                const int cfg = bn_row_config(x, s_par[v], s_card);
                 uint64_t level;
                 if ((obs >> v) & 1ull) {                     // uniform per work item: no divergence
-                    level = (uint64_t)bn_level(e0, e1, e2, v);
+                    level = (uint64_t)bn_level(ev, v);
                     w *= cpt[s_base[v] + cfg * r + (int)level];
                 } else {
-                    const uint32_t* T = thr + s_base[v] + cfg * r;
-                    const uint32_t h = dvs_draw(dvs_draw(key, (uint32_t)v), (uint32_t)p) >> 1;
-                    level = 0ull;
-                    for (int k = 0; k < r - 1; ++k) level += h >= T[k] ? 1ull : 0ull;
+                    level = bn_draw_level(thr + s_base[v] + cfg * r, r, dvs_draw(dvs_draw(key, (uint32_t)v), (uint32_t)p) >> 1);
                 }
                 in_event = in_event && ((s_event[v] >> level) & 1u);
-                level <<= 4 * (v & 15);
-                if (v < 16) w0 |= level;
-                else if (v < 32) w1 |= level;
-                else w2 |= level;
+                x = bn_row_with(x, v, level);
             }
         }
         if (live && a.particles) {
-            uint64_t* out = a.particles + slot * a.words;
-            out[0] = w0;
-            if (a.words > 1) out[1] = w1;
-            if (a.words > 2) out[2] = w2;
+            bn_row_store(a.particles + slot * a.words, x, a.words);
             a.pweights[slot] = w;
         }
         if (!live) w = 0.0;                                  // absent particles count +0 in every cell
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(256) void k_bn_lw(BnLwArgs a) {
         bn_lw_tree(red, 3, tid);
         if (tid < 3) part[tid] = red[tid * 256];
         for (int t = 0; t < a.T; ++t) {
-            const int v = s_tgt[t], r = s_card[v], lvl = bn_level(w0, w1, w2, v);
+            const int v = s_tgt[t], r = s_card[v], lvl = bn_level(x, v);
             for (int k0 = 0; k0 < r; k0 += BN_LW_BATCH) {
                 const int nb = r - k0 < BN_LW_BATCH ? r - k0 : BN_LW_BATCH;
                 __syncthreads();
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(256) void k_bn_lw_fold(BnLwArgs a) {
             int v = 0, t = (c - 3) >> 4;                     // the t-th target in ascending id
             for (uint64_t tm = a.targets; tm; tm &= tm - 1ull, --t)
                 if (t == 0) {
-                    v = hc_ctz64(tm);
+                    v = dvs_ctz64(tm);
                     break;
                 }
             valid = ((c - 3) & 15) < a.card[v];
@@ -217,26 +195,23 @@ __global__ __launch_bounds__(256) void k_bn_lw_fold(BnLwArgs a) {
     }
 }
 
+// what k_bn_sample_prep reads of a likelihood-weighting call: the network and the sampler's workspace
+static inline BnSampleArgs bn_lw_prep_args(const BnLwArgs& a) {
+    BnSampleArgs p = {};
+    p.n = a.n, p.words = a.words, p.n_cells = a.n_cells;
+    p.card = a.card, p.parents = a.parents, p.offsets = a.offsets, p.cpt = a.cpt;
+    p.header = a.header, p.thr = a.thr, p.status = a.status;
+    return p;
+}
+
 void dvs_launch_bn_lw(const BnLwArgs& in, uint64_t seed, dvs_stream_t st) {
     BnLwArgs a = in;
     a.words = bic_words(a.n);
-    a.seed_lo = (uint32_t)(seed & 0xffffffffull);
-    a.seed_hi = (uint32_t)(seed >> 32);
+    dvs_seed_split(a, seed);
     a.T = 0;
     for (uint64_t tm = a.targets; tm; tm &= tm - 1ull) ++a.T;
     a.cells = 3 + 16 * a.T;
-    BnSampleArgs prep = {};
-    prep.n = a.n;
-    prep.words = a.words;
-    prep.n_cells = a.n_cells;
-    prep.card = a.card;
-    prep.parents = a.parents;
-    prep.offsets = a.offsets;
-    prep.cpt = a.cpt;
-    prep.header = a.header;
-    prep.thr = a.thr;
-    prep.status = a.status;
-    DVS_LAUNCH(k_bn_sample_prep, dim3(1), dim3(256), 0, st, prep);
+    DVS_LAUNCH(k_bn_sample_prep, dim3(1), dim3(256), 0, st, bn_lw_prep_args(a));
     DVS_LAUNCH(k_bn_lw_check, dim3((unsigned)((a.Q + 255) / 256)), dim3(256), 0, st, a);
     const long long items = (long long)a.Q * a.chunks;
     const long long cap = (long long)(a.cus > 0 ? a.cus : 256) * BN_LW_GROUPS_PER_CU;
@@ -270,9 +245,9 @@ __global__ __launch_bounds__(256) void k_bn_blanket(BnBlanketArgs a) {
         const long long lo = a.offsets[fam], hi = a.offsets[fam + 1], r = a.card[tid];
         const uint64_t pm = a.parents[fam] & ~(1ull << tid);
         bool ok = r >= 1 && r <= 16 && !(n < 64 && (pm >> n)) && lo >= 0 && hi <= a.cpt_cells;
-        long long q = 1;
-        for (uint64_t m = pm; m && ok; m &= m - 1ull) {
-            q *= a.card[hc_ctz64(m)];
+        long long q = 1;                                     // bn_family_layout<false>'s walk, kept here: one lane per variable
+        for (uint64_t m = pm; m && ok; m &= m - 1ull) {      // walks at once, and the shared routine's two exits cost this
+            q *= a.card[dvs_ctz64(m)];                       // kernel three more SGPRs
             ok = q * r <= 0x7fffffffLL;
         }
         if (!ok || hi - lo != q * r) s_ok = 0;
@@ -286,11 +261,10 @@ __global__ __launch_bounds__(256) void k_bn_blanket(BnBlanketArgs a) {
     const int rt = a.card[tg];                               // the width of a posterior row, whatever the family looks like
     double* post = a.posterior ? a.posterior + ((size_t)b * a.rows + row) * rt : nullptr;
     unsigned char* pred = a.pred + (size_t)b * a.rows + row;
-    const uint64_t* src = a.data + (size_t)row * a.words;
-    uint64_t w0 = src[0], w1 = a.words > 1 ? src[1] : 0ull, w2 = a.words > 2 ? src[2] : 0ull;
+    BnRow x = bn_row_load(a.data + (size_t)row * a.words, a.words);
     bool ok = s_ok != 0;
     for (int v = 0; v < n; ++v)
-        if (v != tg && bn_level(w0, w1, w2, v) >= s_card[v]) ok = false;          // the target's own column is ignored
+        if (v != tg && bn_level(x, v) >= s_card[v]) ok = false;                // the target's own column is ignored
     if (!ok) {
         if (s_ok) atomicOr(a.status, 16);                    // a level code >= card
         else if (row == 0) atomicOr(a.status, 16);           // a malformed family
@@ -298,22 +272,16 @@ __global__ __launch_bounds__(256) void k_bn_blanket(BnBlanketArgs a) {
         *pred = 255;
         return;
     }
-    const uint64_t clear = ~(15ull << (4 * (tg & 15)));
-    if (tg < 16) w0 &= clear;
-    else if (tg < 32) w1 &= clear;
-    else w2 &= clear;
+    const uint64_t clear = ~(15ull << (4 * (tg & 15)));      // the target's nibble: product() puts each level there in turn
+    if (tg < 16) x.w0 &= clear;
+    else if (tg < 32) x.w1 &= clear;
+    else x.w2 &= clear;
     const auto product = [&](const int k) -> double {        // theta_t(k | pa), then times the children in ascending id
 #pragma clang fp contract(off)
-        const uint64_t lk = (uint64_t)k << (4 * (tg & 15));
-        const uint64_t x0 = tg < 16 ? w0 | lk : w0, x1 = tg >= 16 && tg < 32 ? w1 | lk : w1, x2 = tg >= 32 ? w2 | lk : w2;
+        const BnRow xk = bn_row_with(x, tg, (uint64_t)k);
         const auto theta = [&](const int c) -> double {
-            int cfg = 0, stride = 1;
-            for (uint64_t pm = s_par[c]; pm; pm &= pm - 1ull) {
-                const int u = hc_ctz64(pm);
-                cfg += bn_level(x0, x1, x2, u) * stride;
-                stride *= s_card[u];
-            }
-            return a.cpt[s_base[c] + (long long)cfg * s_card[c] + bn_level(x0, x1, x2, c)];
+            const int cfg = bn_row_config(xk, s_par[c], s_card);
+            return a.cpt[s_base[c] + (long long)cfg * s_card[c] + bn_level(xk, c)];
         };
         double p = theta(tg);
         if (a.use_children)

@@ -32,11 +32,6 @@ struct MatchLane {
     int l1, l2;                  // labels (the decoded one signed: PACE label - 3)
 };
 
-__device__ __forceinline__ uint64_t match_shfl64(uint64_t v, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __device__ __forceinline__ unsigned match_mix(unsigned x) {
     x ^= x >> 16;
     x *= 0x7feb352du;
@@ -98,7 +93,7 @@ __device__ bool match_verify(const MatchLane& g, int lane, int n, bool labelled,
     bool bad = real && inv < 0;
     for (int w = 0; w < n; ++w) {
         const int u = __shfl(inv, w);
-        const uint64_t S = match_shfl64(g.p1, u < 0 ? 0 : u);
+        const uint64_t S = dvs_bcast64(g.p1, u < 0 ? 0 : u);
         const uint64_t img = __ballot(inv >= 0 && ((S >> (inv & 63)) & 1ull));
         if (lane == w) bad = bad || g.p2 != img;
     }
@@ -136,7 +131,7 @@ __device__ int match_search(const MatchLane& g, int lane, int n, bool labelled, 
     for (;;) {
         if (descend) {           // candidates of depth d
             const int v = __shfl(ord, d);
-            const uint64_t pv = match_shfl64(g.p1, v), cv = match_shfl64(g.c1, v);
+            const uint64_t pv = dvs_bcast64(g.p1, v), cv = dvs_bcast64(g.c1, v);
             const unsigned colv = (unsigned)__shfl((int)col1, v);
             const int lv = __shfl(g.l1, v);
             const bool mapped = inv >= 0;
@@ -153,7 +148,7 @@ __device__ int match_search(const MatchLane& g, int lane, int n, bool labelled, 
             const int w = __shfl(pick, d);
             if (lane == w) inv = -1;
             used &= ~(1ull << w);
-            cand = match_shfl64(stk, d);
+            cand = dvs_bcast64(stk, d);
             continue;
         }
         if (nodes >= budget) return -1;

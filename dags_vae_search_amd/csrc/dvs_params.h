@@ -4,42 +4,18 @@
 // histogram adds and the status atomicOr: two runs give equal bytes.
 //
 //   k_bn_fit             one workgroup per (structure, variable): the dense (configuration, level) table in dynamic LDS, counted
-//                        by integer atomics with the scorer's loop (bn_family_score, mode 0); the thread that owns configuration
+//                        by the scorer's routine (bn_dense_count, here with the range guard); the thread that owns configuration
 //                        j takes N_j and writes its r cells.  No sort path: a table above 36 864 cells is refused.
 //   k_bn_sample_prep     one workgroup: thread 0 orders the variables and checks the slots; all threads then check the rows of
 //                        the tables and write their u32 thresholds.
-//   k_bn_sample          one thread per row: the variables in the prep's order, the row's levels in three u64 registers, one
+//   k_bn_sample          one thread per row: the variables in the prep's order, the row's levels in registers (BnRow), one
 //                        counter-based draw per (row, variable); thresholds from LDS when the tables fit DVS_BN_SAMPLE_LDS_CELLS.
 //   k_bn_loglik_prep     one workgroup per (structure, variable): checks the slot and writes log(theta) of its cells.
 //   k_bn_loglik_rows     one thread per row, one workgroup per 256 rows of one structure: the row term, then a fixed tree.
 //   k_bn_loglik_sum      one workgroup per structure: thread t adds the chunk partials t, t + 256, ... in ascending order, then
 //                        the same tree.
 #pragma once
-#include "dvs_search_args.h"
-
-__device__ __forceinline__ double bn_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// The parents of v below n as (id, mixed-radix stride) pairs, lowest id fastest — par_stride of bn_family_score — and q, the
-// product of their level counts, as far as it stays within `limit` cells together with the r levels of v.  Returns the number
-// of parents, or -1 for a parent bit >= n or a table beyond the limit.  One thread calls it.
-__device__ __forceinline__ int bn_family_layout(uint64_t pm, const int v, const int n, const uint8_t* card, const long long limit,
-                                                int* par_id, int* par_stride, long long* q_out) {
-    pm &= ~(1ull << v);
-    const long long r = card[v] ? card[v] : 1;               // a variable of no levels: the caller refuses it
-    long long q = 1;
-    int np = 0;
-    for (; pm; pm &= pm - 1ull) {
-        const int p = hc_ctz64(pm);
-        if (p >= n) return -1;
-        par_id[np] = p;
-        par_stride[np] = (int)q;
-        q *= card[p];
-        if (q * r > limit) return -1;
-        ++np;
-    }
-    *q_out = q;
-    return q * r > limit ? -1 : np;
-}
+#include "dvs_bn_common.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_bn_fit
@@ -53,7 +29,7 @@ __global__ __launch_bounds__(256) void k_bn_fit(BnFitArgs a) {
     const int r = a.card[v];
     if (tid == 0) {
         long long q = 0;
-        int np = bn_family_layout(a.parents[fam], v, a.n, a.card, BIC_MAX_BINS, par_id, par_stride, &q);
+        int np = bn_family_layout(a.parents[fam] & ~(1ull << v), a.n, a.card, r, BIC_MAX_BINS, par_id, par_stride, &q);
         const long long lo = a.offsets[fam], hi = a.offsets[fam + 1];
         if (np >= 0 && (r < 1 || lo < 0 || hi - lo != q * r || hi > a.cpt_cells)) np = -1;
         s_np = np;
@@ -67,16 +43,9 @@ __global__ __launch_bounds__(256) void k_bn_fit(BnFitArgs a) {
     }
     unsigned* hist = (unsigned*)smem;
     const int q = s_q, bins = q * r;
-    for (int i = tid; i < bins; i += blockDim.x) hist[i] = 0u;
-    __syncthreads();
-    for (int s = tid; s < a.S; s += blockDim.x) {
-        const uint64_t* row = a.data + (size_t)s * a.words;
-        int key = 0;
-        for (int i = 0; i < np; ++i) key += bic_level(row, par_id[i]) * par_stride[i];
-        const int idx = key * r + bic_level(row, v);
-        if (idx < bins) atomicAdd(&hist[idx], 1u);           // a level code >= card is never written out of the table
-    }
-    __syncthreads();
+    // guarded: a level code >= card is never written out of the table
+    bn_dense_count<false, true>(hist, bins, a.data, a.words, a.S, nullptr, np, par_id, par_stride,
+                                [&](const uint64_t* row, int key) { return key * r + bic_level(row, v); });
     double* out = a.cpt + a.offsets[fam];
     {
 #pragma clang fp contract(off)
@@ -102,9 +71,8 @@ __global__ __launch_bounds__(256) void k_bn_fit(BnFitArgs a) {
 void dvs_launch_bn_fit(const BnFitArgs& in, dvs_stream_t st) {
     BnFitArgs a = in;
     a.words = bic_words(a.n);
-    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    DVS_SET_LDS(k_bn_fit, lds);
-    DVS_LAUNCH(k_bn_fit, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
+    DVS_SET_LDS(k_bn_fit, bn_table_lds());
+    DVS_LAUNCH(k_bn_fit, dim3((unsigned)a.B * a.n), dim3(256), bn_table_lds(), st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -118,15 +86,11 @@ __global__ __launch_bounds__(256) void k_bn_sample_prep(BnSampleArgs a) {
     const long long base = a.offsets[0];
     if (tid == 0) {
         int state = 0;
-        const uint64_t below_n = (1ull << n) - 1ull;         // n <= 48
         for (int v = 0; v < n && !state; ++v) {              // the slots: every table as long as its family says
-            long long q = 1;
+            long long q = 0;
             const long long r = a.card[v], lo = a.offsets[v] - base, hi = a.offsets[v + 1] - base;
-            bool ok = !(a.parents[v] & ~below_n) && r >= 1 && r <= 16 && lo >= 0 && hi <= a.n_cells;
-            for (uint64_t pm = a.parents[v] & below_n & ~(1ull << v); pm && ok; pm &= pm - 1ull) {
-                q *= a.card[hc_ctz64(pm)];
-                ok = q * r <= a.n_cells;
-            }
+            const bool ok = r >= 1 && r <= 16 && lo >= 0 && hi <= a.n_cells &&
+                            bn_family_layout<false>(a.parents[v] & ~(1ull << v), n, a.card, r, a.n_cells, nullptr, nullptr, &q) >= 0;
             if (!ok || hi - lo != q * r) state = 16;
         }
         if (!state && a.offsets[n] - base != a.n_cells) state = 16;
@@ -191,9 +155,7 @@ __global__ __launch_bounds__(256) void k_bn_sample(BnSampleArgs a) {
     if (!a.header[BN_HDR_DRAWABLE]) return;                  // uniform: the prep refused the network
     if (tid < n) {
         s_order[tid] = a.header[tid];
-        s_base[tid] = (int)(a.offsets[tid] - a.offsets[0]);
-        s_card[tid] = a.card[tid];
-        s_par[tid] = a.parents[tid] & ~(1ull << tid);
+        bn_stage_var(tid, tid, a.offsets, a.card, a.parents, s_base, s_card, s_par);
     }
     const uint32_t* thr = a.thr;
     if (STAGED) {
@@ -206,36 +168,21 @@ __global__ __launch_bounds__(256) void k_bn_sample(BnSampleArgs a) {
     if (row >= a.rows) return;
     const uint32_t g = a.row_offset + (uint32_t)row;
     const uint32_t key = dvs_site_key(a.seed_lo, a.seed_hi, DVS_SITE_BN_SAMPLE, g);
-    uint64_t w0 = 0ull, w1 = 0ull, w2 = 0ull;
+    BnRow x = {0ull, 0ull, 0ull};
     for (int i = 0; i < n; ++i) {
         const int v = s_order[i], r = s_card[v];
-        int cfg = 0, stride = 1;
-        for (uint64_t pm = s_par[v]; pm; pm &= pm - 1ull) {
-            const int p = hc_ctz64(pm);
-            const uint64_t w = p < 16 ? w0 : p < 32 ? w1 : w2;
-            cfg += (int)((w >> (4 * (p & 15))) & 15ull) * stride;
-            stride *= s_card[p];
-        }
+        const int cfg = bn_row_config(x, s_par[v], s_card);
         const uint32_t* T = thr + s_base[v] + cfg * r;
         const uint32_t h = dvs_draw(key, (uint32_t)v) >> 1;
-        uint64_t level = 0ull;
-        for (int k = 0; k < r - 1; ++k) level += h >= T[k] ? 1ull : 0ull;
-        level <<= 4 * (v & 15);
-        if (v < 16) w0 |= level;
-        else if (v < 32) w1 |= level;
-        else w2 |= level;
+        x = bn_row_with(x, v, bn_draw_level(T, r, h));
     }
-    uint64_t* out = a.out + (size_t)row * a.words;
-    out[0] = w0;
-    if (a.words > 1) out[1] = w1;
-    if (a.words > 2) out[2] = w2;
+    bn_row_store(a.out + (size_t)row * a.words, x, a.words);
 }
 
 void dvs_launch_bn_sample(const BnSampleArgs& in, uint64_t seed, dvs_stream_t st) {
     BnSampleArgs a = in;
     a.words = bic_words(a.n);
-    a.seed_lo = (uint32_t)(seed & 0xffffffffull);
-    a.seed_hi = (uint32_t)(seed >> 32);
+    dvs_seed_split(a, seed);
     DVS_LAUNCH(k_bn_sample_prep, dim3(1), dim3(256), 0, st, a);
     const unsigned grid = (unsigned)((a.rows + 255) / 256);
     if (a.n_cells <= DVS_BN_SAMPLE_LDS_CELLS) {
@@ -255,9 +202,8 @@ __global__ __launch_bounds__(256) void k_bn_loglik_prep(BnLoglikArgs a) {
     const size_t fam = blockIdx.x;
     const long long base = a.offsets[0], lo = a.offsets[fam] - base, hi = a.offsets[fam + 1] - base;
     if (tid == 0) {
-        int ids[48], strides[48];
         long long q = 0;
-        const int np = bn_family_layout(a.parents[fam], v, a.n, a.card, 0x7fffffffLL, ids, strides, &q);
+        const int np = bn_family_layout<false>(a.parents[fam] & ~(1ull << v), a.n, a.card, a.card[v], 0x7fffffffLL, nullptr, nullptr, &q);
         const bool ok = np >= 0 && a.card[v] >= 1 && lo >= 0 && hi - lo == q * a.card[v] && hi <= a.log_cells;
         s_cells = ok ? hi - lo : -1;
         a.fam_ok[fam] = ok ? 1 : 0;
@@ -279,46 +225,31 @@ __global__ __launch_bounds__(256) void k_bn_loglik_rows(BnLoglikArgs a) {
     __syncthreads();
     if (tid < n) {
         const size_t fam = (size_t)b * n + tid;
-        s_base[tid] = (int)(a.offsets[fam] - a.offsets[0]);
-        s_card[tid] = a.card[tid];
-        s_par[tid] = a.parents[fam] & ~(1ull << tid);
+        bn_stage_var(tid, fam, a.offsets, a.card, a.parents, s_base, s_card, s_par);
         if (!a.fam_ok[fam]) s_ok = 0;
     }
     __syncthreads();
     const long long row = (long long)chunk * 256 + tid;
     double term = 0.0;
     if (row < a.rows) {
-        const uint64_t* src = a.data + (size_t)row * a.words;
-        const uint64_t w0 = src[0], w1 = a.words > 1 ? src[1] : 0ull, w2 = a.words > 2 ? src[2] : 0ull;
+        const BnRow x = bn_row_load(a.data + (size_t)row * a.words, a.words);
         bool ok = s_ok != 0;
-        for (int v = 0; v < n; ++v) {
-            const uint64_t w = v < 16 ? w0 : v < 32 ? w1 : w2;
-            if ((int)((w >> (4 * (v & 15))) & 15ull) >= s_card[v]) ok = false;
-        }
+        for (int v = 0; v < n; ++v)
+            if (bn_level(x, v) >= s_card[v]) ok = false;
         if (!ok) {
             if (s_ok) atomicOr(a.status, 16);                // a level code >= card; a refused family has said so already
             term = bn_nan();
         } else {
             for (int v = 0; v < n; ++v) {
-                int cfg = 0, stride = 1;
-                for (uint64_t pm = s_par[v]; pm; pm &= pm - 1ull) {
-                    const int p = hc_ctz64(pm);
-                    const uint64_t w = p < 16 ? w0 : p < 32 ? w1 : w2;
-                    cfg += (int)((w >> (4 * (p & 15))) & 15ull) * stride;
-                    stride *= s_card[p];
-                }
-                const uint64_t w = v < 16 ? w0 : v < 32 ? w1 : w2;
-                term += a.logs[s_base[v] + cfg * (int)s_card[v] + (int)((w >> (4 * (v & 15))) & 15ull)];
+                const int cfg = bn_row_config(x, s_par[v], s_card);
+                term += a.logs[s_base[v] + cfg * (int)s_card[v] + bn_level(x, v)];
             }
         }
         if (a.per_row) a.per_row[(size_t)b * a.rows + row] = term;
     }
     red[tid] = term;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
+    dvs_block_sum256(tid, red);
     if (tid == 0) a.partials[(size_t)b * a.chunks + chunk] = red[0];
 }
 
@@ -330,10 +261,7 @@ __global__ __launch_bounds__(256) void k_bn_loglik_sum(BnLoglikArgs a) {
     for (int c = tid; c < a.chunks; c += 256) s += p[c];
     red[tid] = s;
     __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] += red[tid + k];
-        __syncthreads();
-    }
+    dvs_block_sum256(tid, red);
     if (tid == 0) a.out[blockIdx.x] = red[0];
 }
 

@@ -1,14 +1,22 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor (k_bic.hip
-// with dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_exact.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device
-// code: the kernel files and the C-ABI layer (dvs_api_search.inc) both include it.  An entry point validates and fills the
+// with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_infer.h /
+// dvs_exact.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
 #pragma once
 #include "dvs_kernels.h"
 
 struct DvsDecodeState;           // dvs_decode.h
+
+// the seed_lo / seed_hi of an argument block (marked "launcher" below): the halves dvs_site_key takes
+template <class Args>
+inline void dvs_seed_split(Args& a, uint64_t seed) {
+    a.seed_lo = (uint32_t)(seed & 0xffffffffull);
+    a.seed_hi = (uint32_t)(seed >> 32);
+}
 
 // ---- reconstruction matching (dvs_match.h) ---------------------------------------------------------------------------
 struct MatchArgs {

@@ -1,10 +1,10 @@
 // Bootstrap arc strengths and the averaged network, next to the scorer and the searches they batch.  Included
 // by k_bic.hip after dvs_exact.h.  Semantics: include/dvs.h.
 //
-//   k_bic_local_rows<FAMILY>   k_bic_local / k_bn_toggle with a row set per structure: the workgroup resolves
-//   k_bn_toggle_rows<FAMILY>   rows + set_of[dag] * set_size once and hands it to bn_family_score<FAMILY, true>, whose two row
-//                              loads go through it.  Everything else is the plain kernels' code, so a structure's cells are the
-//                              bytes the plain entry point writes on the gathered data set.
+//   k_bic_local_rows<FAMILY>   k_bic_local / k_bn_toggle with a row set per structure: the plain kernels' bodies (bic_local_cell,
+//   k_bn_toggle_rows<FAMILY>   bn_toggle_cell) with ROWS, where the workgroup resolves rows + set_of[dag] * set_size once and
+//                              hands it to bn_family_score<FAMILY, true>, whose two row loads go through it.  So a structure's
+//                              cells are the bytes the plain entry point writes on the gathered data set.
 //   k_bootstrap_rows           one thread per drawn index: a function of (seed, global set index, position) only.
 //   k_arc_strength             one wave per 64 structures, lane = structure.  For every variable v the lane loads its row v
 //                              and a ballot per u turns the wave's 64 rows into the bit matrix M[v][u] (bit l: structure l has
@@ -17,81 +17,28 @@
 //                              before it: a total order, so no ties); the insertion is serial over the ranks with lane =
 //                              variable and the lane's ancestors in one u64, as k_hc_step keeps them.
 #pragma once
-#include "dvs_search_args.h"
-
-__device__ __forceinline__ const int* rs_rows(const RowSetArgs& r, int dag) {
-    const int set = r.set_of != nullptr ? r.set_of[dag] : dag;
-    return r.rows + (size_t)set * (size_t)r.set_size;
-}
+#include "dvs_hillclimb.h"
 
 template <int FAMILY>
 __global__ __launch_bounds__(256) void k_bic_local_rows(BicRowsArgs a) {
-    DVS_DYN_LDS(smem);
-    const int v = blockIdx.x % a.s.n, dag = blockIdx.x / a.s.n;
-    const size_t cell = (size_t)dag * a.s.n + v;
-    const double score = bn_family_score<FAMILY, true>(a.s, v, a.s.parents + cell, 0ull, smem, rs_rows(a.r, dag));
-    if (threadIdx.x == 0) a.s.local[cell] = score;
+    bic_local_cell<FAMILY, true>(a.s, &a.r);
 }
-
-// k_bn_toggle (dvs_hillclimb.h), row for row
 template <int FAMILY>
 __global__ __launch_bounds__(256) void k_bn_toggle_rows(ToggleRowsArgs a) {
-    DVS_DYN_LDS(smem);
-    const ToggleArgs& t = a.t;
-    const int n = t.s.n;
-    const int u = blockIdx.x % n, row = blockIdx.x / n;
-    int dag, v;
-    if (t.worklist != nullptr) {
-        v = t.worklist[row];
-        dag = row >> 1;
-        if (v < 0 || v >= n || u == v) return;
-    } else {
-        v = row % n;
-        dag = row / n;
-    }
-    const size_t cell = (size_t)dag * n + v;
-    const double score =
-        bn_family_score<FAMILY, true>(t.s, v, t.s.parents + cell, u == v ? 0ull : 1ull << u, smem, rs_rows(a.r, dag));
-    if (threadIdx.x == 0) {
-        if (u == v) {
-            t.s.local[cell] = score;
-            t.toggles[cell * n + u] = __longlong_as_double(0x7ff8000000000000LL);
-        } else {
-            t.toggles[cell * n + u] = score;
-        }
-    }
+    bn_toggle_cell<FAMILY, true>(a.t, &a.r);
 }
-
-__global__ __launch_bounds__(256) void k_bic_sum(BicArgs a);       // k_bic.hip, below the includes
 
 void dvs_launch_bic_rows(const BicRowsArgs& in, dvs_stream_t st) {
     BicRowsArgs a = in;
     a.s.words = bic_words(a.s.n);
-    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    const dim3 grid((unsigned)a.s.B * a.s.n);
-    if (a.s.type <= DVS_SCORE_BIC) {
-        DVS_SET_LDS(k_bic_local_rows<0>, lds);
-        DVS_LAUNCH_AS("k_bic_local_rows", k_bic_local_rows<0>, grid, dim3(256), lds, st, a);
-    } else {
-        DVS_SET_LDS(k_bic_local_rows<1>, lds);
-        DVS_LAUNCH_AS("k_bn_local_rows_dirichlet", k_bic_local_rows<1>, grid, dim3(256), lds, st, a);
-    }
+    BN_LAUNCH_FAMILY(a.s.type, k_bic_local_rows, "k_bic_local_rows", "k_bn_local_rows_dirichlet", dim3((unsigned)a.s.B * a.s.n), st, a);
     DVS_LAUNCH(k_bic_sum, dim3((a.s.B + 255) / 256), dim3(256), 0, st, a.s);
 }
 
 void dvs_launch_bn_toggle_rows(const ToggleRowsArgs& in, dvs_stream_t st) {
     ToggleRowsArgs a = in;
     a.t.s.words = bic_words(a.t.s.n);
-    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    const unsigned rows = a.t.worklist != nullptr ? 2u * (unsigned)a.t.s.B : (unsigned)a.t.s.B * (unsigned)a.t.s.n;
-    const dim3 grid(rows * (unsigned)a.t.s.n);
-    if (a.t.s.type <= DVS_SCORE_BIC) {
-        DVS_SET_LDS(k_bn_toggle_rows<0>, lds);
-        DVS_LAUNCH_AS("k_bn_toggle_rows", k_bn_toggle_rows<0>, grid, dim3(256), lds, st, a);
-    } else {
-        DVS_SET_LDS(k_bn_toggle_rows<1>, lds);
-        DVS_LAUNCH_AS("k_bn_toggle_rows_dirichlet", k_bn_toggle_rows<1>, grid, dim3(256), lds, st, a);
-    }
+    BN_LAUNCH_FAMILY(a.t.s.type, k_bn_toggle_rows, "k_bn_toggle_rows", "k_bn_toggle_rows_dirichlet", bn_toggle_grid(a.t), st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -107,8 +54,7 @@ __global__ __launch_bounds__(256) void k_bootstrap_rows(BootRowsArgs a) {
 
 void dvs_launch_bootstrap_rows(const BootRowsArgs& in, uint64_t seed, dvs_stream_t st) {
     BootRowsArgs a = in;
-    a.seed_lo = (uint32_t)(seed & 0xffffffffull);
-    a.seed_hi = (uint32_t)(seed >> 32);
+    dvs_seed_split(a, seed);
     const size_t total = (size_t)a.n_sets * (size_t)a.set_size;
     DVS_LAUNCH(k_bootstrap_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
 }
@@ -158,24 +104,6 @@ void dvs_launch_arc_strength(const ArcStrengthArgs& a, dvs_stream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 constexpr int AVG_MAX_PAIRS = 48 * 47 / 2;
 
-__device__ __forceinline__ int avg_wave_max(int x, int lane) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const int o = __shfl(x, lane ^ s);
-        x = o > x ? o : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int avg_wave_min(int x, int lane) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const int o = __shfl(x, lane ^ s);
-        x = o < x ? o : x;
-    }
-    return x;
-}
-
 __global__ __launch_bounds__(64) void k_averaged_network(AvgNetArgs a) {
     __shared__ int s_A[AVG_MAX_PAIRS], s_code[AVG_MAX_PAIRS], s_order[AVG_MAX_PAIRS];
     __shared__ uint32_t s_gap[AVG_MAX_PAIRS];                // |D - D'|
@@ -206,8 +134,8 @@ __global__ __launch_bounds__(64) void k_averaged_network(AvgNetArgs a) {
             least = A < least ? A : least;
         }
         const bool have = __ballot(some) != 0ull;
-        below = avg_wave_max(below, lane);
-        least = avg_wave_min(least, lane);
+        below = dvs_wave_max(below, lane);
+        least = dvs_wave_min(least, lane);
         min_any = (P == 0 ? 0 : (have ? below : least)) + 1;
     }
     // rank of every significant pair: A descending, |D - D'| descending, u n + v ascending
@@ -226,9 +154,7 @@ __global__ __launch_bounds__(64) void k_averaged_network(AvgNetArgs a) {
         }
         s_order[rank] = p;
     }
-    int n_sig = n_sig_lane;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) n_sig += __shfl(n_sig, lane ^ s);
+    const int n_sig = dvs_wave_sum(n_sig_lane, lane);
     dvs_wave_sync();
     uint64_t row = 0ull, reach = 0ull;                       // lane = variable: its parents, its ancestors
     int placed = 0, dropped = 0, ties = 0;
@@ -238,14 +164,14 @@ __global__ __launch_bounds__(64) void k_averaged_network(AvgNetArgs a) {
         const int D = C[2 * (u * n + v) + 1], Dr = C[2 * (v * n + u) + 1];
         const bool tie = D == Dr;
         int t = D >= Dr ? u : v, h = D >= Dr ? v : u;        // t -> h; a tie tries u -> v first
-        uint64_t reach_t = hc_bcast64(reach, t);
+        uint64_t reach_t = dvs_bcast64(reach, t);
         bool cyc = ((reach_t >> h) & 1ull) != 0ull;          // h is an ancestor of t
         if (tie) {
             ++ties;
             if (cyc) {                                       // then v -> u cannot close a cycle: the graph is acyclic
                 t = v;
                 h = u;
-                reach_t = hc_bcast64(reach, t);
+                reach_t = dvs_bcast64(reach, t);
                 cyc = ((reach_t >> h) & 1ull) != 0ull;
             }
         }

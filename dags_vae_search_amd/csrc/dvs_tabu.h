@@ -10,9 +10,7 @@
 //   k_hc_perturb   one uniformly random legal move per structure: per-lane bit rows of the legal adds, deletes and reversals,
 //                  a shuffle prefix over lanes per op, the draw of site DVS_SITE_HC_PERTURB scaled to the count.
 #pragma once
-#include "dvs_search_args.h"
-
-__device__ __forceinline__ int hc_ctz64(uint64_t x) { return __popcll((x & (0ull - x)) - 1ull); }
+#include "dvs_hillclimb.h"
 
 __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
     const HcArgs& a = t.h;
@@ -20,18 +18,10 @@ __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
     if (b >= a.B) return;
     const int n = a.n;
     const int nsteps = a.steps[b];
-    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) {          // wave-uniform
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
     const size_t base = (size_t)b * n;
     HcLane c;
-    const int fl = hc_load(c, n, lane, a.parents, a.local, base);
-    if (fl) {
-        if (lane == 0) a.flags[b] = fl;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
+    if (a.converged[b] != 0 || a.flags[b] != 0 || nsteps >= a.step_cap) return hc_sit_out(0, lane, b, a.flags, a.worklist);
+    if (const int fl = hc_load(c, n, lane, a.parents, a.local, base)) return hc_sit_out(fl, lane, b, a.flags, a.worklist);
     const double* T = a.toggles + base * n;
     const int nn = n * n;
     // the best seen so far; on the first call the start itself, S = L[0] + L[1] + ... left to right (k_bic_sum's order)
@@ -57,9 +47,9 @@ __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
         const uint64_t rows = __ballot(diff != 0ull);
         const int k = __popcll(rows);
         if (k != 1 && k != 2) continue;
-        const int v1 = hc_ctz64(rows), v2 = k == 2 ? hc_ctz64(rows & (rows - 1ull)) : v1;
-        const uint64_t d1 = hc_bcast64(diff, v1), d2 = hc_bcast64(diff, v2);
-        const uint64_t r1 = hc_bcast64(c.row, v1), r2 = hc_bcast64(c.row, v2);
+        const int v1 = dvs_ctz64(rows), v2 = k == 2 ? dvs_ctz64(rows & (rows - 1ull)) : v1;
+        const uint64_t d1 = dvs_bcast64(diff, v1), d2 = dvs_bcast64(diff, v2);
+        const uint64_t r1 = dvs_bcast64(c.row, v1), r2 = dvs_bcast64(c.row, v2);
         if (k == 1) {
             if (__popcll(d1) != 1) continue;
             if (lane == v1) {
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
     if (lane == 0) t.visited[b] = seen + 1;
     if (bcode == HC_NO_MOVE) {
         if (lane == 0) a.converged[b] = 1;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
+        hc_sit_out(0, lane, b, a.flags, a.worklist);
     } else {
         const int op = bcode / nn, mv = (bcode % nn) / n, mu = bcode % n;
         // S' from the local scores as they will stand, in the same order
@@ -103,13 +93,7 @@ __global__ __launch_bounds__(256) void k_tabu_step(TabuArgs t) {
         if (lane == 0) {
             t.stall[b] = st;
             if (conv) a.converged[b] = 1;
-            a.steps[b] = nsteps + 1;
-            if (a.trace != nullptr) {
-                int64_t* tr = a.trace + ((size_t)b * a.step_cap + nsteps) * 2;
-                tr[0] = bcode;
-                tr[1] = (int64_t)__double_as_longlong(best);
-            }
-            atomicAdd(a.active, 1);
+            hc_record(a, b, nsteps, bcode, best);
         }
     }
     if (write_best) {
@@ -139,18 +123,10 @@ __global__ __launch_bounds__(256) void k_hc_perturb(PerturbArgs a) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= a.B) return;
     const int n = a.n;
-    if (a.flags[b] != 0) {                                                         // wave-uniform
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
     const size_t base = (size_t)b * n;
     HcLane c;
-    const int fl = hc_load(c, n, lane, a.parents, a.local, base);
-    if (fl) {
-        if (lane == 0) a.flags[b] = fl;
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
+    if (a.flags[b] != 0) return hc_sit_out(0, lane, b, a.flags, a.worklist);
+    if (const int fl = hc_load(c, n, lane, a.parents, a.local, base)) return hc_sit_out(fl, lane, b, a.flags, a.worklist);
     const double* T = a.toggles + base * n;
     uint64_t m[3] = {0ull, 0ull, 0ull};                                            // bit u: the move op on u -> lane is legal
     hc_moves(c, T, a.max_parents, a.forbidden, [&](int op, int u, double) {
@@ -166,10 +142,7 @@ __global__ __launch_bounds__(256) void k_hc_perturb(PerturbArgs a) {
         total[op] = __shfl(incl[op], 63);
     }
     const uint32_t M = (uint32_t)(total[0] + total[1] + total[2]);
-    if (M == 0u) {
-        if (lane < 2) a.worklist[2 * b + lane] = -1;
-        return;
-    }
+    if (M == 0u) return hc_sit_out(0, lane, b, a.flags, a.worklist);
     const uint32_t r = dvs_draw(dvs_site_key(a.seed_lo, a.seed_hi, DVS_SITE_HC_PERTURB, (uint32_t)b), a.draw_index);
     int k = (int)(((uint64_t)r * (uint64_t)M) >> 32);                               // < M; the bias is at most M / 2^32
     int op = 0;
@@ -187,14 +160,13 @@ __global__ __launch_bounds__(256) void k_hc_perturb(PerturbArgs a) {
     const bool owner = k >= lo && k < hi;
     uint64_t rest = mine;
     for (int j = lo; owner && j < k; ++j) rest &= rest - 1ull;                      // drop the k - lo lowest set bits
-    const int v = hc_ctz64(__ballot(owner));
-    const int u = __shfl(owner ? hc_ctz64(rest) : 0, v);
+    const int v = dvs_ctz64(__ballot(owner));
+    const int u = __shfl(owner ? dvs_ctz64(rest) : 0, v);
     hc_apply(c, op * n * n + v * n + u, a.parents, a.local, T, base, a.worklist, b);
 }
 
 void dvs_launch_hc_perturb(const PerturbArgs& in, uint64_t seed, dvs_stream_t st) {
     PerturbArgs a = in;
-    a.seed_lo = (uint32_t)(seed & 0xffffffffull);
-    a.seed_hi = (uint32_t)(seed >> 32);
+    dvs_seed_split(a, seed);
     DVS_LAUNCH(k_hc_perturb, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
 }

@@ -27,8 +27,6 @@ struct DvsRecordW {              // compact per-DAG record of the wide path (864
     uint64_t allowed[DVS_WTOK];  // bit j: token i may attend token j
 };
 
-__device__ __forceinline__ int dvs_ctz64(uint64_t v) { return __builtin_ctzll(v); }
-
 // rows of real tokens in tile `w` of an N-token DAG
 __device__ __forceinline__ int dvs_rows_of(int N, int w) {
     const int nl = N - 16 * w;

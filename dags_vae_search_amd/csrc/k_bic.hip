@@ -19,22 +19,7 @@
 // before the sum: one more pass over the table rows (dense) or over the sorted keys (sort), an integer count.  lgamma is
 // the device math library's, in fp64; its two arguments that do not depend on the cell, lgamma(a_j) and lgamma(a_jk), are
 // taken once per workgroup.  Family 1 is VALU-bound by lgamma (two per occupied cell and row) — no MFMA there either.
-#include "dvs_search_args.h"
-
-constexpr int BIC_MAX_BINS = 36864;          // q_v * r_v histogram bins that fit LDS (144 KB of u32 counters)
-
-static inline int bic_words(int n) { return (n + 15) / 16; }       // 4-bit level codes, 16 variables per 64-bit word
-
-__device__ __forceinline__ double bn_lgamma(double x) {
-#ifdef DVS_EMU
-    int sign;                    // the emulator runs workgroups on several host threads: libm's lgamma writes a global
-    return lgamma_r(x, &sign);
-#else
-    return lgamma(x);
-#endif
-}
-
-__device__ __forceinline__ int bic_level(const uint64_t* row, int var) { return (int)((row[var >> 4] >> (4 * (var & 15))) & 15ull); }
+#include "dvs_bn_common.h"
 
 constexpr int BIC_MAX_SORT = 16384;          // samples the sort path can hold in LDS (64-bit keys)
 
@@ -84,13 +69,14 @@ __device__ __forceinline__ void bn_prior(const BicArgs& a, int r, double q, cons
 //
 // bn_family_score is the whole of that for one (variable, parent set): the local score of variable v under the parent mask
 // (*pmask ^ flip) with v's own bit masked off.  Every thread of the workgroup calls it (it holds barriers); thread 0 gets
-// the score, NaN (and status bit 4) when the family is refused.  k_bic_local instantiates it with flip = 0 for the mask as
-// it stands, k_bn_toggle (dvs_hillclimb.h) with one bit flipped: the same instructions in the same order, so the two
-// kernels give equal bytes for equal parent sets.
+// the score, NaN (and status bit 4) when the family is refused.  k_bic_local calls it with flip = 0 for the mask as it
+// stands, k_bn_toggle (dvs_hillclimb.h) with one bit flipped: one function, so the two kernels give equal bytes for equal
+// parent sets.  It walks the mask itself instead of calling bn_family_layout: the same walk lays out the sort keys and
+// keeps q (as a double) past the dense limit, where the shared routine stops.
 //
-// ROWS (dvs_strength.h: k_bic_local_rows, k_bn_toggle_rows): sample s of the workgroup's data set is row rows[s] of a.data and
-// a.S is the set's size; nothing else changes, and the counts do not depend on the order of the rows, so the score is, bit
-// for bit, that of the gathered data set.  The instantiations without ROWS never read `rows`.
+// ROWS (the *_rows kernels of dvs_strength.h): sample s of the workgroup's data set is row rows[s] of a.data and a.S is the
+// set's size; nothing else changes, and the counts do not depend on the order of the rows, so the score is, bit for bit,
+// that of the gathered data set.  The instantiations without ROWS never read `rows`.
 template <int FAMILY, bool ROWS = false>
 __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v, const uint64_t* pmask, const uint64_t flip,
                                                   char* smem, const int* rows = nullptr) {
@@ -131,21 +117,14 @@ __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v,
     const int np = s_np, mode = s_mode;
     if (mode < 0) {
         if (threadIdx.x == 0) atomicOr(a.status, 16);
-        return __longlong_as_double(0x7ff8000000000000LL);
+        return bn_nan();
     }
     double acc = 0.0;
     if (mode == 0) {
         unsigned* hist = (unsigned*)smem;
         const int q = (int)s_q, bins = q * r;
-        for (int i = threadIdx.x; i < bins; i += blockDim.x) hist[i] = 0u;
-        __syncthreads();
-        for (int s = threadIdx.x; s < a.S; s += blockDim.x) {
-            const uint64_t* row = a.data + (size_t)(ROWS ? rows[s] : s) * a.words;
-            int key = 0;
-            for (int i = 0; i < np; ++i) key += bic_level(row, par_id[i]) * par_stride[i];
-            atomicAdd(&hist[key * r + bic_level(row, v)], 1u);
-        }
-        __syncthreads();
+        bn_dense_count<ROWS, false>(hist, bins, a.data, a.words, a.S, rows, np, par_id, par_stride,
+                                    [&](const uint64_t* row, int key) { return key * r + bic_level(row, v); });
         if constexpr (FAMILY == 0) {
             for (int j = threadIdx.x; j < q; j += blockDim.x) {
                 unsigned nj = 0;
@@ -241,10 +220,7 @@ __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v,
     }
     red[threadIdx.x] = acc;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
+    dvs_block_sum256((int)threadIdx.x, red);
     double score = 0.0;
     if (threadIdx.x == 0) {
         if constexpr (FAMILY == 0) {
@@ -257,13 +233,26 @@ __device__ __forceinline__ double bn_family_score(const BicArgs& a, const int v,
     return score;
 }
 
-template <int FAMILY>
-__global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
+// k_bic_local and k_bic_local_rows (dvs_strength.h): one workgroup per (DAG, variable); r is read with ROWS only
+template <int FAMILY, bool ROWS>
+__device__ __forceinline__ void bic_local_cell(const BicArgs& a, const RowSetArgs* r) {
     DVS_DYN_LDS(smem);
     const int v = blockIdx.x % a.n, dag = blockIdx.x / a.n;
     const size_t cell = (size_t)dag * a.n + v;
-    const double score = bn_family_score<FAMILY>(a, v, a.parents + cell, 0ull, smem);
+    const double score = bn_family_score<FAMILY, ROWS>(a, v, a.parents + cell, 0ull, smem, ROWS ? rs_rows(*r, dag) : nullptr);
     if (threadIdx.x == 0) a.local[cell] = score;
+}
+template <int FAMILY>
+__global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
+    bic_local_cell<FAMILY, false>(a, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
+    const int dag = blockIdx.x * blockDim.x + threadIdx.x;
+    if (dag >= a.B) return;
+    double s = 0.0;
+    for (int v = 0; v < a.n; ++v) s += a.local[(size_t)dag * a.n + v];
+    a.out[dag] = s;
 }
 
 #include "dvs_hillclimb.h"
@@ -275,25 +264,10 @@ __global__ __launch_bounds__(256) void k_bic_local(BicArgs a) {
 #include "dvs_exact.h"
 #include "dvs_strength.h"
 
-__global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
-    const int dag = blockIdx.x * blockDim.x + threadIdx.x;
-    if (dag >= a.B) return;
-    double s = 0.0;
-    for (int v = 0; v < a.n; ++v) s += a.local[(size_t)dag * a.n + v];
-    a.out[dag] = s;
-}
-
 void dvs_launch_bic(const BicArgs& in, dvs_stream_t st) {
     BicArgs a = in;
     a.words = bic_words(a.n);
-    const size_t lds = (size_t)BIC_MAX_BINS * sizeof(unsigned);
-    if (a.type <= DVS_SCORE_BIC) {
-        DVS_SET_LDS(k_bic_local<0>, lds);
-        DVS_LAUNCH_AS("k_bic_local", k_bic_local<0>, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
-    } else {
-        DVS_SET_LDS(k_bic_local<1>, lds);
-        DVS_LAUNCH_AS("k_bn_local_dirichlet", k_bic_local<1>, dim3((unsigned)a.B * a.n), dim3(256), lds, st, a);
-    }
+    BN_LAUNCH_FAMILY(a.type, k_bic_local, "k_bic_local", "k_bn_local_dirichlet", dim3((unsigned)a.B * a.n), st, a);
     DVS_LAUNCH(k_bic_sum, dim3((a.B + 255) / 256), dim3(256), 0, st, a);
 }
 
@@ -321,15 +295,7 @@ __global__ __launch_bounds__(256) void k_gp_predict(GpArgs a) {
         }
         acc += a.alpha[m] * exp(-(double)d2 * a.inv2l2);
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        // 64-bit shuffle as two 32-bit halves
-        long long bits = __double_as_longlong(acc);
-        int lo = (int)(bits & 0xffffffffLL), hi = (int)(bits >> 32);
-        lo = __shfl_xor(lo, s);
-        hi = __shfl_xor(hi, s);
-        acc += __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-    }
+    acc = dvs_wave_sum(acc, lane);
     if (lane == 0) a.out[q] = a.constant + a.outputscale * acc;
 }
 
@@ -365,17 +331,6 @@ __global__ __launch_bounds__(256) void k_gp_kernel(GpKernArgs a) {
     }
     a.K[i] = a.outputscale * exp(-d2 * a.inv2l2);
 }
-__device__ __forceinline__ double dvs_wave_sum_f64(double v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const long long bits = __double_as_longlong(v);
-        int lo = (int)(bits & 0xffffffffLL), hi = (int)(bits >> 32);
-        lo = __shfl_xor(lo, s);
-        hi = __shfl_xor(hi, s);
-        v += __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-    }
-    return v;
-}
 __global__ __launch_bounds__(256) void k_gp_kernel_bwd(GpKernArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ra = blockIdx.x * 4 + wave;
@@ -407,11 +362,11 @@ __global__ __launch_bounds__(256) void k_gp_kernel_bwd(GpKernArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < DVS_GP_MAXD; ++k) {
-        const double s = dvs_wave_sum_f64(acc[k]);
+        const double s = dvs_wave_sum(acc[k], lane);
         if (lane == 0 && k < a.D) a.dxa[(size_t)ra * a.D + k] = s * a.inv_l2;
     }
-    sl = dvs_wave_sum_f64(sl);
-    so = dvs_wave_sum_f64(so);
+    sl = dvs_wave_sum(sl, lane);
+    so = dvs_wave_sum(so, lane);
     if (lane == 0) {
         a.rows[2 * (size_t)ra] = sl * a.inv_l3;
         a.rows[2 * (size_t)ra + 1] = so * a.inv_o;

@@ -45,14 +45,6 @@ static_assert(GPA_VGPR_ARRAYS + 32 <= GPA_VGPR_BUDGET, "accumulators + B fragmen
 static_assert(GPA_MAXD <= 2 * 16, "gradient: one wave per 16 dimensions, at most 2 slices");
 static_assert(GPA_MAXD / 16 <= GPA_WAVES, "gradient slices need a wave each");
 
-__device__ __forceinline__ double gpa_shfl_xor(double v, int s) {
-    const long long bits = __double_as_longlong(v);
-    int lo = (int)(bits & 0xffffffffLL), hi = (int)(bits >> 32);
-    lo = __shfl_xor(lo, s);
-    hi = __shfl_xor(hi, s);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 __global__ __launch_bounds__(GPA_THREADS, 2) void k_gp_acquire(GpAcqArgs a) {
     extern __shared__ double gpa_lds[];
     double* Kt = gpa_lds;                                   // [Mp][16]
@@ -137,8 +129,8 @@ __global__ __launch_bounds__(GPA_THREADS, 2) void k_gp_acquire(GpAcqArgs a) {
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int s = 1; s < 16; s <<= 1) {
-            qp[r] += gpa_shfl_xor(qp[r], s);
-            lp[r] += gpa_shfl_xor(lp[r], s);
+            qp[r] += dvs_shfl_xor(qp[r], lane, s);
+            lp[r] += dvs_shfl_xor(lp[r], lane, s);
         }
         if (qc == 0) {
             red[wave * GPA_Q + kr + 4 * r] = qp[r];

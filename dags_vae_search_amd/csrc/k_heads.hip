@@ -184,13 +184,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs a) {
     s0[threadIdx.x] = r;
     s1[threadIdx.x] = k;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            s0[threadIdx.x] += s0[threadIdx.x + s];
-            s1[threadIdx.x] += s1[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    dvs_block_sum256((int)threadIdx.x, s0, s1);
     if (threadIdx.x == 0) {
         const float recon = s0[0], kld = s1[0];
         const float total = recon + a.beta * kld;

@@ -17,7 +17,8 @@ mkdir -p "$tmp/a" "$tmp/b"
     "${HIPCC:-/opt/rocm/bin/hipcc} $flags '$tmp/old/dags_vae_search_amd/csrc/{}' -o '$tmp/a/{}.s' 2>/dev/null || true
      ${HIPCC:-/opt/rocm/bin/hipcc} $flags '$root/dags_vae_search_amd/csrc/{}' -o '$tmp/b/{}.s'"
 # one file per kernel symbol: <sym>.isa = instruction text from the symbol's label to its end label (comments dropped),
-# <sym>.res = its .amdhsa_* descriptor lines and the resource lines of its metadata entry
+# <sym>.res = its .amdhsa_* descriptor lines and the resource lines of its metadata entry.  Block labels lose the
+# function's ordinal in the file (.LBB12_3 -> .LBB_3), so moving a kernel within its file changes nothing
 split() {
     awk -v out="$2" '
         function flush(   i) { if (mname != "") for (i = 0; i < nm; ++i) print mline[i] >> (out "/" mname ".res"); nm = 0; mname = "" }
@@ -28,7 +29,7 @@ split() {
         /^\t\.end_amdhsa_kernel/ { kd = ""; next }
         kd != "" { print > (out "/" kd ".res"); next }
         /^\t\.section/ { code = 0 }
-        code { sub(/[ \t]*;.*/, ""); if ($0 != "") print > (out "/" sym ".isa") }
+        code { sub(/[ \t]*;.*/, ""); gsub(/\.LBB[0-9]+_/, ".LBB_"); if ($0 != "") print > (out "/" sym ".isa") }
         /^  - \./ { flush() }
         /^    \.name:/ { mname = $2 }
         /^(  - |    )\.(agpr_count|vgpr_count|sgpr_count|sgpr_spill_count|vgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):/ { sub(/^  - /, "    "); mline[nm++] = $0 }
