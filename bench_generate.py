@@ -38,7 +38,7 @@ def main():
     args = ap.parse_args()
     from dags_vae_search_amd import _lib as dl
     from dags_vae_search_amd import create_encoder_dataset, encoder_dag_train_schema, generate_dags
-    from dags_vae_search_amd.engine import _nbytes, _ptr, _stream
+    from dags_vae_search_amd._lib import nbytes, ptr, stream
     from dags_vae_search_amd.generate import draw_edge_counts
     from dags_vae_search_amd.synthetic import synthetic_dags
     dev = "cuda:0"
@@ -61,8 +61,8 @@ def main():
         groups = {}
         for k in range(0, 8):
             def call():
-                dl.check(lib, lib.dvs_generate_dags(B, n, card, 1 if wide else 0, _ptr(edges), 1, 0, 100, k << dl.GEN_GROUP_SHIFT,
-                                                    _ptr(labels), _ptr(preds), _nbytes(preds), _ptr(attempts), _stream()), what)
+                dl.check(lib, lib.dvs_generate_dags(B, n, card, 1 if wide else 0, ptr(edges), 1, 0, 100, k << dl.GEN_GROUP_SHIFT,
+                                                    ptr(labels), ptr(preds), nbytes(preds), ptr(attempts), stream()), what)
             groups["auto" if k == 0 else str(1 << (k - 1))] = timed(call, args.reps) * 1e3
         row["kernel_ms_by_lanes_per_dag"] = groups
         rows.append(row)

@@ -51,7 +51,7 @@ def main():
         net = pm.Network(name, card, masks[0], [fitted.table(v).cpu().numpy() for v in range(n)])
         base = {"name": name, "n": n, "cells": int(fitted.cpt.numel())}
         target = n - 1
-        one = ev._data[:1].contiguous()
+        one = ev.packed[:1].contiguous()
         none = torch.zeros(1, dtype=torch.int64, device="cuda")
         some = torch.tensor([1 | (1 << (n // 2))], dtype=torch.int64, device="cuda")      # two observed variables
 

@@ -66,7 +66,7 @@ def per_replicate(ev, name, metric, replicates, seed, **args):
     rows = bootstrap_rows(replicates, ev.n_samples, ev.n_samples, seed=seed)
     nets = []
     for r in range(replicates):
-        one = BNLearnWrapper.from_packed(name, metric, ev._data[rows[r].long()], ev._card_host, iss=ev.iss)
+        one = BNLearnWrapper.from_packed(name, metric, ev.packed[rows[r].long()], ev.card_host, iss=ev.iss)
         nets.append(hill_climb(one, batch=1, **args).parents)
     return arc_strength(torch.cat(nets))
 

@@ -10,6 +10,9 @@ import os
 from ctypes import (POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32,
                     c_uint64, c_void_p)
 
+import numpy as np
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libdvs_hip.so"
 
@@ -28,6 +31,11 @@ CI_TYPES = {"mi": 0, "x2": 1, "mi-adf": 2, "x2-adf": 3}   # dvs_ci_type, by bnle
 CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
 FIT_METHODS = {"mle": 0, "bayes": 1}   # dvs_fit_method, by bnlearn's name
 FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
+# bits of the BN entry points' status word (device int32, zeroed by the caller), as include/dvs.h defines them
+STATUS_CYCLE = 1              # bit 0 (dvs_bn_sample, dvs_bn_lw): the structure has a cycle
+STATUS_REFUSED = 16           # bit 4: a family, test, row or query was refused (NaN in its cells alone); worded per call site
+STATUS_LABELS = 32            # bit 5 (dvs_bic_parent_masks): a DAG's labels are not a permutation of 0..n_vars-1
+STATUS_NOT_PROBABILITY = 64   # bit 6 (dvs_bn_sample, dvs_bn_lw): a table row is not a probability vector
 LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
 SCORE_TYPES = {"loglik": 0, "aic": 1, "bic": 2, "bde": 3, "bds": 4, "k2": 5, "bdj": 6}   # dvs_score_type, by bnlearn's name
 
@@ -298,17 +306,103 @@ def check(lib, code: int, what: str):
         raise RuntimeError(f"{what} failed with code {code}: {msg.decode() if msg else ''}")
 
 
+# ---- the device-call layer: how every module of this package hands tensors, the stream and seeds to the library, and the
+# refusals several entry points share.  A new module takes these from here instead of restating them.
+def ptr(t, offset: int = 0):
+    """a tensor's device address (plus ``offset`` bytes) as a pointer argument; None (a nullable argument left out) stays NULL"""
+    return None if t is None else c_void_p(t.data_ptr() + offset)
+
+
+def nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def stream():
+    return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def seed64(seed) -> int:
+    """any Python int as the c_uint64 seed argument: its low 64 bits"""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def need_cuda(what, device):
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {device}); this package has no CPU path")
+
+
+def require_cuda(t, what: str):
+    if not t.is_cuda:
+        raise RuntimeError(f"dags_vae_search_amd: {what} must live on the GPU (got device {t.device}); "
+                           f"this package has no CPU path")
+
+
+def workspace_bytes(lib, name: str, *args) -> int:
+    """a ``*_bytes`` size query; 0 is its refusal, raised with the library's last error"""
+    n = int(getattr(lib, name)(*args))
+    if n == 0:
+        check(lib, 1, name)
+    return n
+
+
+def level_counts(card):
+    """n level counts as a list of ints"""
+    card = [int(c) for c in card]
+    if not 1 <= len(card) <= MAX_TOKENS or any(not 1 <= c <= 16 for c in card):
+        raise ValueError("card must hold 1..48 level counts in 1..16")
+    return card
+
+
+def packed_rows(what, data, n):
+    """``data``: an evaluator over n variables (bic.py) or packed int64 rows [S >= 1, ceil(n / 16)] -> the rows, contiguous"""
+    if not torch.is_tensor(data) and hasattr(data, "packed"):
+        if data.n_vars != n:
+            raise ValueError(f"{what}: the evaluator has {data.n_vars} variables, the network {n}")
+        data = data.packed
+    if not torch.is_tensor(data) or data.dtype != torch.int64 or data.ndim != 2 or data.shape[1] != (n + 15) // 16 or data.shape[0] < 1:
+        raise ValueError(f"{what}: data must be an evaluator or packed int64 rows [S >= 1, {(n + 15) // 16}]")
+    need_cuda(what, data.device)
+    return data.contiguous()
+
+
+def parent_masks(what, name, t, n=None):
+    """a batch of parent masks (or PDAG rows) on the device: int64 [B >= 1, n <= 48], contiguous"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: {name} must be a torch tensor of parent masks")
+    need_cuda(what, t.device)
+    if t.dtype != torch.int64 or t.ndim != 2 or t.shape[0] < 1 or not 1 <= t.shape[1] <= MAX_TOKENS or (n is not None and t.shape[1] != n):
+        raise ValueError(f"{what}: {name} must be int64 [B >= 1, {n if n is not None else 'n <= 48'}] parent masks")
+    return t.contiguous()
+
+
+def forbidden_rows(forbidden, n, device):
+    """``forbidden`` (None, a tensor, or anything numpy reads as n unsigned 64-bit rows) -> None or int64 [n] on the device"""
+    if forbidden is None:
+        return None
+    if not torch.is_tensor(forbidden):
+        forbidden = torch.as_tensor(np.asarray(forbidden).astype(np.uint64).view(np.int64))
+    forb = forbidden.to(device=device, dtype=torch.int64).contiguous()
+    if forb.shape != (n,):
+        raise ValueError(f"forbidden must be [{n}] bit rows")
+    return forb
+
+
+def check_network_status(what, st: int):
+    """the refusals dvs_bn_sample and dvs_bn_lw share: a cycle, a table row that is not a probability vector"""
+    if st & STATUS_CYCLE:
+        raise ValueError(f"{what}: the structure has a cycle")
+    if st & STATUS_NOT_PROBABILITY:
+        raise ValueError(f"{what}: a table row is not a probability vector (a NaN or negative cell, or a sum further than 1e-9 from 1)")
+
+
 def make_shape(batch: int, n_tokens: int, n_classes: int, training: bool = False, dropout: float = 0.15,
                beta: float = 0.005, eps_scale: float = 0.01, dag_offset: int = 0, seed: int = 0) -> DvsShape:
     return DvsShape(int(batch), int(n_tokens), int(n_classes), 1 if training else 0, float(dropout), float(beta),
-                    float(eps_scale), int(dag_offset) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF)
+                    float(eps_scale), int(dag_offset) & 0xFFFFFFFF, seed64(seed))
 
 
 def record_bytes(lib, shape: DvsShape) -> int:
-    n = int(lib.dvs_record_bytes(ctypes.byref(shape)))
-    if n == 0:
-        check(lib, 1, "dvs_record_bytes")
-    return n
+    return workspace_bytes(lib, "dvs_record_bytes", ctypes.byref(shape))
 
 
 def is_wide(n_tokens: int, n_classes: int) -> bool:

@@ -14,7 +14,6 @@ maximised, as the search (search.py) and the predictor data (predictor_data.py) 
 from __future__ import annotations
 
 import csv
-import ctypes
 import math
 from typing import List, Sequence
 
@@ -41,11 +40,104 @@ PENALISED_SCORES = ("aic", "bic")        # take k
 DIRICHLET_SCORES = ("bde", "bds")        # take iss
 
 
-class BNLearnWrapper:
+class _Scorer:
+    """The scorer launches of both evaluators.  ``_source(B)`` names the evaluator that holds the data set and the
+    arguments that follow ``status``: none (dvs_bic_scores / dvs_bn_scores, dvs_bn_toggle_scores) or the row sets of the
+    ``_rows`` entry points, which take the same arguments up to there (include/dvs.h)."""
+
+    def launch_scores(self, parents, scratch, out, status):
+        """The scorer on the caller's buffers, unchecked: ``parents`` int64 [B, n_vars] contiguous on the device ->
+        ``scratch`` f64 [B, n_vars] (the local scores), ``out`` f64 [B], ``status`` int32 [1] (bit 4: a family was refused).
+        The default-penalty bic of a plain evaluator is dvs_bic_scores; everything else dvs_bn_scores."""
+        base, row_args = self._source(parents.shape[0])
+        p = dl.ptr
+        head = (parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(base.card), p(parents))
+        tail = (p(scratch), p(out), p(status), *row_args, dl.stream())
+        if self.metric_name == "bic" and self.k is None and not row_args:
+            name = "dvs_bic_scores"
+        else:
+            name = "dvs_bn_scores_rows" if row_args else "dvs_bn_scores"
+            head += (dl.SCORE_TYPES[self.metric_name], base.score_arg)
+        dl.check(self.lib, getattr(self.lib, name)(*head, *tail), name)
+
+    def score_masks(self, parents: torch.Tensor, local: bool = False):
+        """parents: int64 [B, n_vars] bit rows in data-set variable indices (bit u of [b, v] <=> u -> v); -> f64 [B], or
+        with ``local`` (scores f64 [B], per-variable local scores f64 [B, n_vars])."""
+        parents = parents.to(self.device).contiguous()
+        B = parents.shape[0]
+        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.launch_scores(parents, scratch, out, status)
+        if int(status.item()) & dl.STATUS_REFUSED:
+            raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
+                             "cells; sorted samples: 16 384 samples, 63 key bits)")
+        return (out, scratch) if local else out
+
+    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
+        """The single-edge neighbourhood of every structure (dvs_bn_toggle_scores, DESIGN.md §14) -> (L f64 [B, n_vars],
+        T f64 [B, n_vars, n_vars]) on the device: L the local scores as ``score_masks(local=True)`` gives them, T[b, v, u]
+        the local score of v with bit u of ``parents[b, v]`` flipped (NaN on the diagonal and where the family is refused:
+        that move is not available).  ``worklist`` (int32 [2 B], ``hill_climb``'s) with ``out=(L, T)`` recomputes only
+        the rows it names, in place.  ``return_status`` appends the status word (bit 4: some family was refused)."""
+        parents = parents.to(self.device).contiguous()
+        B, n = parents.shape
+        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
+        base, row_args = self._source(B)
+        if out is None:
+            if worklist is not None:
+                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
+            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
+                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
+        L, T = out
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = dl.ptr
+        name = "dvs_bn_toggle_scores_rows" if row_args else "dvs_bn_toggle_scores"
+        dl.check(self.lib, getattr(self.lib, name)(
+            B, n, base.n_samples, p(base.packed), p(base.card), p(parents), dl.SCORE_TYPES[self.metric_name], base.score_arg,
+            p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), *row_args, dl.stream()), name)
+        return (L, T, status) if return_status else (L, T)
+
+
+class BNLearnWrapper(_Scorer):
+    """``packed`` (int64 [S, ceil(n / 16)], 4-bit level codes), ``card`` (uint8 [n]) and its host copy ``card_host`` are the
+    data set on the device; ``score_arg`` is the score type's argument as the library takes it."""
+
     def __init__(self, dataset_name: str, metric_name: str = "bic", data=None, device="cuda", *, iss=None, k=None):
         """``data``: path of a CSV with a header row of variable names, or a level-coded integer array [S, n].
         ``metric_name``: one of ``_lib.SCORE_TYPES``; ``k``: the penalty coefficient of aic (default 1) / bic (default
         log(S) / 2); ``iss``: the imaginary sample size of bde / bds (default 1)."""
+        self._set_score(dataset_name, metric_name, iss, k)
+        if data is None:
+            raise ValueError("pass data=<csv path or level-coded array>: the reference's R data sets are not bundled")
+        arr = load_discrete_csv(data)[1] if isinstance(data, str) else np.asarray(data)
+        if arr.ndim != 2 or arr.shape[1] > dl.MAX_TOKENS or arr.min() < 0 or arr.max() > 15:
+            raise ValueError("data must be [samples, n_vars <= 48] with level codes 0..15")
+        words = (arr.shape[1] + 15) // 16
+        packed = np.zeros((arr.shape[0], words), np.uint64)
+        for i in range(arr.shape[1]):
+            packed[:, i // 16] |= arr[:, i].astype(np.uint64) << np.uint64(4 * (i % 16))
+        # card_host: pc.py sizes the CI tables' LDS from it
+        device = torch.device(device)
+        self._set_data(torch.from_numpy(packed.view(np.int64)).to(device), [int(c) for c in arr.max(0) + 1], device)
+
+    @classmethod
+    def from_packed(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, card, *, iss=None, k=None):
+        """An evaluator around rows that are already packed on the device (int64 [S, ceil(n / 16)], 4-bit level codes:
+        what ``sample`` returns and ``packed`` holds), with no host round trip.  ``card`` (n level counts, 1..16) is taken as
+        given, not read off the rows: a sample may miss a level.  ``metric_name``, ``iss`` and ``k`` as in ``__init__``."""
+        self = cls.__new__(cls)
+        self._set_score(dataset_name, metric_name, iss, k)
+        card = dl.level_counts(card)
+        n = len(card)
+        if not torch.is_tensor(packed) or packed.device.type != "cuda":
+            raise RuntimeError("dags_vae_search_amd: from_packed takes rows on the GPU; this package has no CPU path")
+        if packed.dtype != torch.int64 or packed.ndim != 2 or packed.shape[0] < 1 or packed.shape[1] != (n + 15) // 16:
+            raise ValueError(f"packed must be int64 [S >= 1, {(n + 15) // 16}] for {n} variables")
+        self._set_data(packed.contiguous(), card, packed.device)
+        return self
+
+    def _set_score(self, dataset_name, metric_name, iss, k):
         if metric_name not in dl.SCORE_TYPES:
             raise NotImplementedError(f"built scores: {', '.join(sorted(dl.SCORE_TYPES))} (got {metric_name!r})")
         if iss is not None and metric_name not in DIRICHLET_SCORES:
@@ -56,58 +148,20 @@ class BNLearnWrapper:
             raise ValueError(f"iss must be finite and > 0 (got {iss!r})")
         if k is not None and not (math.isfinite(k) and k >= 0):
             raise ValueError(f"k must be finite and >= 0 (got {k!r})")
-        if data is None:
-            raise ValueError("pass data=<csv path or level-coded array>: the reference's R data sets are not bundled")
-        self.dataset_name = dataset_name
-        self.metric_name = metric_name
-        self.iss, self.k = iss, k
-        arg = iss if iss is not None else k
-        self._score_arg = float("nan") if arg is None else float(arg)      # NaN: the type's default (include/dvs.h)
-        arr = load_discrete_csv(data)[1] if isinstance(data, str) else np.asarray(data)
-        if arr.ndim != 2 or arr.shape[1] > dl.MAX_TOKENS or arr.min() < 0 or arr.max() > 15:
-            raise ValueError("data must be [samples, n_vars <= 48] with level codes 0..15")
-        self.n_samples, self.n_vars = arr.shape
-        words = (self.n_vars + 15) // 16
-        packed = np.zeros((self.n_samples, words), np.uint64)
-        for i in range(self.n_vars):
-            packed[:, i // 16] |= arr[:, i].astype(np.uint64) << np.uint64(4 * (i % 16))
-        self.lib = dl.load()
-        self.device = torch.device(device)
-        self._data = torch.from_numpy(packed.view(np.int64)).to(self.device)
-        self._card_host = [int(c) for c in arr.max(0) + 1]                 # pc.py sizes the CI tables' LDS from it
-        self._card = torch.from_numpy((arr.max(0) + 1).astype(np.uint8)).to(self.device)
-
-    @classmethod
-    def from_packed(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, card, *, iss=None, k=None):
-        """An evaluator around rows that are already packed on the device (int64 [S, ceil(n / 16)], 4-bit level codes:
-        what ``sample`` returns and ``_data`` holds), with no host round trip.  ``card`` (n level counts, 1..16) is taken as
-        given, not read off the rows: a sample may miss a level.  ``metric_name``, ``iss`` and ``k`` as in ``__init__``."""
-        if metric_name not in dl.SCORE_TYPES:
-            raise NotImplementedError(f"built scores: {', '.join(sorted(dl.SCORE_TYPES))} (got {metric_name!r})")
-        if iss is not None and not (metric_name in DIRICHLET_SCORES and math.isfinite(iss) and iss > 0):
-            raise ValueError(f"iss is the argument of {' / '.join(DIRICHLET_SCORES)}, finite and > 0 (got {iss!r} for {metric_name!r})")
-        if k is not None and not (metric_name in PENALISED_SCORES and math.isfinite(k) and k >= 0):
-            raise ValueError(f"k is the argument of {' / '.join(PENALISED_SCORES)}, finite and >= 0 (got {k!r} for {metric_name!r})")
-        card = [int(c) for c in card]
-        n = len(card)
-        if not torch.is_tensor(packed) or packed.device.type != "cuda":
-            raise RuntimeError("dags_vae_search_amd: from_packed takes rows on the GPU; this package has no CPU path")
-        if not 1 <= n <= dl.MAX_TOKENS or any(not 1 <= c <= 16 for c in card):
-            raise ValueError("card must hold 1..48 level counts in 1..16")
-        if packed.dtype != torch.int64 or packed.ndim != 2 or packed.shape[0] < 1 or packed.shape[1] != (n + 15) // 16:
-            raise ValueError(f"packed must be int64 [S >= 1, {(n + 15) // 16}] for {n} variables")
-        self = cls.__new__(cls)
         self.dataset_name, self.metric_name = dataset_name, metric_name
         self.iss, self.k = iss, k
         arg = iss if iss is not None else k
-        self._score_arg = float("nan") if arg is None else float(arg)
-        self.n_samples, self.n_vars = int(packed.shape[0]), n
+        self.score_arg = float("nan") if arg is None else float(arg)       # NaN: the type's default (include/dvs.h)
+
+    def _set_data(self, packed, card_host, device):
         self.lib = dl.load()
-        self.device = packed.device
-        self._data = packed.contiguous()
-        self._card_host = card
-        self._card = torch.tensor(card, dtype=torch.uint8, device=self.device)
-        return self
+        self.device = device
+        self.n_samples, self.n_vars = int(packed.shape[0]), len(card_host)
+        self.packed, self.card_host = packed, card_host
+        self.card = torch.tensor(card_host, dtype=torch.uint8, device=self.device)
+
+    def _source(self, B):
+        return self, ()
 
     def _parent_masks(self, graphs: Sequence, label_key: str) -> np.ndarray:
         n = self.n_vars
@@ -124,28 +178,6 @@ class BNLearnWrapper:
         masks = self._parent_masks(labeled_graphs, label_key)
         return self.score_masks(torch.from_numpy(masks.view(np.int64))).cpu().tolist()
 
-    def score_masks(self, parents: torch.Tensor, local: bool = False):
-        """parents: int64 [B, n_vars] bit rows in data-set variable indices (bit u of [b, v] <=> u -> v); -> f64 [B], or
-        with ``local`` (scores f64 [B], per-variable local scores f64 [B, n_vars])."""
-        parents = parents.to(self.device).contiguous()
-        B = parents.shape[0]
-        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
-        out = torch.empty(B, dtype=torch.float64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if self.metric_name == "bic" and self.k is None:
-            dl.check(self.lib, self.lib.dvs_bic_scores(B, self.n_vars, self.n_samples, p(self._data), p(self._card), p(parents),
-                                                       p(scratch), p(out), p(status), stream), "dvs_bic_scores")
-        else:
-            dl.check(self.lib, self.lib.dvs_bn_scores(B, self.n_vars, self.n_samples, p(self._data), p(self._card), p(parents),
-                                                      dl.SCORE_TYPES[self.metric_name], self._score_arg, p(scratch), p(out),
-                                                      p(status), stream), "dvs_bn_scores")
-        if int(status.item()) & 16:
-            raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
-                             "cells; sorted samples: 16 384 samples, 63 key bits)")
-        return (out, scratch) if local else out
-
     def _compact_parent_masks(self, batch):
         """(parent masks, the relabelling's status word), both on the device and unchecked"""
         labels =batch.labels.to(self.device).contiguous()
@@ -154,11 +186,9 @@ class BNLearnWrapper:
         assert n == self.n_vars, f"Expected {self.n_vars} vertices, but got {n}"                             # bnlearn.py:34
         parents = torch.empty(B, n, dtype=torch.int64, device=self.device)
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = dl.ptr
         dl.check(self.lib, self.lib.dvs_bic_parent_masks(B, n, 1 if preds.dtype == torch.int64 else 0, p(labels), p(preds),
-                                                         p(parents), p(status),
-                                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                 "dvs_bic_parent_masks")
+                                                         p(parents), p(status), dl.stream()), "dvs_bic_parent_masks")
         return parents, status
 
     def compact_parent_masks(self, batch) -> torch.Tensor:
@@ -166,7 +196,7 @@ class BNLearnWrapper:
         relabelling of bnlearn.py:34-45 as one HIP launch (dvs_bic_parent_masks).  What ``score_masks``, ``toggle_scores``
         and ``hill_climb`` take."""
         parents, status = self._compact_parent_masks(batch)
-        if int(status.item()) & 32:
+        if int(status.item()) & dl.STATUS_LABELS:
             raise AssertionError(f"Expected graph labels from 0 to {self.n_vars - 1}")                        # bnlearn.py:35
         return parents
 
@@ -176,32 +206,9 @@ class BNLearnWrapper:
         the host."""
         parents, status = self._compact_parent_masks(batch)
         out = self.score_masks(parents)
-        if int(status.item()) & 32:
+        if int(status.item()) & dl.STATUS_LABELS:
             raise AssertionError(f"Expected graph labels from 0 to {self.n_vars - 1}")                        # bnlearn.py:35
         return out
-
-    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
-        """The single-edge neighbourhood of every structure (dvs_bn_toggle_scores, DESIGN.md §14) -> (L f64 [B, n_vars],
-        T f64 [B, n_vars, n_vars]) on the device: L the local scores as ``score_masks(local=True)`` gives them, T[b, v, u]
-        the local score of v with bit u of ``parents[b, v]`` flipped (NaN on the diagonal and where the family is refused:
-        that move is not available).  ``worklist`` (int32 [2 B], ``hill_climb``'s) with ``out=(L, T)`` recomputes only
-        the rows it names, in place.  ``return_status`` appends the status word (bit 4: some family was refused)."""
-        parents = parents.to(self.device).contiguous()
-        B, n = parents.shape
-        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
-        if out is None:
-            if worklist is not None:
-                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
-            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
-                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
-        L, T = out
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        dl.check(self.lib, self.lib.dvs_bn_toggle_scores(
-            B, n, self.n_samples, p(self._data), p(self._card), p(parents), dl.SCORE_TYPES[self.metric_name], self._score_arg,
-            None if worklist is None else p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_toggle_scores")
-        return (L, T, status) if return_status else (L, T)
 
     def with_rows(self, rows: torch.Tensor, set_of=None) -> "RowSetEvaluator":
         """A view of this evaluator in which every structure of a batch is scored on its own multiset of rows
@@ -214,7 +221,7 @@ class BNLearnWrapper:
         return self.score_batch([labeled_graph], label_key)[0]
 
 
-class RowSetEvaluator:
+class RowSetEvaluator(_Scorer):
     """``BNLearnWrapper.with_rows``: the base evaluator's data, score and device, with structure b counted over the rows
     ``rows[set_of[b]]``.  ``n_samples`` is the set size: every score is, bit for bit, the base score type on the gathered
     data set (bic's default penalty is log(set_size) / 2).  The indices are checked here, once: the device does not."""
@@ -243,51 +250,10 @@ class RowSetEvaluator:
     def compact_parent_masks(self, batch) -> torch.Tensor:
         return self.base.compact_parent_masks(batch)
 
-    def _row_args(self, B):
+    def _source(self, B):
         if self.set_of is None:
             if B > self.n_sets:
                 raise ValueError(f"{B} structures but {self.n_sets} row sets: pass set_of")
         elif self.set_of.numel() != B:
             raise ValueError(f"{B} structures but set_of names {self.set_of.numel()}")
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        return p(self.rows), self.n_samples, self.n_sets, p(self.set_of)
-
-    def score_masks(self, parents: torch.Tensor, local: bool = False):
-        """``BNLearnWrapper.score_masks`` with structure b on its own rows"""
-        base = self.base
-        parents = parents.to(self.device).contiguous()
-        B = parents.shape[0]
-        row_args = self._row_args(B)
-        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
-        out = torch.empty(B, dtype=torch.float64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        dl.check(self.lib, self.lib.dvs_bn_scores_rows(
-            B, self.n_vars, base.n_samples, p(base._data), p(base._card), p(parents), dl.SCORE_TYPES[self.metric_name],
-            base._score_arg, p(scratch), p(out), p(status), *row_args,
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_scores_rows")
-        if int(status.item()) & 16:
-            raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
-                             "cells; sorted samples: 16 384 samples, 63 key bits)")
-        return (out, scratch) if local else out
-
-    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
-        """``BNLearnWrapper.toggle_scores`` with structure b on its own rows"""
-        base = self.base
-        parents = parents.to(self.device).contiguous()
-        B, n = parents.shape
-        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
-        row_args = self._row_args(B)
-        if out is None:
-            if worklist is not None:
-                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
-            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
-                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
-        L, T = out
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        dl.check(self.lib, self.lib.dvs_bn_toggle_scores_rows(
-            B, n, base.n_samples, p(base._data), p(base._card), p(parents), dl.SCORE_TYPES[self.metric_name], base._score_arg,
-            None if worklist is None else p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), *row_args,
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dvs_bn_toggle_scores_rows")
-        return (L, T, status) if return_status else (L, T)
+        return self.base, (dl.ptr(self.rows), self.n_samples, self.n_sets, dl.ptr(self.set_of))

@@ -10,7 +10,6 @@ The definitions are those of include/dvs.h (dvs_cpdag, dvs_pdag_compare).  Parit
 """
 from __future__ import annotations
 
-import ctypes
 from typing import NamedTuple, Tuple
 
 import torch
@@ -29,28 +28,14 @@ class StructureComparison(NamedTuple):
     hamming: torch.Tensor                  # int32 [B]: pairs adjacent in exactly one of the two
 
 
-def _masks(what, name, t, n=None):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: {name} must be a torch tensor of parent masks")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {t.device}); this package has no CPU path")
-    if t.dtype != torch.int64 or t.ndim != 2 or t.shape[0] < 1 or not 1 <= t.shape[1] <= MAX_VARS or (n is not None and t.shape[1] != n):
-        raise ValueError(f"{what}: {name} must be int64 [B >= 1, {n if n is not None else 'n <= 48'}] parent masks")
-    return t.contiguous()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _cpdag(what, name, parents):
-    lib = dl.load()
+def cpdag_of(what, name, parents):
+    """``cpdag`` of masks that ``_lib.parent_masks`` has checked; ``what`` and ``name`` word the refusal"""
+    lib, p = dl.load(), dl.ptr
     B, n = parents.shape
     with torch.cuda.device(parents.device):
         out = torch.empty_like(parents)
         flags = torch.empty(B, dtype=torch.int32, device=parents.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        dl.check(lib, lib.dvs_cpdag(B, n, _p(parents), _p(out), out.numel() * 8, _p(flags), stream), "dvs_cpdag")
+        dl.check(lib, lib.dvs_cpdag(B, n, p(parents), p(out), out.numel() * 8, p(flags), dl.stream()), "dvs_cpdag")
         bad = torch.nonzero(flags).reshape(-1)
         if bad.numel():
             fl = flags.cpu()
@@ -64,7 +49,7 @@ def cpdag(parents: torch.Tensor) -> torch.Tensor:
     """int64 [B, n] parent masks of DAGs (any variable order) -> int64 [B, n] CPDAGs: an edge is directed iff it has that
     direction in every DAG of the Markov equivalence class.  The rows are a canonical key of the class.  A row set with a
     cycle, a self-loop or a parent bit >= n raises ``ValueError`` naming the rows."""
-    return _cpdag("cpdag", "parents", _masks("cpdag", "parents", parents))
+    return cpdag_of("cpdag", "parents", dl.parent_masks("cpdag", "parents", parents))
 
 
 def compare_structures(parents: torch.Tensor, target: torch.Tensor, *, equivalence: bool = True) -> StructureComparison:
@@ -75,20 +60,19 @@ def compare_structures(parents: torch.Tensor, target: torch.Tensor, *, equivalen
     on the CPDAGs.  ``False`` compares the masks as given (DAGs, or PDAGs the caller already has): a reversed arc is then
     shd 1, fp 1, fn 1.  ``hamming`` counts the skeleton differences either way.  All fields are int32 [B] on the device."""
     what = "compare_structures"
-    a = _masks(what, "parents", parents)
+    a = dl.parent_masks(what, "parents", parents)
     B, n = a.shape
     if torch.is_tensor(target) and target.ndim == 1:
         target = target[None, :]
-    t = _masks(what, "target", target, n)
+    t = dl.parent_masks(what, "target", target, n)
     if t.shape[0] not in (1, B) or t.device != a.device:
         raise ValueError(f"{what}: target must be [{n}] or [{B}, {n}] on {a.device}")
     if equivalence:
-        a, t = _cpdag(what, "parents", a), _cpdag(what, "target", t)
-    lib = dl.load()
+        a, t = cpdag_of(what, "parents", a), cpdag_of(what, "target", t)
+    lib, p = dl.load(), dl.ptr
     with torch.cuda.device(a.device):
         counts = torch.empty(B, 5, dtype=torch.int32, device=a.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        dl.check(lib, lib.dvs_pdag_compare(B, n, _p(a), _p(t), t.shape[0], _p(counts), counts.numel() * 4, stream), "dvs_pdag_compare")
+        dl.check(lib, lib.dvs_pdag_compare(B, n, p(a), p(t), t.shape[0], p(counts), counts.numel() * 4, dl.stream()), "dvs_pdag_compare")
     return StructureComparison(*(counts[:, k].contiguous() for k in range(5)))
 
 

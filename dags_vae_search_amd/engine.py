@@ -11,24 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib as dl
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _nbytes(t: torch.Tensor) -> int:
-    return t.numel() * t.element_size()
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _require_cuda(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"dags_vae_search_amd: {what} must live on the GPU (got device {t.device}); "
-                           f"this package has no CPU path")
+from ._lib import nbytes, ptr, require_cuda, stream
 
 
 class PaceEngine:
@@ -58,10 +41,8 @@ class PaceEngine:
     def workspace(self, batch: int, device) -> torch.Tensor:
         if self._ws is None or self._ws_batch != batch or self._ws.device != device:
             shape = self.shape(batch)
-            nbytes = self.lib.dvs_workspace_bytes(ctypes.byref(shape))
-            if nbytes == 0:
-                dl.check(self.lib, 1, "dvs_workspace_bytes")
-            self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=device)   # slab padding must stay 0
+            ws_bytes = dl.workspace_bytes(self.lib, "dvs_workspace_bytes", ctypes.byref(shape))
+            self._ws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.float32, device=device)   # slab padding must stay 0
             self._ws_batch = batch
             self._records = torch.empty(batch * self.record_bytes, dtype=torch.uint8, device=device)
             if not self._status_external or self._status.device != device:
@@ -91,7 +72,7 @@ class PaceEngine:
         tm = features["target_masks"]
         for name, t in (("vertex_label_features", lab), ("vertex_position_features", pos),
                         ("adjacency_matrices", adj), ("target_masks", tm)):
-            _require_cuda(t, name)
+            require_cuda(t, name)
         B, N, C = lab.shape
         if N != self.n_tokens or C != self.n_classes:
             raise AssertionError(f"Expected [B,{self.n_tokens},{self.n_classes}] label features, got {tuple(lab.shape)}")
@@ -112,9 +93,9 @@ class PaceEngine:
         if zero_status:
             self._status.zero_()
         shape = self.shape(B)
-        dl.check(self.lib, self.lib.dvs_pack_features(ctypes.byref(shape), _ptr(lab), _ptr(pos), _ptr(adj), _ptr(tm),
-                                                      _ptr(self._records), _nbytes(self._records), _ptr(self._status),
-                                                      _stream()),
+        dl.check(self.lib, self.lib.dvs_pack_features(ctypes.byref(shape), ptr(lab), ptr(pos), ptr(adj), ptr(tm),
+                                                      ptr(self._records), nbytes(self._records), ptr(self._status),
+                                                      stream()),
                  "dvs_pack_features")
         if check:
             st = self._read_status()
@@ -127,8 +108,8 @@ class PaceEngine:
                       zero_status: bool = True) -> torch.Tensor:
         """dvs_build_records: row codec (labels u8 [B,n], preds [B,n]: i16 bit pattern of u16 masks on the one-tile
         path, i64 on the wide path) -> records, all on the device."""
-        _require_cuda(labels, "labels")
-        _require_cuda(preds, "preds")
+        require_cuda(labels, "labels")
+        require_cuda(preds, "preds")
         B, n = labels.shape
         if n != self.n_tokens - 3 or tuple(preds.shape) != (B, n):
             raise AssertionError(f"Expected {self.n_tokens - 3}, got instead {n}")
@@ -138,8 +119,8 @@ class PaceEngine:
         if zero_status:
             self._status.zero_()
         shape = self.shape(B)
-        dl.check(self.lib, self.lib.dvs_build_records(ctypes.byref(shape), _ptr(labels), _ptr(preds), _ptr(self._records),
-                                                      _nbytes(self._records), _ptr(self._status), _stream()),
+        dl.check(self.lib, self.lib.dvs_build_records(ctypes.byref(shape), ptr(labels), ptr(preds), ptr(self._records),
+                                                      nbytes(self._records), ptr(self._status), stream()),
                  "dvs_build_records")
         if check:
             st = self._read_status()
@@ -154,22 +135,22 @@ class PaceEngine:
         """host_tail (pinned float32 words, the first four are used) + host_seq (24 bits): the device writes [total, recon, kld,
         (seq << 8) | flags | validation bits] there with one 16-byte store (include/dvs.h: dvs_loss_forward_notify) and re-arms
         the validation word in the same kernel."""
-        _require_cuda(params, "parameters")
+        require_cuda(params, "parameters")
         ws = self.workspace(shape.batch, params.device)
         if losses.numel() < dl.LOSS_FLOATS:
             raise ValueError(f"losses must hold {dl.LOSS_FLOATS} floats")
         if host_tail is None:
-            dl.check(self.lib, self.lib.dvs_loss_forward(ctypes.byref(shape), _ptr(self._records), _nbytes(self._records),
-                                                         _ptr(params), params.numel(), _ptr(ws), _nbytes(ws), _ptr(eps),
-                                                         _ptr(self._status), _ptr(losses), _ptr(mu), _ptr(logvar), _stream()),
+            dl.check(self.lib, self.lib.dvs_loss_forward(ctypes.byref(shape), ptr(self._records), nbytes(self._records),
+                                                         ptr(params), params.numel(), ptr(ws), nbytes(ws), ptr(eps),
+                                                         ptr(self._status), ptr(losses), ptr(mu), ptr(logvar), stream()),
                      "dvs_loss_forward")
             return
         if not host_tail.is_pinned() or host_tail.numel() < 4 or host_tail.dtype != torch.float32 or host_tail.data_ptr() % 16:
             raise ValueError("host_tail must be at least 4 pinned float32 words, 16-byte aligned")
         dl.check(self.lib, self.lib.dvs_loss_forward_notify(
-            ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
-            _ptr(eps), _ptr(self._status), _ptr(losses), _ptr(mu), _ptr(logvar), host_tail.data_ptr(), int(host_seq) & 0xFFFFFF,
-            _stream()), "dvs_loss_forward_notify")
+            ctypes.byref(shape), ptr(self._records), nbytes(self._records), ptr(params), params.numel(), ptr(ws), nbytes(ws),
+            ptr(eps), ptr(self._status), ptr(losses), ptr(mu), ptr(logvar), host_tail.data_ptr(), int(host_seq) & 0xFFFFFF,
+            stream()), "dvs_loss_forward_notify")
 
     def loss_backward(self, shape, params: torch.Tensor, gcoef: torch.Tensor, grads: torch.Tensor,
                       clip_scratch: Optional[torch.Tensor] = None):
@@ -182,23 +163,23 @@ class PaceEngine:
             if clip_scratch.numel() < dl.CLIP_SCRATCH_FLOATS or clip_scratch.dtype != torch.float32:
                 raise ValueError(f"clip_scratch must hold {dl.CLIP_SCRATCH_FLOATS} float32 words")
             dl.check(self.lib, self.lib.dvs_loss_backward_sq(
-                ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
-                _ptr(gcoef), _ptr(grads), _ptr(clip_scratch), _stream()), "dvs_loss_backward_sq")
+                ctypes.byref(shape), ptr(self._records), nbytes(self._records), ptr(params), params.numel(), ptr(ws), nbytes(ws),
+                ptr(gcoef), ptr(grads), ptr(clip_scratch), stream()), "dvs_loss_backward_sq")
             return
-        dl.check(self.lib, self.lib.dvs_loss_backward(ctypes.byref(shape), _ptr(self._records), _nbytes(self._records),
-                                                      _ptr(params), params.numel(), _ptr(ws), _nbytes(ws), _ptr(gcoef),
-                                                      _ptr(grads), _stream()), "dvs_loss_backward")
+        dl.check(self.lib, self.lib.dvs_loss_backward(ctypes.byref(shape), ptr(self._records), nbytes(self._records),
+                                                      ptr(params), params.numel(), ptr(ws), nbytes(ws), ptr(gcoef),
+                                                      ptr(grads), stream()), "dvs_loss_backward")
 
     def loss_forward_defer(self, shape, params: torch.Tensor, eps: Optional[torch.Tensor],
                            mu: Optional[torch.Tensor] = None, logvar: Optional[torch.Tensor] = None):
         """dvs_loss_forward_defer: the forward up to the decoder, without the loss head; loss_backward_emit must follow."""
-        _require_cuda(params, "parameters")
+        require_cuda(params, "parameters")
         if self.wide:
             raise ValueError("loss_forward_defer: one-tile path only")
         ws = self.workspace(shape.batch, params.device)
         dl.check(self.lib, self.lib.dvs_loss_forward_defer(
-            ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
-            _ptr(eps), _ptr(mu), _ptr(logvar), _stream()), "dvs_loss_forward_defer")
+            ctypes.byref(shape), ptr(self._records), nbytes(self._records), ptr(params), params.numel(), ptr(ws), nbytes(ws),
+            ptr(eps), ptr(mu), ptr(logvar), stream()), "dvs_loss_forward_defer")
 
     def loss_backward_emit(self, shape, params: torch.Tensor, gcoef: torch.Tensor, grads: torch.Tensor, losses: torch.Tensor,
                            clip_scratch: Optional[torch.Tensor] = None, host_tail: Optional[torch.Tensor] = None,
@@ -216,27 +197,27 @@ class PaceEngine:
                                       or host_tail.data_ptr() % 16):
             raise ValueError("host_tail must be at least 4 pinned float32 words, 16-byte aligned")
         dl.check(self.lib, self.lib.dvs_loss_backward_emit(
-            ctypes.byref(shape), _ptr(self._records), _nbytes(self._records), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
-            _ptr(gcoef), _ptr(grads), _ptr(clip_scratch), _ptr(self._status), _ptr(losses),
-            None if host_tail is None else host_tail.data_ptr(), int(host_seq) & 0xFFFFFF, _stream()), "dvs_loss_backward_emit")
+            ctypes.byref(shape), ptr(self._records), nbytes(self._records), ptr(params), params.numel(), ptr(ws), nbytes(ws),
+            ptr(gcoef), ptr(grads), ptr(clip_scratch), ptr(self._status), ptr(losses),
+            None if host_tail is None else host_tail.data_ptr(), int(host_seq) & 0xFFFFFF, stream()), "dvs_loss_backward_emit")
 
     def encode(self, shape, params: torch.Tensor, mu: torch.Tensor, logvar: torch.Tensor):
         ws = self.workspace(shape.batch, params.device)
-        dl.check(self.lib, self.lib.dvs_encode(ctypes.byref(shape), _ptr(self._records), _nbytes(self._records),
-                                               _ptr(params), params.numel(), _ptr(ws), _nbytes(ws), _ptr(mu), _ptr(logvar),
-                                               _stream()), "dvs_encode")
+        dl.check(self.lib, self.lib.dvs_encode(ctypes.byref(shape), ptr(self._records), nbytes(self._records),
+                                               ptr(params), params.numel(), ptr(ws), nbytes(ws), ptr(mu), ptr(logvar),
+                                               stream()), "dvs_encode")
 
     def decode(self, shape, params: torch.Tensor, z: torch.Tensor, uniforms: Optional[torch.Tensor]) -> torch.Tensor:
         """dvs_decode: the whole autoregressive generation loop on the device.  Returns the raw dvs_decode_state
         records as a uint8 tensor [B, DECODE_STATE_BYTES]."""
-        _require_cuda(params, "parameters")
-        _require_cuda(z, "z")
+        require_cuda(params, "parameters")
+        require_cuda(z, "z")
         B = z.shape[0]
         ws = self.workspace(B, params.device)
         state = torch.empty(B, dl.DECODE_STATE_BYTES, dtype=torch.uint8, device=params.device)
-        dl.check(self.lib, self.lib.dvs_decode(ctypes.byref(shape), _ptr(params), params.numel(), _ptr(ws), _nbytes(ws),
-                                               _ptr(self._records), _nbytes(self._records), _ptr(z), _ptr(uniforms),
-                                               _ptr(state), _nbytes(state), _stream()), "dvs_decode")
+        dl.check(self.lib, self.lib.dvs_decode(ctypes.byref(shape), ptr(params), params.numel(), ptr(ws), nbytes(ws),
+                                               ptr(self._records), nbytes(self._records), ptr(z), ptr(uniforms),
+                                               ptr(state), nbytes(state), stream()), "dvs_decode")
         return state
 
     def clip_adam(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, max_norm, scratch, guard=None,
@@ -245,14 +226,14 @@ class PaceEngine:
         when either is non-zero (include/dvs.h).  from_partials: `scratch` already holds the partial sums of squares of
         `grads` (loss_backward(clip_scratch=scratch) wrote them): dvs_clip_adam_from_partials, one launch instead of two."""
         fn = self.lib.dvs_clip_adam_from_partials if from_partials else self.lib.dvs_clip_adam
-        dl.check(self.lib, fn(params.numel(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), lr, beta1, beta2, eps,
-                              int(step), float(max_norm), _ptr(scratch), _ptr(guard), _stream()),
+        dl.check(self.lib, fn(params.numel(), ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2, eps,
+                              int(step), float(max_norm), ptr(scratch), ptr(guard), stream()),
                  "dvs_clip_adam_from_partials" if from_partials else "dvs_clip_adam")
 
     def activation(self, batch: int, slot: int) -> torch.Tensor:
         out = torch.empty(batch, 16 * self.tiles, 64, dtype=torch.float32, device=self._ws.device)
         shape = self.shape(batch)
-        dl.check(self.lib, self.lib.dvs_debug_activation(ctypes.byref(shape), _ptr(self._ws), slot, _ptr(out), _stream()),
+        dl.check(self.lib, self.lib.dvs_debug_activation(ctypes.byref(shape), ptr(self._ws), slot, ptr(out), stream()),
                  "dvs_debug_activation")
         return out
 
@@ -260,7 +241,7 @@ class PaceEngine:
         """[batch, 2] = per-DAG {reconstruction loss, KL term} of the last step (debug / test access)."""
         out = torch.empty(batch, 2, dtype=torch.float32, device=self._ws.device)
         shape = self.shape(batch)
-        dl.check(self.lib, self.lib.dvs_debug_dag_losses(ctypes.byref(shape), _ptr(self._ws), _ptr(out), _stream()),
+        dl.check(self.lib, self.lib.dvs_debug_dag_losses(ctypes.byref(shape), ptr(self._ws), ptr(out), stream()),
                  "dvs_debug_dag_losses")
         return out
 

@@ -12,11 +12,9 @@ bytes.  Parity with an external exact solver is unpinned; the result rests on th
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Optional
 
-import numpy as np
 import torch
 
 from . import _lib as dl
@@ -31,10 +29,6 @@ class ExactResult:
     order: torch.Tensor                    # int32 [B, n]: a topological order of parents (parents[order[k]] within order[:k])
     flags: torch.Tensor                    # int32 [B]: always zero on return (a set flag raises)
     rescored: Optional[torch.Tensor] = None    # exact_search: evaluator.score_masks(parents), the other summation order
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _refuse_size(what, n, batch=1):
@@ -53,8 +47,7 @@ def exact_from_tables(tables: torch.Tensor, *, max_parents: Optional[int] = None
     what = "exact_from_tables"
     if not torch.is_tensor(tables):
         raise TypeError(f"{what}: tables must be a torch tensor")
-    if tables.device.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {tables.device}); this package has no CPU path")
+    dl.need_cuda(what, tables.device)
     if tables.dtype != torch.float64 or tables.ndim != 3 or tables.shape[0] < 1 or tables.shape[2] < 1:
         raise ValueError(f"{what}: tables must be float64 [B >= 1, 2^n, n]")
     B, rows, n = tables.shape
@@ -65,23 +58,16 @@ def exact_from_tables(tables: torch.Tensor, *, max_parents: Optional[int] = None
     tables = tables.contiguous()
     dev = tables.device
     with torch.cuda.device(dev):
-        forb = None
-        if forbidden is not None:
-            forb = torch.as_tensor(np.asarray(forbidden).astype(np.uint64).view(np.int64) if not torch.is_tensor(forbidden)
-                                   else forbidden).to(device=dev, dtype=torch.int64).contiguous()
-            if forb.shape != (n,):
-                raise ValueError(f"forbidden must be [{n}] bit rows")
-        ws_bytes = int(lib.dvs_exact_workspace_bytes(B, n))
-        if ws_bytes == 0:
-            dl.check(lib, 1, "dvs_exact_workspace_bytes")
+        forb = dl.forbidden_rows(forbidden, n, dev)
+        ws_bytes = dl.workspace_bytes(lib, "dvs_exact_workspace_bytes", B, n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         parents = torch.empty(B, n, dtype=torch.int64, device=dev)
         order = torch.empty(B, n, dtype=torch.int32, device=dev)
         scores = torch.empty(B, dtype=torch.float64, device=dev)
         flags = torch.empty(B, dtype=torch.int32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        dl.check(lib, lib.dvs_exact_search(B, n, _p(tables), tables.numel() * 8, 0 if max_parents is None else int(max_parents),
-                                           _p(forb), _p(ws), ws_bytes, _p(parents), _p(order), _p(scores), _p(flags), stream),
+        p = dl.ptr
+        dl.check(lib, lib.dvs_exact_search(B, n, p(tables), tables.numel() * 8, 0 if max_parents is None else int(max_parents),
+                                           p(forb), p(ws), ws_bytes, p(parents), p(order), p(scores), p(flags), dl.stream()),
                  "dvs_exact_search")
         bad = torch.nonzero(flags).reshape(-1)
         if bad.numel():
@@ -97,9 +83,8 @@ def local_score_table(evaluator, *, max_parents: Optional[int] = None, chunk: in
     that parent set is not available).  With ``max_parents = k`` only the rows with ``popcount(S) <= k + 1`` are scored and
     the rest of the table is NaN."""
     what = "local_score_table"
-    dev, n, lib = evaluator.device, evaluator.n_vars, evaluator.lib
-    if dev.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {dev}); this package has no CPU path")
+    dev, n = evaluator.device, evaluator.n_vars
+    dl.need_cuda(what, dev)
     _refuse_size(what, n)
     if chunk < 1:
         raise ValueError("chunk must be >= 1")
@@ -115,8 +100,6 @@ def local_score_table(evaluator, *, max_parents: Optional[int] = None, chunk: in
             S = S[pop <= int(max_parents) + 1]
         own = ~(torch.ones(n, dtype=torch.int64, device=dev) << torch.arange(n, dtype=torch.int64, device=dev))
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        default_bic = evaluator.metric_name == "bic" and evaluator.k is None
         for r0 in range(0, S.numel(), chunk):
             sel = S[r0:r0 + chunk]
             m = sel.numel()
@@ -124,13 +107,7 @@ def local_score_table(evaluator, *, max_parents: Optional[int] = None, chunk: in
             # uncapped, the rows of a chunk are the table's rows r0 .. r0 + m - 1: the scorer's scratch is the table itself
             scratch = torch.empty(m, n, dtype=torch.float64, device=dev) if capped else table[r0:r0 + m]
             out = torch.empty(m, dtype=torch.float64, device=dev)
-            if default_bic:
-                dl.check(lib, lib.dvs_bic_scores(m, n, evaluator.n_samples, _p(evaluator._data), _p(evaluator._card), _p(parents),
-                                                 _p(scratch), _p(out), _p(status), stream), "dvs_bic_scores")
-            else:
-                dl.check(lib, lib.dvs_bn_scores(m, n, evaluator.n_samples, _p(evaluator._data), _p(evaluator._card), _p(parents),
-                                                dl.SCORE_TYPES[evaluator.metric_name], evaluator._score_arg, _p(scratch),
-                                                _p(out), _p(status), stream), "dvs_bn_scores")
+            evaluator.launch_scores(parents, scratch, out, status)
             if capped:
                 table[sel] = scratch
     return table

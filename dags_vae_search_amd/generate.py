@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as dl
-from .engine import _nbytes, _ptr, _require_cuda, _stream
+from ._lib import nbytes, ptr, require_cuda, stream
 from .records import CompactBatch, CompactDagDataset
 
 logger = logging.getLogger(__name__)
@@ -72,7 +72,7 @@ def generate_dags(n: int, card: int, num_edges: Union[int, torch.Tensor], count:
     DAG b depends on (seed, dag_offset + b) only."""
     flags = _flags(label_random_method, accept_isolates, accept_no_connectivity)
     if torch.is_tensor(num_edges):
-        _require_cuda(num_edges, "num_edges")
+        require_cuda(num_edges, "num_edges")
         dev = num_edges.device
         m = num_edges.to(torch.int32).contiguous().reshape(-1)
         if count is not None and int(count) != m.numel():
@@ -91,9 +91,9 @@ def generate_dags(n: int, card: int, num_edges: Union[int, torch.Tensor], count:
         labels = torch.empty((B, n), dtype=torch.uint8, device=dev)
         preds = torch.empty((B, n), dtype=torch.int64 if wide else torch.int16, device=dev)
         attempts = torch.empty(B, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_generate_dags(B, int(n), int(card), 1 if wide else 0, _ptr(m), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                            int(dag_offset), int(try_limit), flags, _ptr(labels), _ptr(preds), _nbytes(preds),
-                                            _ptr(attempts), _stream()), "dvs_generate_dags")
+        dl.check(lib, lib.dvs_generate_dags(B, int(n), int(card), 1 if wide else 0, ptr(m), dl.seed64(seed),
+                                            int(dag_offset), int(try_limit), flags, ptr(labels), ptr(preds), nbytes(preds),
+                                            ptr(attempts), stream()), "dvs_generate_dags")
     return CompactBatch(labels, preds), attempts
 
 
@@ -105,8 +105,8 @@ def draw_edge_counts(schema, count: int, *, seed: int, dag_offset: int = 0, devi
     table = torch.tensor([[m for m, _ in schema], np.cumsum([w for _, w in schema]).tolist()], dtype=torch.int32).to(dev)
     out = torch.empty(int(count), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        dl.check(lib, lib.dvs_generate_edge_counts(int(count), len(schema), _ptr(table[0]), _ptr(table[1]),
-                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(dag_offset), _ptr(out), _stream()),
+        dl.check(lib, lib.dvs_generate_edge_counts(int(count), len(schema), ptr(table[0]), ptr(table[1]),
+                                                   dl.seed64(seed), int(dag_offset), ptr(out), stream()),
                  "dvs_generate_edge_counts")
     return out
 

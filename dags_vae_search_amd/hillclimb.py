@@ -12,11 +12,9 @@ shares this module's starts, argument handling and round loop.  No whitelist.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import _lib as dl
@@ -47,8 +45,7 @@ class _Search:
     def __init__(self, what, evaluator, starts, batch, max_steps, max_parents, forbidden, check_every, restarts, perturb, trace):
         self.what, self.ev = what, evaluator
         self.lib, dev, n = evaluator.lib, evaluator.device, evaluator.n_vars
-        if dev.type != "cuda":
-            raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {dev}); this package has no CPU path")
+        dl.need_cuda(what, dev)
         if max_steps < 1 or check_every < 1:
             raise ValueError("max_steps and check_every must be >= 1")
         if restarts < 0 or perturb < 1:
@@ -68,13 +65,7 @@ class _Search:
         self.max_steps, self.check_every, self.restarts, self.perturb = int(max_steps), int(check_every), int(restarts), int(perturb)
         self.cap = 0 if max_parents is None else int(max_parents)
         with torch.cuda.device(dev):
-            self.forb = None
-            if forbidden is not None:
-                forb = torch.as_tensor(np.asarray(forbidden).astype(np.uint64).view(np.int64) if not torch.is_tensor(forbidden)
-                                       else forbidden).to(device=dev, dtype=torch.int64).contiguous()
-                if forb.shape != (n,):
-                    raise ValueError(f"forbidden must be [{n}] bit rows")
-                self.forb = forb
+            self.forb = dl.forbidden_rows(forbidden, n, dev)
             self.worklist = torch.full((2 * B,), -1, dtype=torch.int32, device=dev)
             self.steps = torch.zeros(B, dtype=torch.int32, device=dev)
             self.converged = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -83,26 +74,22 @@ class _Search:
             self.tr = torch.zeros(B, self.max_steps, 2, dtype=torch.int64, device=dev) if trace else None
         self.rounds = 0
 
-    @staticmethod
-    def p(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
     def step_args(self, min_delta, slot):
         """the arguments dvs_hc_step and dvs_tabu_step have in common: (batch .. active)"""
-        p, tr = self.p, self.tr
+        p, tr = dl.ptr, self.tr
         return (self.B, self.n, p(self.parents), p(self.L), p(self.T), self.T.numel() * 8, self.cap, float(min_delta),
                 p(self.forb), self.max_steps, p(self.worklist), p(self.steps), p(self.converged), p(self.flags), p(tr),
-                0 if tr is None else tr.numel() * 8, ctypes.c_void_p(self.active.data_ptr() + 4 * slot))
+                0 if tr is None else tr.numel() * 8, p(self.active, 4 * slot))
 
     def run(self, launch_step, round_best, reset_round, seed):
         """``launch_step(slot, stream)`` enqueues one step kernel counting into ``active[slot]``; ``round_best()`` gives the
         (parents, scores) a round ends with; ``reset_round()`` clears the step kernel's own state.  Returns the best
         (parents, scores) over the rounds, or None with ``restarts == 0`` (nothing to fold)."""
-        ev, p = self.ev, self.p
+        ev, p = self.ev, dl.ptr
         best = None
         with torch.cuda.device(self.dev):
             self.L, self.T = ev.toggle_scores(self.parents)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = dl.stream()
             for rnd in range(self.restarts + 1):
                 if rnd:
                     # from the best so far: one full pass, then `perturb` random legal moves, each with its incremental pass
@@ -111,7 +98,7 @@ class _Search:
                     for k in range(self.perturb):
                         dl.check(self.lib, self.lib.dvs_hc_perturb(
                             self.B, self.n, p(self.parents), p(self.L), p(self.T), self.T.numel() * 8, self.cap, p(self.forb),
-                            p(self.worklist), p(self.flags), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            p(self.worklist), p(self.flags), dl.seed64(seed),
                             (rnd * self.perturb + k) & 0xFFFFFFFF, stream), "dvs_hc_perturb")
                         ev.toggle_scores(self.parents, worklist=self.worklist, out=(self.L, self.T))
                     self.steps.zero_()

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib as dl
 from .bic import BNLearnWrapper
-from .params import FittedBN, _need_cuda, _p, _stream
+from .params import FittedBN
 
 PREDICT_METHODS = ("parents", "exact", "bayes-lw")
 
@@ -63,10 +63,10 @@ def _evidence(fitted: FittedBN, evidence, what):
         return rows, torch.tensor([_mask_of(evidence, n, what)], dtype=torch.int64, device=dev)
     rows, observed = evidence
     if isinstance(rows, BNLearnWrapper):
-        rows = rows._data
+        rows = rows.packed
     if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.ndim != 2 or rows.shape[1] != words or rows.shape[0] < 1:
         raise ValueError(f"{what}: evidence rows must be packed int64 [Q >= 1, {words}]")
-    _need_cuda(what, rows.device)
+    dl.need_cuda(what, rows.device)
     if torch.is_tensor(observed):
         if observed.dtype != torch.int64 or observed.shape != (rows.shape[0],):
             raise ValueError(f"{what}: observed must be an int or an int64 tensor [{rows.shape[0]}]")
@@ -82,34 +82,29 @@ def _lw(fitted: FittedBN, rows, observed, *, n_particles, seed, index=0, event=N
         query_offset=0, what="likelihood weighting"):
     """one dvs_bn_lw -> (sums f64 [Q, 3], marginals f64 [Q, T, 16] or None, particles int64 [Q, M, words] or None, weights f64
     [Q, M] or None); the refusals of the status word raise ValueError"""
-    _need_cuda(what, fitted.device)
+    dl.need_cuda(what, fitted.device)
     if not 0 <= int(index) < fitted.batch:
         raise ValueError(f"{what}: index must be in [0, {fitted.batch})")
     if int(n_particles) < 1 or int(query_offset) < 0:
         raise ValueError(f"{what}: n must be >= 1 and query_offset >= 0")
-    n, dev, lib = fitted.n_vars, fitted.device, dl.load()
+    n, dev, lib, p = fitted.n_vars, fitted.device, dl.load(), dl.ptr
     Q, M, T = rows.shape[0], int(n_particles), bin(targets).count("1")
     lo, hi = fitted.offsets_host[index * n], fitted.offsets_host[(index + 1) * n]
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.dvs_bn_lw_workspace_bytes(hi - lo, n, Q, M, targets))
-        if ws_bytes == 0:
-            dl.check(lib, 1, "dvs_bn_lw_workspace_bytes")
+        ws_bytes = dl.workspace_bytes(lib, "dvs_bn_lw_workspace_bytes", hi - lo, n, Q, M, targets)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         sums = torch.empty(Q, 3, dtype=torch.float64, device=dev)
         marg = torch.empty(Q, T, 16, dtype=torch.float64, device=dev) if T else None
         parts = torch.empty(Q, M, rows.shape[1], dtype=torch.int64, device=dev) if particles else None
         wts = torch.empty(Q, M, dtype=torch.float64, device=dev) if particles else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_bn_lw(n, Q, M, _p(fitted.card), _p(fitted.parents[index]), _p(fitted.offsets[index * n:]),
-                                    _p(fitted.cpt), hi - lo, _p(rows), _p(observed), _p(event), targets,
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(query_offset), _p(ws), ws_bytes, _p(sums), _p(marg),
-                                    _p(parts), _p(wts), _p(status), _stream()), "dvs_bn_lw")
+        dl.check(lib, lib.dvs_bn_lw(n, Q, M, p(fitted.card), p(fitted.parents[index]), p(fitted.offsets[index * n:]),
+                                    p(fitted.cpt), hi - lo, p(rows), p(observed), p(event), targets,
+                                    dl.seed64(seed), int(query_offset), p(ws), ws_bytes, p(sums), p(marg),
+                                    p(parts), p(wts), p(status), dl.stream()), "dvs_bn_lw")
         st = int(status.item())
-    if st & 1:
-        raise ValueError(f"{what}: the structure has a cycle")
-    if st & 64:
-        raise ValueError(f"{what}: a table row is not a probability vector (a NaN or negative cell, or a sum further than 1e-9 from 1)")
-    if st & 16:
+    dl.check_network_status(what, st)
+    if st & dl.STATUS_REFUSED:
         raise ValueError(f"{what}: an evidence level is at or above its variable's level count, or the tables do not match the structure")
     return sums, marg, parts, wts
 
@@ -156,32 +151,20 @@ def posterior(fitted: FittedBN, targets, evidence, *, n: int = 10000, seed: int,
     return marg / sums[:, 0, None, None]
 
 
-def _packed_rows(fitted: FittedBN, data, what):
-    n = fitted.n_vars
-    if isinstance(data, BNLearnWrapper):
-        if data.n_vars != n:
-            raise ValueError(f"{what}: the evaluator has {data.n_vars} variables, the network {n}")
-        data = data._data
-    if not torch.is_tensor(data) or data.dtype != torch.int64 or data.ndim != 2 or data.shape[1] != (n + 15) // 16 or data.shape[0] < 1:
-        raise ValueError(f"{what}: data must be an evaluator or packed int64 rows [S >= 1, {(n + 15) // 16}]")
-    _need_cuda(what, data.device)
-    return data.contiguous()
-
-
 def _blanket(fitted: FittedBN, data, target, use_children, prob, index=None, what="predict"):
     """dvs_bn_blanket_posterior for structure ``index`` (None: the whole batch) -> (pred uint8 [B, S], posterior [B, S, r] or None)"""
-    n, dev, lib = fitted.n_vars, fitted.device, dl.load()
+    n, dev, lib, p = fitted.n_vars, fitted.device, dl.load(), dl.ptr
     B, first = (fitted.batch, 0) if index is None else (1, int(index))
     S, r = data.shape[0], fitted.card_host[target]
     with torch.cuda.device(dev):
         post = torch.empty(B, S, r, dtype=torch.float64, device=dev) if prob else None
         pred = torch.empty(B, S, dtype=torch.uint8, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_bn_blanket_posterior(B, n, S, _p(data), _p(fitted.card), _p(fitted.parents[first:]),
-                                                   _p(fitted.offsets[first * n:]), _p(fitted.cpt), fitted.cpt.numel() * 8,
-                                                   int(target), int(use_children), _p(post), _p(pred), _p(status), _stream()),
+        dl.check(lib, lib.dvs_bn_blanket_posterior(B, n, S, p(data), p(fitted.card), p(fitted.parents[first:]),
+                                                   p(fitted.offsets[first * n:]), p(fitted.cpt), fitted.cpt.numel() * 8,
+                                                   int(target), int(use_children), p(post), p(pred), p(status), dl.stream()),
                  "dvs_bn_blanket_posterior")
-        if int(status.item()) & 16:
+        if int(status.item()) & dl.STATUS_REFUSED:
             raise ValueError(f"{what}: a row has a level code at or above its variable's level count, or the tables do not match the structure")
     return pred, post
 
@@ -196,14 +179,14 @@ def predict(fitted: FittedBN, target: int, data, *, method: str = "parents", n: 
     ``query_offset + i``).  The lowest level wins a tie; a row whose posterior is NaN (an all-zero product, sum w = 0)
     predicts 255."""
     what = "predict"
-    _need_cuda(what, fitted.device)
+    dl.need_cuda(what, fitted.device)
     if method not in PREDICT_METHODS:
         raise ValueError(f"method must be one of {PREDICT_METHODS} (got {method!r})")
     if not 0 <= int(target) < fitted.n_vars:
         raise ValueError(f"{what}: target must be in [0, {fitted.n_vars})")
     if not 0 <= int(index) < fitted.batch:
         raise ValueError(f"{what}: index must be in [0, {fitted.batch})")
-    data = _packed_rows(fitted, data, what)
+    data = dl.packed_rows(what, data, fitted.n_vars)
     target = int(target)
     if method != "bayes-lw":
         pred, post = _blanket(fitted, data, target, method == "exact", prob, index, what)

@@ -11,7 +11,6 @@ is not pinned against an R run.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import List, Sequence
 
@@ -22,19 +21,6 @@ from . import _lib as dl
 from .bic import BNLearnWrapper
 
 UNOBSERVED = {"nan": 0, "uniform": 1}      # an unobserved parent configuration under mle: NaN cells, or 1 / r
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_cuda(what, device):
-    if torch.device(device).type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {device}); this package has no CPU path")
 
 
 def _family(card, row, v):
@@ -91,11 +77,9 @@ class FittedBN:
     def from_tables(cls, parents, card, tables, device="cuda") -> "FittedBN":
         """One network from hand-written tables: ``parents`` n parent rows (ints), ``card`` n level counts, ``tables[v]`` the
         [q, r] table of variable v (rows: parent configurations, lowest parent id fastest)."""
-        _need_cuda("FittedBN.from_tables", device)
-        card = [int(c) for c in card]
+        dl.need_cuda("FittedBN.from_tables", device)
+        card = dl.level_counts(card)
         n = len(card)
-        if not 1 <= n <= dl.MAX_TOKENS or any(not 1 <= c <= 16 for c in card):
-            raise ValueError("card must hold 1..48 level counts in 1..16")
         host = np.array([[int(r) for r in parents]], np.uint64)
         if host.shape != (1, n) or len(tables) != n:
             raise ValueError(f"parents and tables must have one entry per variable ({n})")
@@ -118,7 +102,7 @@ def bn_fit(evaluator, parents, *, method: str = "mle", iss=None, unobserved: str
     (N_jk + a) / (N_j + r a), a = iss / (r q); ``iss`` defaults to 1).  The rows are read back once to lay out the tables; a
     family of more than 36 864 cells raises ValueError before anything is launched."""
     what = "bn_fit"
-    _need_cuda(what, evaluator.device)
+    dl.need_cuda(what, evaluator.device)
     if method not in dl.FIT_METHODS:
         raise ValueError(f"method must be one of {sorted(dl.FIT_METHODS)} (got {method!r})")
     if unobserved not in UNOBSERVED:
@@ -130,7 +114,7 @@ def bn_fit(evaluator, parents, *, method: str = "mle", iss=None, unobserved: str
         raise ValueError(f"iss must be finite and > 0 (got {iss!r})")
     if not torch.is_tensor(parents) or parents.dtype != torch.int64 or parents.ndim not in (1, 2):
         raise ValueError(f"{what}: parents must be an int64 tensor [n] or [B, n] of parent masks")
-    n, card = evaluator.n_vars, evaluator._card_host
+    n, card = evaluator.n_vars, evaluator.card_host
     dev = evaluator.device
     parents = parents.reshape(-1, parents.shape[-1]).to(dev).contiguous()
     if parents.shape[1] != n or parents.shape[0] < 1:
@@ -152,11 +136,11 @@ def bn_fit(evaluator, parents, *, method: str = "mle", iss=None, unobserved: str
         offsets = torch.tensor(off, dtype=torch.int64, device=dev)
         cpt = torch.empty(max(off[-1], B * n), dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        lib = evaluator.lib
-        dl.check(lib, lib.dvs_bn_fit(B, n, evaluator.n_samples, _p(evaluator._data), _p(evaluator._card), _p(parents),
-                                     dl.FIT_METHODS[method], iss, UNOBSERVED[unobserved], _p(offsets), _p(cpt), cpt.numel() * 8,
-                                     _p(status), _stream()), "dvs_bn_fit")
-    return FittedBN(parents, evaluator._card, offsets, cpt[:off[-1]], host, card, off)
+        lib, p = evaluator.lib, dl.ptr
+        dl.check(lib, lib.dvs_bn_fit(B, n, evaluator.n_samples, p(evaluator.packed), p(evaluator.card), p(parents),
+                                     dl.FIT_METHODS[method], iss, UNOBSERVED[unobserved], p(offsets), p(cpt), cpt.numel() * 8,
+                                     p(status), dl.stream()), "dvs_bn_fit")
+    return FittedBN(parents, evaluator.card, offsets, cpt[:off[-1]], host, card, off)
 
 
 def sample(fitted: FittedBN, n_rows: int, *, seed: int, row_offset: int = 0, index: int = 0) -> torch.Tensor:
@@ -166,28 +150,23 @@ def sample(fitted: FittedBN, n_rows: int, *, seed: int, row_offset: int = 0, ind
     ``row_offset`` — or spread over devices — and gives the same rows.  A cycle, or a table row that is not a probability
     vector (a NaN or negative cell, a sum further than 1e-9 from 1), raises ValueError."""
     what = "sample"
-    _need_cuda(what, fitted.device)
+    dl.need_cuda(what, fitted.device)
     if not 0 <= int(index) < fitted.batch:
         raise ValueError(f"{what}: index must be in [0, {fitted.batch})")
     if int(n_rows) < 1 or int(row_offset) < 0:
         raise ValueError(f"{what}: n_rows must be >= 1 and row_offset >= 0")
-    n, dev, lib = fitted.n_vars, fitted.device, dl.load()
+    n, dev, lib, p = fitted.n_vars, fitted.device, dl.load(), dl.ptr
     lo, hi = fitted.offsets_host[index * n], fitted.offsets_host[(index + 1) * n]
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.dvs_bn_sample_workspace_bytes(hi - lo, n))
-        if ws_bytes == 0:
-            dl.check(lib, 1, "dvs_bn_sample_workspace_bytes")
+        ws_bytes = dl.workspace_bytes(lib, "dvs_bn_sample_workspace_bytes", hi - lo, n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         out = torch.empty(int(n_rows), (n + 15) // 16, dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_bn_sample(n, int(n_rows), _p(fitted.card), _p(fitted.parents[index]), _p(fitted.offsets[index * n:]),
-                                        _p(fitted.cpt), hi - lo, int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), _p(ws), ws_bytes,
-                                        _p(out), _p(status), _stream()), "dvs_bn_sample")
+        dl.check(lib, lib.dvs_bn_sample(n, int(n_rows), p(fitted.card), p(fitted.parents[index]), p(fitted.offsets[index * n:]),
+                                        p(fitted.cpt), hi - lo, dl.seed64(seed), int(row_offset), p(ws), ws_bytes,
+                                        p(out), p(status), dl.stream()), "dvs_bn_sample")
         st = int(status.item())
-    if st & 1:
-        raise ValueError(f"{what}: the structure has a cycle")
-    if st & 64:
-        raise ValueError(f"{what}: a table row is not a probability vector (a NaN or negative cell, or a sum further than 1e-9 from 1)")
+    dl.check_network_status(what, st)
     if st:
         raise ValueError(f"{what}: the tables do not match the structure (status {st})")
     return out
@@ -199,16 +178,9 @@ def log_likelihood(fitted: FittedBN, data, *, per_row: bool = False):
     [B, S]).  A row that meets theta = 0 counts -inf and one that meets a NaN cell NaN; a level code at or above a variable's
     level count raises ValueError."""
     what = "log_likelihood"
-    _need_cuda(what, fitted.device)
-    n, B, dev, lib = fitted.n_vars, fitted.batch, fitted.device, dl.load()
-    if isinstance(data, BNLearnWrapper):
-        if data.n_vars != n:
-            raise ValueError(f"{what}: the evaluator has {data.n_vars} variables, the network {n}")
-        data = data._data
-    if not torch.is_tensor(data) or data.dtype != torch.int64 or data.ndim != 2 or data.shape[1] != (n + 15) // 16 or data.shape[0] < 1:
-        raise ValueError(f"{what}: data must be an evaluator or packed int64 rows [S >= 1, {(n + 15) // 16}]")
-    _need_cuda(what, data.device)
-    data = data.contiguous()
+    dl.need_cuda(what, fitted.device)
+    n, B, dev, lib, p = fitted.n_vars, fitted.batch, fitted.device, dl.load(), dl.ptr
+    data = dl.packed_rows(what, data, n)
     S = data.shape[0]
     up = lambda x: (x + 255) & ~255
     chunks = (S + 255) // 256
@@ -218,9 +190,9 @@ def log_likelihood(fitted: FittedBN, data, *, per_row: bool = False):
         rows = torch.empty(B, S, dtype=torch.float64, device=dev) if per_row else None
         out = torch.empty(B, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_bn_loglik(B, n, S, _p(data), _p(fitted.card), _p(fitted.parents), _p(fitted.offsets), _p(fitted.cpt),
-                                        _p(rows), _p(out), _p(ws), ws_bytes, _p(status), _stream()), "dvs_bn_loglik")
-        if int(status.item()) & 16:
+        dl.check(lib, lib.dvs_bn_loglik(B, n, S, p(data), p(fitted.card), p(fitted.parents), p(fitted.offsets), p(fitted.cpt),
+                                        p(rows), p(out), p(ws), ws_bytes, p(status), dl.stream()), "dvs_bn_loglik")
+        if int(status.item()) & dl.STATUS_REFUSED:
             raise ValueError(f"{what}: a row has a level code at or above its variable's level count, or the tables do not match the structure")
     return (out, rows) if per_row else out
 
@@ -249,7 +221,7 @@ def cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 0, method
     is the argument of "pred-lw" alone; a row that predicts 255 counts as wrong).  "pred-lw" runs one likelihood-weighting call
     per structure and part; the other two take the whole batch of structures in one call per part.  bnlearn has "pred" and "pred-lw"; "pred-exact" is what "pred-lw" approximates."""
     what = "cross_validate"
-    _need_cuda(what, evaluator.device)
+    dl.need_cuda(what, evaluator.device)
     S = evaluator.n_samples
     if not 2 <= int(folds) <= S:
         raise ValueError(f"{what}: folds must be in [2, {S}]")
@@ -269,10 +241,10 @@ def cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 0, method
         done = 0
         for f, part in enumerate(parts):
             rest = torch.cat([p for g, p in enumerate(parts) if g != f])
-            train = BNLearnWrapper.from_packed(evaluator.dataset_name, evaluator.metric_name, evaluator._data[rest],
-                                               evaluator._card_host, iss=evaluator.iss, k=evaluator.k)
+            train = BNLearnWrapper.from_packed(evaluator.dataset_name, evaluator.metric_name, evaluator.packed[rest],
+                                               evaluator.card_host, iss=evaluator.iss, k=evaluator.k)
             fitted = bn_fit(train, parents, method=method, iss=iss)
-            held = evaluator._data[part]
+            held = evaluator.packed[part]
             if loss == "logl":
                 ll = log_likelihood(fitted, held)
             else:

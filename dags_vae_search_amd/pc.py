@@ -11,7 +11,6 @@ bnlearn's ``ci.test`` / ``pc.stable`` rests on them and is not pinned against an
 """
 from __future__ import annotations
 
-import ctypes
 from math import comb
 from typing import List, NamedTuple, Optional
 
@@ -34,18 +33,9 @@ class PCResult(NamedTuple):
     flags: int                             # 0, or 1 when the directed part of ``pdag`` has a cycle
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _evaluator(what, evaluator):
-    if evaluator.device.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {evaluator.device}); this package has no CPU path")
-    return evaluator._card_host
+    dl.need_cuda(what, evaluator.device)
+    return evaluator.card_host
 
 
 def _test_type(test):
@@ -63,11 +53,11 @@ def _max_cells(card, level):
 
 
 def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk):
-    lib, T = evaluator.lib, cond.numel()
+    lib, T, p = evaluator.lib, cond.numel(), dl.ptr
     for t0 in range(0, T, chunk):
         m = min(chunk, T - t0)
-        dl.check(lib, lib.dvs_ci_tests(m, evaluator.n_vars, evaluator.n_samples, _p(evaluator._data), _p(evaluator._card),
-                                       _p(pairs[t0:]), _p(cond[t0:]), typ, max_cells, _p(out[t0:]), m * 24, _p(status), _stream()),
+        dl.check(lib, lib.dvs_ci_tests(m, evaluator.n_vars, evaluator.n_samples, p(evaluator.packed), p(evaluator.card),
+                                       p(pairs[t0:]), p(cond[t0:]), typ, max_cells, p(out[t0:]), m * 24, p(status), dl.stream()),
                  "dvs_ci_tests")
 
 
@@ -149,7 +139,7 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
         raise ValueError("chunk must be >= 1")
     if max_cond is not None and int(max_cond) < 0:
         raise ValueError("max_cond must be >= 0 or None")
-    dev, n, lib = evaluator.device, evaluator.n_vars, evaluator.lib
+    dev, n, lib, p = evaluator.device, evaluator.n_vars, evaluator.lib, dl.ptr
     full = (1 << n) - 1
     adj = [full & ~(1 << v) for v in range(n)]
     tests_per_level, refused_total = [], 0
@@ -178,11 +168,11 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
             cond = torch.empty(T, dtype=torch.int64, device=dev)
             out = torch.empty(T, 3, dtype=torch.float64, device=dev)
             result = torch.empty(P, 2, dtype=torch.int64, device=dev)
-            dl.check(lib, lib.dvs_pc_expand(P, n, level, _p(d_adj), _p(d_xy), _p(d_off), T, _p(pairs), _p(cond), T * 8, _stream()),
+            dl.check(lib, lib.dvs_pc_expand(P, n, level, p(d_adj), p(d_xy), p(d_off), T, p(pairs), p(cond), T * 8, dl.stream()),
                      "dvs_pc_expand")
             _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk)
-            dl.check(lib, lib.dvs_pc_reduce(P, n, _p(d_xy), _p(d_off), T, _p(cond), _p(out), float(alpha), _p(d_adj), _p(d_next),
-                                            _p(sepsets), n * n * 8, _p(result), P * 16, _p(refused), _stream()), "dvs_pc_reduce")
+            dl.check(lib, lib.dvs_pc_reduce(P, n, p(d_xy), p(d_off), T, p(cond), p(out), float(alpha), p(d_adj), p(d_next),
+                                            p(sepsets), n * n * 8, p(result), P * 16, p(refused), dl.stream()), "dvs_pc_reduce")
             adj = [int(a) for a in d_next.cpu().numpy().view(np.uint64)]        # the level's one read-back
             refused_total += int(refused.cpu()[0])
             tests_per_level.append(T)
@@ -191,8 +181,8 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
         pdag = torch.empty(n, dtype=torch.int64, device=dev)
         conflicts = torch.empty(1, dtype=torch.int32, device=dev)
         flags = torch.empty(1, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_pc_orient(1, n, _p(skeleton), _p(sepsets), n * n * 8, _p(pdag), n * 8, _p(conflicts), _p(flags),
-                                        _stream()), "dvs_pc_orient")
+        dl.check(lib, lib.dvs_pc_orient(1, n, p(skeleton), p(sepsets), n * n * 8, p(pdag), n * 8, p(conflicts), p(flags),
+                                        dl.stream()), "dvs_pc_orient")
         conflicts, flags = int(conflicts.cpu()[0]), int(flags.cpu()[0])
     return PCResult(pdag, skeleton, sepsets, tests_per_level, refused_total, conflicts, flags)
 
@@ -203,8 +193,7 @@ def skeleton_blacklist(skeleton: torch.Tensor) -> torch.Tensor:
     what = "skeleton_blacklist"
     if not torch.is_tensor(skeleton):
         raise TypeError(f"{what}: skeleton must be a torch tensor of adjacency rows")
-    if skeleton.device.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: {what} runs on the GPU (got device {skeleton.device}); this package has no CPU path")
+    dl.need_cuda(what, skeleton.device)
     if skeleton.dtype != torch.int64 or skeleton.ndim != 1 or not 1 <= skeleton.shape[0] <= MAX_VARS:
         raise ValueError(f"{what}: skeleton must be int64 [n <= 48] adjacency rows")
     n = skeleton.shape[0]

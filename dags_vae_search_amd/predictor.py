@@ -24,7 +24,6 @@ per-query work (mean, variance, EI and its gradient) is one HIP launch (csrc/k_g
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict
@@ -67,7 +66,7 @@ def vfe_loss_and_grad(lib, stream, X: torch.Tensor, y: torch.Tensor, flat: torch
     Z = flat[:M * D].view(M, D)
     rn, rc, ro, rl = raw if raw is not None else flat[M * D:].tolist()
     s2, o, l, c = _sp(rn) + 1e-4, _sp(ro), _sp(rl), rc
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = dl.ptr
     f64 = dict(dtype=torch.float64, device=dev)
     Kuu = torch.empty(M, M, **f64)
     Kuf = torch.empty(M, n, **f64)
@@ -200,10 +199,10 @@ class GPRegressionModel:
         m = torch.zeros_like(flat)
         v = torch.zeros_like(flat)
         scratch = torch.zeros(dl.CLIP_SCRATCH_FLOATS, dtype=torch.float32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = dl.ptr
         hist = []
         for it in range(1, iterations + 1):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = dl.stream()
             loss, grad = vfe_loss_and_grad(self.lib, stream, X, y, flat, M)
             dl.check(self.lib, self.lib.dvs_clip_adam(flat.numel(), p(flat), p(grad), p(m), p(v), lr, 0.9, 0.999, 1e-8, it, -1.0,
                                                       p(scratch), None, stream), "dvs_clip_adam")
@@ -235,11 +234,10 @@ class GPRegressionModel:
         if D != self.inducing_points.shape[1]:
             raise AssertionError(f"Expected latent vectors of size {self.inducing_points.shape[1]}, got {D}")
         out = torch.empty(B, dtype=torch.float64, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = dl.ptr
         dl.check(self.lib, self.lib.dvs_gp_predict(B, self.inducing_points.shape[0], D, p(x), p(self.inducing_points),
                                                    p(self._alpha), self.outputscale, self.lengthscale, self.constant,
-                                                   p(out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                 "dvs_gp_predict")
+                                                   p(out), dl.stream()), "dvs_gp_predict")
         return out
 
 
@@ -317,11 +315,10 @@ class GPRegressionModel:
             out = (torch.empty(B, **f64), torch.empty(B, **f64), torch.empty(B, **f64),
                    torch.empty(B, D, dtype=torch.float32, device=self.device) if grad else None)
         mean, var, ei, g = out
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = dl.ptr
         dl.check(self.lib, self.lib.dvs_gp_acquire(B, M, D, M + 1, p(x), p(self.inducing_points), p(W), float(c0),
                                                    self.outputscale, self.lengthscale, self.constant, float(best), float(xi),
-                                                   p(mean), p(var), p(ei), p(g) if grad else None,
-                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                   p(mean), p(var), p(ei), p(g) if grad else None, dl.stream()),
                  "dvs_gp_acquire")
         return mean, var, ei, (g if grad else None)
 

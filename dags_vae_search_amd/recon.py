@@ -15,7 +15,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib as dl
-from .engine import _nbytes, _ptr, _require_cuda, _stream
+from ._lib import nbytes, ptr, require_cuda, stream
 from .features import _as_labels_edges
 from .records import CompactBatch, encode_graphs
 
@@ -29,7 +29,7 @@ def match_decoded(targets: CompactBatch, states: torch.Tensor, repeats: int, car
     """Flags (device uint8 [B * repeats]) of decoded rows ``states`` (device uint8 [B * repeats, DECODE_STATE_BYTES], row k
     decoded from target k // repeats): bit 0 ``LabeledDag.is_valid_graph``, bit 1 ``graph_equals(attributes_match=False)``,
     bit 2 ``graph_equals``, bit 3 undecided (bits 1-2 unspecified).  ``card``: the toolkit's label cardinality."""
-    _require_cuda(states, "states")
+    require_cuda(states, "states")
     lib = dl.load()
     dev = states.device
     B, n = targets.labels.shape
@@ -41,8 +41,8 @@ def match_decoded(targets: CompactBatch, states: torch.Tensor, repeats: int, car
     preds = targets.preds.to(dev).contiguous().to(torch.int64 if wide else torch.int16)
     states = states.contiguous()
     flags = torch.empty(rows, dtype=torch.uint8, device=dev)
-    dl.check(lib, lib.dvs_match_decoded(B, n, int(card), int(repeats), 1 if wide else 0, _ptr(labels), _ptr(preds),
-                                        _ptr(states), _nbytes(states), int(budget), _ptr(flags), _stream()),
+    dl.check(lib, lib.dvs_match_decoded(B, n, int(card), int(repeats), 1 if wide else 0, ptr(labels), ptr(preds),
+                                        ptr(states), nbytes(states), int(budget), ptr(flags), stream()),
              "dvs_match_decoded")
     return flags
 

@@ -25,7 +25,6 @@ label-permutation data sets (every vertex stands for its own variable: asia, sac
 """
 from __future__ import annotations
 
-import ctypes
 import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -34,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib as dl
-from .engine import _nbytes, _ptr, _require_cuda, _stream
+from ._lib import nbytes, ptr, require_cuda, stream
 from .features import LabeledDag, _as_labels_edges
 from .predictor import expected_improvement_host
 from .records import CompactBatch, decode_graphs, encode_graphs
@@ -127,7 +126,7 @@ def hash_keys(keys: torch.Tensor, hash_mask: int = _ALL_ONES) -> torch.Tensor:
 
 
 def _decoded_structures(states: torch.Tensor, n: int, hash_mask: int = _ALL_ONES):
-    _require_cuda(states, "states")
+    require_cuda(states, "states")
     if states.dtype != torch.uint8 or states.dim() != 2 or states.shape[1] != dl.DECODE_STATE_BYTES:
         raise AssertionError(f"Expected states uint8 [B, {dl.DECODE_STATE_BYTES}], got {states.dtype} {tuple(states.shape)}")
     lib = dl.load()
@@ -141,9 +140,9 @@ def _decoded_structures(states: torch.Tensor, n: int, hash_mask: int = _ALL_ONES
     keys = torch.empty(B, n, dtype=torch.int64, device=dev)
     hashes = torch.empty(B, dtype=torch.int64, device=dev)
     if B:
-        dl.check(lib, lib.dvs_decoded_structures(B, n, 1 if wide else 0, _ptr(states), _nbytes(states), hash_mask & _ALL_ONES,
-                                                 _ptr(flags), _ptr(labels), _ptr(preds), _ptr(keys), _nbytes(keys),
-                                                 _ptr(hashes), _stream()), "dvs_decoded_structures")
+        dl.check(lib, lib.dvs_decoded_structures(B, n, 1 if wide else 0, ptr(states), nbytes(states), hash_mask & _ALL_ONES,
+                                                 ptr(flags), ptr(labels), ptr(preds), ptr(keys), nbytes(keys),
+                                                 ptr(hashes), stream()), "dvs_decoded_structures")
     return flags, CompactBatch(labels, preds), keys, hashes
 
 
@@ -182,7 +181,7 @@ class StructureSet:
 
     def _verdicts(self, keys: torch.Tensor, hashes: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
         """FILTER_NEW / FILTER_SEEN / FILTER_DUPLICATE / 0 per row (uint8 [B]); the set is not changed."""
-        _require_cuda(keys, "keys")
+        require_cuda(keys, "keys")
         B = keys.shape[0]
         if tuple(keys.shape) != (B, self.n_vars) or keys.dtype != torch.int64 or tuple(hashes.shape) != (B,) or \
                 hashes.dtype != torch.int64 or tuple(flags.shape) != (B,) or flags.dtype != torch.uint8:
@@ -194,9 +193,9 @@ class StructureSet:
         keys, flags = keys.contiguous(), flags.contiguous()
         sorted_hashes, order = torch.sort(hashes, stable=True)      # equal hashes stay in draw order
         S = len(self)
-        dl.check(lib, lib.dvs_structset_filter(B, self.n_vars, _ptr(sorted_hashes), _ptr(order), _ptr(keys), _nbytes(keys),
-                                               _ptr(flags), S, _ptr(self.hashes) if S else None,
-                                               _ptr(self.keys) if S else None, _nbytes(self.keys), _ptr(out), _stream()),
+        dl.check(lib, lib.dvs_structset_filter(B, self.n_vars, ptr(sorted_hashes), ptr(order), ptr(keys), nbytes(keys),
+                                               ptr(flags), S, ptr(self.hashes) if S else None,
+                                               ptr(self.keys) if S else None, nbytes(self.keys), ptr(out), stream()),
                  "dvs_structset_filter")
         return out
 
@@ -298,13 +297,11 @@ def optimize_acquisition(gp, starts: torch.Tensor, lo: torch.Tensor, hi: torch.T
     m = torch.zeros_like(x)
     v = torch.zeros_like(x)
     scratch = torch.zeros(dl.CLIP_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
     for it in range(1, steps + 1):
         _, _, _, g = gp._acquire(x, best, xi, variance, grad=True, out=bufs)
         g.neg_()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        dl.check(gp.lib, gp.lib.dvs_clip_adam(x.numel(), p(x), p(g), p(m), p(v), lr, 0.9, 0.999, 1e-8, it, -1.0, p(scratch),
-                                              None, stream), "dvs_clip_adam")
+        dl.check(gp.lib, gp.lib.dvs_clip_adam(x.numel(), ptr(x), ptr(g), ptr(m), ptr(v), lr, 0.9, 0.999, 1e-8, it, -1.0,
+                                              ptr(scratch), None, stream()), "dvs_clip_adam")
         torch.maximum(torch.minimum(x, hi), lo, out=x)
     ei = gp.expected_improvement(x, best, xi, variance)
     return x, ei

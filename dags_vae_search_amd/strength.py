@@ -14,7 +14,6 @@ Parity with an R run is not pinned.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from fractions import Fraction
@@ -23,30 +22,21 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import _lib as dl
-from .compare import _cpdag, _masks
+from .compare import cpdag_of
 from .hillclimb import hill_climb
 from .tabu import tabu_search
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def bootstrap_rows(n_sets: int, set_size: int, n_samples: int, *, seed: int, set_offset: int = 0, device="cuda") -> torch.Tensor:
     """int32 [n_sets, set_size] row indices drawn with replacement from 0 .. n_samples - 1 (dvs_bootstrap_rows).  Set r is a
     function of (``seed``, ``set_offset`` + r) only, so a request may be cut into calls or shards."""
     device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: bootstrap_rows runs on the GPU (got device {device}); this package has no CPU path")
+    dl.need_cuda("bootstrap_rows", device)
     lib = dl.load()
     with torch.cuda.device(device):
         rows = torch.empty(int(n_sets), int(set_size), dtype=torch.int32, device=device)
-        dl.check(lib, lib.dvs_bootstrap_rows(int(n_sets), int(set_size), int(n_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                             int(set_offset), _p(rows), _stream()), "dvs_bootstrap_rows")
+        dl.check(lib, lib.dvs_bootstrap_rows(int(n_sets), int(set_size), int(n_samples), dl.seed64(seed),
+                                             int(set_offset), dl.ptr(rows), dl.stream()), "dvs_bootstrap_rows")
     return rows
 
 
@@ -84,7 +74,7 @@ class ArcStrength:
 def _accumulate(counts: torch.Tensor, pdag: torch.Tensor):
     lib = dl.load()
     B, n = pdag.shape
-    dl.check(lib, lib.dvs_arc_strength(B, n, _p(pdag), _p(counts), counts.numel() * 4, _stream()), "dvs_arc_strength")
+    dl.check(lib, lib.dvs_arc_strength(B, n, dl.ptr(pdag), dl.ptr(counts), counts.numel() * 4, dl.stream()), "dvs_arc_strength")
 
 
 def arc_strength(structures: torch.Tensor, *, cpdag: bool = True) -> ArcStrength:
@@ -92,9 +82,9 @@ def arc_strength(structures: torch.Tensor, *, cpdag: bool = True) -> ArcStrength
     ``cpdag=False``.  ``cpdag=True`` (boot.strength's default) counts over the CPDAGs of the DAGs, so an arc that is
     reversible within its equivalence class counts half for either direction."""
     what = "arc_strength"
-    x = _masks(what, "structures", structures)
+    x = dl.parent_masks(what, "structures", structures)
     if cpdag:
-        x = _cpdag(what, "structures", x)
+        x = cpdag_of(what, "structures", x)
     n = x.shape[1]
     with torch.cuda.device(x.device):
         counts = torch.zeros(n, n, 2, dtype=torch.int32, device=x.device)
@@ -140,7 +130,7 @@ def boot_strength(evaluator, *, replicates: int = 200, m: Optional[int] = None, 
             rows = bootstrap_rows(b, size, evaluator.n_samples, seed=seed, set_offset=set_offset + at, device=dev)
             res = search(evaluator.with_rows(rows), batch=b, **args)
             exhausted += int((res.converged == 0).sum())
-            _accumulate(counts, _cpdag("boot_strength", "networks", res.parents) if cpdag else res.parents.contiguous())
+            _accumulate(counts, cpdag_of("boot_strength", "networks", res.parents) if cpdag else res.parents.contiguous())
             if return_networks:
                 nets.append(res.parents)
     return ArcStrength(counts[..., 0].contiguous(), counts[..., 1].contiguous(), R, exhausted,
@@ -157,10 +147,9 @@ class AveragedNetwork:
 
 
 def _averaged(strength: ArcStrength, min_any: Sequence[int]):
-    lib = dl.load()
+    lib, p = dl.load(), dl.ptr
     dev = strength.any.device
-    if dev.type != "cuda":
-        raise RuntimeError(f"dags_vae_search_amd: averaged_network runs on the GPU (got device {dev}); this package has no CPU path")
+    dl.need_cuda("averaged_network", dev)
     n, G = strength.any.shape[0], len(min_any)
     with torch.cuda.device(dev):
         counts = torch.stack([strength.any, strength.dir2], -1).to(torch.int32)[None].expand(G, n, n, 2).contiguous()
@@ -168,8 +157,8 @@ def _averaged(strength: ArcStrength, min_any: Sequence[int]):
         ma = torch.tensor([int(x) for x in min_any], dtype=torch.int32, device=dev)
         parents = torch.empty(G, n, dtype=torch.int64, device=dev)
         info = torch.empty(G, 4, dtype=torch.int32, device=dev)
-        dl.check(lib, lib.dvs_averaged_network(G, n, _p(counts), _p(nn), _p(ma), _p(parents), parents.numel() * 8, _p(info),
-                                               _stream()), "dvs_averaged_network")
+        dl.check(lib, lib.dvs_averaged_network(G, n, p(counts), p(nn), p(ma), p(parents), parents.numel() * 8, p(info),
+                                               dl.stream()), "dvs_averaged_network")
     return parents, info.cpu().tolist()
 
 

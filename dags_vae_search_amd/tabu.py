@@ -48,7 +48,7 @@ def tabu_search(evaluator, starts=None, *, batch: Optional[int] = None, max_step
     if max_tabu < 1:
         raise ValueError("max_tabu must be >= 1")
     s = _Search("tabu_search", evaluator, starts, batch, max_steps, max_parents, forbidden, check_every, restarts, perturb, trace)
-    lib, B, n, p = s.lib, s.B, s.n, s.p
+    lib, B, n, p = s.lib, s.B, s.n, dl.ptr
     with torch.cuda.device(s.dev):
         ring = torch.zeros(B, int(tabu), n, dtype=torch.int64, device=s.dev)
         visited = torch.zeros(B, dtype=torch.int32, device=s.dev)

@@ -86,7 +86,7 @@ def test_bn_fit_surface_equals_the_raw_call_and_refuses_an_oversized_family():
     from dags_vae_search_amd import BNLearnWrapper, FittedBN, bn_fit
     case = pm.fit_case("sixS1000")
     ev = BNLearnWrapper("six", "bic", data=case.data)
-    ev = BNLearnWrapper.from_packed("six", "bic", ev._data, case.card)          # card as given: variable 1 misses its top level
+    ev = BNLearnWrapper.from_packed("six", "bic", ev.packed, case.card)          # card as given: variable 1 misses its top level
     offsets = pm.offsets_of(case.card, case.masks)
     for method, iss, unobserved in (("mle", None, "nan"), ("mle", None, "uniform"), ("bayes", 10.0, "nan")):
         f = bn_fit(ev, _dev_masks(case.masks), method=method, iss=iss, unobserved=unobserved)
@@ -125,7 +125,7 @@ def test_sample_surface_from_tables_chunks_and_from_packed_scores():
     masks = _dev_masks(np.stack([net.masks, np.zeros(3, U64)]))
     packed = BNLearnWrapper.from_packed("hand", "bic", rows, net.card)
     unpacked = BNLearnWrapper("hand", "bic", data=ref)
-    assert packed._card_host == unpacked._card_host                              # every level was drawn here
+    assert packed.card_host == unpacked.card_host                              # every level was drawn here
     assert packed.score_masks(masks).cpu().numpy().tobytes() == unpacked.score_masks(masks).cpu().numpy().tobytes()
     bde = BNLearnWrapper.from_packed("hand", "bde", rows, net.card, iss=10.0)
     assert bde.score_masks(masks).cpu().numpy().tobytes() == \
@@ -150,7 +150,7 @@ def test_log_likelihood_surface_equals_the_raw_call():
     out, rows = log_likelihood(f, ev, per_row=True)
     assert out.is_cuda and out.dtype == torch.float64 and rows.shape == (3, 1000)
     assert out.cpu().numpy().tobytes() == raw_out.tobytes() and rows.cpu().numpy().tobytes() == raw_rows.tobytes()
-    assert log_likelihood(f, ev._data).cpu().numpy().tobytes() == raw_out.tobytes()
+    assert log_likelihood(f, ev.packed).cpu().numpy().tobytes() == raw_out.tobytes()
     high = data.copy()
     high[7, 3] = 5
     with pytest.raises(ValueError, match="level code"):

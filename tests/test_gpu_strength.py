@@ -105,7 +105,7 @@ def test_bootstrap_rows_and_with_rows_validation():
     got = view.score_masks(P)
     for b in range(6):                                                     # structure b on set b = the gathered evaluator
         from dags_vae_search_amd import BNLearnWrapper
-        one = BNLearnWrapper.from_packed("asia", "bic", ev._data[rows[b].long()], ev._card_host)
+        one = BNLearnWrapper.from_packed("asia", "bic", ev.packed[rows[b].long()], ev.card_host)
         assert st.same_bytes(one.score_masks(P[b:b + 1]).cpu().numpy(), got[b:b + 1].cpu().numpy())
     with pytest.raises(ValueError, match="row sets"):
         view.score_masks(torch.cat([P, P]))
@@ -183,7 +183,7 @@ def _plain_replicates(ev, metric, search, replicates, seed, **kw):
     rows = bootstrap_rows(replicates, ev.n_samples, ev.n_samples, seed=seed)
     out = []
     for r in range(replicates):
-        one = BNLearnWrapper.from_packed("asia", metric, ev._data[rows[r].long()], ev._card_host, iss=ev.iss)
+        one = BNLearnWrapper.from_packed("asia", metric, ev.packed[rows[r].long()], ev.card_host, iss=ev.iss)
         out.append(search(one, batch=1, **kw).parents)
     return out
 
