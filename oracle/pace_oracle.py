@@ -310,12 +310,13 @@ def loss_direct(P, cfg: PaceConfig, features: Dict, beta: float = 0.005, trainin
 
 class OracleTrainer:
     """train_batch (experiments/03_synthetic_12/main.py:95-118) over leaf parameter tensors:
-    zero_grad, loss_direct(train), backward, clip_grad_norm_(1.0), Adam(lr 1e-4) step."""
+    zero_grad, loss_direct(train), backward, clip_grad_norm_(1.0), Adam(lr 1e-4) step.  ``dtype`` = torch.float64 keeps the
+    parameters and the optimiser state in double precision (the features passed to ``step`` must match)."""
 
     def __init__(self, cfg: PaceConfig, params: Dict[str, torch.Tensor], lr: float = 1e-4,
-                 max_grad_norm: float = 1.0):
+                 max_grad_norm: float = 1.0, dtype: torch.dtype = torch.float32):
         self.cfg = cfg
-        self.P = {k: v.clone().float().requires_grad_(True) for k, v in params.items()}
+        self.P = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in params.items()}
         self.opt = torch.optim.Adam(list(self.P.values()), lr=lr)
         self.max_grad_norm = max_grad_norm
 

@@ -36,6 +36,16 @@ class EmuModel:
         self.record_bytes = dl.record_bytes(self.lib, self.shape)
         self.records = np.zeros(batch * self.record_bytes, np.uint8)
         self.batch = batch
+        # optimiser state of a multi-step run (clip_adam): the gradient of the last backward, the flat moments, the clip scratch
+        self.grads = None
+        self.exp_avg = np.zeros(self.P, np.float32)
+        self.exp_avg_sq = np.zeros(self.P, np.float32)
+        self.clip_scratch = np.zeros(dl.CLIP_SCRATCH_FLOATS, np.float32)
+
+    def advance_seed(self):
+        """The next step's mask seed, as PaceVaeV3._next_seed counts it: the low word of shape.seed is the step number."""
+        self.shape.seed = dl.seed64(self.shape.seed + 1)
+        return int(self.shape.seed)
 
     def pack(self, feats):
         lab = np.ascontiguousarray(feats["vertex_label_features"], np.float32)
@@ -72,7 +82,38 @@ class EmuModel:
             dl.check(self.lib, self.lib.dvs_loss_backward(ctypes.byref(self.shape), ptr(self.records), self.records.nbytes,
                                                           ptr(self.flat), self.flat.size, ptr(self.ws), self.ws.nbytes,
                                                           ptr(gcoef), ptr(grads), None), "backward")
+        self.grads = grads
         return {name: grads[off:off + int(np.prod(shp))].reshape(shp) for name, off, shp in self.table}, grads
+
+    def _step_args(self):
+        return (ctypes.byref(self.shape), ptr(self.records), self.records.nbytes, ptr(self.flat), self.flat.size, ptr(self.ws),
+                self.ws.nbytes)
+
+    def forward_defer(self, eps=None):
+        """dvs_loss_forward_defer: the forward without the loss head; backward_emit must follow."""
+        e = None if eps is None else np.ascontiguousarray(eps, np.float32)
+        dl.check(self.lib, self.lib.dvs_loss_forward_defer(*self._step_args(), ptr(e), None, None, None), "forward_defer")
+
+    def backward_emit(self, host_seq, g_recon=1.0, g_kld=0.005, clip_scratch=None):
+        """dvs_loss_backward_emit behind forward_defer -> (flat gradient, losses, the 16-byte host packet as uint32[4])."""
+        gcoef = np.asarray([g_recon, g_kld], np.float32)
+        self.grads = np.full(self.P, np.nan, np.float32)
+        losses = np.full(dl.LOSS_FLOATS, np.nan, np.float32)
+        buf = np.zeros(8, np.float32)
+        tail = buf[(-buf.ctypes.data % 16) // 4:][:4]             # the packet is one 16-byte store: aligned
+        dl.check(self.lib, self.lib.dvs_loss_backward_emit(*self._step_args(), ptr(gcoef), ptr(self.grads), ptr(clip_scratch),
+                                                           ptr(self.status), ptr(losses), ptr(tail), host_seq, None),
+                 "backward_emit")
+        return self.grads, losses, tail.view(np.uint32).copy()
+
+    def clip_adam(self, step, lr, max_norm, from_partials=False, guard=None, betas=(0.9, 0.999), eps=1e-8):
+        """dvs_clip_adam / dvs_clip_adam_from_partials over the flat buffers: parameters, the last backward's gradient (clipped
+        in place), the moments; self.clip_scratch holds [sum of squares, coefficient, partials] (from_partials: a backward with
+        clip_scratch=self.clip_scratch wrote the partials)."""
+        fn = self.lib.dvs_clip_adam_from_partials if from_partials else self.lib.dvs_clip_adam
+        g = None if guard is None else np.ascontiguousarray(guard, np.float32)
+        dl.check(self.lib, fn(self.P, ptr(self.flat), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), lr, betas[0],
+                              betas[1], eps, int(step), float(max_norm), ptr(self.clip_scratch), ptr(g), None), "clip_adam")
 
     def activation(self, slot):
         out = np.zeros((self.batch, 16 * ((self.cfg.N + 15) // 16), 64), np.float32)

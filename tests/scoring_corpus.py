@@ -10,7 +10,7 @@ References
         free-standing: wherever q * r <= 2^24 it must equal oracle.bic.local_score to 1e-12 (bic_reference asserts it).
   GP    gp_kernel_ref / gp_kernel_backward_ref / gp_predict_ref: the formulas of include/dvs.h in float64, points taken as
         float32 and promoted.
-  Adam  clip_adam_ref: torch.nn.utils.clip_grad_norm_ + torch.optim.Adam on the CPU in float64.
+  Adam  adam_ref / clip_adam_ref: torch.nn.utils.clip_grad_norm_ + torch.optim.Adam on the CPU in float64.
 
 Tolerances are derived, not measured.
   BIC, dvs_gp_kernel, dvs_gp_kernel_backward: fp64 on both sides.  An output is a sum of at most S (BIC) or nb (GP) terms,
@@ -742,21 +742,53 @@ def adam_inputs(n):
 HYPER = tuple(float(np.float32(x)) for x in (0.05, 0.9, 0.999, 1e-8))       # lr, betas, eps as the float32 the ABI carries
 
 
-def clip_adam_ref(p, g, m, v, max_norm):
-    """torch.nn.utils.clip_grad_norm_ + torch.optim.Adam in float64 on the CPU, from the given moments at ADAM_STEP."""
+def adam_ref(p, g, m, v, step, hyper=HYPER, max_norm=None):
+    """torch.optim.Adam in float64 on the CPU: step number `step` (1-based) from the given moments, behind
+    torch.nn.utils.clip_grad_norm_ when `max_norm` is given.  `hyper` = (lr, beta1, beta2, eps).  Returns (norm before
+    clipping or None, the gradient Adam saw, exp_avg, exp_avg_sq, parameters)."""
     import torch
-    lr, b1, b2, eps = HYPER
+    lr, b1, b2, eps = hyper
     w = torch.nn.Parameter(torch.from_numpy(p.astype(np.float64)))
     w.grad = torch.from_numpy(g.astype(np.float64))
     opt = torch.optim.Adam([w], lr=lr, betas=(b1, b2), eps=eps)
-    opt.state[w] = {"step": torch.tensor(float(ADAM_STEP - 1)), "exp_avg": torch.from_numpy(m.astype(np.float64)),
+    opt.state[w] = {"step": torch.tensor(float(step - 1)), "exp_avg": torch.from_numpy(m.astype(np.float64)),
                     "exp_avg_sq": torch.from_numpy(v.astype(np.float64))}
-    norm = float(torch.nn.utils.clip_grad_norm_([w], float(max_norm)))
+    norm = None if max_norm is None else float(torch.nn.utils.clip_grad_norm_([w], float(max_norm)))
     clipped = w.grad.detach().numpy().copy()
     opt.step()
     st = opt.state[w]
-    assert int(st["step"]) == ADAM_STEP
+    assert int(st["step"]) == step
     return norm, clipped, st["exp_avg"].numpy().copy(), st["exp_avg_sq"].numpy().copy(), w.detach().numpy().copy()
+
+
+def clip_adam_ref(p, g, m, v, max_norm):
+    """torch.nn.utils.clip_grad_norm_ + torch.optim.Adam in float64 on the CPU, from the given moments at ADAM_STEP."""
+    return adam_ref(p, g, m, v, ADAM_STEP, HYPER, max_norm)
+
+
+def bias_correction_rounding(b1, b2, step):
+    """Relative error of the parameter update that the float32 bias corrections 1 - powf(b, step) can add.  powf is within
+    one ulp (2 * 2^-24 relative) of b^step; the subtraction from 1 is exact for b^step >= 0.5 and one rounding otherwise,
+    but it turns that ulp into b^step / (1 - b^step) ulps of the difference.  The update is proportional to
+    sqrt(1 - b2^step) / (1 - b1^step), so beta2's share enters by half."""
+    a1, a2 = b1 ** step / (1.0 - b1 ** step), b2 ** step / (1.0 - b2 ** step)
+    return 2 * F32_EPS * (a1 + 0.5 * a2)
+
+
+def adam_tolerances(p, gc, m, v, upd, b1, b2, rcoef=0.0, rbias=0.0, floor=0.0, upd_terms=None):
+    """Per-element tolerances (exp_avg, exp_avg_sq, parameters) of one float32 Adam step, derived in check_clip_adam's
+    docstring: 8 * 2^-24 of the absolute terms each quantity is made of, `rcoef` (relative error of a clip coefficient that
+    the reference gradient `gc` does not carry yet) once on exp_avg's gradient term and twice on exp_avg_sq's and on the
+    update `upd` = |new p - p|, `rbias` (bias_correction_rounding) on the update, `floor` absolute (float32 underflow).
+    `upd_terms`: the update's absolute terms where they are not |upd| itself: the update is a ratio exp_avg / denominator, so
+    when b1 m and (1 - b1) g cancel in exp_avg its terms are (b1 |m| + (1 - b1) |g|) / |exp_avg| times larger than it."""
+    p, gc, m, v = (np.abs(np.asarray(a, np.float64)) for a in (p, gc, m, v))
+    t1, t2 = b1 * m, (1 - b1) * gc
+    tol_m = 8 * F32_EPS * (t1 + t2) + rcoef * t2 + floor
+    t1, t2 = b2 * v, (1 - b2) * gc * gc
+    tol_v = 8 * F32_EPS * (t1 + t2) + 2 * rcoef * t2 + floor
+    tol_p = 8 * F32_EPS * (p + (upd if upd_terms is None else upd_terms)) + (2 * rcoef + rbias) * upd + floor
+    return tol_m, tol_v, tol_p
 
 
 def run_clip_adam(be, n, p, g, m, v, max_norm, guard=(0.0, 0.0), partials=None):
@@ -783,7 +815,8 @@ def check_clip_adam(be, n):
     (1 - b1) g c once, exp_avg_sq's (1 - b2) (g c)^2 twice, the parameter update (a ratio m / sqrt(v)) at most twice; a
     parameter's absolute terms are |p| and |update|.  The library's float32 bias corrections 1 - powf(b, 7) (the subtraction
     amplifies powf's rounding by b^7 / (1 - b^7), 142 for b = 0.999: about 4e-6 of the update) get no term of their own:
-    they fit inside 8 * 2^-24 |p| here (measured worst |P - ref| / tolerance: 0.14 on the emulator build)."""
+    they fit inside 8 * 2^-24 |p| here (measured worst |P - ref| / tolerance: 0.14 on the emulator build); at small steps
+    they do not, and tests/train_steps_common.py adds bias_correction_rounding.  adam_tolerances holds the arithmetic."""
     lr, b1, b2, eps = HYPER
     p, g, m, v, max_norm = adam_inputs(n)
     norm, cg, cm, cv, cp = clip_adam_ref(p, g, m, v, max_norm)
@@ -801,12 +834,10 @@ def check_clip_adam(be, n):
         assert abs(float(scratch[1]) - coef) <= rcoef * coef, (tag, "coefficient", float(scratch[1]), coef)
         gc = np.abs(cg)
         assert (np.abs(G - cg) <= (8 * F32_EPS + rcoef) * gc).all(), (tag, "clipped gradient")
-        t1, t2 = np.abs(b1 * m.astype(np.float64)), (1 - b1) * gc
-        assert (np.abs(M - cm) <= 8 * F32_EPS * (t1 + t2) + rcoef * t2).all(), (tag, "exp_avg")
-        t1, t2 = b2 * v.astype(np.float64), (1 - b2) * gc * gc
-        assert (np.abs(V - cv) <= 8 * F32_EPS * (t1 + t2) + 2 * rcoef * t2).all(), (tag, "exp_avg_sq")
         upd = np.abs(cp - p.astype(np.float64))
-        tol = 8 * F32_EPS * (np.abs(p.astype(np.float64)) + upd) + 2 * rcoef * upd
+        tol_m, tol_v, tol = adam_tolerances(p, gc, m, v, upd, b1, b2, rcoef=rcoef)
+        assert (np.abs(M - cm) <= tol_m).all(), (tag, "exp_avg")
+        assert (np.abs(V - cv) <= tol_v).all(), (tag, "exp_avg_sq")
         assert (np.abs(P - cp) <= tol).all(), (tag, "parameters", float((np.abs(P - cp) / tol).max()))
         assert (upd > 1e-3).all()                   # the update is visible in float32 next to |p| <= 2
         worst = max(worst, float((np.abs(P - cp) / tol).max()))
