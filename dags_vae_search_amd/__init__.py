@@ -22,6 +22,10 @@ from .compare import StructureComparison, compare_structures, cpdag, equivalence
 from .exact import ExactResult, exact_from_tables, exact_search, local_score_table  # noqa: F401
 from .pc import PCResult, ci_test, ci_tests, pc_stable, skeleton_blacklist  # noqa: F401
 from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, sample  # noqa: F401
+# posterior.py is imported before infer.py: loading a submodule binds its name in the package, and the name `posterior` must end
+# up as infer.posterior, the function it has always been (the module stays reachable as dags_vae_search_amd.posterior in
+# sys.modules and through `from dags_vae_search_amd.posterior import ...`)
+from .posterior import ArcPosterior, arc_posterior, arc_posterior_from_tables  # noqa: F401
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, the exact arc posterior, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -788,6 +788,44 @@ extern "C" int dvs_exact_search(int32_t batch, int32_t n_vars, const double* tab
     call_begin();
     dvs_launch_exact(a, (dvs_stream_t)stream);
     return call_end("dvs_exact_search");
+}
+
+// ---- exact arc posterior (dvs_posterior.h) ---------------------------------------------------------------------------
+extern "C" size_t dvs_arc_posterior_workspace_bytes(int32_t batch, int32_t n_vars) {
+    if (exact_dims("dvs_arc_posterior_workspace_bytes", batch, n_vars)) return 0;
+    return dvs_posterior_layout(batch, n_vars).total;
+}
+
+extern "C" int dvs_arc_posterior(int32_t batch, int32_t n_vars, const double* table, size_t table_bytes, int32_t max_parents,
+                                 const uint64_t* forbidden, const double* size_prior, void* workspace, size_t workspace_bytes,
+                                 double* prob, double* log_z, double* family, size_t family_bytes, int32_t* flags, void* stream) {
+    if (int e = exact_dims("dvs_arc_posterior", batch, n_vars)) return e;
+    if (!table || !workspace || !prob || !log_z || !flags) return fail(10, "dvs_arc_posterior: null pointer");
+    const size_t cells = ((size_t)batch << n_vars) * n_vars;
+    if (table_bytes < cells * 8) return fail_size("dvs_arc_posterior: table_bytes < batch * 2^n_vars * n_vars * 8", cells * 8);
+    const PosteriorLayout l = dvs_posterior_layout(batch, n_vars);
+    if (workspace_bytes < l.total)
+        return fail_size("dvs_arc_posterior: workspace_bytes < dvs_arc_posterior_workspace_bytes", l.total);
+    if (family && family_bytes < cells * 8)
+        return fail_size("dvs_arc_posterior: family_bytes < batch * 2^n_vars * n_vars * 8", cells * 8);
+    PosteriorArgs a = {};
+    a.B = batch;
+    a.n = n_vars;
+    a.max_parents = max_parents;
+    a.table = table;
+    a.forbidden = forbidden;
+    a.size_prior = size_prior;
+    a.alpha = (double*)((char*)workspace + l.alpha);
+    a.L = (double*)((char*)workspace + l.L);
+    a.Rb = (double*)((char*)workspace + l.Rb);
+    a.partial = (double*)((char*)workspace + l.partial);
+    a.prob = prob;
+    a.log_z = log_z;
+    a.family = family;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_arc_posterior(a, (dvs_stream_t)stream);
+    return call_end("dvs_arc_posterior");
 }
 
 // ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------

@@ -1,8 +1,8 @@
 // Argument blocks and launcher prototypes of the search side: reconstruction matching, search candidates, the graph
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
-// climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search and the GP predictor (k_bic.hip
-// with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h / dvs_infer.h /
-// dvs_exact.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
+// predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
+// dvs_infer.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -359,6 +359,55 @@ struct ExactArgs {
     int* flags;                  // [B], written: 1 no admissible DAG (score -inf)
 };
 void dvs_launch_exact(const ExactArgs& a, dvs_stream_t st);
+
+// ---- exact arc posterior (dvs_posterior.h) ---------------------------------------------------------------------------
+// How k_post_arcs divides the 2^n parent sets of a table: a workgroup of 256 threads takes `rows` = 256 / n consecutive P
+// per sweep (thread = (row, v)) and `sweeps` sweeps, so `groups` workgroups cover a table and leave one partial sum each.
+struct PosteriorSplit {
+    int rows, sweeps, groups;
+};
+inline PosteriorSplit dvs_posterior_split(int n_vars) {
+    const long long total = 1ll << n_vars;
+    PosteriorSplit s;
+    s.rows = 256 / n_vars;
+    const long long wide = (long long)s.rows * 2048;         // at most about 2048 partials per table
+    s.sweeps = (int)((total + wide - 1) / wide);
+    if (s.sweeps < 8) s.sweeps = 8;
+    const long long per = (long long)s.rows * s.sweeps;
+    s.groups = (int)((total + per - 1) / per);
+    return s;
+}
+// The workspace of dvs_arc_posterior (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.
+struct PosteriorLayout {
+    size_t alpha, L, Rb, partial, total;         // byte offsets, and the size of the whole
+};
+inline PosteriorLayout dvs_posterior_layout(int batch, int n_vars) {
+    const size_t subsets = (size_t)batch << n_vars, cells = subsets * n_vars;
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    PosteriorLayout l;
+    l.alpha = 0;
+    l.L = up(cells * 8);
+    l.Rb = l.L + up(subsets * 8);
+    l.partial = l.Rb + up(subsets * 8);
+    l.total = l.partial + up((size_t)batch * dvs_posterior_split(n_vars).groups * n_vars * n_vars * 8);
+    return l;
+}
+struct PosteriorArgs {
+    int B, n, max_parents;
+    int rows, sweeps, groups;    // launcher: dvs_posterior_split(n)
+    const double* table;         // [B][2^n][n], as ExactArgs::table
+    const uint64_t* forbidden;   // [n] or null
+    const double* size_prior;    // [n] or null: added to every admissible cell by popcount(P)
+    double* alpha;               // workspace [B][2^n][n]: alpha, then gamma in the same cells
+    double* L;                   // workspace [B][2^n]
+    double* Rb;                  // workspace [B][2^n]
+    double* partial;             // workspace [B][groups][n][n]
+    double* prob;                // [B][n][n]: [u][v] = P(u -> v)
+    double* log_z;               // [B][2]: L[all], Rb[all]
+    double* family;              // null or [B][2^n][n]
+    int* flags;                  // [B], written: 1 no admissible DAG (log_z -inf)
+};
+void dvs_launch_arc_posterior(const PosteriorArgs& a, dvs_stream_t st);
 
 // ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------
 // The row-set fields live beside BicArgs / ToggleArgs, not inside them: the kernels of the plain entry points take the

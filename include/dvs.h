@@ -695,6 +695,47 @@ int dvs_exact_search(int32_t batch, int32_t n_vars, const double* table, size_t 
                      const uint64_t* forbidden, void* workspace, size_t workspace_bytes, uint64_t* parents, int32_t* order,
                      double* score, int32_t* flags, void* stream);
 
+/* Exact posterior arc probabilities: P(u -> v | data) summed over every DAG, by the subset dynamic programme
+ * of Koivisto and Sood (2004) with the feature step of Koivisto (2006).  With bde or k2 local scores exp(cell) is a marginal
+ * likelihood and the result is Bayesian model averaging; log_z is then the log marginal likelihood of the data under the
+ * structure prior.  table, admissible, max_parents and forbidden are exactly those of dvs_exact_search.  size_prior (device
+ * f64 [n_vars], nullable: all zeros): size_prior[k] is added to every admissible cell with popcount(P) = k.  f(v,P) is the
+ * resulting value, -inf where P is not admissible for v.  Everything below is a natural log in fp64; lse is log-sum-exp, and
+ * lse of nothing or of all -inf is -inf, never NaN.  V is the full set.
+ *   alpha[S][v]   for v not in S: the lse of f(v,P) over the admissible P that are subsets of S.
+ *   L[W]          L[0] = 0; for non-empty W the lse over v in W of alpha[W \ v][v] + L[W \ v].
+ *   Rb[T]         Rb[0] = 0; for non-empty T the lse over v in T of alpha[V \ T][v] + Rb[T \ v] (v is the first of T to be
+ *                 placed after V \ T).
+ *   log_z         L[V]; log_z_back = Rb[V] is the same sum taken in the other order, a built-in cross-check.
+ *   gamma[P][v]   for v not in P: the lse over all S that contain P and not v of L[S] + Rb[V \ S \ v] (-inf for v in P).
+ *   family[P][v]  exp(f(v,P) + gamma[P][v] - log_z): the posterior probability that the parent set of v is exactly P; 0 where
+ *                 P is not admissible.  Every exponent is <= 0 up to rounding: this one step is in the linear domain.
+ *   prob[u][v]    the sum over the P that contain u of family[P][v] = P(u -> v | data); a forbidden arc is exactly 0.0.
+ *   flags[t]      1 when log_z is -inf (no admissible DAG): prob and family are then all zero and no NaN appears anywhere;
+ *                 otherwise 0.
+ * Each cell of L and Rb is one max, one exp per term in ascending v and one log; alpha and gamma are folded bit by bit with
+ * pairwise log-adds; the sums of prob have a fixed order: two runs give equal bytes.  Cells of alpha with v in S are
+ * unspecified.
+ * THE PRIOR IS ORDER-MODULAR, NOT UNIFORM OVER DAGS: it is uniform over the n! variable orders and, apart from size_prior,
+ * uniform over the admissible parent sets within an order, so a DAG's prior weight is proportional to its number of linear
+ * extensions (the empty graph counts n! times, a chain once).  This is the known bias of the method (Koivisto and Sood 2004,
+ * Friedman and Koller 2003), kept deliberately: removing it costs 3^n.
+ * Outputs: prob f64 [batch][n_vars][n_vars], log_z f64 [batch][2] (forward, backward), family f64 [batch][2^n_vars][n_vars]
+ * (nullable: not stored), flags i32 [batch].  workspace (dvs_arc_posterior_workspace_bytes bytes) holds the stages for callers
+ * and tests to read, each array starting at the next multiple of 256 bytes: gamma (alpha until the chains are done) f64
+ * [batch][2^n_vars][n_vars], then L f64 [batch][2^n_vars], then Rb f64 [batch][2^n_vars], then the per-workgroup partial sums
+ * of prob, f64 [batch][G][n_vars][n_vars] with rows = 256 / n_vars, sweeps = max(8, ceil(2^n_vars / (2048 rows))) and
+ * G = ceil(2^n_vars / (rows sweeps)).  Checked before anything is enqueued, in this order and with the codes of
+ * dvs_exact_search: batch > 0 (2), n_vars in [1, 20] (3), batch * 2^n_vars * n_vars < 2^31 (2), null pointers (10; forbidden,
+ * size_prior and family may be null), table_bytes, workspace_bytes, then family_bytes when family is given (14 with the
+ * needed size).  dvs_arc_posterior_workspace_bytes returns 0 (and sets dvs_last_error) when the first three fail.  Parity with
+ * an external implementation is unpinned: the result rests on these definitions and on brute force over all DAGs of up to
+ * five vertices.  (Added in ABI 202 as pure additions: the version number stays.) */
+size_t dvs_arc_posterior_workspace_bytes(int32_t batch, int32_t n_vars);
+int dvs_arc_posterior(int32_t batch, int32_t n_vars, const double* table, size_t table_bytes, int32_t max_parents,
+                      const uint64_t* forbidden, const double* size_prior, void* workspace, size_t workspace_bytes,
+                      double* prob, double* log_z, double* family, size_t family_bytes, int32_t* flags, void* stream);
+
 /* Model averaging: bnlearn's boot.strength, custom.strength, inclusion.threshold and averaged.network as
  * five building blocks.  All are pure additions to ABI 202: the version number stays.
  *
