@@ -26,6 +26,8 @@ from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, 
 # up as infer.posterior, the function it has always been (the module stays reachable as dags_vae_search_amd.posterior in
 # sys.modules and through `from dags_vae_search_amd.posterior import ...`)
 from .posterior import ArcPosterior, arc_posterior, arc_posterior_from_tables  # noqa: F401
+# ordermc.py is named after no function it exports, so it needs no such care
+from .ordermc import FamilyScores, OrderMCMCResult, family_scores, order_mcmc  # noqa: F401
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

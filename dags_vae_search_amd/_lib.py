@@ -219,6 +219,17 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     #  prob, log_z, family (nullable), family_bytes, flags, stream)
     lib.dvs_arc_posterior.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.dvs_order_mcmc.restype = c_int
+    # (chains, n_vars, n_families, steps, offsets, sets, sets_bytes, scores, scores_bytes, seed, chain_offset, step_offset,
+    #  burn_in, thin, window, init, order, log_score, accepted, sums, sums_bytes, kept, best_score, best_parents,
+    #  trace (nullable), trace_bytes, flags, stream)
+    lib.dvs_order_mcmc.argtypes = [c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                   c_uint64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                   c_void_p]
+    lib.dvs_order_mcmc_finish.restype = c_int
+    # (chains, n_vars, sums, sums_bytes, kept, prob, stream)
+    lib.dvs_order_mcmc_finish.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
     lib.dvs_bn_scores_rows.restype = c_int
     # (... as dvs_bn_scores up to status ..., rows, set_size, n_sets, set_of (nullable), stream)
     lib.dvs_bn_scores_rows.argtypes = lib.dvs_bn_scores.argtypes[:-1] + [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
@@ -269,7 +280,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
 
 
 EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_bn_fit", "dvs_bn_sample_workspace_bytes", "dvs_bn_sample", "dvs_bn_loglik", "dvs_bn_lw_workspace_bytes", "dvs_bn_lw", "dvs_bn_blanket_posterior", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_arc_posterior_workspace_bytes", "dvs_arc_posterior", "dvs_bn_scores_rows", "dvs_bn_toggle_scores_rows", "dvs_bootstrap_rows", "dvs_arc_strength", "dvs_averaged_network", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
+           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_bn_fit", "dvs_bn_sample_workspace_bytes", "dvs_bn_sample", "dvs_bn_loglik", "dvs_bn_lw_workspace_bytes", "dvs_bn_lw", "dvs_bn_blanket_posterior", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_arc_posterior_workspace_bytes", "dvs_arc_posterior", "dvs_order_mcmc", "dvs_order_mcmc_finish", "dvs_bn_scores_rows", "dvs_bn_toggle_scores_rows", "dvs_bootstrap_rows", "dvs_arc_strength", "dvs_averaged_network", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
            "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_dag_losses", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 

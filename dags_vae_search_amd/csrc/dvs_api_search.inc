@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, the exact arc posterior, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, the exact arc posterior, order MCMC, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -826,6 +826,88 @@ extern "C" int dvs_arc_posterior(int32_t batch, int32_t n_vars, const double* ta
     call_begin();
     dvs_launch_arc_posterior(a, (dvs_stream_t)stream);
     return call_end("dvs_arc_posterior");
+}
+
+// ---- order MCMC over family lists (dvs_ordermc.h) --------------------------------------------------------------------
+// after the counts: n_vars, then the size of sums
+static int order_mcmc_shape(const char* fn, int chains, int n_vars) {
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if ((int64_t)chains * n_vars * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: chains * n_vars^2 must be < 2^31", fn);
+    return 0;
+}
+
+extern "C" int dvs_order_mcmc(int32_t chains, int32_t n_vars, int64_t n_families, int32_t steps, const int64_t* offsets,
+                              const uint64_t* sets, size_t sets_bytes, const double* scores, size_t scores_bytes, uint64_t seed,
+                              int64_t chain_offset, int64_t step_offset, int64_t burn_in, int32_t thin, int32_t window,
+                              int32_t init, int32_t* order, double* log_score, int32_t* accepted, double* sums,
+                              size_t sums_bytes, int32_t* kept, double* best_score, uint64_t* best_parents, double* trace,
+                              size_t trace_bytes, int32_t* flags, void* stream) {
+    const char* fn = "dvs_order_mcmc";
+    if (chains <= 0) return fail(2, "dvs_order_mcmc: chains must be > 0");
+    if (steps < 0) return fail(2, "dvs_order_mcmc: steps must be >= 0");
+    if (n_families < 1 || n_families > (int64_t)0x7fffffff) return fail(2, "dvs_order_mcmc: n_families must be in [1, 2^31 - 1]");
+    if (int e = order_mcmc_shape(fn, chains, n_vars)) return e;
+    if (!offsets || !sets || !scores || !order || !log_score || !accepted || !sums || !kept || !best_score || !best_parents || !flags)
+        return fail(10, "dvs_order_mcmc: null pointer");
+    if (chain_offset < 0 || step_offset < 0) return fail(12, "dvs_order_mcmc: chain_offset and step_offset must be >= 0");
+    const int widest = n_vars > 2 ? n_vars - 1 : 1;
+    if (window < 1 || window > widest) return fail(13, "dvs_order_mcmc: window must be in [1, max(1, n_vars - 1)]");
+    if (thin < 1) return fail(13, "dvs_order_mcmc: thin must be >= 1");
+    if (burn_in < 0) return fail(13, "dvs_order_mcmc: burn_in must be >= 0");
+    if (init != 0 && init != 1) return fail(13, "dvs_order_mcmc: init must be 0 or 1");
+    if (step_offset > (int64_t)0xffffffff || 3 * (step_offset + (int64_t)steps) >= ((int64_t)1 << 32))
+        return fail(13, "dvs_order_mcmc: 3 * (step_offset + steps) must be < 2^32");
+    if (sets_bytes < (size_t)n_families * 8) return fail_size("dvs_order_mcmc: sets_bytes < n_families * 8", (size_t)n_families * 8);
+    if (scores_bytes < (size_t)n_families * 8) return fail_size("dvs_order_mcmc: scores_bytes < n_families * 8", (size_t)n_families * 8);
+    const size_t cells = (size_t)chains * n_vars * n_vars;
+    if (sums_bytes < cells * 8) return fail_size("dvs_order_mcmc: sums_bytes < chains * n_vars^2 * 8", cells * 8);
+    if (trace && trace_bytes < (size_t)chains * steps * 8)
+        return fail_size("dvs_order_mcmc: trace_bytes < chains * steps * 8", (size_t)chains * steps * 8);
+    OrderMcmcArgs a = {};
+    a.C = chains;
+    a.n = n_vars;
+    a.steps = steps;
+    a.thin = thin;
+    a.window = window;
+    a.init = init;
+    a.F = n_families;
+    a.chain_offset = (uint32_t)chain_offset;     // the global chain index is taken mod 2^32
+    a.step_offset = (uint32_t)step_offset;
+    a.burn_in = burn_in > (int64_t)0xffffffff ? 0xffffffffu : (uint32_t)burn_in;     // no step index reaches 2^32 / 3
+    a.offsets = (const long long*)offsets;
+    a.sets = sets;
+    a.scores = scores;
+    a.order = order;
+    a.log_score = log_score;
+    a.accepted = accepted;
+    a.sums = sums;
+    a.kept = kept;
+    a.best_score = best_score;
+    a.best_parents = best_parents;
+    a.trace = trace;
+    a.flags = flags;
+    call_begin();
+    dvs_launch_order_mcmc(a, seed, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_order_mcmc_finish(int32_t chains, int32_t n_vars, const double* sums, size_t sums_bytes, const int32_t* kept,
+                                     double* prob, void* stream) {
+    const char* fn = "dvs_order_mcmc_finish";
+    if (chains <= 0) return fail(2, "dvs_order_mcmc_finish: chains must be > 0");
+    if (int e = order_mcmc_shape(fn, chains, n_vars)) return e;
+    if (!sums || !kept || !prob) return fail(10, "dvs_order_mcmc_finish: null pointer");
+    const size_t cells = (size_t)chains * n_vars * n_vars;
+    if (sums_bytes < cells * 8) return fail_size("dvs_order_mcmc_finish: sums_bytes < chains * n_vars^2 * 8", cells * 8);
+    OrderMcmcFinishArgs a = {};
+    a.C = chains;
+    a.n = n_vars;
+    a.sums = sums;
+    a.kept = kept;
+    a.prob = prob;
+    call_begin();
+    dvs_launch_order_mcmc_finish(a, (dvs_stream_t)stream);
+    return call_end(fn);
 }
 
 // ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------

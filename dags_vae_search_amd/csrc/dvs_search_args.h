@@ -409,6 +409,37 @@ struct PosteriorArgs {
 };
 void dvs_launch_arc_posterior(const PosteriorArgs& a, dvs_stream_t st);
 
+// ---- order MCMC over family lists (dvs_ordermc.h) --------------------------------------------------------------------
+// The dynamic LDS of k_omc_chain: the lanes' arc accumulators [256][n | 1] and the chain's sums [n][n], both f64.
+inline size_t dvs_omc_lds(int n_vars) { return ((size_t)256 * (n_vars | 1) + (size_t)n_vars * n_vars) * 8; }
+struct OrderMcmcArgs {
+    int C, n, steps, thin, window, init;
+    long long F;                 // families in the list, < 2^31
+    uint32_t seed_lo, seed_hi;   // launcher, from `seed`
+    uint32_t chain_offset;       // the global chain index is taken mod 2^32
+    uint32_t step_offset, burn_in;   // 3 (step_offset + steps) < 2^32 is checked; a burn_in beyond that keeps nothing
+    const long long* offsets;    // [n + 1]
+    const uint64_t* sets;        // [F]
+    const double* scores;        // [F]
+    int* order;                  // [C][n], in and out
+    double* log_score;           // [C]
+    int* accepted;               // [C], accumulated
+    double* sums;                // [C][n][n], accumulated
+    int* kept;                   // [C], accumulated
+    double* best_score;          // [C], in and out
+    uint64_t* best_parents;      // [C][n], in and out
+    double* trace;               // null or [C][steps]
+    int* flags;                  // [1], written by k_omc_check
+};
+void dvs_launch_order_mcmc(const OrderMcmcArgs& a, uint64_t seed, dvs_stream_t st);
+struct OrderMcmcFinishArgs {
+    int C, n;
+    const double* sums;          // [C][n][n]
+    const int* kept;             // [C]
+    double* prob;                // [n][n]
+};
+void dvs_launch_order_mcmc_finish(const OrderMcmcFinishArgs& a, dvs_stream_t st);
+
 // ---- row sets, bootstrap, arc strength, averaged network (dvs_strength.h) ---------------------------------------------
 // The row-set fields live beside BicArgs / ToggleArgs, not inside them: the kernels of the plain entry points take the
 // argument blocks they always took.

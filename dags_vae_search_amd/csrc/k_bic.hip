@@ -263,6 +263,7 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
 #include "dvs_infer.h"
 #include "dvs_exact.h"
 #include "dvs_posterior.h"
+#include "dvs_ordermc.h"
 #include "dvs_strength.h"
 
 void dvs_launch_bic(const BicArgs& in, dvs_stream_t st) {

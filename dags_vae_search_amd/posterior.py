@@ -26,34 +26,46 @@ from .exact import _refuse_size, local_score_table
 from .strength import ArcStrength
 
 
+class ArcProbabilities:
+    """What every result that carries ``prob`` (f64 [..., n, n], [u, v] = P(u -> v | data)) derives from it: ``ArcPosterior``
+    here and ``OrderMCMCResult`` of ordermc.py share these formulas, so ``averaged_network`` and ``inclusion_threshold`` take
+    either unchanged."""
+
+    @property
+    def strength(self) -> torch.Tensor:
+        """f64 [..., n, n]: P(u and v are adjacent) = prob + its transpose"""
+        return self.prob + self.prob.transpose(-1, -2)
+
+    @property
+    def direction(self) -> torch.Tensor:
+        """f64 [..., n, n]: prob / strength, 0 where strength is 0"""
+        s = self.strength
+        return torch.where(s > 0, self.prob / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(s))
+
+    @staticmethod
+    def counts(prob: torch.Tensor, resolution) -> ArcStrength:
+        """one [n, n] matrix as the counts of ``resolution`` = R imaginary networks: a = min(R, floor(R prob)) per direction,
+        ``any[u, v] = a_uv + a_vu`` and ``dir2[u, v] = 2 a_uv`` (so ``any / R`` is within 2 / R of ``strength``)"""
+        R = int(resolution)
+        if not 1 <= R < 1 << 29:
+            raise ValueError(f"to_arc_strength: resolution must be in [1, 2^29) (got {resolution!r})")
+        a = torch.clamp(torch.floor(prob * float(R)), max=float(R)).to(torch.int32)
+        return ArcStrength((a + a.t()).contiguous(), (2 * a).contiguous(), R)
+
+
 @dataclass
-class ArcPosterior:
+class ArcPosterior(ArcProbabilities):
     prob: torch.Tensor                     # f64 [B, n, n]: [b, u, v] = P(u -> v | data)
     log_z: torch.Tensor                    # f64 [B]: log of the sum over all (order, parent sets), L[all] of include/dvs.h
     log_z_back: torch.Tensor               # f64 [B]: the same sum taken in the other order, Rb[all]
     families: Optional[torch.Tensor]       # f64 [B, 2^n, n] or None: [b, P, v] = P(the parent set of v is exactly P)
     flags: torch.Tensor                    # int32 [B]: always zero on return (a set flag raises)
 
-    @property
-    def strength(self) -> torch.Tensor:
-        """f64 [B, n, n]: P(u and v are adjacent) = prob + its transpose"""
-        return self.prob + self.prob.transpose(-1, -2)
-
-    @property
-    def direction(self) -> torch.Tensor:
-        """f64 [B, n, n]: prob / strength, 0 where strength is 0"""
-        s = self.strength
-        return torch.where(s > 0, self.prob / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(s))
-
     def to_arc_strength(self, b: int = 0, resolution: int = 1_000_000) -> ArcStrength:
         """table ``b`` as the counts of ``resolution`` = R imaginary networks, so that ``averaged_network`` and
         ``inclusion_threshold`` take the exact posterior unchanged: a = min(R, floor(R prob)) per direction,
         ``any[u, v] = a_uv + a_vu`` and ``dir2[u, v] = 2 a_uv`` (so ``any / R`` is within 2 / R of ``strength``)."""
-        R = int(resolution)
-        if not 1 <= R < 1 << 29:
-            raise ValueError(f"to_arc_strength: resolution must be in [1, 2^29) (got {resolution!r})")
-        a = torch.clamp(torch.floor(self.prob[b] * float(R)), max=float(R)).to(torch.int32)
-        return ArcStrength((a + a.t()).contiguous(), (2 * a).contiguous(), R)
+        return self.counts(self.prob[b], resolution)
 
 
 def _size_prior(what, parent_prior, n, dev):

@@ -736,6 +736,75 @@ int dvs_arc_posterior(int32_t batch, int32_t n_vars, const double* table, size_t
                       const uint64_t* forbidden, const double* size_prior, void* workspace, size_t workspace_bytes,
                       double* prob, double* log_z, double* family, size_t family_bytes, int32_t* flags, void* stream);
 
+/* Order MCMC: posterior arc probabilities and an order-space structure search for n_vars <= 48, by the
+ * Metropolis sampler over variable orders of Friedman and Koller (2003).  Its stationary distribution is the order-modular
+ * posterior of dvs_arc_posterior restricted to the families of the list, so for n_vars <= 20 that call is its exact yardstick.
+ * THE PRIOR IS ORDER-MODULAR, NOT UNIFORM OVER DAGS (see dvs_arc_posterior): uniform over the n! orders and over the listed
+ * parent sets within an order, so a DAG weighs in with its number of linear extensions.
+ *
+ * The family list replaces the 2^n table: offsets (device i64 [n_vars + 1]), sets (device u64 [n_families]), scores (device f64
+ * [n_families]).  The families of v are the entries offsets[v] .. offsets[v + 1] - 1; offsets[0] = 0, offsets[n_vars] =
+ * n_families, every variable has at least one entry and its entry 0 is the empty set; a mask of v holds neither bit v nor a
+ * bit >= n_vars; scores are finite (f(v, P) of dvs_arc_posterior, the inadmissible sets left out).  These properties are
+ * checked ON THE DEVICE by a first kernel; nothing is read back.  flags (device i32 [1]) is written: 0, or the bits 1 (offsets),
+ * 2 (an entry 0 that is not the empty set), 4 (a mask bit), 8 (a score that is not finite), and the run is then skipped: every
+ * other output stays untouched.  Bit 16: a chain whose `order` (init = 0) is not a permutation of 0 .. n_vars - 1; that chain
+ * alone is skipped.
+ *
+ * Definitions (natural logs, fp64).  For a variable v and a set Q of variables, a family j of v is consistent with Q when
+ * sets[j] & ~Q == 0.
+ *   term(v, Q)    the log-sum-exp of scores[j] over the consistent families of v: never empty (entry 0).  Computed as
+ *                 bestf + log(sum of exp(scores[j] - bestf)).
+ *   bestf(v, Q)   the largest consistent score; arg(v, Q) its mask; exact ties go to the lower list index.
+ *   pred(v)       the variables before v in the order; the score of an order is the sum over v of term(v, pred(v)), added
+ *                 in ascending v.
+ * Terms are always recomputed from the list, never updated incrementally: nothing drifts, and a cached term is the bytes a
+ * fresh one would be.
+ * Randomness.  Chain c has the global index g = (chain_offset + c) mod 2^32 and the key K = dvs_site_key(seed_lo, seed_hi, 700,
+ * g) of csrc/dvs_device.h (oracle/rng.py restates dvs_site_key and dvs_draw).  init = 1: the start order is a Fisher-Yates
+ * shuffle of the identity with the key K' of site 701: for k = n_vars - 1 down to 1, j = (uint64(dvs_draw(K', k)) * (k + 1))
+ * >> 32, positions k and j are swapped.  init = 0: the caller's order.  Step s of the call is the global step t = step_offset
+ * + s with the draws r0 = dvs_draw(K, 3 t), r1 = dvs_draw(K, 3 t + 1), r2 = dvs_draw(K, 3 t + 2):
+ *   i = (r0 * (n_vars - 1)) >> 32,  m = min(window, n_vars - 1 - i),  j = i + 1 + ((r1 * m) >> 32)
+ * and the proposal swaps the variables at positions i and j.  The probability of a pair of positions does not depend on the
+ * state, so the proposal is symmetric.  Delta = S_new - S_old, each S the sum of the terms of the variables at positions
+ * i .. j (of the proposed and of the current order) added in ascending position; one subtraction.  The proposal is accepted iff
+ * log((r2 + 0.5) * 2^-32) < Delta.  n_vars = 1 proposes nothing.  A chain is a function of (seed, g, step index) only: a run
+ * cut into calls with step_offset (order, accepted, sums, kept, best_score and best_parents handed on) or into shards with
+ * chain_offset gives the bytes of the uncut run.
+ * Kept samples.  After the accept decision of every global step t >= burn_in with (t - burn_in) % thin == 0:
+ *   sums[c][u][v] += the sum over the consistent families j of v that contain u of exp(scores[j] - term(v, pred(v)))
+ *                    = P(u -> v | order), the Rao-Blackwellised arc indicator;  kept[c] += 1.
+ * Summation order (fixed: two runs give equal bytes).  Lane i of the chain's 256 takes a variable's families offsets[v] + i,
+ * + 256, ... in that order, for the largest score, the sum of a term and the per-parent sums of a kept sample alike.  The 64
+ * lanes of a wave meet in an xor butterfly (32, 16, ..., 1) for a term and are added in lane order for a kept sample; the four
+ * waves are added in wave order.  No floating-point atomics.  The caller zeroes sums, kept and accepted and sets best_score to
+ * -inf before the first call; later calls accumulate.
+ * Best DAG seen.  At the start of a call and after every accepted move the order's best consistent DAG has the score sum over
+ * v of bestf(v, pred(v)), added in ascending v; a strictly larger value replaces best_score[c], and arg(v, pred(v)) replaces
+ * best_parents[c][v].
+ * Outputs: order i32 [chains][n_vars] (in with init = 0, out always: position -> variable), log_score f64 [chains] (the final
+ * order's score), accepted i32 [chains], sums f64 [chains][n_vars][n_vars], kept i32 [chains], best_score f64 [chains],
+ * best_parents u64 [chains][n_vars], trace f64 [chains][steps] (nullable: the order's score after each step), flags i32 [1].
+ *
+ * dvs_order_mcmc_finish adds the chains' sums in a fixed tree (thread i adds chains i, i + 256, ... in that order, then the
+ * tree of 128, 64, ..., 1) and kept as integers: prob[u][v] (device f64 [n_vars][n_vars]) = sum / kept, 0.0 when nothing was
+ * kept.  The per-chain arrays stay for the between-chain spread.
+ *
+ * Checked before anything is enqueued, in this order: chains > 0, steps >= 0, n_families in [1, 2^31 - 1] (2), n_vars in
+ * [1, 48] (3), chains * n_vars^2 < 2^31 (2), null pointers (10; trace may be null), chain_offset >= 0 and step_offset >= 0
+ * (12), window in [1, max(1, n_vars - 1)], thin >= 1, burn_in >= 0, init in {0, 1}, 3 (step_offset + steps) < 2^32 (13), then
+ * sets_bytes, scores_bytes, sums_bytes and, when trace is given, trace_bytes (14 with the needed size).
+ * dvs_order_mcmc_finish: chains > 0 (2), n_vars (3), the product (2), null pointers (10), sums_bytes (14).  (Added in ABI 202
+ * as pure additions: the version number stays.) */
+int dvs_order_mcmc(int32_t chains, int32_t n_vars, int64_t n_families, int32_t steps, const int64_t* offsets,
+                   const uint64_t* sets, size_t sets_bytes, const double* scores, size_t scores_bytes, uint64_t seed,
+                   int64_t chain_offset, int64_t step_offset, int64_t burn_in, int32_t thin, int32_t window, int32_t init,
+                   int32_t* order, double* log_score, int32_t* accepted, double* sums, size_t sums_bytes, int32_t* kept,
+                   double* best_score, uint64_t* best_parents, double* trace, size_t trace_bytes, int32_t* flags, void* stream);
+int dvs_order_mcmc_finish(int32_t chains, int32_t n_vars, const double* sums, size_t sums_bytes, const int32_t* kept,
+                          double* prob, void* stream);
+
 /* Model averaging: bnlearn's boot.strength, custom.strength, inclusion.threshold and averaged.network as
  * five building blocks.  All are pure additions to ABI 202: the version number stays.
  *
