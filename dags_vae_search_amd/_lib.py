@@ -7,7 +7,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32,
+import re
+from ctypes import (POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32,
                     c_uint64, c_void_p)
 
 import numpy as np
@@ -15,29 +16,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libdvs_hip.so"
-
-D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
-MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
-TILE_TOKENS = 16
-DECODE_STATE_BYTES = 440
-CLIP_SCRATCH_FLOATS = 4096  # DVS_CLIP_SCRATCH_FLOATS
-RECORD_BYTES = 96         # one-tile path; record_bytes(lib, shape) gives the size that applies
-LOSS_FLOATS = 5           # DVS_LOSS_FLOATS: total, recon, kld, non-finite flag, invalid-features flag
-ABI_VERSION = 202         # DVS_VERSION of include/dvs.h this binding was written against
-GP_ACQ_MAX_INDUCING = 1023  # DVS_GP_ACQ_MAX_INDUCING
-STRUCT_HASH_INVALID = 0x7FFFFFFFFFFFFFFF  # DVS_STRUCT_HASH_INVALID
-GEN_LABELS_CHOICE, GEN_ACCEPT_ISOLATES, GEN_ACCEPT_NO_CONNECTIVITY, GEN_GROUP_SHIFT = 1, 2, 4, 8   # DVS_GEN_* flags
-CI_TYPES = {"mi": 0, "x2": 1, "mi-adf": 2, "x2-adf": 3}   # dvs_ci_type, by bnlearn's name
-CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
-FIT_METHODS = {"mle": 0, "bayes": 1}   # dvs_fit_method, by bnlearn's name
-FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
-# bits of the BN entry points' status word (device int32, zeroed by the caller), as include/dvs.h defines them
-STATUS_CYCLE = 1              # bit 0 (dvs_bn_sample, dvs_bn_lw): the structure has a cycle
-STATUS_REFUSED = 16           # bit 4: a family, test, row or query was refused (NaN in its cells alone); worded per call site
-STATUS_LABELS = 32            # bit 5 (dvs_bic_parent_masks): a DAG's labels are not a permutation of 0..n_vars-1
-STATUS_NOT_PROBABILITY = 64   # bit 6 (dvs_bn_sample, dvs_bn_lw): a table row is not a probability vector
-LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
-SCORE_TYPES = {"loglik": 0, "aic": 1, "bic": 2, "bde": 3, "bds": 4, "k2": 5, "bdj": 6}   # dvs_score_type, by bnlearn's name
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs.h")
 
 
 class DvsShape(Structure):
@@ -50,238 +29,96 @@ class DvsParamEntry(Structure):
     _fields_ = [("name", c_char * 64), ("offset", c_int64), ("rows", c_int32), ("cols", c_int32)]
 
 
+# ---- include/dvs.h is the one statement of the C ABI: the binding and the mirrored constants are read from it
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "uint32_t": c_uint32, "uint64_t": c_uint64,
+            "size_t": c_size_t, "float": c_float, "double": c_double, "void": None}
+_STRUCT_POINTERS = {"dvs_shape": POINTER(DvsShape), "dvs_param_entry": POINTER(DvsParamEntry)}
+_INT = r"(0[xX][0-9a-fA-F]+|\d+)[uUlL]*"
+
+
+def parse_header(text: str):
+    """C header text -> (signatures, constants).  signatures: {name: (restype, [(arg_name, ctype), ...])} in header order;
+    constants: the integer ``#define DVS_*`` values and the enum members.  A statement that is not a typedef block or a
+    prototype over the types above raises ValueError naming it: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text.replace("\\\n", " "), flags=re.S)
+    constants = {name: int(value, 0) for name, value in
+                 re.findall(rf"^[ \t]*#[ \t]*define[ \t]+(DVS_\w+)[ \t]+{_INT}[ \t]*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", text):
+        for member in filter(None, (m.strip() for m in body.split(","))):
+            m = re.fullmatch(rf"(\w+)\s*=\s*{_INT}", member)
+            if not m:
+                raise ValueError(f"include/dvs.h: enum member without a plain integer value: {member!r}")
+            constants[m.group(1)] = int(m.group(2), 0)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'\btypedef\b[^;{]*\{[^}]*\}[^;]*;|extern\s+"C"\s*\{|\}', "", text)
+    signatures = {}
+    for stmt in filter(None, (" ".join(st.split()) for st in text.split(";"))):
+        m = re.fullmatch(r"(const char ?\*|\w+) ?(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise ValueError(f"include/dvs.h: not a prototype: {stmt!r}")
+        ret, name, params = m.groups()
+        if ret != "const char*" and ret not in _SCALARS:
+            raise ValueError(f"include/dvs.h: {name}: unknown return type {ret!r}")
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            pm = re.fullmatch(r"(?:const )?(\w+) ?(\*?) ?(\w+)", param.strip())
+            if not pm or (not pm.group(2) and _SCALARS.get(pm.group(1)) is None):
+                raise ValueError(f"include/dvs.h: {name}: unknown parameter type in {param.strip()!r}")
+            base, pointer, arg = pm.groups()
+            args.append((arg, _STRUCT_POINTERS.get(base, c_void_p) if pointer else _SCALARS[base]))
+        signatures[name] = (c_char_p if ret == "const char*" else _SCALARS[ret], args)
+    return signatures, constants
+
+
+def _read_header():
+    if not os.path.exists(HEADER):
+        raise RuntimeError(f"include/dvs.h not found at {HEADER}: the binding of {LIB_NAME} is read from it")
+    with open(HEADER) as f:
+        return parse_header(f.read())
+
+
+SIGNATURES, _H = _read_header()
+EXPORTS = list(SIGNATURES)
+
+D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
+MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
+TILE_TOKENS = 16
+DECODE_STATE_BYTES = _H["DVS_DECODE_STATE_BYTES"]
+CLIP_SCRATCH_FLOATS = _H["DVS_CLIP_SCRATCH_FLOATS"]
+RECORD_BYTES = _H["DVS_RECORD_BYTES"]   # one-tile path; record_bytes(lib, shape) gives the size that applies
+LOSS_FLOATS = _H["DVS_LOSS_FLOATS"]     # total, recon, kld, non-finite flag, invalid-features flag
+ABI_VERSION = _H["DVS_VERSION"]
+GP_ACQ_MAX_INDUCING = _H["DVS_GP_ACQ_MAX_INDUCING"]
+STRUCT_HASH_INVALID = _H["DVS_STRUCT_HASH_INVALID"]
+GEN_LABELS_CHOICE, GEN_ACCEPT_ISOLATES, GEN_ACCEPT_NO_CONNECTIVITY, GEN_GROUP_SHIFT = (
+    _H["DVS_GEN_" + k] for k in ("LABELS_CHOICE", "ACCEPT_ISOLATES", "ACCEPT_NO_CONNECTIVITY", "GROUP_SHIFT"))
+
+
+def _by_bnlearn_name(prefix, keys):
+    """{bnlearn's name: the value of the header's enum member}, e.g. "mi-adf" -> DVS_CI_MI_ADF"""
+    return {k: _H[prefix + k.upper().replace("-", "_")] for k in keys}
+
+
+CI_TYPES = _by_bnlearn_name("DVS_CI_", ("mi", "x2", "mi-adf", "x2-adf"))   # dvs_ci_type
+CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
+FIT_METHODS = _by_bnlearn_name("DVS_FIT_", ("mle", "bayes"))   # dvs_fit_method
+FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
+# bits of the BN entry points' status word (device int32, zeroed by the caller), as include/dvs.h defines them
+STATUS_CYCLE = 1              # bit 0 (dvs_bn_sample, dvs_bn_lw): the structure has a cycle
+STATUS_REFUSED = 16           # bit 4: a family, test, row or query was refused (NaN in its cells alone); worded per call site
+STATUS_LABELS = 32            # bit 5 (dvs_bic_parent_masks): a DAG's labels are not a permutation of 0..n_vars-1
+STATUS_NOT_PROBABILITY = 64   # bit 6 (dvs_bn_sample, dvs_bn_lw): a table row is not a probability vector
+LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
+SCORE_TYPES = _by_bnlearn_name("DVS_SCORE_", ("loglik", "aic", "bic", "bde", "bds", "k2", "bdj"))   # dvs_score_type
+
+
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h on a loaded library."""
-    P = POINTER
-    lib.dvs_version.restype = c_int
-    lib.dvs_last_error.restype = c_char_p
-    lib.dvs_device_cus.restype = c_int
-    lib.dvs_param_count.restype = c_int64
-    lib.dvs_param_count.argtypes = [P(DvsShape)]
-    lib.dvs_param_table.restype = c_int
-    lib.dvs_param_table.argtypes = [P(DvsShape), P(DvsParamEntry), c_int]
-    lib.dvs_workspace_bytes.restype = c_size_t
-    lib.dvs_workspace_bytes.argtypes = [P(DvsShape)]
-    lib.dvs_record_bytes.restype = c_size_t
-    lib.dvs_record_bytes.argtypes = [P(DvsShape)]
-    lib.dvs_pack_features.restype = c_int
-    # (shape, label 1-hot, position 1-hot, adjacency, target masks, records, records_bytes, status, stream)
-    lib.dvs_pack_features.argtypes = [P(DvsShape), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
-                                      c_void_p]
-    lib.dvs_build_records.restype = c_int
-    # (shape, labels, preds, records, records_bytes, status, stream)
-    lib.dvs_build_records.argtypes = [P(DvsShape), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_loss_forward.restype = c_int
-    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, eps, status, losses, mu, logvar, stream)
-    lib.dvs_loss_forward.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_loss_forward_notify.restype = c_int
-    # (... as dvs_loss_forward ..., logvar, host_tail (pinned, 8 words), host_seq, stream)
-    lib.dvs_loss_forward_notify.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
-    lib.dvs_loss_backward.restype = c_int
-    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, gcoef, grads, stream)
-    lib.dvs_loss_backward.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                      c_void_p, c_void_p]
-    lib.dvs_loss_backward_sq.restype = c_int
-    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, gcoef, grads, clip_scratch, stream)
-    lib.dvs_loss_backward_sq.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                         c_void_p, c_void_p, c_void_p]
-    lib.dvs_loss_forward_defer.restype = c_int
-    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, eps, mu, logvar, stream)
-    lib.dvs_loss_forward_defer.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                           c_void_p, c_void_p, c_void_p]
-    lib.dvs_loss_backward_emit.restype = c_int
-    # (... as dvs_loss_backward_sq ..., clip_scratch, status, losses, host_tail (pinned), host_seq, stream)
-    lib.dvs_loss_backward_emit.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]
-    lib.dvs_encode.restype = c_int
-    # (shape, records, records_bytes, params, n_params, workspace, workspace_bytes, mu, logvar, stream)
-    lib.dvs_encode.argtypes = [P(DvsShape), c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
-                               c_void_p]
-    lib.dvs_decode.restype = c_int
-    # (shape, params, n_params, workspace, workspace_bytes, records, records_bytes, z, uniforms, state, state_bytes, stream)
-    lib.dvs_decode.argtypes = [P(DvsShape), c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
-                               c_void_p, c_size_t, c_void_p]
-    lib.dvs_match_decoded.restype = c_int
-    # (batch, n_vars, card, repeats, preds_are_u64, labels, preds, states, state_bytes, budget, flags, stream)
-    lib.dvs_match_decoded.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
-                                      c_int32, c_void_p, c_void_p]
-    lib.dvs_decoded_structures.restype = c_int
-    # (batch, n_vars, preds_are_u64, states, state_bytes, hash_mask, flags, labels, preds, keys, keys_bytes, hashes, stream)
-    lib.dvs_decoded_structures.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_size_t, c_uint64, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_structset_filter.restype = c_int
-    # (batch, n_vars, sorted_hashes, order, keys, keys_bytes, flags, seen_count, seen_hashes, seen_keys, seen_keys_bytes,
-    #  out, stream)
-    lib.dvs_structset_filter.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32,
-                                         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_generate_dags.restype = c_int
-    # (batch, n_vars, card, preds_are_u64, num_edges, seed, dag_offset, try_limit, flags, labels, preds, preds_bytes, attempts,
-    #  stream)
-    lib.dvs_generate_dags.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_int64, c_int32, c_int32,
-                                      c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_generate_edge_counts.restype = c_int
-    # (batch, n_entries, edge_counts, cum_weights, seed, dag_offset, num_edges, stream)
-    lib.dvs_generate_edge_counts.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p]
-    lib.dvs_debug_launch.restype = c_int
-    lib.dvs_debug_launch.argtypes = [c_size_t, c_void_p]
-    lib.dvs_bic_scores.restype = c_int
-    lib.dvs_bic_scores.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p]
-    lib.dvs_bn_scores.restype = c_int
-    lib.dvs_bn_scores.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_double, c_void_p,
-                                  c_void_p, c_void_p, c_void_p]
-    lib.dvs_bn_toggle_scores.restype = c_int
-    # (batch, n_vars, n_samples, data, card, parents, score_type, score_arg, worklist (nullable), local, local_bytes, toggles,
-    #  toggles_bytes, status, stream)
-    lib.dvs_bn_toggle_scores.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_double,
-                                         c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_hc_step.restype = c_int
-    # (batch, n_vars, parents, local, toggles, toggles_bytes, max_parents, min_delta, forbidden (nullable), step_cap, worklist,
-    #  steps, converged, flags, trace (nullable), trace_bytes, active, stream)
-    lib.dvs_hc_step.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, ctypes.c_double, c_void_p,
-                                c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_tabu_step.restype = c_int
-    # (... as dvs_hc_step up to active ..., tabu_len, ring, ring_bytes, visited, max_stall, stall, best_score, best_parents,
-    #  best_bytes, stream)
-    lib.dvs_tabu_step.argtypes = lib.dvs_hc_step.argtypes[:-1] + [c_int32, c_void_p, c_size_t, c_void_p, c_int32, c_void_p,
-                                                                  c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.dvs_hc_perturb.restype = c_int
-    # (batch, n_vars, parents, local, toggles, toggles_bytes, max_parents, forbidden (nullable), worklist, flags, seed,
-    #  draw_index, stream)
-    lib.dvs_hc_perturb.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_void_p,
-                                   c_void_p, c_uint64, c_uint32, c_void_p]
-    lib.dvs_cpdag.restype = c_int
-    # (batch, n_vars, parents, pdag, pdag_bytes, flags, stream)
-    lib.dvs_cpdag.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_pdag_compare.restype = c_int
-    # (batch, n_vars, a, b, b_rows, counts, counts_bytes, stream)
-    lib.dvs_pdag_compare.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]
-    lib.dvs_ci_tests.restype = c_int
-    # (n_tests, n_vars, n_samples, data, card, pairs, cond, test_type, max_cells, out, out_bytes, status, stream)
-    lib.dvs_ci_tests.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                 c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_pc_expand.restype = c_int
-    # (n_pairs, n_vars, level, adj, pair_xy, offsets, n_tests, pairs, cond, tests_bytes, stream)
-    lib.dvs_pc_expand.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                  c_size_t, c_void_p]
-    lib.dvs_pc_reduce.restype = c_int
-    # (n_pairs, n_vars, pair_xy, offsets, n_tests, cond, out, alpha, adj, adj_next, sepset, sepset_bytes, result,
-    #  result_bytes, refused, stream)
-    lib.dvs_pc_reduce.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_double,
-                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_pc_orient.restype = c_int
-    # (batch, n_vars, skeleton, sepsets, sepsets_bytes, pdag, pdag_bytes, conflicts, flags, stream)
-    lib.dvs_pc_orient.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
-                                  c_void_p]
-    lib.dvs_bn_fit.restype = c_int
-    # (batch, n_vars, n_samples, data, card, parents, method, iss, unobserved, offsets, cpt, cpt_bytes, status, stream)
-    lib.dvs_bn_fit.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_double, c_int32,
-                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_bn_sample_workspace_bytes.restype = c_size_t
-    lib.dvs_bn_sample_workspace_bytes.argtypes = [c_int64, c_int32]
-    lib.dvs_bn_sample.restype = c_int
-    # (n_vars, n_rows, card, parents, offsets, cpt, n_cells, seed, row_offset, workspace, workspace_bytes, data_out, status,
-    #  stream)
-    lib.dvs_bn_sample.argtypes = [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_int64,
-                                  c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
-    lib.dvs_bn_loglik.restype = c_int
-    # (batch, n_vars, n_rows, data, card, parents, offsets, cpt, per_row (nullable), out, workspace, workspace_bytes, status,
-    #  stream)
-    lib.dvs_bn_loglik.argtypes = [c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_bn_lw_workspace_bytes.restype = c_size_t
-    lib.dvs_bn_lw_workspace_bytes.argtypes = [c_int64, c_int32, c_int64, c_int64, c_uint64]
-    lib.dvs_bn_lw.restype = c_int
-    # (n_vars, n_queries, n_particles, card, parents, offsets, cpt, n_cells, evidence, observed, event (nullable), targets, seed,
-    #  query_offset, workspace, workspace_bytes, sums, marginals (nullable), particles (nullable), particle_weights (nullable),
-    #  status, stream)
-    lib.dvs_bn_lw.argtypes = [c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                              c_void_p, c_uint64, c_uint64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_void_p]
-    lib.dvs_bn_blanket_posterior.restype = c_int
-    # (batch, n_vars, n_rows, data, card, parents, offsets, cpt, cpt_bytes, target, use_children, posterior (nullable), pred,
-    #  status, stream)
-    lib.dvs_bn_blanket_posterior.argtypes = [c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_size_t, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_exact_workspace_bytes.restype = c_size_t
-    lib.dvs_exact_workspace_bytes.argtypes = [c_int32, c_int32]
-    lib.dvs_exact_search.restype = c_int
-    # (batch, n_vars, table, table_bytes, max_parents, forbidden (nullable), workspace, workspace_bytes, parents, order, score,
-    #  flags, stream)
-    lib.dvs_exact_search.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p, c_void_p, c_size_t, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_arc_posterior_workspace_bytes.restype = c_size_t
-    lib.dvs_arc_posterior_workspace_bytes.argtypes = [c_int32, c_int32]
-    lib.dvs_arc_posterior.restype = c_int
-    # (batch, n_vars, table, table_bytes, max_parents, forbidden (nullable), size_prior (nullable), workspace, workspace_bytes,
-    #  prob, log_z, family (nullable), family_bytes, flags, stream)
-    lib.dvs_arc_posterior.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
-                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_order_mcmc.restype = c_int
-    # (chains, n_vars, n_families, steps, offsets, sets, sets_bytes, scores, scores_bytes, seed, chain_offset, step_offset,
-    #  burn_in, thin, window, init, order, log_score, accepted, sums, sums_bytes, kept, best_score, best_parents,
-    #  trace (nullable), trace_bytes, flags, stream)
-    lib.dvs_order_mcmc.argtypes = [c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                   c_uint64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
-                                   c_void_p]
-    lib.dvs_order_mcmc_finish.restype = c_int
-    # (chains, n_vars, sums, sums_bytes, kept, prob, stream)
-    lib.dvs_order_mcmc_finish.argtypes = [c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
-    lib.dvs_bn_scores_rows.restype = c_int
-    # (... as dvs_bn_scores up to status ..., rows, set_size, n_sets, set_of (nullable), stream)
-    lib.dvs_bn_scores_rows.argtypes = lib.dvs_bn_scores.argtypes[:-1] + [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
-    lib.dvs_bn_toggle_scores_rows.restype = c_int
-    # (... as dvs_bn_toggle_scores up to status ..., rows, set_size, n_sets, set_of (nullable), stream)
-    lib.dvs_bn_toggle_scores_rows.argtypes = lib.dvs_bn_toggle_scores.argtypes[:-1] + [c_void_p, c_int32, c_int32, c_void_p,
-                                                                                      c_void_p]
-    lib.dvs_bootstrap_rows.restype = c_int
-    # (n_sets, set_size, n_samples, seed, set_offset, rows, stream)
-    lib.dvs_bootstrap_rows.argtypes = [c_int32, c_int32, c_int32, c_uint64, c_int64, c_void_p, c_void_p]
-    lib.dvs_arc_strength.restype = c_int
-    # (batch, n_vars, pdag, counts, counts_bytes, stream)
-    lib.dvs_arc_strength.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.dvs_averaged_network.restype = c_int
-    # (groups, n_vars, counts, n_networks, min_any, parents, parents_bytes, info, stream)
-    lib.dvs_averaged_network.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.dvs_bic_parent_masks.restype = c_int
-    lib.dvs_bic_parent_masks.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_gp_predict.restype = c_int
-    lib.dvs_gp_predict.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
-                                   ctypes.c_double, c_void_p, c_void_p]
-    lib.dvs_gp_kernel.restype = c_int
-    lib.dvs_gp_kernel.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p,
-                                  c_void_p]
-    lib.dvs_gp_kernel_backward.restype = c_int
-    lib.dvs_gp_kernel_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, ctypes.c_double,
-                                           ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_gp_acquire.restype = c_int
-    # (batch, n_inducing, dim, ld, x, inducing, weights [P | alpha], c0, outputscale, lengthscale, constant, best, xi,
-    #  mean, var, ei, grad (nullable), stream)
-    lib.dvs_gp_acquire.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p] + [ctypes.c_double] * 6 + \
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.dvs_clip_adam.restype = c_int
-    # (n, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, max_norm, scratch, guard, stream)
-    lib.dvs_clip_adam.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
-                                  c_int64, c_float, c_void_p, c_void_p, c_void_p]
-    lib.dvs_clip_adam_from_partials.restype = c_int
-    lib.dvs_clip_adam_from_partials.argtypes = lib.dvs_clip_adam.argtypes
-    lib.dvs_profile_enable.restype = None
-    lib.dvs_profile_enable.argtypes = [c_int]
-    lib.dvs_profile_collect.restype = c_int
-    lib.dvs_profile_collect.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int]
-    lib.dvs_debug_activation.restype = c_int
-    lib.dvs_debug_activation.argtypes = [P(DvsShape), c_void_p, c_int, c_void_p, c_void_p]
-    lib.dvs_debug_dag_losses.restype = c_int
-    lib.dvs_debug_dag_losses.argtypes = [P(DvsShape), c_void_p, c_void_p, c_void_p]
+    for name, (restype, args) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = [ctype for _, ctype in args]
     return lib
-
-
-EXPORTS = ["dvs_version", "dvs_last_error", "dvs_device_cus", "dvs_param_count", "dvs_param_table",
-           "dvs_workspace_bytes", "dvs_record_bytes", "dvs_pack_features", "dvs_build_records", "dvs_loss_forward", "dvs_loss_forward_notify", "dvs_loss_backward", "dvs_loss_backward_sq", "dvs_loss_forward_defer", "dvs_loss_backward_emit", "dvs_encode", "dvs_decode", "dvs_match_decoded", "dvs_decoded_structures", "dvs_structset_filter", "dvs_generate_dags", "dvs_generate_edge_counts", "dvs_bic_scores", "dvs_bn_scores", "dvs_bn_toggle_scores", "dvs_hc_step", "dvs_tabu_step", "dvs_hc_perturb", "dvs_cpdag", "dvs_pdag_compare", "dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient", "dvs_bn_fit", "dvs_bn_sample_workspace_bytes", "dvs_bn_sample", "dvs_bn_loglik", "dvs_bn_lw_workspace_bytes", "dvs_bn_lw", "dvs_bn_blanket_posterior", "dvs_exact_workspace_bytes", "dvs_exact_search", "dvs_arc_posterior_workspace_bytes", "dvs_arc_posterior", "dvs_order_mcmc", "dvs_order_mcmc_finish", "dvs_bn_scores_rows", "dvs_bn_toggle_scores_rows", "dvs_bootstrap_rows", "dvs_arc_strength", "dvs_averaged_network", "dvs_bic_parent_masks", "dvs_gp_predict", "dvs_gp_kernel", "dvs_gp_kernel_backward", "dvs_gp_acquire",
-           "dvs_clip_adam", "dvs_clip_adam_from_partials", "dvs_debug_activation", "dvs_debug_dag_losses", "dvs_debug_launch", "dvs_profile_enable", "dvs_profile_collect"]
 
 
 def profile_collect(lib):

@@ -21,6 +21,7 @@ import itertools
 import numpy as np
 
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 RULES = ("R1", "R2", "R3")
@@ -434,55 +435,42 @@ def validation_cases(D):
     pairs where two checks fail and the earlier one decides.  D: a dummy non-null pointer, never dereferenced."""
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):         # at: {"i<index>": value} replaces base[index]
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
+    c = entry("dvs_cpdag", cases, batch=8, n_vars=12, parents=D, pdag=D, pdag_bytes=768, flags=D, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(2, "batch must be > 0", batch=-3)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars must be < 2^31", batch=1 << 26, n_vars=32, pdag_bytes=1 << 40)
+    c(10, "null pointer", parents=None)
+    c(10, "null pointer", pdag=None)
+    c(10, "null pointer", flags=None)
+    c(14, "pdag_bytes < batch * n_vars * 8 = 768", pdag_bytes=767)
+    c(2, "batch must be > 0", batch=0, n_vars=49)                                      # batch before n_vars
+    c(3, "n_vars must be in [1, 48]", batch=1 << 30, n_vars=49)                        # n_vars before the product
+    c(2, "batch * n_vars must be < 2^31", batch=1 << 26, n_vars=32, parents=None)      # the product before null
+    c(10, "null pointer", flags=None, pdag_bytes=0)                                    # null before pdag_bytes
 
-    # (batch, n_vars, parents, pdag, pdag_bytes, flags, stream)
-    c = entry("dvs_cpdag", [8, 12, D, D, 768, D, None])
-    c(2, "dvs_cpdag: batch must be > 0", i0=0)
-    c(2, "dvs_cpdag: batch must be > 0", i0=-3)
-    c(3, "dvs_cpdag: n_vars must be in [1, 48]", i1=0)
-    c(3, "dvs_cpdag: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_cpdag: batch * n_vars must be < 2^31", i0=1 << 26, i1=32, i4=1 << 40)
-    c(10, "dvs_cpdag: null pointer", i2=None)
-    c(10, "dvs_cpdag: null pointer", i3=None)
-    c(10, "dvs_cpdag: null pointer", i5=None)
-    c(14, "dvs_cpdag: pdag_bytes < batch * n_vars * 8 = 768", i4=767)
-    c(2, "dvs_cpdag: batch must be > 0", i0=0, i1=49)                              # batch before n_vars
-    c(3, "dvs_cpdag: n_vars must be in [1, 48]", i0=1 << 30, i1=49)                # n_vars before the product
-    c(2, "dvs_cpdag: batch * n_vars must be < 2^31", i0=1 << 26, i1=32, i2=None)   # the product before null
-    c(10, "dvs_cpdag: null pointer", i5=None, i4=0)                                # null before pdag_bytes
-
-    # (batch, n_vars, a, b, b_rows, counts, counts_bytes, stream)
-    c = entry("dvs_pdag_compare", [8, 12, D, D, 8, D, 160, None])
-    c(2, "dvs_pdag_compare: batch must be > 0", i0=0)
-    c(3, "dvs_pdag_compare: n_vars must be in [1, 48]", i1=0)
-    c(3, "dvs_pdag_compare: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_pdag_compare: batch * n_vars must be < 2^31", i0=1 << 26, i1=32, i4=1, i6=1 << 40)
-    c(10, "dvs_pdag_compare: null pointer", i2=None)
-    c(10, "dvs_pdag_compare: null pointer", i3=None)
-    c(10, "dvs_pdag_compare: null pointer", i5=None)
-    c(12, "dvs_pdag_compare: b_rows must be 1 or batch", i4=0)
-    c(12, "dvs_pdag_compare: b_rows must be 1 or batch", i4=7)
-    c(14, "dvs_pdag_compare: counts_bytes < batch * 20 = 160", i6=159)
-    c(14, "dvs_pdag_compare: counts_bytes < batch * 20 = 160", i4=1, i6=159)
-    c(2, "dvs_pdag_compare: batch must be > 0", i0=0, i1=49)                       # batch before n_vars
-    c(3, "dvs_pdag_compare: n_vars must be in [1, 48]", i1=49, i2=None)            # range before null
-    c(2, "dvs_pdag_compare: batch * n_vars must be < 2^31", i0=1 << 26, i1=32, i3=None)    # the product before null
-    c(10, "dvs_pdag_compare: null pointer", i3=None, i4=3)                         # null before b_rows
-    c(12, "dvs_pdag_compare: b_rows must be 1 or batch", i4=2, i6=0)               # b_rows before counts_bytes
+    c = entry("dvs_pdag_compare", cases, batch=8, n_vars=12, a=D, b=D, b_rows=8, counts=D, counts_bytes=160, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars must be < 2^31", batch=1 << 26, n_vars=32, b_rows=1, counts_bytes=1 << 40)
+    c(10, "null pointer", a=None)
+    c(10, "null pointer", b=None)
+    c(10, "null pointer", counts=None)
+    c(12, "b_rows must be 1 or batch", b_rows=0)
+    c(12, "b_rows must be 1 or batch", b_rows=7)
+    c(14, "counts_bytes < batch * 20 = 160", counts_bytes=159)
+    c(14, "counts_bytes < batch * 20 = 160", b_rows=1, counts_bytes=159)
+    c(2, "batch must be > 0", batch=0, n_vars=49)                                      # batch before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, a=None)                               # range before null
+    c(2, "batch * n_vars must be < 2^31", batch=1 << 26, n_vars=32, b=None)            # the product before null
+    c(10, "null pointer", b=None, b_rows=3)                                            # null before b_rows
+    c(12, "b_rows must be 1 or batch", b_rows=2, counts_bytes=0)                       # b_rows before counts_bytes
     return cases
 
 
 def check_argument_refusals(lib, D):
     cases = validation_cases(D)
     assert {fn for fn, *_ in cases} == {"dvs_cpdag", "dvs_pdag_compare"}
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)

@@ -30,6 +30,7 @@ from tests import bn_score_corpus as bn
 from tests import cpdag_corpus as cp
 from tests import hillclimb_corpus as hc
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 NO_ARG = 0xFFFFFFFF
@@ -474,44 +475,35 @@ def check_real(real, name, sample_seed=3):
 # 5. Argument refusals (no device needed: everything is checked before anything is enqueued)
 # ---------------------------------------------------------------------------------------------------------------------
 def validation_cases(D):
-    """(arguments, return code, text dvs_last_error must contain) of dvs_exact_search: every check, and the pairs where two
-    checks fail and the earlier one decides.  D: a dummy non-null pointer, never dereferenced."""
-    fn = "dvs_exact_search"
+    """(entry point, arguments, return code, text dvs_last_error must contain) of dvs_exact_search: every check, and the pairs
+    where two checks fail and the earlier one decides.  D: a dummy non-null pointer, never dereferenced."""
     tb, wb = 3 * 256 * 8 * 8, layout(3, 8)[4]
-    # (batch, n_vars, table, table_bytes, max_parents, forbidden, workspace, workspace_bytes, parents, order, score, flags, stream)
-    base = [3, 8, D, tb, 0, None, D, wb, D, D, D, D, None]
     cases = []
-
-    def c(code, text, **at):
-        args = list(base)
-        for k, v in at.items():
-            args[int(k[1:])] = v
-        cases.append((args, code, f"{fn}: {text}"))
-
-    c(2, "batch must be > 0", i0=0)
-    c(2, "batch must be > 0", i0=-2)
-    c(3, "n_vars must be in [1, 20]", i1=0)
-    c(3, "n_vars must be in [1, 20]", i1=21)
-    c(2, "batch * 2^n_vars * n_vars must be < 2^31", i0=128, i1=20, i3=1 << 40, i7=1 << 40)      # 2^27 * 20 > 2^31
-    c(2, "batch * 2^n_vars * n_vars must be < 2^31", i0=1 << 30, i1=1, i3=1 << 40, i7=1 << 40)      # 2^31 exactly
-    for i in (2, 6, 8, 9, 10, 11):
-        c(10, "null pointer", **{f"i{i}": None})
-    c(14, f"table_bytes < batch * 2^n_vars * n_vars * 8 = {tb}", i3=tb - 1)
-    c(14, f"workspace_bytes < dvs_exact_workspace_bytes = {wb}", i7=wb - 1)
-    c(14, f"workspace_bytes < dvs_exact_workspace_bytes = {layout(5, 20)[4]}", i0=5, i1=20, i3=1 << 40, i7=0)
-    c(2, "batch must be > 0", i0=0, i1=21)                                       # batch before n_vars
-    c(3, "n_vars must be in [1, 20]", i0=1 << 30, i1=21)                         # n_vars before the product
-    c(2, "batch * 2^n_vars * n_vars must be < 2^31", i0=128, i1=20, i2=None)     # the product before null
-    c(10, "null pointer", i11=None, i3=0, i7=0)                                  # null before the sizes
-    c(14, f"table_bytes < batch * 2^n_vars * n_vars * 8 = {tb}", i3=0, i7=0)     # table_bytes before workspace_bytes
+    c = entry("dvs_exact_search", cases, batch=3, n_vars=8, table=D, table_bytes=tb, max_parents=0, forbidden=None, workspace=D,
+              workspace_bytes=wb, parents=D, order=D, score=D, flags=D, stream=None)
+    big = dict(table_bytes=1 << 40, workspace_bytes=1 << 40)
+    c(2, "batch must be > 0", batch=0)
+    c(2, "batch must be > 0", batch=-2)
+    c(3, "n_vars must be in [1, 20]", n_vars=0)
+    c(3, "n_vars must be in [1, 20]", n_vars=21)
+    c(2, "batch * 2^n_vars * n_vars must be < 2^31", batch=128, n_vars=20, **big)      # 2^27 * 20 > 2^31
+    c(2, "batch * 2^n_vars * n_vars must be < 2^31", batch=1 << 30, n_vars=1, **big)   # 2^31 exactly
+    for name in ("table", "workspace", "parents", "order", "score", "flags"):
+        c(10, "null pointer", **{name: None})
+    c(14, f"table_bytes < batch * 2^n_vars * n_vars * 8 = {tb}", table_bytes=tb - 1)
+    c(14, f"workspace_bytes < dvs_exact_workspace_bytes = {wb}", workspace_bytes=wb - 1)
+    c(14, f"workspace_bytes < dvs_exact_workspace_bytes = {layout(5, 20)[4]}", batch=5, n_vars=20, table_bytes=1 << 40,
+      workspace_bytes=0)
+    c(2, "batch must be > 0", batch=0, n_vars=21)                                      # batch before n_vars
+    c(3, "n_vars must be in [1, 20]", batch=1 << 30, n_vars=21)                        # n_vars before the product
+    c(2, "batch * 2^n_vars * n_vars must be < 2^31", batch=128, n_vars=20, table=None)   # the product before null
+    c(10, "null pointer", flags=None, table_bytes=0, workspace_bytes=0)                # null before the sizes
+    c(14, f"table_bytes < batch * 2^n_vars * n_vars * 8 = {tb}", table_bytes=0, workspace_bytes=0)   # table_bytes before workspace_bytes
     return cases
 
 
 def check_argument_refusals(lib, D):
-    for args, code, text in validation_cases(D):
-        got = lib.dvs_exact_search(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg) == (code, True), (args, got, msg)
+    run(lib, validation_cases(D))
     for batch, n in ((1, 1), (3, 8), (5, 20), (1, 14)):
         assert lib.dvs_exact_workspace_bytes(batch, n) == layout(batch, n)[4]
     for (batch, n), text in (((0, 8), "batch must be > 0"), ((1, 0), "n_vars must be in [1, 20]"), ((1, 21), "n_vars must be in [1, 20]"),

@@ -33,6 +33,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import params_corpus as pm
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 SITE_BN_LW = 501
@@ -768,61 +769,55 @@ def cv_pred_reference(data, card, masks, folds, seed, iss, target, loss, M=500):
 def validation_cases(D):
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
-
     # (n_vars, n_queries, n_particles, card, parents, offsets, cpt, n_cells, evidence, observed, event, targets, seed,
     #  query_offset, workspace, workspace_bytes, sums, marginals, particles, particle_weights, status, stream)
     need = 256 + 512 + 256 + 1792                    # 100 cells, 3 queries; 3 * 2 chunks * (3 + 2 * 16) cells * 8 = 1680 -> 1792
-    c = entry("dvs_bn_lw", [12, 3, 300, D, D, D, D, 100, D, D, None, 0b101, 7, 0, D, need, D, D, None, None, D, None])
-    c(2, "dvs_bn_lw: n_queries and n_particles must be in [1, 2^31 - 1]", i1=0)
-    c(2, "dvs_bn_lw: n_queries and n_particles must be in [1, 2^31 - 1]", i2=0)
-    c(2, "dvs_bn_lw: n_queries and n_particles must be in [1, 2^31 - 1]", i2=1 << 31)
-    c(3, "dvs_bn_lw: n_vars must be in [1, 48]", i0=0)
-    c(3, "dvs_bn_lw: n_vars must be in [1, 48]", i0=49)
-    c(2, "dvs_bn_lw: n_cells must be in [n_vars, 2^31 - 1]", i7=11)
-    c(2, "dvs_bn_lw: n_queries * ceil(n_particles / 256) must be < 2^31", i1=1 << 24, i2=1 << 16, i15=1 << 60)
-    c(12, "dvs_bn_lw: targets has a bit at or above n_vars", i11=1 << 12)
-    c(12, "dvs_bn_lw: query_offset must be >= 0", i13=-1)
-    for i in (3, 4, 5, 6, 8, 9, 14, 16, 20):
-        c(10, "dvs_bn_lw: null pointer", **{f"i{i}": None})
-    c(12, "dvs_bn_lw: marginals goes with targets != 0, and only with it", i17=None)
-    c(12, "dvs_bn_lw: marginals goes with targets != 0, and only with it", i11=0)
-    c(12, "dvs_bn_lw: particles and particle_weights are both null or both given", i18=D)
-    c(12, "dvs_bn_lw: particles and particle_weights are both null or both given", i19=D)
-    c(14, f"dvs_bn_lw: workspace_bytes < dvs_bn_lw_workspace_bytes = {need}", i15=need - 1)
-    c(2, "dvs_bn_lw: n_queries and n_particles must be in", i1=0, i0=49)         # the counts before n_vars
-    c(3, "dvs_bn_lw: n_vars must be in [1, 48]", i0=49, i7=0)                    # n_vars before n_cells
-    c(2, "dvs_bn_lw: n_cells must be in", i7=0, i11=1 << 12)                     # n_cells before targets
-    c(12, "dvs_bn_lw: targets has a bit", i11=1 << 12, i13=-1)                   # targets before query_offset
-    c(12, "dvs_bn_lw: query_offset must be >= 0", i13=-1, i3=None)               # query_offset before null
-    c(10, "dvs_bn_lw: null pointer", i20=None, i17=None)                         # null before marginals / targets
-    c(12, "dvs_bn_lw: marginals goes with", i17=None, i18=D)                     # marginals before particles
-    c(12, "dvs_bn_lw: particles and particle_weights", i18=D, i15=0)             # particles before workspace_bytes
+    c = entry("dvs_bn_lw", cases, n_vars=12, n_queries=3, n_particles=300, card=D, parents=D, offsets=D, cpt=D, n_cells=100,
+              evidence=D, observed=D, event=None, targets=0b101, seed=7, query_offset=0, workspace=D, workspace_bytes=need,
+              sums=D, marginals=D, particles=None, particle_weights=None, status=D, stream=None)
+    c(2, "n_queries and n_particles must be in [1, 2^31 - 1]", n_queries=0)
+    c(2, "n_queries and n_particles must be in [1, 2^31 - 1]", n_particles=0)
+    c(2, "n_queries and n_particles must be in [1, 2^31 - 1]", n_particles=1 << 31)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "n_cells must be in [n_vars, 2^31 - 1]", n_cells=11)
+    c(2, "n_queries * ceil(n_particles / 256) must be < 2^31", n_queries=1 << 24, n_particles=1 << 16, workspace_bytes=1 << 60)
+    c(12, "targets has a bit at or above n_vars", targets=1 << 12)
+    c(12, "query_offset must be >= 0", query_offset=-1)
+    for name in ("card", "parents", "offsets", "cpt", "evidence", "observed", "workspace", "sums", "status"):
+        c(10, "null pointer", **{name: None})
+    c(12, "marginals goes with targets != 0, and only with it", marginals=None)
+    c(12, "marginals goes with targets != 0, and only with it", targets=0)
+    c(12, "particles and particle_weights are both null or both given", particles=D)
+    c(12, "particles and particle_weights are both null or both given", particle_weights=D)
+    c(14, f"workspace_bytes < dvs_bn_lw_workspace_bytes = {need}", workspace_bytes=need - 1)
+    c(2, "n_queries and n_particles must be in", n_queries=0, n_vars=49)               # the counts before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, n_cells=0)                            # n_vars before n_cells
+    c(2, "n_cells must be in", n_cells=0, targets=1 << 12)                             # n_cells before targets
+    c(12, "targets has a bit", targets=1 << 12, query_offset=-1)                       # targets before query_offset
+    c(12, "query_offset must be >= 0", query_offset=-1, card=None)                     # query_offset before null
+    c(10, "null pointer", status=None, marginals=None)                                 # null before marginals / targets
+    c(12, "marginals goes with", marginals=None, particles=D)                          # marginals before particles
+    c(12, "particles and particle_weights", particles=D, workspace_bytes=0)            # particles before workspace_bytes
 
-    # (batch, n_vars, n_rows, data, card, parents, offsets, cpt, cpt_bytes, target, use_children, posterior, pred, status, stream)
-    c = entry("dvs_bn_blanket_posterior", [3, 6, 300, D, D, D, D, D, 144, 2, 1, None, D, D, None])
-    c(2, "dvs_bn_blanket_posterior: batch must be > 0", i0=0)
-    c(2, "dvs_bn_blanket_posterior: n_rows must be in [1, 2^31 - 1]", i2=0)
-    c(3, "dvs_bn_blanket_posterior: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_bn_blanket_posterior: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", i0=1 << 30, i1=48, i8=1 << 50)
-    c(12, "dvs_bn_blanket_posterior: target must be in [0, n_vars)", i9=6)
-    c(12, "dvs_bn_blanket_posterior: target must be in [0, n_vars)", i9=-1)
-    c(12, "dvs_bn_blanket_posterior: use_children must be 0 or 1", i10=2)
-    for i in (3, 4, 5, 6, 7, 12, 13):
-        c(10, "dvs_bn_blanket_posterior: null pointer", **{f"i{i}": None})
-    c(14, "dvs_bn_blanket_posterior: cpt_bytes < batch * n_vars * 8 = 144", i8=143)
-    c(2, "dvs_bn_blanket_posterior: batch must be > 0", i0=0, i2=0)              # batch before n_rows
-    c(2, "dvs_bn_blanket_posterior: n_rows must be in", i2=0, i1=49)             # n_rows before n_vars
-    c(3, "dvs_bn_blanket_posterior: n_vars must be in [1, 48]", i1=49, i9=-1)    # n_vars before target
-    c(12, "dvs_bn_blanket_posterior: target must be in", i9=6, i10=2)            # target before use_children
-    c(12, "dvs_bn_blanket_posterior: use_children must be", i10=2, i3=None)      # use_children before null
-    c(10, "dvs_bn_blanket_posterior: null pointer", i13=None, i8=0)              # null before cpt_bytes
+    c = entry("dvs_bn_blanket_posterior", cases, batch=3, n_vars=6, n_rows=300, data=D, card=D, parents=D, offsets=D, cpt=D,
+              cpt_bytes=144, target=2, use_children=1, posterior=None, pred=D, status=D, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(2, "n_rows must be in [1, 2^31 - 1]", n_rows=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", batch=1 << 30, n_vars=48, cpt_bytes=1 << 50)
+    c(12, "target must be in [0, n_vars)", target=6)
+    c(12, "target must be in [0, n_vars)", target=-1)
+    c(12, "use_children must be 0 or 1", use_children=2)
+    for name in ("data", "card", "parents", "offsets", "cpt", "pred", "status"):
+        c(10, "null pointer", **{name: None})
+    c(14, "cpt_bytes < batch * n_vars * 8 = 144", cpt_bytes=143)
+    c(2, "batch must be > 0", batch=0, n_rows=0)                                       # batch before n_rows
+    c(2, "n_rows must be in", n_rows=0, n_vars=49)                                     # n_rows before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, target=-1)                            # n_vars before target
+    c(12, "target must be in", target=6, use_children=2)                               # target before use_children
+    c(12, "use_children must be", use_children=2, data=None)                           # use_children before null
+    c(10, "null pointer", status=None, cpt_bytes=0)                                    # null before cpt_bytes
     return cases
 
 
@@ -830,10 +825,7 @@ def check_argument_refusals(lib, D=None):
     D = ctypes.c_void_p(4096) if D is None else D                                # never dereferenced
     cases = validation_cases(D)
     assert {fn for fn, *_ in cases} == {"dvs_bn_lw", "dvs_bn_blanket_posterior"}
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)
     assert lib.dvs_bn_lw_workspace_bytes(100, 12, 3, 300, 0b101) == 2816
     for args, text in (((100, 0, 3, 300, 0), "n_vars must be in [1, 48]"), ((11, 12, 3, 300, 0), "n_cells must be in"),
                        ((100, 12, 0, 300, 0), "n_queries and n_particles"), ((100, 12, 3, 300, 1 << 12), "targets has a bit")):

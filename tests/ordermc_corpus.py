@@ -47,6 +47,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import exact_corpus as ex
 from tests import posterior_corpus as po
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 INF = float("inf")
@@ -524,73 +525,60 @@ def check_flags(drv):
 def validation_cases(D):
     """(entry point, arguments, return code, text dvs_last_error must contain): every check, and the pairs where two checks
     fail and the earlier one decides.  D: a dummy non-null pointer, never dereferenced."""
-    fn = "dvs_order_mcmc"
     C, n, F, steps = 8, 10, 500, 100
-    # 0 chains, 1 n_vars, 2 n_families, 3 steps, 4 offsets, 5 sets, 6 sets_bytes, 7 scores, 8 scores_bytes, 9 seed,
-    # 10 chain_offset, 11 step_offset, 12 burn_in, 13 thin, 14 window, 15 init, 16 order, 17 log_score, 18 accepted, 19 sums,
-    # 20 sums_bytes, 21 kept, 22 best_score, 23 best_parents, 24 trace, 25 trace_bytes, 26 flags, 27 stream
-    base = [C, n, F, steps, D, D, F * 8, D, F * 8, 7, 0, 0, 20, 10, 1, 1, D, D, D, D, C * n * n * 8, D, D, D, D, C * steps * 8, D, None]
     cases = []
+    c = entry("dvs_order_mcmc", cases, chains=C, n_vars=n, n_families=F, steps=steps, offsets=D, sets=D, sets_bytes=F * 8,
+              scores=D, scores_bytes=F * 8, seed=7, chain_offset=0, step_offset=0, burn_in=20, thin=10, window=1, init=1,
+              order=D, log_score=D, accepted=D, sums=D, sums_bytes=C * n * n * 8, kept=D, best_score=D, best_parents=D,
+              trace=D, trace_bytes=C * steps * 8, flags=D, stream=None)
+    c(2, "chains must be > 0", chains=0)
+    c(2, "steps must be >= 0", steps=-1)
+    c(2, "n_families must be in [1, 2^31 - 1]", n_families=0)
+    c(2, "n_families must be in [1, 2^31 - 1]", n_families=1 << 31)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "chains * n_vars^2 must be < 2^31", chains=1 << 20, n_vars=48, sums_bytes=1 << 40, trace_bytes=1 << 40)
+    for name in ("offsets", "sets", "scores", "order", "log_score", "accepted", "sums", "kept", "best_score", "best_parents",
+                 "flags"):
+        c(10, "null pointer", **{name: None})
+    c(12, "chain_offset and step_offset must be >= 0", chain_offset=-1)
+    c(12, "chain_offset and step_offset must be >= 0", step_offset=-1)
+    c(13, "window must be in [1, max(1, n_vars - 1)]", window=0)
+    c(13, "window must be in [1, max(1, n_vars - 1)]", window=n)
+    c(13, "window must be in [1, max(1, n_vars - 1)]", n_vars=1, window=2)
+    c(13, "thin must be >= 1", thin=0)
+    c(13, "burn_in must be >= 0", burn_in=-1)
+    c(13, "init must be 0 or 1", init=2)
+    c(13, "3 * (step_offset + steps) must be < 2^32", step_offset=(1 << 32) // 3 - steps + 1)
+    c(13, "3 * (step_offset + steps) must be < 2^32", step_offset=1 << 40)
+    c(14, f"sets_bytes < n_families * 8 = {F * 8}", sets_bytes=F * 8 - 1)
+    c(14, f"scores_bytes < n_families * 8 = {F * 8}", scores_bytes=F * 8 - 1)
+    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", sums_bytes=C * n * n * 8 - 1)
+    c(14, f"trace_bytes < chains * steps * 8 = {C * steps * 8}", trace_bytes=C * steps * 8 - 1)
+    c(2, "chains must be > 0", chains=0, n_vars=49)                                    # counts before n_vars
+    c(2, "steps must be >= 0", steps=-1, n_families=0)                                 # steps before n_families
+    c(3, "n_vars must be in [1, 48]", n_vars=49, offsets=None)                         # n_vars before null
+    c(10, "null pointer", flags=None, chain_offset=-1)                                 # null before the offsets
+    c(12, "chain_offset and step_offset must be >= 0", step_offset=-1, window=0)       # offsets before the arguments
+    c(13, "window must be in [1, max(1, n_vars - 1)]", window=0, thin=0)               # window before thin
+    c(13, "thin must be >= 1", thin=0, step_offset=1 << 40)                            # thin before the draw bound
+    c(13, "3 * (step_offset + steps) must be < 2^32", step_offset=1 << 40, sets_bytes=0)   # arguments before the sizes
+    c(14, f"sets_bytes < n_families * 8 = {F * 8}", sets_bytes=0, scores_bytes=0)      # sets before scores
+    c(14, f"scores_bytes < n_families * 8 = {F * 8}", scores_bytes=0, sums_bytes=0)    # scores before sums
+    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", sums_bytes=0, trace_bytes=0)   # sums before trace
+    c(14, "sets_bytes", trace=None, trace_bytes=0, sets_bytes=0)                       # a null trace takes no size; sets_bytes decides
 
-    def c(code, text, **at):
-        args = list(base)
-        for k, v in at.items():
-            args[int(k[1:])] = v
-        cases.append((fn, args, code, f"{fn}: {text}"))
-
-    c(2, "chains must be > 0", i0=0)
-    c(2, "steps must be >= 0", i3=-1)
-    c(2, "n_families must be in [1, 2^31 - 1]", i2=0)
-    c(2, "n_families must be in [1, 2^31 - 1]", i2=1 << 31)
-    c(3, "n_vars must be in [1, 48]", i1=0)
-    c(3, "n_vars must be in [1, 48]", i1=49)
-    c(2, "chains * n_vars^2 must be < 2^31", i0=1 << 20, i1=48, i20=1 << 40, i25=1 << 40)
-    for i in (4, 5, 7, 16, 17, 18, 19, 21, 22, 23, 26):
-        c(10, "null pointer", **{f"i{i}": None})
-    c(12, "chain_offset and step_offset must be >= 0", i10=-1)
-    c(12, "chain_offset and step_offset must be >= 0", i11=-1)
-    c(13, "window must be in [1, max(1, n_vars - 1)]", i14=0)
-    c(13, "window must be in [1, max(1, n_vars - 1)]", i14=n)
-    c(13, "window must be in [1, max(1, n_vars - 1)]", i1=1, i14=2)
-    c(13, "thin must be >= 1", i13=0)
-    c(13, "burn_in must be >= 0", i12=-1)
-    c(13, "init must be 0 or 1", i15=2)
-    c(13, "3 * (step_offset + steps) must be < 2^32", i11=(1 << 32) // 3 - steps + 1)
-    c(13, "3 * (step_offset + steps) must be < 2^32", i11=1 << 40)
-    c(14, f"sets_bytes < n_families * 8 = {F * 8}", i6=F * 8 - 1)
-    c(14, f"scores_bytes < n_families * 8 = {F * 8}", i8=F * 8 - 1)
-    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", i20=C * n * n * 8 - 1)
-    c(14, f"trace_bytes < chains * steps * 8 = {C * steps * 8}", i25=C * steps * 8 - 1)
-    c(2, "chains must be > 0", i0=0, i1=49)                                        # counts before n_vars
-    c(2, "steps must be >= 0", i3=-1, i2=0)                                        # steps before n_families
-    c(3, "n_vars must be in [1, 48]", i1=49, i4=None)                              # n_vars before null
-    c(10, "null pointer", i26=None, i10=-1)                                        # null before the offsets
-    c(12, "chain_offset and step_offset must be >= 0", i11=-1, i14=0)              # offsets before the arguments
-    c(13, "window must be in [1, max(1, n_vars - 1)]", i14=0, i13=0)               # window before thin
-    c(13, "thin must be >= 1", i13=0, i11=1 << 40)                                 # thin before the draw bound
-    c(13, "3 * (step_offset + steps) must be < 2^32", i11=1 << 40, i6=0)           # arguments before the sizes
-    c(14, f"sets_bytes < n_families * 8 = {F * 8}", i6=0, i8=0)                    # sets before scores
-    c(14, f"scores_bytes < n_families * 8 = {F * 8}", i8=0, i20=0)                 # scores before sums
-    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", i20=0, i25=0)   # sums before trace
-    ok_without_trace = list(base)
-    ok_without_trace[24], ok_without_trace[25], ok_without_trace[6] = None, 0, 0   # a null trace takes no size; sets_bytes decides
-    cases.append((fn, ok_without_trace, 14, f"{fn}: sets_bytes"))
-
-    fn = "dvs_order_mcmc_finish"
-    base = [C, n, D, C * n * n * 8, D, D, None]                                    # chains, n_vars, sums, sums_bytes, kept, prob
-    c(2, "chains must be > 0", i0=0)
-    c(3, "n_vars must be in [1, 48]", i1=49)
-    c(2, "chains * n_vars^2 must be < 2^31", i0=1 << 20, i1=48)
-    for i in (2, 4, 5):
-        c(10, "null pointer", **{f"i{i}": None})
-    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", i3=C * n * n * 8 - 1)
-    c(3, "n_vars must be in [1, 48]", i1=0, i2=None)                               # n_vars before null
-    c(10, "null pointer", i5=None, i3=0)                                           # null before the size
+    c = entry("dvs_order_mcmc_finish", cases, chains=C, n_vars=n, sums=D, sums_bytes=C * n * n * 8, kept=D, prob=D, stream=None)
+    c(2, "chains must be > 0", chains=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "chains * n_vars^2 must be < 2^31", chains=1 << 20, n_vars=48)
+    for name in ("sums", "kept", "prob"):
+        c(10, "null pointer", **{name: None})
+    c(14, f"sums_bytes < chains * n_vars^2 * 8 = {C * n * n * 8}", sums_bytes=C * n * n * 8 - 1)
+    c(3, "n_vars must be in [1, 48]", n_vars=0, sums=None)                             # n_vars before null
+    c(10, "null pointer", prob=None, sums_bytes=0)                                     # null before the size
     return cases
 
 
 def check_argument_refusals(lib, D):
-    for fn, args, code, text in validation_cases(D):
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg) == (code, True), (fn, args, got, msg)
+    run(lib, validation_cases(D))

@@ -28,6 +28,7 @@ import numpy as np
 
 from oracle import rng as orng
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 MAX_CELLS = 36864            # include/dvs.h: the dense table of dvs_bn_fit
@@ -626,79 +627,68 @@ def check_loglik_equals_scorer(be, name):
 def validation_cases(D):
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
-
     nan, inf = float("nan"), float("inf")
-    # (batch, n_vars, n_samples, data, card, parents, method, iss, unobserved, offsets, cpt, cpt_bytes, status, stream)
-    c = entry("dvs_bn_fit", [4, 12, 100, D, D, D, 1, 1.0, 0, D, D, 384, D, None])
-    c(2, "dvs_bn_fit: batch and n_samples must be > 0", i0=0)
-    c(2, "dvs_bn_fit: batch and n_samples must be > 0", i2=0)
-    c(3, "dvs_bn_fit: n_vars must be in [1, 48]", i1=0)
-    c(3, "dvs_bn_fit: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_bn_fit: batch * n_vars must be < 2^31", i0=1 << 30, i1=48, i11=1 << 50)
-    c(12, "dvs_bn_fit: method is not a dvs_fit_method", i6=2)
-    c(12, "dvs_bn_fit: method is not a dvs_fit_method", i6=-1)
+    c = entry("dvs_bn_fit", cases, batch=4, n_vars=12, n_samples=100, data=D, card=D, parents=D, method=1, iss=1.0,
+              unobserved=0, offsets=D, cpt=D, cpt_bytes=384, status=D, stream=None)
+    c(2, "batch and n_samples must be > 0", batch=0)
+    c(2, "batch and n_samples must be > 0", n_samples=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars must be < 2^31", batch=1 << 30, n_vars=48, cpt_bytes=1 << 50)
+    c(12, "method is not a dvs_fit_method", method=2)
+    c(12, "method is not a dvs_fit_method", method=-1)
     for bad in (0.0, -1.0, nan, inf):
-        c(13, "dvs_bn_fit: iss must be finite and > 0", i7=bad)
-    c(12, "dvs_bn_fit: unobserved must be 0 (NaN) or 1 (uniform)", i8=2)
-    for i in (3, 4, 5, 9, 10, 12):
-        c(10, "dvs_bn_fit: null pointer", **{f"i{i}": None})
-    c(14, "dvs_bn_fit: cpt_bytes < batch * n_vars * 8 = 384", i11=383)
-    c(2, "dvs_bn_fit: batch and n_samples must be > 0", i0=0, i1=49)               # sizes before n_vars
-    c(3, "dvs_bn_fit: n_vars must be in [1, 48]", i1=49, i6=9)                     # n_vars before the method
-    c(12, "dvs_bn_fit: method is not a dvs_fit_method", i6=9, i7=nan)              # the method before iss
-    c(13, "dvs_bn_fit: iss must be finite and > 0", i7=nan, i8=2)                  # iss before unobserved
-    c(12, "dvs_bn_fit: unobserved must be", i8=2, i3=None)                         # unobserved before null
-    c(10, "dvs_bn_fit: null pointer", i12=None, i11=0)                             # null before cpt_bytes
+        c(13, "iss must be finite and > 0", iss=bad)
+    c(12, "unobserved must be 0 (NaN) or 1 (uniform)", unobserved=2)
+    for name in ("data", "card", "parents", "offsets", "cpt", "status"):
+        c(10, "null pointer", **{name: None})
+    c(14, "cpt_bytes < batch * n_vars * 8 = 384", cpt_bytes=383)
+    c(2, "batch and n_samples must be > 0", batch=0, n_vars=49)                        # sizes before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, method=9)                             # n_vars before the method
+    c(12, "method is not a dvs_fit_method", method=9, iss=nan)                         # the method before iss
+    c(13, "iss must be finite and > 0", iss=nan, unobserved=2)                         # iss before unobserved
+    c(12, "unobserved must be", unobserved=2, data=None)                               # unobserved before null
+    c(10, "null pointer", status=None, cpt_bytes=0)                                    # null before cpt_bytes
 
-    # (n_vars, n_rows, card, parents, offsets, cpt, n_cells, seed, row_offset, workspace, workspace_bytes, data_out, status, stream)
-    c = entry("dvs_bn_sample", [12, 1000, D, D, D, D, 100, 7, 0, D, 768, D, D, None])
-    c(2, "dvs_bn_sample: n_rows must be in [1, 2^31 - 1]", i1=0)
-    c(2, "dvs_bn_sample: n_rows must be in [1, 2^31 - 1]", i1=1 << 31)
-    c(3, "dvs_bn_sample: n_vars must be in [1, 48]", i0=0)
-    c(3, "dvs_bn_sample: n_vars must be in [1, 48]", i0=49)
-    c(2, "dvs_bn_sample: n_cells must be in [n_vars, 2^31 - 1]", i6=11)
-    c(2, "dvs_bn_sample: n_cells must be in [n_vars, 2^31 - 1]", i6=1 << 31, i10=1 << 40)
-    c(12, "dvs_bn_sample: row_offset must be >= 0", i8=-1)
-    for i in (2, 3, 4, 5, 9, 11, 12):
-        c(10, "dvs_bn_sample: null pointer", **{f"i{i}": None})
-    c(14, "dvs_bn_sample: workspace_bytes < dvs_bn_sample_workspace_bytes = 768", i10=767)
-    c(2, "dvs_bn_sample: n_rows must be in [1, 2^31 - 1]", i1=0, i0=49)             # n_rows before n_vars
-    c(3, "dvs_bn_sample: n_vars must be in [1, 48]", i0=49, i6=0)                  # n_vars before n_cells
-    c(2, "dvs_bn_sample: n_cells must be in", i6=0, i8=-1)                         # n_cells before row_offset
-    c(12, "dvs_bn_sample: row_offset must be >= 0", i8=-1, i2=None)                # row_offset before null
-    c(10, "dvs_bn_sample: null pointer", i12=None, i10=0)                          # null before workspace_bytes
+    c = entry("dvs_bn_sample", cases, n_vars=12, n_rows=1000, card=D, parents=D, offsets=D, cpt=D, n_cells=100, seed=7,
+              row_offset=0, workspace=D, workspace_bytes=768, data_out=D, status=D, stream=None)
+    c(2, "n_rows must be in [1, 2^31 - 1]", n_rows=0)
+    c(2, "n_rows must be in [1, 2^31 - 1]", n_rows=1 << 31)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "n_cells must be in [n_vars, 2^31 - 1]", n_cells=11)
+    c(2, "n_cells must be in [n_vars, 2^31 - 1]", n_cells=1 << 31, workspace_bytes=1 << 40)
+    c(12, "row_offset must be >= 0", row_offset=-1)
+    for name in ("card", "parents", "offsets", "cpt", "workspace", "data_out", "status"):
+        c(10, "null pointer", **{name: None})
+    c(14, "workspace_bytes < dvs_bn_sample_workspace_bytes = 768", workspace_bytes=767)
+    c(2, "n_rows must be in [1, 2^31 - 1]", n_rows=0, n_vars=49)                       # n_rows before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, n_cells=0)                            # n_vars before n_cells
+    c(2, "n_cells must be in", n_cells=0, row_offset=-1)                               # n_cells before row_offset
+    c(12, "row_offset must be >= 0", row_offset=-1, card=None)                         # row_offset before null
+    c(10, "null pointer", status=None, workspace_bytes=0)                              # null before workspace_bytes
 
-    # (batch, n_vars, n_rows, data, card, parents, offsets, cpt, per_row, out, workspace, workspace_bytes, status, stream)
-    c = entry("dvs_bn_loglik", [3, 6, 300, D, D, D, D, D, None, D, D, 656, D, None])
-    c(2, "dvs_bn_loglik: batch must be > 0", i0=0)
-    c(2, "dvs_bn_loglik: n_rows must be in [1, 2^31 - 1]", i2=0)
-    c(3, "dvs_bn_loglik: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_bn_loglik: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", i0=1 << 30, i1=48, i11=1 << 50)
-    c(2, "dvs_bn_loglik: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", i0=1 << 20, i2=1 << 30, i11=1 << 50)
-    for i in (3, 4, 5, 6, 7, 9, 10, 12):
-        c(10, "dvs_bn_loglik: null pointer", **{f"i{i}": None})
-    c(14, "dvs_bn_loglik: workspace_bytes < partials + flags + batch * n_vars * 8 = 656", i11=655)
-    c(2, "dvs_bn_loglik: batch must be > 0", i0=0, i2=0)                           # batch before n_rows
-    c(2, "dvs_bn_loglik: n_rows must be in", i2=0, i1=49)                          # n_rows before n_vars
-    c(3, "dvs_bn_loglik: n_vars must be in [1, 48]", i1=49, i3=None)               # n_vars before null
-    c(10, "dvs_bn_loglik: null pointer", i12=None, i11=0)                          # null before workspace_bytes
+    c = entry("dvs_bn_loglik", cases, batch=3, n_vars=6, n_rows=300, data=D, card=D, parents=D, offsets=D, cpt=D,
+              per_row=None, out=D, workspace=D, workspace_bytes=656, status=D, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(2, "n_rows must be in [1, 2^31 - 1]", n_rows=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", batch=1 << 30, n_vars=48, workspace_bytes=1 << 50)
+    c(2, "batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", batch=1 << 20, n_rows=1 << 30, workspace_bytes=1 << 50)
+    for name in ("data", "card", "parents", "offsets", "cpt", "out", "workspace", "status"):
+        c(10, "null pointer", **{name: None})
+    c(14, "workspace_bytes < partials + flags + batch * n_vars * 8 = 656", workspace_bytes=655)
+    c(2, "batch must be > 0", batch=0, n_rows=0)                                       # batch before n_rows
+    c(2, "n_rows must be in", n_rows=0, n_vars=49)                                     # n_rows before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, data=None)                            # n_vars before null
+    c(10, "null pointer", status=None, workspace_bytes=0)                              # null before workspace_bytes
     return cases
 
 
 def check_argument_refusals(lib, D):
     cases = validation_cases(D)
     assert {fn for fn, *_ in cases} == {"dvs_bn_fit", "dvs_bn_sample", "dvs_bn_loglik"}
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)
     # the fourth entry point returns a size: 0 and the reason for arguments out of range
     assert lib.dvs_bn_sample_workspace_bytes(100, 12) == 768 and lib.dvs_bn_sample_workspace_bytes(12, 12) == 512
     for n_cells, n_vars, text in ((100, 0, "n_vars must be in [1, 48]"), (100, 49, "n_vars must be in [1, 48]"),

@@ -38,6 +38,7 @@ import numpy as np
 
 from tests import cpdag_corpus as cp
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 MAX_CELLS = 36864
@@ -680,92 +681,80 @@ def check_e2e_raw(be, name, S, typ):
 def validation_cases(D):
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
-
     nan = float("nan")
-    # (n_tests, n_vars, n_samples, data, card, pairs, cond, test_type, max_cells, out, out_bytes, status, stream)
-    c = entry("dvs_ci_tests", [8, 12, 100, D, D, D, D, 0, 729, D, 192, D, None])
-    c(2, "dvs_ci_tests: n_tests and n_samples must be > 0", i0=0)
-    c(2, "dvs_ci_tests: n_tests and n_samples must be > 0", i2=-1)
-    c(3, "dvs_ci_tests: n_vars must be in [1, 48]", i1=0)
-    c(3, "dvs_ci_tests: n_vars must be in [1, 48]", i1=49)
-    c(12, "dvs_ci_tests: test_type is not a dvs_ci_type", i7=4)
-    c(12, "dvs_ci_tests: test_type is not a dvs_ci_type", i7=-1)
-    c(13, "dvs_ci_tests: max_cells must be in [1, 36864]", i8=0)
-    c(13, "dvs_ci_tests: max_cells must be in [1, 36864]", i8=36865)
-    for i in (3, 4, 5, 6, 9, 11):
-        c(10, "dvs_ci_tests: null pointer", **{f"i{i}": None})
-    c(14, "dvs_ci_tests: out_bytes < n_tests * 24 = 192", i10=191)
-    c(2, "dvs_ci_tests: n_tests and n_samples must be > 0", i0=0, i1=49)            # sizes before n_vars
-    c(3, "dvs_ci_tests: n_vars must be in [1, 48]", i1=49, i7=9)                   # n_vars before the type
-    c(12, "dvs_ci_tests: test_type is not a dvs_ci_type", i7=9, i8=0)              # the type before max_cells
-    c(13, "dvs_ci_tests: max_cells must be in [1, 36864]", i8=0, i3=None)          # max_cells before null
-    c(10, "dvs_ci_tests: null pointer", i11=None, i10=0)                           # null before out_bytes
+    c = entry("dvs_ci_tests", cases, n_tests=8, n_vars=12, n_samples=100, data=D, card=D, pairs=D, cond=D, test_type=0,
+              max_cells=729, out=D, out_bytes=192, status=D, stream=None)
+    c(2, "n_tests and n_samples must be > 0", n_tests=0)
+    c(2, "n_tests and n_samples must be > 0", n_samples=-1)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(12, "test_type is not a dvs_ci_type", test_type=4)
+    c(12, "test_type is not a dvs_ci_type", test_type=-1)
+    c(13, "max_cells must be in [1, 36864]", max_cells=0)
+    c(13, "max_cells must be in [1, 36864]", max_cells=36865)
+    for name in ("data", "card", "pairs", "cond", "out", "status"):
+        c(10, "null pointer", **{name: None})
+    c(14, "out_bytes < n_tests * 24 = 192", out_bytes=191)
+    c(2, "n_tests and n_samples must be > 0", n_tests=0, n_vars=49)                    # sizes before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, test_type=9)                          # n_vars before the type
+    c(12, "test_type is not a dvs_ci_type", test_type=9, max_cells=0)                  # the type before max_cells
+    c(13, "max_cells must be in [1, 36864]", max_cells=0, data=None)                   # max_cells before null
+    c(10, "null pointer", status=None, out_bytes=0)                                    # null before out_bytes
 
-    # (n_pairs, n_vars, level, adj, pair_xy, offsets, n_tests, pairs, cond, tests_bytes, stream)
-    c = entry("dvs_pc_expand", [10, 12, 2, D, D, D, 300, D, D, 2400, None])
-    c(2, "dvs_pc_expand: n_pairs must be in [1, 1128]", i0=0)
-    c(2, "dvs_pc_expand: n_pairs must be in [1, 1128]", i0=1129)
-    c(3, "dvs_pc_expand: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_pc_expand: n_tests must be in [1, 2^31 - 1]", i6=0)
-    c(2, "dvs_pc_expand: n_tests must be in [1, 2^31 - 1]", i6=1 << 31, i9=1 << 40)
-    c(13, "dvs_pc_expand: level must be in [0, 46]", i2=-1)
-    c(13, "dvs_pc_expand: level must be in [0, 46]", i2=47)
-    for i in (3, 4, 5, 7, 8):
-        c(10, "dvs_pc_expand: null pointer", **{f"i{i}": None})
-    c(14, "dvs_pc_expand: tests_bytes < n_tests * 8 = 2400", i9=2399)
-    c(2, "dvs_pc_expand: n_pairs must be in [1, 1128]", i0=0, i1=49)               # n_pairs before n_vars
-    c(3, "dvs_pc_expand: n_vars must be in [1, 48]", i1=0, i6=0)                   # n_vars before n_tests
-    c(2, "dvs_pc_expand: n_tests must be in [1, 2^31 - 1]", i6=0, i2=47)           # n_tests before the level
-    c(13, "dvs_pc_expand: level must be in [0, 46]", i2=47, i3=None)               # the level before null
-    c(10, "dvs_pc_expand: null pointer", i8=None, i9=0)                            # null before tests_bytes
+    c = entry("dvs_pc_expand", cases, n_pairs=10, n_vars=12, level=2, adj=D, pair_xy=D, offsets=D, n_tests=300, pairs=D,
+              cond=D, tests_bytes=2400, stream=None)
+    c(2, "n_pairs must be in [1, 1128]", n_pairs=0)
+    c(2, "n_pairs must be in [1, 1128]", n_pairs=1129)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "n_tests must be in [1, 2^31 - 1]", n_tests=0)
+    c(2, "n_tests must be in [1, 2^31 - 1]", n_tests=1 << 31, tests_bytes=1 << 40)
+    c(13, "level must be in [0, 46]", level=-1)
+    c(13, "level must be in [0, 46]", level=47)
+    for name in ("adj", "pair_xy", "offsets", "pairs", "cond"):
+        c(10, "null pointer", **{name: None})
+    c(14, "tests_bytes < n_tests * 8 = 2400", tests_bytes=2399)
+    c(2, "n_pairs must be in [1, 1128]", n_pairs=0, n_vars=49)                         # n_pairs before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=0, n_tests=0)                             # n_vars before n_tests
+    c(2, "n_tests must be in [1, 2^31 - 1]", n_tests=0, level=47)                      # n_tests before the level
+    c(13, "level must be in [0, 46]", level=47, adj=None)                              # the level before null
+    c(10, "null pointer", cond=None, tests_bytes=0)                                    # null before tests_bytes
 
-    # (n_pairs, n_vars, pair_xy, offsets, n_tests, cond, out, alpha, adj, adj_next, sepset, sepset_bytes, result, result_bytes,
-    #  refused, stream)
-    c = entry("dvs_pc_reduce", [10, 12, D, D, 300, D, D, 0.05, D, D, D, 1152, D, 160, D, None])
-    c(2, "dvs_pc_reduce: n_pairs must be in [1, 1128]", i0=0)
-    c(3, "dvs_pc_reduce: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_pc_reduce: n_tests must be in [1, 2^31 - 1]", i4=0)
-    c(13, "dvs_pc_reduce: alpha must be in [0, 1]", i7=nan)
-    c(13, "dvs_pc_reduce: alpha must be in [0, 1]", i7=1.5)
-    c(13, "dvs_pc_reduce: alpha must be in [0, 1]", i7=-0.1)
-    for i in (2, 3, 5, 6, 8, 9, 10, 12, 14):
-        c(10, "dvs_pc_reduce: null pointer", **{f"i{i}": None})
-    c(14, "dvs_pc_reduce: sepset_bytes < n_vars^2 * 8 = 1152", i11=1151)
-    c(14, "dvs_pc_reduce: result_bytes < n_pairs * 16 = 160", i13=159)
-    c(2, "dvs_pc_reduce: n_tests must be in [1, 2^31 - 1]", i4=0, i7=nan)          # n_tests before alpha
-    c(13, "dvs_pc_reduce: alpha must be in [0, 1]", i7=2.0, i2=None)               # alpha before null
-    c(10, "dvs_pc_reduce: null pointer", i14=None, i11=0)                          # null before sepset_bytes
-    c(14, "dvs_pc_reduce: sepset_bytes <", i11=0, i13=0)                           # sepset_bytes before result_bytes
+    c = entry("dvs_pc_reduce", cases, n_pairs=10, n_vars=12, pair_xy=D, offsets=D, n_tests=300, cond=D, out=D, alpha=0.05,
+              adj=D, adj_next=D, sepset=D, sepset_bytes=1152, result=D, result_bytes=160, refused=D, stream=None)
+    c(2, "n_pairs must be in [1, 1128]", n_pairs=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "n_tests must be in [1, 2^31 - 1]", n_tests=0)
+    c(13, "alpha must be in [0, 1]", alpha=nan)
+    c(13, "alpha must be in [0, 1]", alpha=1.5)
+    c(13, "alpha must be in [0, 1]", alpha=-0.1)
+    for name in ("pair_xy", "offsets", "cond", "out", "adj", "adj_next", "sepset", "result", "refused"):
+        c(10, "null pointer", **{name: None})
+    c(14, "sepset_bytes < n_vars^2 * 8 = 1152", sepset_bytes=1151)
+    c(14, "result_bytes < n_pairs * 16 = 160", result_bytes=159)
+    c(2, "n_tests must be in [1, 2^31 - 1]", n_tests=0, alpha=nan)                     # n_tests before alpha
+    c(13, "alpha must be in [0, 1]", alpha=2.0, pair_xy=None)                          # alpha before null
+    c(10, "null pointer", refused=None, sepset_bytes=0)                                # null before sepset_bytes
+    c(14, "sepset_bytes <", sepset_bytes=0, result_bytes=0)                            # sepset_bytes before result_bytes
 
-    # (batch, n_vars, skeleton, sepsets, sepsets_bytes, pdag, pdag_bytes, conflicts, flags, stream)
-    c = entry("dvs_pc_orient", [8, 12, D, D, 9216, D, 768, D, D, None])
-    c(2, "dvs_pc_orient: batch must be > 0", i0=0)
-    c(3, "dvs_pc_orient: n_vars must be in [1, 48]", i1=0)
-    c(3, "dvs_pc_orient: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_pc_orient: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48, i4=1 << 40, i6=1 << 40)
-    for i in (2, 3, 5, 7, 8):
-        c(10, "dvs_pc_orient: null pointer", **{f"i{i}": None})
-    c(14, "dvs_pc_orient: sepsets_bytes < batch * n_vars^2 * 8 = 9216", i4=9215)
-    c(14, "dvs_pc_orient: pdag_bytes < batch * n_vars * 8 = 768", i6=767)
-    c(2, "dvs_pc_orient: batch must be > 0", i0=0, i1=49)                          # batch before n_vars
-    c(3, "dvs_pc_orient: n_vars must be in [1, 48]", i0=1 << 30, i1=49)            # n_vars before the product
-    c(2, "dvs_pc_orient: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48, i2=None)     # the product before null
-    c(10, "dvs_pc_orient: null pointer", i8=None, i4=0)                            # null before sepsets_bytes
-    c(14, "dvs_pc_orient: sepsets_bytes <", i4=0, i6=0)                            # sepsets_bytes before pdag_bytes
+    c = entry("dvs_pc_orient", cases, batch=8, n_vars=12, skeleton=D, sepsets=D, sepsets_bytes=9216, pdag=D, pdag_bytes=768,
+              conflicts=D, flags=D, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48, sepsets_bytes=1 << 40, pdag_bytes=1 << 40)
+    for name in ("skeleton", "sepsets", "pdag", "conflicts", "flags"):
+        c(10, "null pointer", **{name: None})
+    c(14, "sepsets_bytes < batch * n_vars^2 * 8 = 9216", sepsets_bytes=9215)
+    c(14, "pdag_bytes < batch * n_vars * 8 = 768", pdag_bytes=767)
+    c(2, "batch must be > 0", batch=0, n_vars=49)                                      # batch before n_vars
+    c(3, "n_vars must be in [1, 48]", batch=1 << 30, n_vars=49)                        # n_vars before the product
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48, skeleton=None)   # the product before null
+    c(10, "null pointer", flags=None, sepsets_bytes=0)                                 # null before sepsets_bytes
+    c(14, "sepsets_bytes <", sepsets_bytes=0, pdag_bytes=0)                            # sepsets_bytes before pdag_bytes
     return cases
 
 
 def check_argument_refusals(lib, D):
     cases = validation_cases(D)
     assert {fn for fn, *_ in cases} == {"dvs_ci_tests", "dvs_pc_expand", "dvs_pc_reduce", "dvs_pc_orient"}
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)

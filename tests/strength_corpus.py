@@ -24,6 +24,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import bn_score_corpus as bn
 from tests import scoring_corpus as sc
+from tests.abi_cases import entry, run
 
 U64 = np.uint64
 NAN = float("nan")
@@ -604,54 +605,41 @@ def check_closed_form_threshold(count=1000):
 def validation_cases(D):
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
+    c = entry("dvs_bootstrap_rows", cases, n_sets=8, set_size=100, n_samples=97, seed=7, set_offset=0, rows=D, stream=None)
+    c(2, "n_sets must be > 0", n_sets=0)
+    c(13, "set_size and n_samples must be >= 1", set_size=0)
+    c(13, "set_size and n_samples must be >= 1", n_samples=0)
+    c(2, "n_sets * set_size must be < 2^31", n_sets=1 << 16, set_size=1 << 15)
+    c(12, "set_offset must be >= 0", set_offset=-1)
+    c(10, "null pointer", rows=None)
+    c(2, "n_sets must be > 0", n_sets=0, set_size=0)                                   # n_sets before set_size
+    c(13, "set_size and n_samples", n_samples=0, rows=None)                            # sizes before null
 
-    # (n_sets, set_size, n_samples, seed, set_offset, rows, stream)
-    c = entry("dvs_bootstrap_rows", [8, 100, 97, 7, 0, D, None])
-    c(2, "dvs_bootstrap_rows: n_sets must be > 0", i0=0)
-    c(13, "dvs_bootstrap_rows: set_size and n_samples must be >= 1", i1=0)
-    c(13, "dvs_bootstrap_rows: set_size and n_samples must be >= 1", i2=0)
-    c(2, "dvs_bootstrap_rows: n_sets * set_size must be < 2^31", i0=1 << 16, i1=1 << 15)
-    c(12, "dvs_bootstrap_rows: set_offset must be >= 0", i4=-1)
-    c(10, "dvs_bootstrap_rows: null pointer", i5=None)
-    c(2, "dvs_bootstrap_rows: n_sets must be > 0", i0=0, i1=0)                       # n_sets before set_size
-    c(13, "dvs_bootstrap_rows: set_size and n_samples", i2=0, i5=None)              # sizes before null
+    c = entry("dvs_arc_strength", cases, batch=8, n_vars=12, pdag=D, counts=D, counts_bytes=1152, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(10, "null pointer", pdag=None)
+    c(10, "null pointer", counts=None)
+    c(14, "counts_bytes < n_vars^2 * 8 = 1152", counts_bytes=1151)
+    c(10, "null pointer", counts=None, counts_bytes=0)                                 # null before counts_bytes
 
-    # (batch, n_vars, pdag, counts, counts_bytes, stream)
-    c = entry("dvs_arc_strength", [8, 12, D, D, 1152, None])
-    c(2, "dvs_arc_strength: batch must be > 0", i0=0)
-    c(3, "dvs_arc_strength: n_vars must be in [1, 48]", i1=49)
-    c(10, "dvs_arc_strength: null pointer", i2=None)
-    c(10, "dvs_arc_strength: null pointer", i3=None)
-    c(14, "dvs_arc_strength: counts_bytes < n_vars^2 * 8 = 1152", i4=1151)
-    c(10, "dvs_arc_strength: null pointer", i3=None, i4=0)                           # null before counts_bytes
-
-    # (groups, n_vars, counts, n_networks, min_any, parents, parents_bytes, info, stream)
-    c = entry("dvs_averaged_network", [4, 12, D, D, D, D, 384, D, None])
-    c(2, "dvs_averaged_network: groups must be > 0", i0=0)
-    c(3, "dvs_averaged_network: n_vars must be in [1, 48]", i1=0)
-    c(2, "dvs_averaged_network: groups * n_vars^2 * 2 must be < 2^31", i0=1 << 20, i1=48, i6=1 << 40)
-    for i in (2, 3, 4, 5, 7):
-        c(10, "dvs_averaged_network: null pointer", **{f"i{i}": None})
-    c(14, "dvs_averaged_network: parents_bytes < groups * n_vars * 8 = 384", i6=383)
-    c(3, "dvs_averaged_network: n_vars must be in [1, 48]", i1=49, i2=None)          # range before null
-    c(10, "dvs_averaged_network: null pointer", i7=None, i6=0)                       # null before parents_bytes
+    c = entry("dvs_averaged_network", cases, groups=4, n_vars=12, counts=D, n_networks=D, min_any=D, parents=D,
+              parents_bytes=384, info=D, stream=None)
+    c(2, "groups must be > 0", groups=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=0)
+    c(2, "groups * n_vars^2 * 2 must be < 2^31", groups=1 << 20, n_vars=48, parents_bytes=1 << 40)
+    for name in ("counts", "n_networks", "min_any", "parents", "info"):
+        c(10, "null pointer", **{name: None})
+    c(14, "parents_bytes < groups * n_vars * 8 = 384", parents_bytes=383)
+    c(3, "n_vars must be in [1, 48]", n_vars=49, counts=None)                          # range before null
+    c(10, "null pointer", info=None, parents_bytes=0)                                  # null before parents_bytes
     return cases
 
 
 def check_argument_refusals(lib, D):
     cases = validation_cases(D)
     assert {fn for fn, *_ in cases} == {"dvs_bootstrap_rows", "dvs_arc_strength", "dvs_averaged_network"}
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)
 
 
 def toggle_plan():

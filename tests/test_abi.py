@@ -6,6 +6,7 @@ import re
 import pytest
 
 from dags_vae_search_amd import _lib as dl
+from tests.abi_cases import entry, run
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,6 +26,65 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert set(names) == set(dl.EXPORTS)          # the Python binding covers the whole header
+
+
+def test_binding_is_derived_from_the_header_with_the_types_the_hand_written_table_had():
+    """dl.SIGNATURES (what bind() declares) on the real header: restype and argtypes of the entry points that cover every kind
+    of type the header uses, written out as the hand-written table had them."""
+    from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+    P, S = c_void_p, POINTER(dl.DvsShape)
+    expected = {
+        "dvs_version": (c_int, []),
+        "dvs_last_error": (c_char_p, []),
+        "dvs_param_table": (c_int, [S, POINTER(dl.DvsParamEntry), c_int]),
+        "dvs_profile_enable": (None, [c_int]),
+        "dvs_profile_collect": (c_int, [P, c_int, P, P, c_int]),
+        "dvs_loss_forward_notify": (c_int, [S, P, c_size_t, P, c_int64, P, c_size_t, P, P, P, P, P, P, c_uint32, P]),
+        "dvs_clip_adam": (c_int, [c_int64, P, P, P, P, c_float, c_float, c_float, c_float, c_int64, c_float, P, P, P]),
+        "dvs_bn_lw": (c_int, [c_int32, c_int64, c_int64, P, P, P, P, c_int64, P, P, P, c_uint64, c_uint64, c_int64, P, c_size_t,
+                              P, P, P, P, P, P]),
+        "dvs_order_mcmc": (c_int, [c_int32, c_int32, c_int64, c_int32, P, P, c_size_t, P, c_size_t, c_uint64, c_int64, c_int64,
+                                   c_int64, c_int32, c_int32, c_int32, P, P, P, P, c_size_t, P, P, P, P, c_size_t, P, P]),
+    }
+    for fn, (restype, argtypes) in expected.items():
+        got_restype, args = dl.SIGNATURES[fn]
+        assert (got_restype, [t for _, t in args]) == (restype, argtypes), fn
+    assert [name for name, _ in dl.SIGNATURES["dvs_profile_collect"][1]] == ["names", "name_stride", "counts", "total_ms", "cap"]
+    assert dl.EXPORTS == list(dl.SIGNATURES) and len(dl.EXPORTS) == 64
+    assert (dl.ABI_VERSION, dl.RECORD_BYTES, dl.DECODE_STATE_BYTES, dl.LOSS_FLOATS) == (202, 96, 440, 5)
+    assert dl.STRUCT_HASH_INVALID == 2 ** 63 - 1 and dl.CI_TYPES["mi-adf"] == 2 and dl.FIT_METHODS == {"mle": 0, "bayes": 1}
+
+
+def test_header_parser_on_small_headers():
+    from ctypes import c_double, c_int, c_int32, c_size_t, c_uint64, c_void_p
+    sigs, consts = dl.parse_header("""
+        /* a comment with a call in it: dvs_fake(int a, (char*) b); and more ) ( */
+        #define DVS_BIG 0x7fffffffffffffffull   // dvs_other_fake(
+        #define DVS_SMALL 12
+        typedef enum dvs_kind { DVS_KIND_A = 0, DVS_KIND_B = 3 } dvs_kind;
+        typedef struct dvs_pair { int32_t a; int32_t b; } dvs_pair;
+        size_t dvs_three_lines(int32_t batch,   /* the first */
+                               const uint64_t* rows, double scale,
+                               uint64_t seed);
+        void dvs_nothing(void);
+        int dvs_shaped(const dvs_shape* s, void* stream);
+    """)
+    assert consts == {"DVS_BIG": 2 ** 63 - 1, "DVS_SMALL": 12, "DVS_KIND_A": 0, "DVS_KIND_B": 3}
+    assert list(sigs) == ["dvs_three_lines", "dvs_nothing", "dvs_shaped"]
+    assert sigs["dvs_three_lines"] == (c_size_t, [("batch", c_int32), ("rows", c_void_p), ("scale", c_double), ("seed", c_uint64)])
+    assert sigs["dvs_nothing"] == (None, [])
+    assert sigs["dvs_shaped"] == (c_int, [("s", ctypes.POINTER(dl.DvsShape)), ("stream", c_void_p)])
+    for bad, named in (("int dvs_short_arg(int32_t n, short s);", "dvs_short_arg"), ("int dvs_by_value(dvs_shape s);", "dvs_by_value"),
+                       ("long dvs_long_return(int n);", "dvs_long_return"), ("int dvs_unnamed(int32_t);", "dvs_unnamed"),
+                       ("static int dvs_counter = 0;", "dvs_counter")):
+        with pytest.raises(ValueError, match=named):
+            dl.parse_header(bad)
+
+
+def test_a_missing_header_is_an_error_that_gives_the_path(monkeypatch, tmp_path):
+    monkeypatch.setattr(dl, "HEADER", str(tmp_path / "include" / "dvs.h"))
+    with pytest.raises(RuntimeError, match=re.escape(str(tmp_path / "include" / "dvs.h"))):
+        dl._read_header()
 
 
 def test_host_side_queries_without_a_gpu():
@@ -115,183 +175,169 @@ def _search_validation_cases():
     BIC, K2 = dl.SCORE_TYPES["bic"], dl.SCORE_TYPES["k2"]
     cases = []
 
-    def entry(fn, base):
-        def case(code, text, **at):         # at: {"i<index>": value} replaces base[index]
-            args = list(base)
-            for k, v in at.items():
-                args[int(k[1:])] = v
-            cases.append((fn, args, code, text))
-        return case
+    c = entry("dvs_match_decoded", cases, batch=8, n_vars=12, card=12, repeats=3, preds_are_u64=0, labels=D, preds=D,
+              states=D, state_bytes=24 * SB, budget=100, flags=D, stream=None)
+    c(3, "n_vars must be in [1, 45]", n_vars=46)
+    c(2, "batch * repeats must be <= 2^30", batch=1 << 20, repeats=1 << 11)
+    c(12, "16-bit predecessor rows hold at most 16 vertices", n_vars=17, card=17)
+    c(10, "null pointer", labels=None)
+    c(14, f"state_bytes < batch * repeats * DVS_DECODE_STATE_BYTES = {24 * SB}", state_bytes=24 * SB - 1)
+    c(2, "batch and repeats must be > 0", batch=0, n_vars=46)                          # batch before n_vars
+    c(3, "card must be in [1, 45]", card=46, flags=None)                               # range before null
+    c(12, "budget must be >= 1", budget=0, states=None)                                # budget before null
+    c(10, "null pointer", flags=None, state_bytes=0)                                   # null before state_bytes
 
-    # (batch, n_vars, card, repeats, preds_are_u64, labels, preds, states, state_bytes, budget, flags, stream)
-    c = entry("dvs_match_decoded", [8, 12, 12, 3, 0, D, D, D, 24 * SB, 100, D, None])
-    c(3, "dvs_match_decoded: n_vars must be in [1, 45]", i1=46)
-    c(2, "dvs_match_decoded: batch * repeats must be <= 2^30", i0=1 << 20, i3=1 << 11)
-    c(12, "dvs_match_decoded: 16-bit predecessor rows hold at most 16 vertices", i1=17, i2=17)
-    c(10, "dvs_match_decoded: null pointer", i5=None)
-    c(14, f"dvs_match_decoded: state_bytes < batch * repeats * DVS_DECODE_STATE_BYTES = {24 * SB}", i8=24 * SB - 1)
-    c(2, "dvs_match_decoded: batch and repeats must be > 0", i0=0, i1=46)          # batch before n_vars
-    c(3, "dvs_match_decoded: card must be in [1, 45]", i2=46, i10=None)            # range before null
-    c(12, "dvs_match_decoded: budget must be >= 1", i9=0, i7=None)                 # budget before null
-    c(10, "dvs_match_decoded: null pointer", i10=None, i8=0)                       # null before state_bytes
+    c = entry("dvs_decoded_structures", cases, batch=8, n_vars=12, preds_are_u64=0, states=D, state_bytes=8 * SB,
+              hash_mask=2 ** 63 - 1, flags=D, labels=D, preds=D, keys=D, keys_bytes=768, hashes=D, stream=None)
+    c(3, "n_vars must be in [1, 45]", n_vars=0)
+    c(2, "batch must be <= 2^30", batch=(1 << 30) + 1)
+    c(10, "null pointer", hashes=None)
+    c(14, f"state_bytes < batch * DVS_DECODE_STATE_BYTES = {8 * SB}", state_bytes=8 * SB - 1)
+    c(14, "keys_bytes < batch * n_vars * 8 = 768", keys_bytes=767)
+    c(12, "16-bit predecessor rows", n_vars=17, states=None)                           # row width before null
+    c(14, "state_bytes <", state_bytes=0, keys_bytes=0)                                # state_bytes before keys_bytes
 
-    # (batch, n_vars, preds_are_u64, states, state_bytes, hash_mask, flags, labels, preds, keys, keys_bytes, hashes, stream)
-    c = entry("dvs_decoded_structures", [8, 12, 0, D, 8 * SB, 2 ** 63 - 1, D, D, D, D, 768, D, None])
-    c(3, "dvs_decoded_structures: n_vars must be in [1, 45]", i1=0)
-    c(2, "dvs_decoded_structures: batch must be <= 2^30", i0=(1 << 30) + 1)
-    c(10, "dvs_decoded_structures: null pointer", i11=None)
-    c(14, f"dvs_decoded_structures: state_bytes < batch * DVS_DECODE_STATE_BYTES = {8 * SB}", i4=8 * SB - 1)
-    c(14, "dvs_decoded_structures: keys_bytes < batch * n_vars * 8 = 768", i10=767)
-    c(12, "dvs_decoded_structures: 16-bit predecessor rows", i1=17, i3=None)       # row width before null
-    c(14, "dvs_decoded_structures: state_bytes <", i4=0, i10=0)                    # state_bytes before keys_bytes
+    c = entry("dvs_structset_filter", cases, batch=8, n_vars=12, sorted_hashes=D, order=D, keys=D, keys_bytes=768, flags=D,
+              seen_count=5, seen_hashes=D, seen_keys=D, seen_keys_bytes=480, out=D, stream=None)
+    c(3, "n_vars must be in [1, 45]", n_vars=46)
+    c(2, "batch and seen_count must be >= 0", seen_count=-1)
+    c(10, "null pointer", out=None)
+    c(10, "null pointer (seen set)", seen_hashes=None)
+    c(14, "keys_bytes < batch * n_vars * 8 = 768", keys_bytes=767)
+    c(14, "seen_keys_bytes < seen_count * n_vars * 8 = 480", seen_keys_bytes=479)
+    c(10, "null pointer", sorted_hashes=None, keys_bytes=0)                            # null before keys_bytes
+    c(14, "keys_bytes <", keys_bytes=0, seen_keys_bytes=0)                             # keys_bytes before seen_keys_bytes
 
-    # (batch, n_vars, sorted_hashes, order, keys, keys_bytes, flags, seen_count, seen_hashes, seen_keys, seen_keys_bytes,
-    #  out, stream)
-    c = entry("dvs_structset_filter", [8, 12, D, D, D, 768, D, 5, D, D, 480, D, None])
-    c(3, "dvs_structset_filter: n_vars must be in [1, 45]", i1=46)
-    c(2, "dvs_structset_filter: batch and seen_count must be >= 0", i7=-1)
-    c(10, "dvs_structset_filter: null pointer", i11=None)
-    c(10, "dvs_structset_filter: null pointer (seen set)", i8=None)
-    c(14, "dvs_structset_filter: keys_bytes < batch * n_vars * 8 = 768", i5=767)
-    c(14, "dvs_structset_filter: seen_keys_bytes < seen_count * n_vars * 8 = 480", i10=479)
-    c(10, "dvs_structset_filter: null pointer", i2=None, i5=0)                     # null before keys_bytes
-    c(14, "dvs_structset_filter: keys_bytes <", i5=0, i10=0)                       # keys_bytes before seen_keys_bytes
+    c = entry("dvs_generate_dags", cases, batch=8, n_vars=12, card=12, preds_are_u64=0, num_edges=D, seed=7, dag_offset=0,
+              try_limit=20, flags=0, labels=D, preds=D, preds_bytes=192, attempts=D, stream=None)
+    c(3, "n_vars must be in [2, 45]", n_vars=1)
+    c(12, "unknown bits in flags", flags=8)
+    c(12, "labels without replacement ('sample') need card >= n_vars", card=11)
+    c(12, "predecessor rows are u16 for n_vars <= 13 and u64 above", preds_are_u64=1)
+    c(12, "dag_offset must be >= 0", dag_offset=-1)
+    c(10, "null pointer", attempts=None)
+    c(14, "preds_bytes < batch * n_vars * row bytes = 192", preds_bytes=191)
+    c(14, "preds_bytes < batch * n_vars * row bytes = 1280", n_vars=20, card=20, preds_are_u64=1, preds_bytes=1279)
+    c(12, "try_limit must be in [1, 4096]", try_limit=0, num_edges=None)               # try_limit before null
+    c(10, "null pointer", labels=None, preds_bytes=0)                                  # null before preds_bytes
 
-    # (batch, n_vars, card, preds_are_u64, num_edges, seed, dag_offset, try_limit, flags, labels, preds, preds_bytes,
-    #  attempts, stream)
-    c = entry("dvs_generate_dags", [8, 12, 12, 0, D, 7, 0, 20, 0, D, D, 192, D, None])
-    c(3, "dvs_generate_dags: n_vars must be in [2, 45]", i1=1)
-    c(12, "dvs_generate_dags: unknown bits in flags", i8=8)
-    c(12, "dvs_generate_dags: labels without replacement ('sample') need card >= n_vars", i2=11)
-    c(12, "dvs_generate_dags: predecessor rows are u16 for n_vars <= 13 and u64 above", i3=1)
-    c(12, "dvs_generate_dags: dag_offset must be >= 0", i6=-1)
-    c(10, "dvs_generate_dags: null pointer", i12=None)
-    c(14, "dvs_generate_dags: preds_bytes < batch * n_vars * row bytes = 192", i11=191)
-    c(14, "dvs_generate_dags: preds_bytes < batch * n_vars * row bytes = 1280", i1=20, i2=20, i3=1, i11=1279)
-    c(12, "dvs_generate_dags: try_limit must be in [1, 4096]", i7=0, i4=None)      # try_limit before null
-    c(10, "dvs_generate_dags: null pointer", i9=None, i11=0)                       # null before preds_bytes
+    c = entry("dvs_generate_edge_counts", cases, batch=8, n_entries=4, edge_counts=D, cum_weights=D, seed=7, dag_offset=0,
+              num_edges=D, stream=None)
+    c(2, "batch must be in [1, 2^30]", batch=0)
+    c(12, "n_entries must be in [1, 1024]", n_entries=1025)
+    c(10, "null pointer", num_edges=None)
+    c(12, "dag_offset must be >= 0", dag_offset=-1, edge_counts=None)                  # dag_offset before null
 
-    # (batch, n_entries, edge_counts, cum_weights, seed, dag_offset, num_edges, stream)
-    c = entry("dvs_generate_edge_counts", [8, 4, D, D, 7, 0, D, None])
-    c(2, "dvs_generate_edge_counts: batch must be in [1, 2^30]", i0=0)
-    c(12, "dvs_generate_edge_counts: n_entries must be in [1, 1024]", i1=1025)
-    c(10, "dvs_generate_edge_counts: null pointer", i6=None)
-    c(12, "dvs_generate_edge_counts: dag_offset must be >= 0", i5=-1, i2=None)     # dag_offset before null
+    c = entry("dvs_bic_scores", cases, batch=8, n_vars=12, n_samples=100, data=D, card=D, parents=D, scratch=D, out=D,
+              status=D, stream=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch and n_samples must be > 0", n_samples=0)
+    c(10, "null pointer", scratch=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49, data=None)                            # range before null
 
-    # (batch, n_vars, n_samples, data, card, parents, scratch, out, status, stream)
-    c = entry("dvs_bic_scores", [8, 12, 100, D, D, D, D, D, D, None])
-    c(3, "dvs_bic_scores: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_bic_scores: batch and n_samples must be > 0", i2=0)
-    c(10, "dvs_bic_scores: null pointer", i6=None)
-    c(3, "dvs_bic_scores: n_vars must be in [1, 48]", i1=49, i3=None)              # range before null
+    c = entry("dvs_bn_scores", cases, batch=8, n_vars=12, n_samples=100, data=D, card=D, parents=D, score_type=BIC,
+              score_arg=nan, scratch=D, out=D, status=D, stream=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(10, "null pointer", status=None)
+    c(12, "score_type is not a dvs_score_type", score_type=7)
+    c(13, "loglik, k2 and bdj take no argument (score_arg must be NaN)", score_type=K2, score_arg=1.0)
+    c(13, "k must be finite and >= 0", score_arg=-1.0)
+    c(13, "iss must be finite and > 0", score_type=dl.SCORE_TYPES["bde"], score_arg=0.0)
+    c(10, "null pointer", data=None, score_type=7)                                     # null before score_type
 
-    # (batch, n_vars, n_samples, data, card, parents, score_type, score_arg, scratch, out, status, stream)
-    c = entry("dvs_bn_scores", [8, 12, 100, D, D, D, BIC, nan, D, D, D, None])
-    c(3, "dvs_bn_scores: n_vars must be in [1, 48]", i1=49)
-    c(10, "dvs_bn_scores: null pointer", i10=None)
-    c(12, "dvs_bn_scores: score_type is not a dvs_score_type", i6=7)
-    c(13, "dvs_bn_scores: loglik, k2 and bdj take no argument (score_arg must be NaN)", i6=K2, i7=1.0)
-    c(13, "dvs_bn_scores: k must be finite and >= 0", i7=-1.0)
-    c(13, "dvs_bn_scores: iss must be finite and > 0", i6=dl.SCORE_TYPES["bde"], i7=0.0)
-    c(10, "dvs_bn_scores: null pointer", i3=None, i6=7)                            # null before score_type
-
-    # (batch, n_vars, n_samples, data, card, parents, score_type, score_arg, worklist (nullable), local, local_bytes, toggles,
-    #  toggles_bytes, status, stream)
-    c = entry("dvs_bn_toggle_scores", [8, 12, 100, D, D, D, BIC, nan, None, D, 768, D, 9216, D, None])
-    c(3, "dvs_bn_toggle_scores: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_bn_toggle_scores: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48)
-    c(10, "dvs_bn_toggle_scores: null pointer", i11=None)
-    c(14, "dvs_bn_toggle_scores: local_bytes < batch * n_vars * 8 = 768", i10=767)
-    c(14, "dvs_bn_toggle_scores: toggles_bytes < batch * n_vars^2 * 8 = 9216", i12=9215)
-    c(2, "dvs_bn_toggle_scores: batch and n_samples must be > 0", i0=0, i1=49)     # batch before n_vars
-    c(3, "dvs_bn_toggle_scores: n_vars must be in [1, 48]", i1=49, i9=None)        # range before null
-    c(12, "dvs_bn_toggle_scores: score_type is not a dvs_score_type", i6=-1, i10=0)     # score type before local_bytes
-    c(14, "dvs_bn_toggle_scores: local_bytes <", i10=0, i12=0)                     # local_bytes before toggles_bytes
+    c = entry("dvs_bn_toggle_scores", cases, batch=8, n_vars=12, n_samples=100, data=D, card=D, parents=D, score_type=BIC,
+              score_arg=nan, worklist=None, local=D, local_bytes=768, toggles=D, toggles_bytes=9216, status=D, stream=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48)
+    c(10, "null pointer", toggles=None)
+    c(14, "local_bytes < batch * n_vars * 8 = 768", local_bytes=767)
+    c(14, "toggles_bytes < batch * n_vars^2 * 8 = 9216", toggles_bytes=9215)
+    c(2, "batch and n_samples must be > 0", batch=0, n_vars=49)                        # batch before n_vars
+    c(3, "n_vars must be in [1, 48]", n_vars=49, local=None)                           # range before null
+    c(12, "score_type is not a dvs_score_type", score_type=-1, local_bytes=0)          # score type before local_bytes
+    c(14, "local_bytes <", local_bytes=0, toggles_bytes=0)                             # local_bytes before toggles_bytes
 
     # (batch, n_vars, parents, local, toggles, toggles_bytes, max_parents, min_delta, forbidden (nullable), step_cap, worklist,
     #  steps, converged, flags, trace (nullable), trace_bytes, active, stream)
-    hc = [8, 12, D, D, D, 9216, 0, 0.0, None, 10, D, D, D, D, D, 1280, D, None]
-    c = entry("dvs_hc_step", hc)
-    c(2, "dvs_hc_step: batch must be > 0", i0=0)
-    c(3, "dvs_hc_step: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_hc_step: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48)
-    c(10, "dvs_hc_step: null pointer", i16=None)
-    c(13, "dvs_hc_step: min_delta must not be NaN", i7=nan)
-    c(13, "dvs_hc_step: step_cap must be >= 1", i9=0)
-    c(14, "dvs_hc_step: toggles_bytes < batch * n_vars^2 * 8 = 9216", i5=9215)
-    c(14, "dvs_hc_step: trace_bytes < batch * step_cap * 16 = 1280", i15=1279)
-    c(3, "dvs_hc_step: n_vars must be in [1, 48]", i1=49, i2=None)                 # range before null
-    c(10, "dvs_hc_step: null pointer", i12=None, i9=0)                             # null before step_cap
-    c(13, "dvs_hc_step: step_cap must be >= 1", i9=0, i5=0)                        # step_cap before toggles_bytes
-    c(14, "dvs_hc_step: toggles_bytes <", i5=0, i15=0)                             # toggles_bytes before trace_bytes
+    hc = dict(batch=8, n_vars=12, parents=D, local=D, toggles=D, toggles_bytes=9216, max_parents=0, min_delta=0.0,
+              forbidden=None, step_cap=10, worklist=D, steps=D, converged=D, flags=D, trace=D, trace_bytes=1280, active=D)
+    c = entry("dvs_hc_step", cases, **hc, stream=None)
+    c(2, "batch must be > 0", batch=0)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48)
+    c(10, "null pointer", active=None)
+    c(13, "min_delta must not be NaN", min_delta=nan)
+    c(13, "step_cap must be >= 1", step_cap=0)
+    c(14, "toggles_bytes < batch * n_vars^2 * 8 = 9216", toggles_bytes=9215)
+    c(14, "trace_bytes < batch * step_cap * 16 = 1280", trace_bytes=1279)
+    c(3, "n_vars must be in [1, 48]", n_vars=49, parents=None)                         # range before null
+    c(10, "null pointer", converged=None, step_cap=0)                                  # null before step_cap
+    c(13, "step_cap must be >= 1", step_cap=0, toggles_bytes=0)                        # step_cap before toggles_bytes
+    c(14, "toggles_bytes <", toggles_bytes=0, trace_bytes=0)                           # toggles_bytes before trace_bytes
 
-    # (... as dvs_hc_step up to active ..., tabu_len, ring, ring_bytes, visited, max_stall, stall, best_score, best_parents,
-    #  best_bytes, stream)
-    c = entry("dvs_tabu_step", hc[:-1] + [5, D, 3840, D, 4, D, D, D, 768, None])
-    c(3, "dvs_tabu_step: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_tabu_step: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48)
-    c(10, "dvs_tabu_step: null pointer", i18=None)
-    c(10, "dvs_tabu_step: null pointer", i24=None)
-    c(13, "dvs_tabu_step: min_delta must not be NaN", i7=nan)
-    c(13, "dvs_tabu_step: tabu_len must be >= 1", i17=0)
-    c(13, "dvs_tabu_step: max_stall must be >= 1", i21=0)
-    c(14, "dvs_tabu_step: toggles_bytes < batch * n_vars^2 * 8 = 9216", i5=9215)
-    c(14, "dvs_tabu_step: trace_bytes < batch * step_cap * 16 = 1280", i15=1279)
-    c(14, "dvs_tabu_step: ring_bytes < batch * tabu_len * n_vars * 8 = 3840", i19=3839)
-    c(14, "dvs_tabu_step: best_bytes < batch * n_vars * 8 = 768", i25=767)
-    c(3, "dvs_tabu_step: n_vars must be in [1, 48]", i1=49, i20=None)              # range before null
-    c(13, "dvs_tabu_step: step_cap must be >= 1", i9=0, i17=0)                     # step_cap before tabu_len
-    c(13, "dvs_tabu_step: tabu_len must be >= 1", i17=0, i21=0)                    # tabu_len before max_stall
-    c(14, "dvs_tabu_step: trace_bytes <", i15=0, i19=0)                            # trace_bytes before ring_bytes
-    c(14, "dvs_tabu_step: ring_bytes <", i19=0, i25=0)                             # ring_bytes before best_bytes
+    c = entry("dvs_tabu_step", cases, **hc, tabu_len=5, ring=D, ring_bytes=3840, visited=D, max_stall=4, stall=D,
+              best_score=D, best_parents=D, best_bytes=768, stream=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48)
+    c(10, "null pointer", ring=None)
+    c(10, "null pointer", best_parents=None)
+    c(13, "min_delta must not be NaN", min_delta=nan)
+    c(13, "tabu_len must be >= 1", tabu_len=0)
+    c(13, "max_stall must be >= 1", max_stall=0)
+    c(14, "toggles_bytes < batch * n_vars^2 * 8 = 9216", toggles_bytes=9215)
+    c(14, "trace_bytes < batch * step_cap * 16 = 1280", trace_bytes=1279)
+    c(14, "ring_bytes < batch * tabu_len * n_vars * 8 = 3840", ring_bytes=3839)
+    c(14, "best_bytes < batch * n_vars * 8 = 768", best_bytes=767)
+    c(3, "n_vars must be in [1, 48]", n_vars=49, visited=None)                         # range before null
+    c(13, "step_cap must be >= 1", step_cap=0, tabu_len=0)                             # step_cap before tabu_len
+    c(13, "tabu_len must be >= 1", tabu_len=0, max_stall=0)                            # tabu_len before max_stall
+    c(14, "trace_bytes <", trace_bytes=0, ring_bytes=0)                                # trace_bytes before ring_bytes
+    c(14, "ring_bytes <", ring_bytes=0, best_bytes=0)                                  # ring_bytes before best_bytes
 
-    # (batch, n_vars, parents, local, toggles, toggles_bytes, max_parents, forbidden (nullable), worklist, flags, seed,
-    #  draw_index, stream)
-    c = entry("dvs_hc_perturb", [8, 12, D, D, D, 9216, 0, None, D, D, 7, 0, None])
-    c(2, "dvs_hc_perturb: batch must be > 0", i0=-1)
-    c(3, "dvs_hc_perturb: n_vars must be in [1, 48]", i1=49)
-    c(2, "dvs_hc_perturb: batch * n_vars^2 must be < 2^31", i0=1 << 20, i1=48)
-    c(10, "dvs_hc_perturb: null pointer", i9=None)
-    c(14, "dvs_hc_perturb: toggles_bytes < batch * n_vars^2 * 8 = 9216", i5=9215)
-    c(3, "dvs_hc_perturb: n_vars must be in [1, 48]", i1=0, i3=None)               # range before null
-    c(10, "dvs_hc_perturb: null pointer", i8=None, i5=0)                           # null before toggles_bytes
+    c = entry("dvs_hc_perturb", cases, batch=8, n_vars=12, parents=D, local=D, toggles=D, toggles_bytes=9216, max_parents=0,
+              forbidden=None, worklist=D, flags=D, seed=7, draw_index=0, stream=None)
+    c(2, "batch must be > 0", batch=-1)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(2, "batch * n_vars^2 must be < 2^31", batch=1 << 20, n_vars=48)
+    c(10, "null pointer", flags=None)
+    c(14, "toggles_bytes < batch * n_vars^2 * 8 = 9216", toggles_bytes=9215)
+    c(3, "n_vars must be in [1, 48]", n_vars=0, local=None)                            # range before null
+    c(10, "null pointer", worklist=None, toggles_bytes=0)                              # null before toggles_bytes
 
-    # (batch, n_vars, preds_are_u64, labels, preds, parents, status, stream)
-    c = entry("dvs_bic_parent_masks", [8, 12, 0, D, D, D, D, None])
-    c(3, "dvs_bic_parent_masks: n_vars must be in [1, 48]", i1=49)
-    c(10, "dvs_bic_parent_masks: null pointer", i5=None)
-    c(12, "dvs_bic_parent_masks: 16-bit predecessor rows hold at most 16 vertices", i1=17, i3=None)   # row width before null
+    c = entry("dvs_bic_parent_masks", cases, batch=8, n_vars=12, preds_are_u64=0, labels=D, preds=D, parents=D, status=D,
+              stream=None)
+    c(3, "n_vars must be in [1, 48]", n_vars=49)
+    c(10, "null pointer", parents=None)
+    c(12, "16-bit predecessor rows hold at most 16 vertices", n_vars=17, labels=None)  # row width before null
 
-    # (batch, n_inducing, dim, x, inducing, alpha, outputscale, lengthscale, constant, out, stream)
-    c = entry("dvs_gp_predict", [8, 50, 32, D, D, D, 1.0, 1.0, 0.0, D, None])
-    c(2, "dvs_gp_predict: sizes must be > 0", i1=0)
-    c(10, "dvs_gp_predict: null pointer", i9=None)
-    c(5, "dvs_gp_predict: lengthscale must be > 0", i7=0.0, i3=None)               # lengthscale before null
+    c = entry("dvs_gp_predict", cases, batch=8, n_inducing=50, dim=32, x=D, inducing=D, alpha=D, outputscale=1.0,
+              lengthscale=1.0, constant=0.0, out=D, stream=None)
+    c(2, "sizes must be > 0", n_inducing=0)
+    c(10, "null pointer", out=None)
+    c(5, "lengthscale must be > 0", lengthscale=0.0, x=None)                           # lengthscale before null
 
-    # (na, nb, dim, xa, xb, outputscale, lengthscale, K, stream)
-    c = entry("dvs_gp_kernel", [8, 50, 32, D, D, 1.0, 1.0, D, None])
-    c(2, "dvs_gp_kernel: sizes must be > 0 and dim <= 32", i2=33)
-    c(10, "dvs_gp_kernel: null pointer", i7=None)
-    c(5, "dvs_gp_kernel: lengthscale and outputscale must be > 0", i5=0.0, i3=None)     # outputscale before null
+    c = entry("dvs_gp_kernel", cases, na=8, nb=50, dim=32, xa=D, xb=D, outputscale=1.0, lengthscale=1.0, K=D, stream=None)
+    c(2, "sizes must be > 0 and dim <= 32", dim=33)
+    c(10, "null pointer", K=None)
+    c(5, "lengthscale and outputscale must be > 0", outputscale=0.0, xa=None)          # outputscale before null
 
-    # (na, nb, dim, symmetric, xa, xb, outputscale, lengthscale, G, dxa, row_sums, stream)
-    c = entry("dvs_gp_kernel_backward", [8, 50, 32, 0, D, D, 1.0, 1.0, D, D, D, None])
-    c(2, "dvs_gp_kernel_backward: sizes must be > 0 and dim <= 32", i0=0)
-    c(5, "dvs_gp_kernel_backward: lengthscale and outputscale must be > 0", i7=nan)
-    c(10, "dvs_gp_kernel_backward: null pointer", i10=None)
-    c(12, "dvs_gp_kernel_backward: symmetric needs na == nb", i3=1)
-    c(10, "dvs_gp_kernel_backward: null pointer", i3=1, i8=None)                   # null before symmetric
+    c = entry("dvs_gp_kernel_backward", cases, na=8, nb=50, dim=32, symmetric=0, xa=D, xb=D, outputscale=1.0,
+              lengthscale=1.0, G=D, dxa=D, row_sums=D, stream=None)
+    c(2, "sizes must be > 0 and dim <= 32", na=0)
+    c(5, "lengthscale and outputscale must be > 0", lengthscale=nan)
+    c(10, "null pointer", row_sums=None)
+    c(12, "symmetric needs na == nb", symmetric=1)
+    c(10, "null pointer", symmetric=1, G=None)                                         # null before symmetric
 
-    # (batch, n_inducing, dim, ld, x, inducing, weights, c0, outputscale, lengthscale, constant, best, xi, mean, var, ei,
-    #  grad (nullable), stream)
-    c = entry("dvs_gp_acquire", [8, 50, 32, 51, D, D, D, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, D, D, D, None, None])
-    c(2, "dvs_gp_acquire: sizes must be > 0 and dim <= 32", i2=0)
-    c(2, "dvs_gp_acquire: n_inducing must be <= 1023", i1=1024, i3=1025)
-    c(12, "dvs_gp_acquire: ld must be >= n_inducing + 1 (P | alpha)", i3=50)
-    c(12, "dvs_gp_acquire: c0 must be >= 0", i7=-1.0)
-    c(10, "dvs_gp_acquire: null pointer", i15=None)
-    c(5, "dvs_gp_acquire: lengthscale and outputscale must be > 0", i9=0.0, i1=1024)    # scales before n_inducing
-    c(12, "dvs_gp_acquire: ld must be >= n_inducing + 1", i3=50, i4=None)          # ld before null
+    c = entry("dvs_gp_acquire", cases, batch=8, n_inducing=50, dim=32, ld=51, x=D, inducing=D, weights=D, c0=0.0,
+              outputscale=1.0, lengthscale=1.0, constant=0.0, best=0.0, xi=0.0, mean=D, var=D, ei=D, grad=None, stream=None)
+    c(2, "sizes must be > 0 and dim <= 32", dim=0)
+    c(2, "n_inducing must be <= 1023", n_inducing=1024, ld=1025)
+    c(12, "ld must be >= n_inducing + 1 (P | alpha)", ld=50)
+    c(12, "c0 must be >= 0", c0=-1.0)
+    c(10, "null pointer", ei=None)
+    c(5, "lengthscale and outputscale must be > 0", lengthscale=0.0, n_inducing=1024)  # scales before n_inducing
+    c(12, "ld must be >= n_inducing + 1", ld=50, x=None)                               # ld before null
     return cases
 
 
@@ -303,7 +349,4 @@ def test_search_entry_points_validate_in_a_fixed_order_before_anything_is_enqueu
     cases = _search_validation_cases()
     assert len({fn for fn, *_ in cases}) == 16
     assert lib.dvs_structset_filter(0, 12, None, None, None, 0, None, 0, None, None, 0, None, None) == 0   # an empty batch
-    for fn, args, code, text in cases:
-        got = getattr(lib, fn)(*args)
-        msg = lib.dvs_last_error().decode()
-        assert (got, text in msg, msg.startswith(fn + ":")) == (code, True, True), (fn, args, got, msg)
+    run(lib, cases)
