@@ -32,6 +32,7 @@ import numpy as np
 from scipy.special import gammaln
 
 from tests import scoring_corpus as sc
+from tests.abi_cases import call_rc
 
 MP = mpmath.mp.clone()
 MP.dps = 60
@@ -155,13 +156,11 @@ def bn_reference(case, typ, arg):
 def run_bn(be, data, card, masks, typ, arg=None, type_code=None):
     """one dvs_bn_scores call -> (return code, scratch [B, n], out [B], status)."""
     B, n = masks.shape
-    d, c, m = be.put(sc.pack(data)), be.put(card), be.put(np.ascontiguousarray(masks, sc.U64))
-    scratch, out = be.put(np.full((B, n), -7.0)), be.put(np.full(B, -7.0))
-    status = be.put(np.zeros(1, np.int32))
-    code = TYPE_CODE[typ] if type_code is None else type_code
-    rc = be.lib.dvs_bn_scores(B, n, data.shape[0], be.ptr(d), be.ptr(c), be.ptr(m), code, NAN if arg is None else float(arg),
-                              be.ptr(scratch), be.ptr(out), be.ptr(status), be.stream)
-    return rc, be.get(scratch).copy(), be.get(out).copy(), int(be.get(status)[0])
+    h = dict(data=be.put(sc.pack(data)), card=be.put(card), parents=be.put(np.ascontiguousarray(masks, sc.U64)),
+             scratch=be.put(np.full((B, n), -7.0)), out=be.put(np.full(B, -7.0)), status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bn_scores", batch=B, n_vars=n, n_samples=data.shape[0], **h,
+                 score_type=TYPE_CODE[typ] if type_code is None else type_code, score_arg=NAN if arg is None else float(arg))
+    return rc, be.get(h["scratch"]).copy(), be.get(h["out"]).copy(), int(be.get(h["status"])[0])
 
 
 def check_bn_case(be, case, typ, arg, twice=True):
@@ -348,7 +347,10 @@ def check_dense_and_sort_paths_agree(be):
 
 def check_argument_refusals(lib, ptr):
     """dvs_bn_scores validates before it enqueues: `ptr` is any non-null pointer value (never dereferenced)."""
-    call = lambda code, arg, B=4, n=8, S=100, p=ptr: lib.dvs_bn_scores(B, n, S, p, p, p, code, arg, p, p, p, None)
+    be, p = sc.EmuBackend(lib), ptr                          # nothing is moved: dummy pointers as they are, the null stream
+    call = lambda code, arg, B=4, n=8, S=100, d=p, st=p: call_rc(
+        be, "dvs_bn_scores", batch=B, n_vars=n, n_samples=S, data=d, card=p, parents=p, score_type=code, score_arg=arg, scratch=p,
+        out=p, status=st)
     inf = float("inf")
     for code in (-1, 7, 100):
         assert call(code, NAN) == 12 and b"score_type" in lib.dvs_last_error()
@@ -362,5 +364,4 @@ def check_argument_refusals(lib, ptr):
         assert call(TYPE_CODE[typ], 1.0) == 13
     assert call(TYPE_CODE["bde"], 1.0, B=0) == 2 and call(TYPE_CODE["bde"], 1.0, S=0) == 2
     assert call(TYPE_CODE["bde"], 1.0, n=0) == 3 and call(TYPE_CODE["bde"], 1.0, n=49) == 3
-    assert lib.dvs_bn_scores(4, 8, 100, None, ptr, ptr, TYPE_CODE["bde"], 1.0, ptr, ptr, ptr, None) == 10
-    assert lib.dvs_bn_scores(4, 8, 100, ptr, ptr, ptr, TYPE_CODE["bde"], 1.0, ptr, ptr, None, None) == 10
+    assert call(TYPE_CODE["bde"], 1.0, d=None) == 10 and call(TYPE_CODE["bde"], 1.0, st=None) == 10

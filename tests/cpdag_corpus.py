@@ -21,7 +21,7 @@ import itertools
 import numpy as np
 
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, entry, run
 
 U64 = np.uint64
 RULES = ("R1", "R2", "R3")
@@ -276,8 +276,7 @@ class Driver:
         P = np.ascontiguousarray(P, U64)
         B, n = P.shape
         hP, out, fl = be.put(P), be.put(np.full((B, n), 0xA5A5A5A5A5A5A5A5, U64)), be.put(np.full(B, -7, np.int32))
-        rc = self.lib.dvs_cpdag(B, n, be.ptr(hP), be.ptr(out), B * n * 8, be.ptr(fl), be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_cpdag", batch=B, n_vars=n, parents=hP, pdag=out, pdag_bytes=B * n * 8, flags=fl)
         res = be.get(out).copy(), be.get(fl).copy()
         assert be.get(hP).tobytes() == P.tobytes()                 # the input is not written
         return res
@@ -288,8 +287,7 @@ class Driver:
         A, T = np.ascontiguousarray(A, U64), np.ascontiguousarray(T, U64)
         B, n = A.shape
         hA, hT, out = be.put(A), be.put(T), be.put(np.full((B, 5), -7, np.int32))
-        rc = self.lib.dvs_pdag_compare(B, n, be.ptr(hA), be.ptr(hT), T.shape[0], be.ptr(out), B * 20, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_pdag_compare", batch=B, n_vars=n, a=hA, b=hT, b_rows=T.shape[0], counts=out, counts_bytes=B * 20)
         return be.get(out).copy()
 
 

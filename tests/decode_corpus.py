@@ -64,6 +64,7 @@ from dags_vae_search_amd import _lib as dl
 from oracle import decode as odec
 from oracle import pace_oracle as po
 from oracle import rng as orng
+from tests.abi_cases import call
 from tests.helpers import load_golden
 
 TAU_FACTOR = 32.0
@@ -181,9 +182,8 @@ def run_decode(be, cfg, params, z, U=None, seed=0, dag_offset=0, calls=1):
     out = []
     for _ in range(calls):
         hs = be.put(np.full(B * dl.DECODE_STATE_BYTES, 0xA5, np.uint8))
-        dl.check(lib, lib.dvs_decode(ctypes.byref(shape), be.ptr(hf), P, be.ptr(hw), ws_words * 4, be.ptr(hr),
-                                     B * dl.record_bytes(lib, shape), be.ptr(hz), None if hu is None else be.ptr(hu),
-                                     be.ptr(hs), B * dl.DECODE_STATE_BYTES, be.stream), "dvs_decode")
+        call(be, "dvs_decode", s=ctypes.byref(shape), params=hf, n_params=P, workspace=hw, workspace_bytes=ws_words * 4, records=hr,
+             records_bytes=B * dl.record_bytes(lib, shape), z=hz, uniforms=hu, state_out=hs, state_bytes=B * dl.DECODE_STATE_BYTES)
         out.append(np.array(be.get(hs)).reshape(B, dl.DECODE_STATE_BYTES))
     return out
 

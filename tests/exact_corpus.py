@@ -18,7 +18,6 @@ Sizes of the byte checks (BYTES_SIZES): k_exact_best takes ceil(n / 8) LDS passe
 is one tile and 9 the first with a cross-tile pass (5 + 4 bits), 17 the first with three (6 + 6 + 5); k_exact_sinks walks all
 levels in one workgroup up to n = 9 and takes one launch per level from 10 on; 6, 12 and 14 are sizes the issue names.
 """
-import ctypes
 import functools
 import itertools
 import math
@@ -30,7 +29,7 @@ from tests import bn_score_corpus as bn
 from tests import cpdag_corpus as cp
 from tests import hillclimb_corpus as hc
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, entry, run
 
 U64 = np.uint64
 NO_ARG = 0xFFFFFFFF
@@ -190,9 +189,8 @@ class Driver:
         hp, ho = be.put(np.full((B, n), 0xA5A5A5A5A5A5A5A5, U64)), be.put(np.full((B, n), -7, np.int32))
         hs, hf = be.put(np.full(B, -7.0)), be.put(np.full(B, -7, np.int32))
         forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
-        rc = lib.dvs_exact_search(B, n, be.ptr(hT), tables.nbytes, max_parents or 0, None if forb is None else be.ptr(forb),
-                                  be.ptr(ws), total, be.ptr(hp), be.ptr(ho), be.ptr(hs), be.ptr(hf), be.stream)
-        assert rc == 0, lib.dvs_last_error()
+        call(be, "dvs_exact_search", batch=B, n_vars=n, table=hT, table_bytes=tables.nbytes, max_parents=max_parents or 0,
+             forbidden=forb, workspace=ws, workspace_bytes=total, parents=hp, order=ho, score=hs, flags=hf)
         w = be.get(ws).copy()
         assert be.get(hT).tobytes() == tables.tobytes()                    # the input is not written
         cells = B * rows * n
@@ -378,8 +376,8 @@ class EmuReal:
     def __init__(self, lib, name, typ, arg):
         from tests import tabu_corpus as tb
         self.case, self.typ, self.arg = hc.hc_case(name), typ, arg
-        self.search_drv = tb.EmuTabuDriver(lib, self.case, typ, arg)
         self.be, self.n = sc.EmuBackend(lib), self.case.data.shape[1]
+        self.search_drv = tb.TabuDriver(self.be, self.case, typ, arg)
         self.exact = Driver(self.be)
 
     def local(self, masks):

@@ -1,9 +1,9 @@
 """TEST HELPER: cases, references and the checks themselves for the greedy hill climb (csrc/dvs_hillclimb.h:
 dvs_bn_toggle_scores, dvs_hc_step; dags_vae_search_amd/hillclimb.py), written once and run by tests/test_emu_hillclimb.py
 (emulator build) and tests/test_gpu_hillclimb.py (device).  Data makers and back ends are those of tests/scoring_corpus.py —
-imported, not copied.  The two test modules differ only in the `Driver` that moves buffers and runs the loop: on the device
-it is BNLearnWrapper.toggle_scores / score_masks and hill_climb themselves, on the emulator the same launch sequence over
-numpy buffers through the raw C ABI.
+imported, not copied.  The two test modules differ only in the driver that runs the loop: on the emulator `Driver`, the
+launch sequence of hill_climb through the raw C ABI by argument name (tests/abi_cases.py: call); on the device `GpuDriver`,
+which replaces the toggle table and the climb by BNLearnWrapper.toggle_scores and hill_climb themselves.
 
 References
   select_ref    the move rules of include/dvs.h (dvs_hc_step) restated in Python ints and numpy float64: ancestor closure on
@@ -31,6 +31,7 @@ from oracle import bic as obic
 from oracle import features as ofeat
 from tests import bn_score_corpus as bn
 from tests import scoring_corpus as sc
+from tests.abi_cases import at, call, call_rc
 from tests.helpers import load_npz
 
 U64 = np.uint64
@@ -265,86 +266,89 @@ def reference_climb(name, typ, arg):
 Climb = namedtuple("Climb", "parents scores steps converged flags codes deltas L T")
 
 
-class EmuDriver:
-    """numpy buffers through the raw C ABI of the emulator build: the launch sequence of hillclimb.hill_climb."""
+class Driver:
+    """the raw C ABI on a back end of scoring_corpus, the packed data and the level counts resident on it: the launch
+    sequence of hillclimb.hill_climb"""
 
-    def __init__(self, lib, case, typ, arg):
-        self.be, self.case, self.typ, self.arg = sc.EmuBackend(lib), case, typ, arg
-        self.lib = lib
-        self.d, self.c = sc.pack(case.data), np.ascontiguousarray(case.card)
-        self.S, self.n = case.data.shape
-
-    def _p(self, a):
-        return None if a is None else self.be.ptr(a)
+    def __init__(self, be, case, typ, arg):
+        self.be, self.case, self.typ, self.arg = be, case, typ, arg
+        self.d, self.c = be.put(sc.pack(case.data)), be.put(np.ascontiguousarray(case.card))
 
     def local(self, P):
         rc, scratch, out, status = bn.run_bn(self.be, self.case.data, self.case.card, P, self.typ, self.arg)
         assert rc == 0
         return out, scratch, status
 
+    def _toggle_on(self, B, hP, hwl, hL, hT, hstatus):
+        """one dvs_bn_toggle_scores on handles of this back end"""
+        S, n = self.case.data.shape
+        call(self.be, "dvs_bn_toggle_scores", batch=B, n_vars=n, n_samples=S, data=self.d, card=self.c, parents=hP,
+             score_type=bn.TYPE_CODE[self.typ], score_arg=NAN if self.arg is None else float(self.arg), worklist=hwl, local=hL,
+             local_bytes=B * n * 8, toggles=hT, toggles_bytes=B * n * n * 8, status=hstatus)
+
     def toggle(self, P, worklist=None, out=None):
+        be = self.be
         P = np.ascontiguousarray(P, U64)
         B, n = P.shape
         L, T = out if out is not None else (np.full((B, n), -7.0), np.full((B, n, n), -7.0))
-        status = np.zeros(1, np.int32)
-        rc = self.lib.dvs_bn_toggle_scores(B, n, self.S, self._p(self.d), self._p(self.c), self._p(P), bn.TYPE_CODE[self.typ],
-                                           NAN if self.arg is None else float(self.arg), self._p(worklist), self._p(L),
-                                           L.nbytes, self._p(T), T.nbytes, self._p(status), None)
-        assert rc == 0, self.lib.dvs_last_error()
-        return L, T, int(status[0])
+        hP, hwl = be.put(P), None if worklist is None else be.put(worklist)
+        hL, hT, status = be.put(L), be.put(T), be.put(np.zeros(1, np.int32))
+        self._toggle_on(B, hP, hwl, hL, hT, status)
+        L[...], T[...] = be.get(hL), be.get(hT)
+        return L, T, int(be.get(status)[0])
+
+    def _step_args(self, P, L, T, max_parents, forbidden, min_delta, step_cap, worklist_fill):
+        """the named arguments of one dvs_hc_step on fresh handles, every output at its start value; `active` is the caller's"""
+        be = self.be
+        P, L, T = np.array(P, U64), np.array(L, np.float64), np.ascontiguousarray(T, np.float64)
+        B, n = P.shape
+        zeros = lambda: be.put(np.zeros(B, np.int32))
+        return dict(batch=B, n_vars=n, parents=be.put(P), local=be.put(L), toggles=be.put(T), toggles_bytes=B * n * n * 8,
+                    max_parents=max_parents or 0, min_delta=float(min_delta),
+                    forbidden=None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64)), step_cap=step_cap,
+                    worklist=be.put(np.full(2 * B, worklist_fill, np.int32)), steps=zeros(), converged=zeros(), flags=zeros(),
+                    trace=be.put(np.zeros((B, step_cap, 2), np.int64)), trace_bytes=B * step_cap * 16)
 
     def step(self, P, L, T, max_parents=None, forbidden=None, min_delta=0.0, step_cap=1):
         """one dvs_hc_step on given tables -> (P, L, worklist, steps, converged, flags, trace, active)"""
-        P, L, T = np.array(P, U64), np.array(L, np.float64), np.ascontiguousarray(T, np.float64)
-        B, n = P.shape
-        wl, st, cv, fl = np.full(2 * B, 5, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        tr, act = np.zeros((B, step_cap, 2), np.int64), np.zeros(1, np.int32)
-        forb = None if forbidden is None else np.ascontiguousarray(forbidden, U64)
-        rc = self.lib.dvs_hc_step(B, n, self._p(P), self._p(L), self._p(T), T.nbytes, max_parents or 0, float(min_delta),
-                                  self._p(forb), step_cap, self._p(wl), self._p(st), self._p(cv), self._p(fl), self._p(tr),
-                                  tr.nbytes, self._p(act), None)
-        assert rc == 0, self.lib.dvs_last_error()
-        return P, L, wl, st, cv, fl, tr, int(act[0])
+        be = self.be
+        h = self._step_args(P, L, T, max_parents, forbidden, min_delta, step_cap, 5)
+        act = be.put(np.zeros(1, np.int32))
+        call(be, "dvs_hc_step", **h, active=act)
+        g = lambda k: be.get(h[k]).copy()
+        return g("parents"), g("local"), g("worklist"), g("steps"), g("converged"), g("flags"), g("trace"), int(be.get(act)[0])
 
     def climb(self, starts, max_steps, max_parents=None, forbidden=None, min_delta=0.0, check_every=8):
-        P = np.array(starts, U64)
-        B, n = P.shape
-        wl, st, cv, fl = np.full(2 * B, -1, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        tr, act = np.zeros((B, max_steps, 2), np.int64), np.zeros(max_steps, np.int32)
-        forb = None if forbidden is None else np.ascontiguousarray(forbidden, U64)
-        L, T, _ = self.toggle(P)
+        be = self.be
+        B, n = np.shape(starts)
+        h = self._step_args(starts, np.full((B, n), -7.0), np.full((B, n, n), -7.0), max_parents, forbidden, min_delta, max_steps, -1)
+        act, status = be.put(np.zeros(max_steps, np.int32)), be.put(np.zeros(1, np.int32))
+        self._toggle_on(B, h["parents"], None, h["local"], h["toggles"], status)
         for t in range(max_steps):
-            rc = self.lib.dvs_hc_step(B, n, self._p(P), self._p(L), self._p(T), T.nbytes, max_parents or 0, float(min_delta),
-                                      self._p(forb), max_steps, self._p(wl), self._p(st), self._p(cv), self._p(fl),
-                                      self._p(tr), tr.nbytes, self._p(act[t:]), None)
-            assert rc == 0, self.lib.dvs_last_error()
-            self.toggle(P, worklist=wl, out=(L, T))
-            if (t + 1) % check_every == 0 and act[t] == 0:
+            call(be, "dvs_hc_step", **h, active=at(be, act, 4 * t))
+            self._toggle_on(B, h["parents"], h["worklist"], h["local"], h["toggles"], status)
+            if (t + 1) % check_every == 0 and be.get(act)[t] == 0:
                 break
+        g = lambda k: be.get(h[k]).copy()
+        P, fl, tr = g("parents"), g("flags"), g("trace")
         scores = self.local(P)[0] if not fl.any() else np.full(B, np.nan)
-        return Climb(P, scores, st, cv, fl, tr[..., 0].copy(), tr[..., 1].copy().view(np.float64), L, T)
+        return Climb(P, scores, g("steps"), g("converged"), fl, tr[..., 0].copy(), tr[..., 1].copy().view(np.float64), g("local"),
+                     g("toggles"))
 
 
-class GpuDriver:
-    """the package itself: BNLearnWrapper.score_masks / toggle_scores and hill_climb on cuda:0"""
+class GpuDriver(Driver):
+    """the package itself where it has the call: BNLearnWrapper.toggle_scores and hill_climb on cuda:0"""
 
-    def __init__(self, lib, case, typ, arg):
-        import torch
+    def __init__(self, be, case, typ, arg):
         from dags_vae_search_amd import BNLearnWrapper
-        self.torch, self.case, self.typ, self.arg = torch, case, typ, arg
-        self.lib, self.be = lib, sc.GpuBackend(lib)
+        super().__init__(be, case, typ, arg)
+        self.torch = be.torch
         kw = {} if arg is None else ({"iss": arg} if typ in ("bde", "bds") else {"k": arg})
         assert np.array_equal(case.card, case.data.max(0) + 1)                  # the wrapper takes card from the data
         self.ev = BNLearnWrapper(case.name, typ, data=case.data, **kw)
-        self.n = case.data.shape[1]
 
     def _t(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a, U64).view(np.int64).copy()).cuda()
-
-    def local(self, P):
-        rc, scratch, out, status = bn.run_bn(self.be, self.case.data, self.case.card, P, self.typ, self.arg)
-        assert rc == 0
-        return out, scratch, status
 
     def toggle(self, P, worklist=None, out=None):
         t = self.torch
@@ -356,22 +360,6 @@ class GpuDriver:
             return out[0], out[1], 0
         L, T, status = self.ev.toggle_scores(self._t(P), return_status=True)
         return L.cpu().numpy(), T.cpu().numpy(), int(status.item())
-
-    def step(self, P, L, T, max_parents=None, forbidden=None, min_delta=0.0, step_cap=1):
-        be = self.be
-        P, L, T = np.ascontiguousarray(P, U64), np.ascontiguousarray(L, np.float64), np.ascontiguousarray(T, np.float64)
-        B, n = P.shape
-        hP, hL, hT = be.put(P), be.put(L), be.put(T)
-        wl, st, cv, fl = (be.put(np.full(2 * B, 5, np.int32)), be.put(np.zeros(B, np.int32)), be.put(np.zeros(B, np.int32)),
-                          be.put(np.zeros(B, np.int32)))
-        tr, act = be.put(np.zeros((B, step_cap, 2), np.int64)), be.put(np.zeros(1, np.int32))
-        forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
-        rc = self.lib.dvs_hc_step(B, n, be.ptr(hP), be.ptr(hL), be.ptr(hT), T.nbytes, max_parents or 0, float(min_delta),
-                                  None if forb is None else be.ptr(forb), step_cap, be.ptr(wl), be.ptr(st), be.ptr(cv),
-                                  be.ptr(fl), be.ptr(tr), B * step_cap * 16, be.ptr(act), be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
-        g = lambda h: be.get(h).copy()
-        return g(hP), g(hL), g(wl), g(st), g(cv), g(fl), g(tr), int(g(act)[0])
 
     def climb(self, starts, max_steps, max_parents=None, forbidden=None, min_delta=0.0, check_every=8):
         from dags_vae_search_amd import hill_climb
@@ -656,9 +644,10 @@ def asia_known_score(typ, arg):
 # Argument refusals (no device needed: everything is checked before anything is enqueued)
 # ---------------------------------------------------------------------------------------------------------------------
 def check_argument_refusals(lib, ptr):
-    p = ptr
-    tog = lambda B=4, n=8, S=100, code=2, arg=NAN, lb=4 * 8 * 8, tb=4 * 8 * 8 * 8, d=p, st=p: lib.dvs_bn_toggle_scores(
-        B, n, S, d, p, p, code, arg, None, p, lb, p, tb, st, None)
+    be, p = sc.EmuBackend(lib), ptr                          # nothing is moved: dummy pointers as they are, the null stream
+    tog = lambda B=4, n=8, S=100, code=2, arg=NAN, lb=4 * 8 * 8, tb=4 * 8 * 8 * 8, d=p, st=p: call_rc(
+        be, "dvs_bn_toggle_scores", batch=B, n_vars=n, n_samples=S, data=d, card=p, parents=p, score_type=code, score_arg=arg,
+        worklist=None, local=p, local_bytes=lb, toggles=p, toggles_bytes=tb, status=st)
     last = lambda: lib.dvs_last_error().decode()
     for code in (-1, 7, 100):
         assert tog(code=code) == 12 and "score_type" in last()
@@ -670,8 +659,9 @@ def check_argument_refusals(lib, ptr):
     assert tog(B=0) == 2 and tog(S=0) == 2 and tog(n=0) == 3 and tog(n=49) == 3
     assert tog(B=1 << 20, n=48, lb=1 << 40, tb=1 << 40) == 2
     assert tog(d=None) == 10 and tog(st=None) == 10
-    hc = lambda B=4, n=8, tb=4 * 8 * 8 * 8, md=0.0, cap=10, tr=p, trb=4 * 10 * 16, P=p, act=p: lib.dvs_hc_step(
-        B, n, P, p, p, tb, 0, md, None, cap, p, p, p, p, tr, trb, act, None)
+    hc = lambda B=4, n=8, tb=4 * 8 * 8 * 8, md=0.0, cap=10, tr=p, trb=4 * 10 * 16, P=p, act=p: call_rc(
+        be, "dvs_hc_step", batch=B, n_vars=n, parents=P, local=p, toggles=p, toggles_bytes=tb, max_parents=0, min_delta=md,
+        forbidden=None, step_cap=cap, worklist=p, steps=p, converged=p, flags=p, trace=tr, trace_bytes=trb, active=act)
     assert hc(tb=4 * 8 * 8 * 8 - 1) == 14 and "toggles_bytes" in last() and str(4 * 8 * 8 * 8) in last()
     assert hc(trb=4 * 10 * 16 - 1) == 14 and "trace_bytes" in last() and str(4 * 10 * 16) in last()
     assert hc(md=NAN) == 13 and "min_delta" in last()

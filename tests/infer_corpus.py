@@ -33,7 +33,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import params_corpus as pm
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import call_rc, entry, run
 
 U64 = np.uint64
 SITE_BN_LW = 501
@@ -165,21 +165,17 @@ def run_lw(be, net, evidence, observed, M, seed, query_offset=0, event=None, tar
     up = lambda x: (x + 255) & ~255
     assert need == 256 + up(4 * n_cells) + up(4 * Q) + up(Q * ((M + 255) // 256) * (3 + 16 * T) * 8), need
     ws_bytes = need if ws_bytes is None else ws_bytes
-    hc, hm, ho, ht = be.put(net.card), be.put(net.masks), be.put(offsets), be.put(cpt)
-    he, hob = be.put(pack_levels(np.asarray(evidence, np.uint8))), be.put(np.asarray([int(o) for o in observed], U64))
-    hev = be.put(np.asarray(event, np.uint16)) if event is not None else None
-    ws = be.put(np.zeros(max(need, ws_bytes) // 8 + 1, np.int64))
-    sums = be.put(np.full((Q, 3), SENTINEL))
-    marg = be.put(np.full((Q, T, 16), SENTINEL)) if T else None
-    parts = be.put(np.full((Q, M, words), 0xAAAAAAAAAAAAAAAA, U64)) if want_particles else None
-    wts = be.put(np.full((Q, M), SENTINEL)) if want_particles else None
-    status = be.put(np.zeros(1, np.int32))
-    opt = lambda h: be.ptr(h) if h is not None else None
-    rc = be.lib.dvs_bn_lw(n, Q, M, be.ptr(hc), be.ptr(hm), be.ptr(ho), be.ptr(ht), n_cells, be.ptr(he), be.ptr(hob), opt(hev),
-                          targets, seed, query_offset, be.ptr(ws), ws_bytes, be.ptr(sums), opt(marg), opt(parts), opt(wts),
-                          be.ptr(status), be.stream)
-    get = lambda h: be.get(h).copy() if h is not None else None
-    return LwOut(rc, get(sums), get(marg), get(parts), get(wts), int(be.get(status)[0]))
+    h = dict(card=be.put(net.card), parents=be.put(net.masks), offsets=be.put(offsets), cpt=be.put(cpt),
+             evidence=be.put(pack_levels(np.asarray(evidence, np.uint8))), observed=be.put(np.asarray([int(o) for o in observed], U64)),
+             event=be.put(np.asarray(event, np.uint16)) if event is not None else None,
+             workspace=be.put(np.zeros(max(need, ws_bytes) // 8 + 1, np.int64)), sums=be.put(np.full((Q, 3), SENTINEL)),
+             marginals=be.put(np.full((Q, T, 16), SENTINEL)) if T else None,
+             particles=be.put(np.full((Q, M, words), 0xAAAAAAAAAAAAAAAA, U64)) if want_particles else None,
+             particle_weights=be.put(np.full((Q, M), SENTINEL)) if want_particles else None, status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bn_lw", n_vars=n, n_queries=Q, n_particles=M, n_cells=n_cells, targets=targets, seed=seed,
+                 query_offset=query_offset, workspace_bytes=ws_bytes, **h)
+    get = lambda k: be.get(h[k]).copy() if h[k] is not None else None
+    return LwOut(rc, get("sums"), get("marginals"), get("particles"), get("particle_weights"), int(be.get(h["status"])[0]))
 
 
 def _same(got, ref, what):
@@ -428,13 +424,13 @@ BlanketOut = namedtuple("BlanketOut", "rc posterior pred status")
 def run_blanket(be, data, card, masks, offsets, cpt, target, use_children, want_posterior=True, cpt_bytes=None):
     B, n = masks.shape
     S, r = data.shape[0], int(card[target])
-    d, c, m, o, t = be.put(sc.pack(data)), be.put(card), be.put(masks), be.put(offsets), be.put(cpt)
-    post = be.put(np.full((B, S, r), SENTINEL)) if want_posterior else None
-    pred, status = be.put(np.full((B, S), 77, np.uint8)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bn_blanket_posterior(B, n, S, be.ptr(d), be.ptr(c), be.ptr(m), be.ptr(o), be.ptr(t),
-                                         cpt.size * 8 if cpt_bytes is None else cpt_bytes, target, use_children,
-                                         be.ptr(post) if want_posterior else None, be.ptr(pred), be.ptr(status), be.stream)
-    return BlanketOut(rc, be.get(post).copy() if want_posterior else None, be.get(pred).copy(), int(be.get(status)[0]))
+    h = dict(data=be.put(sc.pack(data)), card=be.put(card), parents=be.put(masks), offsets=be.put(offsets), cpt=be.put(cpt),
+             posterior=be.put(np.full((B, S, r), SENTINEL)) if want_posterior else None,
+             pred=be.put(np.full((B, S), 77, np.uint8)), status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bn_blanket_posterior", batch=B, n_vars=n, n_rows=S, target=target, use_children=use_children,
+                 cpt_bytes=cpt.size * 8 if cpt_bytes is None else cpt_bytes, **h)
+    post = be.get(h["posterior"]).copy() if want_posterior else None
+    return BlanketOut(rc, post, be.get(h["pred"]).copy(), int(be.get(h["status"])[0]))
 
 
 @functools.lru_cache(maxsize=None)

@@ -47,7 +47,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import exact_corpus as ex
 from tests import posterior_corpus as po
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, entry, run
 
 U64 = np.uint64
 INF = float("inf")
@@ -282,20 +282,18 @@ class Driver:
         self.be, self.lib = be, be.lib
 
     def run(self, fam, chains, steps, burn_in, thin, window, seed, chain_offset=0, step_offset=0, init=1, state=None, trace=True):
-        be, lib, n = self.be, self.lib, fam.n
+        be, n = self.be, fam.n
         st = state or fresh_state(n, chains)
         h = {k: be.put(np.ascontiguousarray(getattr(st, k))) for k in vars(fresh_state(1, 1))}
         hoff, hsets, hsc = be.put(fam.offsets), be.put(fam.sets), be.put(fam.scores)
         htrace = be.put(np.full((chains, max(steps, 1)), -7.0)) if trace else None
         hprob, hflags = be.put(np.full((n, n), -7.0)), be.put(np.full(1, -7, np.int32))
-        rc = lib.dvs_order_mcmc(chains, n, fam.F, steps, be.ptr(hoff), be.ptr(hsets), fam.F * 8, be.ptr(hsc), fam.F * 8, seed,
-                                chain_offset, step_offset, burn_in, thin, window, init, be.ptr(h["order"]), be.ptr(h["log_score"]),
-                                be.ptr(h["accepted"]), be.ptr(h["sums"]), chains * n * n * 8, be.ptr(h["kept"]),
-                                be.ptr(h["best_score"]), be.ptr(h["best_parents"]), None if htrace is None else be.ptr(htrace),
-                                chains * steps * 8, be.ptr(hflags), be.stream)
-        assert rc == 0, lib.dvs_last_error()
-        rc = lib.dvs_order_mcmc_finish(chains, n, be.ptr(h["sums"]), chains * n * n * 8, be.ptr(h["kept"]), be.ptr(hprob), be.stream)
-        assert rc == 0, lib.dvs_last_error()
+        call(be, "dvs_order_mcmc", chains=chains, n_vars=n, n_families=fam.F, steps=steps, offsets=hoff, sets=hsets,
+             sets_bytes=fam.F * 8, scores=hsc, scores_bytes=fam.F * 8, seed=seed, chain_offset=chain_offset, step_offset=step_offset,
+             burn_in=burn_in, thin=thin, window=window, init=init, **h, sums_bytes=chains * n * n * 8, trace=htrace,
+             trace_bytes=chains * steps * 8, flags=hflags)                       # h: the state, under the header's names
+        call(be, "dvs_order_mcmc_finish", chains=chains, n_vars=n, sums=h["sums"], sums_bytes=chains * n * n * 8, kept=h["kept"],
+             prob=hprob)
         out = SimpleNamespace(**{k: be.get(v).copy() for k, v in h.items()})
         out.trace = be.get(htrace).copy()[:, :steps] if trace else np.zeros((chains, 0))
         out.prob, out.flags = be.get(hprob).copy(), be.get(hflags).copy()

@@ -28,7 +28,7 @@ import numpy as np
 
 from oracle import rng as orng
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import call_rc, entry, run
 
 U64 = np.uint64
 MAX_CELLS = 36864            # include/dvs.h: the dense table of dvs_bn_fit
@@ -124,11 +124,11 @@ def run_fit(be, data, card, masks, method, iss, unobserved, offsets=None, cpt_ce
     B, n = masks.shape
     offsets = offsets_of(card, masks) if offsets is None else offsets
     cells = int(offsets[-1]) if cpt_cells is None else cpt_cells
-    d, c, m, o = be.put(sc.pack(data)), be.put(card), be.put(masks), be.put(offsets)
-    cpt, status = be.put(np.full(max(cells, B * n), SENTINEL)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bn_fit(B, n, data.shape[0], be.ptr(d), be.ptr(c), be.ptr(m), method, float(iss), unobserved, be.ptr(o),
-                           be.ptr(cpt), max(cells, B * n) * 8, be.ptr(status), be.stream)
-    return rc, be.get(cpt).copy(), int(be.get(status)[0])
+    h = dict(data=be.put(sc.pack(data)), card=be.put(card), parents=be.put(masks), offsets=be.put(offsets),
+             cpt=be.put(np.full(max(cells, B * n), SENTINEL)), status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bn_fit", batch=B, n_vars=n, n_samples=data.shape[0], method=method, iss=float(iss), unobserved=unobserved,
+                 cpt_bytes=max(cells, B * n) * 8, **h)
+    return rc, be.get(h["cpt"]).copy(), int(be.get(h["status"])[0])
 
 
 FitCase = namedtuple("FitCase", "name data card masks refused")
@@ -316,13 +316,12 @@ def run_sample(be, net, n_rows, seed, row_offset=0, offsets=None, cpt=None):
     n_cells = int(offsets[-1] - offsets[0])
     ws_bytes = int(be.lib.dvs_bn_sample_workspace_bytes(n_cells, n))
     assert ws_bytes >= 256 + 4 * n_cells
-    hc, hm, ho, ht = be.put(net.card), be.put(net.masks), be.put(offsets), be.put(cpt)
-    ws = be.put(np.zeros(ws_bytes // 8 + 1, np.int64))
-    out = be.put(np.full((n_rows, (n + 15) // 16), 0xAAAAAAAAAAAAAAAA, U64))
-    status = be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bn_sample(n, n_rows, be.ptr(hc), be.ptr(hm), be.ptr(ho), be.ptr(ht), n_cells, seed, row_offset, be.ptr(ws),
-                              ws_bytes, be.ptr(out), be.ptr(status), be.stream)
-    return rc, be.get(out).copy(), int(be.get(status)[0])
+    h = dict(card=be.put(net.card), parents=be.put(net.masks), offsets=be.put(offsets), cpt=be.put(cpt),
+             workspace=be.put(np.zeros(ws_bytes // 8 + 1, np.int64)), status=be.put(np.zeros(1, np.int32)),
+             data_out=be.put(np.full((n_rows, (n + 15) // 16), 0xAAAAAAAAAAAAAAAA, U64)))
+    rc = call_rc(be, "dvs_bn_sample", n_vars=n, n_rows=n_rows, n_cells=n_cells, seed=seed, row_offset=row_offset,
+                 workspace_bytes=ws_bytes, **h)
+    return rc, be.get(h["data_out"]).copy(), int(be.get(h["status"])[0])
 
 
 def random_tables(card, masks, seed, zero_one=False):
@@ -494,13 +493,12 @@ def run_loglik(be, data, card, masks, offsets, cpt, per_row=True, ws_bytes=None)
     S = data.shape[0]
     need = loglik_workspace_bytes(B, n, S, int(offsets[-1] - offsets[0]))
     ws_bytes = need if ws_bytes is None else ws_bytes
-    d, c, m, o, t = be.put(sc.pack(data)), be.put(card), be.put(masks), be.put(offsets), be.put(cpt)
-    ws = be.put(np.zeros(max(need, ws_bytes) // 8 + 1, np.int64))
-    rows = be.put(np.full((B, S), SENTINEL)) if per_row else None
-    out, status = be.put(np.full(B, SENTINEL)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bn_loglik(B, n, S, be.ptr(d), be.ptr(c), be.ptr(m), be.ptr(o), be.ptr(t), be.ptr(rows) if per_row else None,
-                              be.ptr(out), be.ptr(ws), ws_bytes, be.ptr(status), be.stream)
-    return rc, be.get(rows).copy() if per_row else None, be.get(out).copy(), int(be.get(status)[0])
+    h = dict(data=be.put(sc.pack(data)), card=be.put(card), parents=be.put(masks), offsets=be.put(offsets), cpt=be.put(cpt),
+             workspace=be.put(np.zeros(max(need, ws_bytes) // 8 + 1, np.int64)),
+             per_row=be.put(np.full((B, S), SENTINEL)) if per_row else None, out=be.put(np.full(B, SENTINEL)),
+             status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bn_loglik", batch=B, n_vars=n, n_rows=S, workspace_bytes=ws_bytes, **h)
+    return rc, be.get(h["per_row"]).copy() if per_row else None, be.get(h["out"]).copy(), int(be.get(h["status"])[0])
 
 
 @functools.lru_cache(maxsize=None)
@@ -606,8 +604,8 @@ def check_loglik_equals_scorer(be, name):
     assert rc == 0 and status == 0
     d, c, m = be.put(sc.pack(data)), be.put(card), be.put(masks)
     scratch, score, st = be.put(np.zeros((B, n))), be.put(np.zeros(B)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bn_scores(B, n, S, be.ptr(d), be.ptr(c), be.ptr(m), 0, float("nan"), be.ptr(scratch), be.ptr(score),
-                              be.ptr(st), be.stream)
+    rc = call_rc(be, "dvs_bn_scores", batch=B, n_vars=n, n_samples=S, data=d, card=c, parents=m, score_type=0,
+                 score_arg=float("nan"), scratch=scratch, out=score, status=st)
     score = be.get(score).copy()
     assert rc == 0 and int(be.get(st)[0]) == 0
     for b in range(B):
@@ -697,7 +695,8 @@ def check_argument_refusals(lib, D):
         msg = lib.dvs_last_error().decode()
         assert msg.startswith("dvs_bn_sample_workspace_bytes:") and text in msg, msg
     # mle takes no iss: any number passes the argument checks (the next failing check decides)
-    assert lib.dvs_bn_fit(4, 12, 100, D, D, D, 0, float("nan"), 0, D, D, 0, D, None) == 14
+    assert call_rc(sc.EmuBackend(lib), "dvs_bn_fit", batch=4, n_vars=12, n_samples=100, data=D, card=D, parents=D, method=0,
+                   iss=float("nan"), unobserved=0, offsets=D, cpt=D, cpt_bytes=0, status=D) == 14      # dummy pointers, null stream
 
 
 # ---------------------------------------------------------------------------------------------------------------------

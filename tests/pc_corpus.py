@@ -26,7 +26,6 @@ Tolerances
   guard       pc_ref on data records how close any p-value it evaluates comes to alpha, relative to alpha; the end-to-end
               cases assert that distance > 100 * P_RTOL.  Otherwise the decision would not be defined by the data.
 """
-import ctypes
 import functools
 import itertools
 import math
@@ -38,7 +37,7 @@ import numpy as np
 
 from tests import cpdag_corpus as cp
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import at, call, call_rc, entry, run
 
 U64 = np.uint64
 MAX_CELLS = 36864
@@ -166,11 +165,10 @@ def run_ci(be, data_h, card_h, n, S, tests, typ, max_cells):
     T = len(tests)
     pairs = np.array([[x, y] for x, y, _ in tests], np.int32)
     cond = np.array([mask_of(zs) for _, _, zs in tests], U64)
-    hp, hc = be.put(pairs), be.put(cond)
-    out, status = be.put(np.full((T, 3), -7.0)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_ci_tests(T, n, S, be.ptr(data_h), be.ptr(card_h), be.ptr(hp), be.ptr(hc), TYPE_ID[typ], max_cells,
-                             be.ptr(out), T * 24, be.ptr(status), be.stream)
-    return rc, be.get(out).copy(), int(be.get(status)[0])
+    h = dict(pairs=be.put(pairs), cond=be.put(cond), out=be.put(np.full((T, 3), -7.0)), status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_ci_tests", n_tests=T, n_vars=n, n_samples=S, data=data_h, card=card_h, test_type=TYPE_ID[typ],
+                 max_cells=max_cells, out_bytes=T * 24, **h)
+    return rc, be.get(h["out"]).copy(), int(be.get(h["status"])[0])
 
 
 def p_error(got_p, df, stat):
@@ -263,11 +261,10 @@ def random_adjacency(n, degree, seed):
 
 def run_expand(be, adj, level, pair_xy, offsets):
     T, P, n = offsets[-1], len(pair_xy), len(adj)
-    ha, hx, ho = be.put(np.array(adj, U64)), be.put(np.array(pair_xy, np.int32)), be.put(np.array(offsets, np.int64))
-    pairs, cond = be.put(np.full((T, 2), -7, np.int32)), be.put(np.full(T, 0xA5A5A5A5A5A5A5A5, U64))
-    rc = be.lib.dvs_pc_expand(P, n, level, be.ptr(ha), be.ptr(hx), be.ptr(ho), T, be.ptr(pairs), be.ptr(cond), T * 8, be.stream)
-    assert rc == 0, be.lib.dvs_last_error()
-    return be.get(pairs).copy(), be.get(cond).copy()
+    h = dict(adj=be.put(np.array(adj, U64)), pair_xy=be.put(np.array(pair_xy, np.int32)), offsets=be.put(np.array(offsets, np.int64)),
+             pairs=be.put(np.full((T, 2), -7, np.int32)), cond=be.put(np.full(T, 0xA5A5A5A5A5A5A5A5, U64)))
+    call(be, "dvs_pc_expand", n_pairs=P, n_vars=n, level=level, n_tests=T, tests_bytes=T * 8, **h)
+    return be.get(h["pairs"]).copy(), be.get(h["cond"]).copy()
 
 
 def check_expand(be):
@@ -317,14 +314,13 @@ def reduce_ref(n, adj, pair_xy, offsets, cond, p, alpha, sepset):
 
 def run_reduce(be, n, adj, pair_xy, offsets, cond, out, alpha, sepset):
     P, T = len(pair_xy), offsets[-1]
-    hx, ho = be.put(np.array(pair_xy, np.int32)), be.put(np.array(offsets, np.int64))
-    hc, hout, ha = be.put(np.array(cond, U64)), be.put(np.ascontiguousarray(out, np.float64)), be.put(np.array(adj, U64))
-    nxt, hs = be.put(np.full(n, 0xA5A5A5A5A5A5A5A5, U64)), be.put(sepset.copy())
-    res, ref = be.put(np.full((P, 2), -7, np.int64)), be.put(np.full(1, -7, np.int32))
-    rc = be.lib.dvs_pc_reduce(P, n, be.ptr(hx), be.ptr(ho), T, be.ptr(hc), be.ptr(hout), alpha, be.ptr(ha), be.ptr(nxt),
-                              be.ptr(hs), n * n * 8, be.ptr(res), P * 16, be.ptr(ref), be.stream)
-    assert rc == 0, be.lib.dvs_last_error()
-    return [int(v) for v in be.get(nxt)], be.get(hs).copy(), be.get(res).copy(), int(be.get(ref)[0])
+    h = dict(pair_xy=be.put(np.array(pair_xy, np.int32)), offsets=be.put(np.array(offsets, np.int64)), cond=be.put(np.array(cond, U64)),
+             out=be.put(np.ascontiguousarray(out, np.float64)), adj=be.put(np.array(adj, U64)), sepset=be.put(sepset.copy()),
+             adj_next=be.put(np.full(n, 0xA5A5A5A5A5A5A5A5, U64)), result=be.put(np.full((P, 2), -7, np.int64)),
+             refused=be.put(np.full(1, -7, np.int32)))
+    call(be, "dvs_pc_reduce", n_pairs=P, n_vars=n, n_tests=T, alpha=alpha, sepset_bytes=n * n * 8, result_bytes=P * 16, **h)
+    g = lambda k: be.get(h[k]).copy()
+    return [int(v) for v in g("adj_next")], g("sepset"), g("result"), int(g("refused")[0])
 
 
 def check_reduce(be):
@@ -485,11 +481,10 @@ def oracle_pc(n):
 def run_orient(be, skel, sepsets):
     skel, sepsets = np.ascontiguousarray(skel, U64), np.ascontiguousarray(sepsets, U64)
     B, n = skel.shape
-    hs, hz = be.put(skel), be.put(sepsets)
-    pdag, conf, fl = be.put(np.full((B, n), 0xA5A5A5A5A5A5A5A5, U64)), be.put(np.full(B, -7, np.int32)), be.put(np.full(B, -7, np.int32))
-    rc = be.lib.dvs_pc_orient(B, n, be.ptr(hs), be.ptr(hz), B * n * n * 8, be.ptr(pdag), B * n * 8, be.ptr(conf), be.ptr(fl), be.stream)
-    assert rc == 0, be.lib.dvs_last_error()
-    return be.get(pdag).copy(), be.get(conf).copy(), be.get(fl).copy()
+    h = dict(skeleton=be.put(skel), sepsets=be.put(sepsets), pdag=be.put(np.full((B, n), 0xA5A5A5A5A5A5A5A5, U64)),
+             conflicts=be.put(np.full(B, -7, np.int32)), flags=be.put(np.full(B, -7, np.int32)))
+    call(be, "dvs_pc_orient", batch=B, n_vars=n, sepsets_bytes=B * n * n * 8, pdag_bytes=B * n * 8, **h)
+    return be.get(h["pdag"]).copy(), be.get(h["conflicts"]).copy(), be.get(h["flags"]).copy()
 
 
 def check_orient_all_dags(be, n):
@@ -610,7 +605,6 @@ def e2e_reference(name, S, typ):
 
 def pc_raw(be, data, card, typ, alpha=ALPHA, max_cond=None, chunk=65536):
     """PC-stable through the raw C ABI on a back end: the launch sequence of dags_vae_search_amd/pc.py"""
-    lib = be.lib
     S, n = data.shape
     dh, ch = be.put(sc.pack(data)), be.put(card)
     adj = [((1 << n) - 1) & ~(1 << v) for v in range(n)]
@@ -628,14 +622,15 @@ def pc_raw(be, data, card, typ, alpha=ALPHA, max_cond=None, chunk=65536):
         hx, ho = be.put(np.array(pair_xy, np.int32)), be.put(np.array(offsets, np.int64))
         pairs, cond, out = be.put(np.zeros((T, 2), np.int32)), be.put(np.zeros(T, U64)), be.put(np.zeros((T, 3)))
         res = be.put(np.zeros((P, 2), np.int64))
-        assert lib.dvs_pc_expand(P, n, level, be.ptr(ha), be.ptr(hx), be.ptr(ho), T, be.ptr(pairs), be.ptr(cond), T * 8, be.stream) == 0
+        call(be, "dvs_pc_expand", n_pairs=P, n_vars=n, level=level, adj=ha, pair_xy=hx, offsets=ho, n_tests=T, pairs=pairs,
+             cond=cond, tests_bytes=T * 8)
         for t0 in range(0, T, chunk):
             m = min(chunk, T - t0)
-            off = lambda h, stride: ctypes.c_void_p(be.ptr(h).value + t0 * stride)
-            assert lib.dvs_ci_tests(m, n, S, be.ptr(dh), be.ptr(ch), off(pairs, 8), off(cond, 8), TYPE_ID[typ], max_cells,
-                                    off(out, 24), m * 24, be.ptr(status), be.stream) == 0, lib.dvs_last_error()
-        assert lib.dvs_pc_reduce(P, n, be.ptr(hx), be.ptr(ho), T, be.ptr(cond), be.ptr(out), alpha, be.ptr(ha), be.ptr(hn),
-                                 be.ptr(hsep), n * n * 8, be.ptr(res), P * 16, be.ptr(refused), be.stream) == 0
+            call(be, "dvs_ci_tests", n_tests=m, n_vars=n, n_samples=S, data=dh, card=ch, pairs=at(be, pairs, t0 * 8),
+                 cond=at(be, cond, t0 * 8), test_type=TYPE_ID[typ], max_cells=max_cells, out=at(be, out, t0 * 24), out_bytes=m * 24,
+                 status=status)
+        call(be, "dvs_pc_reduce", n_pairs=P, n_vars=n, pair_xy=hx, offsets=ho, n_tests=T, cond=cond, out=out, alpha=alpha, adj=ha,
+             adj_next=hn, sepset=hsep, sepset_bytes=n * n * 8, result=res, result_bytes=P * 16, refused=refused)
         adj = [int(v) for v in be.get(hn)]
         refused_total += int(be.get(refused)[0])
         per_level.append(T)

@@ -39,7 +39,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from tests import exact_corpus as ex
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, entry, run
 
 U64 = np.uint64
 INF = float("inf")
@@ -263,10 +263,9 @@ class Driver:
         hfam = be.put(np.full((B, rows, n), -7.0)) if family else None
         forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
         prior = None if size_prior is None else be.put(np.ascontiguousarray(size_prior, np.float64))
-        rc = lib.dvs_arc_posterior(B, n, be.ptr(hT), tables.nbytes, max_parents or 0, None if forb is None else be.ptr(forb),
-                                   None if prior is None else be.ptr(prior), be.ptr(ws), total, be.ptr(hp), be.ptr(hz),
-                                   None if hfam is None else be.ptr(hfam), tables.nbytes if family else 0, be.ptr(hf), be.stream)
-        assert rc == 0, lib.dvs_last_error()
+        call(be, "dvs_arc_posterior", batch=B, n_vars=n, table=hT, table_bytes=tables.nbytes, max_parents=max_parents or 0,
+             forbidden=forb, size_prior=prior, workspace=ws, workspace_bytes=total, prob=hp, log_z=hz, family=hfam,
+             family_bytes=tables.nbytes if family else 0, flags=hf)
         w = be.get(ws).copy()
         assert be.get(hT).tobytes() == tables.tobytes()                    # the input is not written
         cells, G = B * rows * n, split(n)[2]

@@ -32,6 +32,7 @@ from collections import namedtuple
 import numpy as np
 
 from oracle import bic as obic
+from tests.abi_cases import call, call_rc
 
 MAX_BINS = 36864          # dense LDS table of k_bic_local (include/dvs.h: "up to 36 864 cells")
 MAX_SORT = 16384          # samples the sorted-samples path holds
@@ -442,12 +443,10 @@ def bic_reference(case):
 def run_bic(be, data, card, masks):
     """one dvs_bic_scores call -> (return code, scratch [B, n], out [B], status)."""
     B, n = masks.shape
-    d, c, m = be.put(pack(data)), be.put(card), be.put(masks)
-    scratch, out = be.put(np.full((B, n), -7.0)), be.put(np.full(B, -7.0))
-    status = be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bic_scores(B, n, data.shape[0], be.ptr(d), be.ptr(c), be.ptr(m), be.ptr(scratch), be.ptr(out),
-                               be.ptr(status), be.stream)
-    return rc, be.get(scratch).copy(), be.get(out).copy(), int(be.get(status)[0])
+    h = dict(data=be.put(pack(data)), card=be.put(card), parents=be.put(masks), scratch=be.put(np.full((B, n), -7.0)),
+             out=be.put(np.full(B, -7.0)), status=be.put(np.zeros(1, np.int32)))
+    rc = call_rc(be, "dvs_bic_scores", batch=B, n_vars=n, n_samples=data.shape[0], **h)
+    return rc, be.get(h["scratch"]).copy(), be.get(h["out"]).copy(), int(be.get(h["status"])[0])
 
 
 def check_bic_case(be, case, twice=True):
@@ -512,7 +511,7 @@ def check_relabel_case(be, name, data, card, labels, preds):
                 want[b, labels[b, v]] |= U64(1) << U64(int(labels[b, u]))
     lab, pr = be.put(labels), be.put(preds)
     got, status = be.put(np.full((B, n), 0xFFFF, U64)), be.put(np.zeros(1, np.int32))
-    rc = be.lib.dvs_bic_parent_masks(B, n, 1, be.ptr(lab), be.ptr(pr), be.ptr(got), be.ptr(status), be.stream)
+    rc = call_rc(be, "dvs_bic_parent_masks", batch=B, n_vars=n, preds_are_u64=1, labels=lab, preds=pr, parents=got, status=status)
     assert rc == 0 and int(be.get(status)[0]) == 0, name
     got = be.get(got).copy()
     assert np.array_equal(got, want), name
@@ -585,10 +584,9 @@ def gp_points(na, nb, D, seed):
 
 def run_gp_kernel(be, xa, xb, o, l):
     na, nb, D = len(xa), len(xb), xa.shape[1]
-    A, Bm = be.put(xa), be.put(xb)
-    K = be.put(np.full((na, nb), np.nan))
-    rc = be.lib.dvs_gp_kernel(na, nb, D, be.ptr(A), be.ptr(Bm), o, l, be.ptr(K), be.stream)
-    return rc, be.get(K).copy()
+    h = dict(xa=be.put(xa), xb=be.put(xb), K=be.put(np.full((na, nb), np.nan)))
+    rc = call_rc(be, "dvs_gp_kernel", na=na, nb=nb, dim=D, outputscale=o, lengthscale=l, **h)
+    return rc, be.get(h["K"]).copy()
 
 
 def check_gp_kernel(be, na, nb, D):
@@ -621,15 +619,13 @@ GUARD = 37          # doubles after the last output element that the kernel must
 
 def run_gp_backward(be, xa, xb, o, l, G, symmetric):
     na, nb, D = len(xa), len(xb), xa.shape[1]
-    A, Bm, Gd = be.put(xa), be.put(xb), be.put(G)
     dxa = np.full(na * D + GUARD, np.nan)
     rows = np.full(na * 2 + GUARD, np.nan)
     dxa[na * D:] = -123.25
     rows[na * 2:] = -123.25
-    dxa, rows = be.put(dxa), be.put(rows)
-    rc = be.lib.dvs_gp_kernel_backward(na, nb, D, symmetric, be.ptr(A), be.ptr(Bm), o, l, be.ptr(Gd), be.ptr(dxa),
-                                       be.ptr(rows), be.stream)
-    return rc, be.get(dxa).copy(), be.get(rows).copy()
+    h = dict(xa=be.put(xa), xb=be.put(xb), G=be.put(G), dxa=be.put(dxa), row_sums=be.put(rows))
+    rc = call_rc(be, "dvs_gp_kernel_backward", na=na, nb=nb, dim=D, symmetric=symmetric, outputscale=o, lengthscale=l, **h)
+    return rc, be.get(h["dxa"]).copy(), be.get(h["row_sums"]).copy()
 
 
 def gp_cotangent(rng, na, nb):
@@ -698,11 +694,9 @@ PREDICT_WEIGHTS = {"sgpr": predict_inputs, "resolved": predict_inputs_resolved}
 def check_gp_predict(be, B, M, D, weights="sgpr"):
     """returns the worst |got - ref| / bound"""
     x, z, alpha, o, l, c = PREDICT_WEIGHTS[weights](B, M, D, seed=B * 7919 + M * 31 + D)
-    X, Z, A = be.put(x), be.put(z), be.put(alpha)
-    out = be.put(np.full(B + GUARD, np.nan))
-    rc = be.lib.dvs_gp_predict(B, M, D, be.ptr(X), be.ptr(Z), be.ptr(A), o, l, c, be.ptr(out), be.stream)
-    assert rc == 0
-    got = be.get(out).copy()
+    h = dict(x=be.put(x), inducing=be.put(z), alpha=be.put(alpha), out=be.put(np.full(B + GUARD, np.nan)))
+    call(be, "dvs_gp_predict", batch=B, n_inducing=M, dim=D, outputscale=o, lengthscale=l, constant=c, **h)
+    got = be.get(h["out"]).copy()
     assert np.isnan(got[B:]).all()
     ref, bound = gp_predict_ref(x, z, alpha, o, l, c)
     err = np.abs(got[:B] - ref)
@@ -798,9 +792,9 @@ def run_clip_adam(be, n, p, g, m, v, max_norm, guard=(0.0, 0.0), partials=None):
     if partials is not None:
         scratch[2:2 + len(partials)] = partials
     scratch, gd = be.put(scratch), be.put(np.asarray(guard, np.float32))
-    fn = be.lib.dvs_clip_adam if partials is None else be.lib.dvs_clip_adam_from_partials
-    rc = fn(n, be.ptr(P), be.ptr(G), be.ptr(M), be.ptr(V), lr, b1, b2, eps, ADAM_STEP, float(max_norm), be.ptr(scratch),
-            be.ptr(gd), be.stream)
+    rc = call_rc(be, "dvs_clip_adam" if partials is None else "dvs_clip_adam_from_partials", n=n, params=P, grads=G, exp_avg=M,
+                 exp_avg_sq=V, lr=lr, beta1=b1, beta2=b2, adam_eps=eps, step=ADAM_STEP, max_norm=float(max_norm), scratch=scratch,
+                 guard=gd)
     return rc, be.get(P).copy(), be.get(G).copy(), be.get(M).copy(), be.get(V).copy(), be.get(scratch).copy()
 
 

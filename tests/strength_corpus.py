@@ -14,7 +14,6 @@ References
 Everything is integers or equality of fp64 bytes: there are no tolerances.  The one statistical check (chi-square of the
 restated draw, CPU only) has a fixed seed and a stated bound.
 """
-import ctypes
 import functools
 import itertools
 from fractions import Fraction
@@ -24,7 +23,7 @@ import numpy as np
 from oracle import rng as orng
 from tests import bn_score_corpus as bn
 from tests import scoring_corpus as sc
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, call_rc, entry, run
 
 U64 = np.uint64
 NAN = float("nan")
@@ -37,53 +36,44 @@ class Driver:
     def __init__(self, be):
         self.be, self.lib = be, be.lib
 
-    def _p(self, h):
-        return None if h is None else self.be.ptr(h)
-
-    def _row_args(self, rows, set_of):
+    def _scorer_args(self, packed, card, masks, typ, arg, rows, set_of):
+        """(entry-point suffix, the named arguments every scorer call shares); the *_rows variants extend them by the row sets"""
+        be = self.be
+        B, n = masks.shape
+        args = dict(batch=B, n_vars=n, n_samples=packed.shape[0], data=be.put(packed), card=be.put(card),
+                    parents=be.put(np.ascontiguousarray(masks, U64)), score_type=bn.TYPE_CODE[typ],
+                    score_arg=NAN if arg is None else float(arg), status=be.put(np.zeros(1, np.int32)))
+        if rows is None:
+            return "", args
         rows = np.ascontiguousarray(rows, np.int32)
-        hr = self.be.put(rows)
-        hs = None if set_of is None else self.be.put(np.ascontiguousarray(set_of, np.int32))
-        return hr, hs, (self._p(hr), rows.shape[1], rows.shape[0], self._p(hs))
+        return "_rows", dict(args, rows=be.put(rows), set_size=rows.shape[1], n_sets=rows.shape[0],
+                             set_of=None if set_of is None else be.put(np.ascontiguousarray(set_of, np.int32)))
 
     def scores(self, packed, card, masks, typ, arg=None, rows=None, set_of=None):
         """one dvs_bn_scores (rows None) or dvs_bn_scores_rows -> (scratch [B, n], out [B], status)"""
         be = self.be
         B, n = masks.shape
-        d, c, m = be.put(packed), be.put(card), be.put(np.ascontiguousarray(masks, U64))
-        scratch, out, status = be.put(np.full((B, n), -7.0)), be.put(np.full(B, -7.0)), be.put(np.zeros(1, np.int32))
-        head = (B, n, packed.shape[0], be.ptr(d), be.ptr(c), be.ptr(m), bn.TYPE_CODE[typ], NAN if arg is None else float(arg),
-                be.ptr(scratch), be.ptr(out), be.ptr(status))
-        if rows is None:
-            rc = self.lib.dvs_bn_scores(*head, be.stream)
-        else:
-            hr, hs, ra = self._row_args(rows, set_of)
-            rc = self.lib.dvs_bn_scores_rows(*head, *ra, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
-        return be.get(scratch).copy(), be.get(out).copy(), int(be.get(status)[0])
+        suffix, args = self._scorer_args(packed, card, masks, typ, arg, rows, set_of)
+        scratch, out = be.put(np.full((B, n), -7.0)), be.put(np.full(B, -7.0))
+        call(be, "dvs_bn_scores" + suffix, **args, scratch=scratch, out=out)
+        return be.get(scratch).copy(), be.get(out).copy(), int(be.get(args["status"])[0])
 
     def toggle(self, packed, card, masks, typ, arg=None, worklist=None, rows=None, set_of=None):
         """one dvs_bn_toggle_scores(_rows) into tables that start as -7 -> (L [B, n], T [B, n, n], status)"""
         be = self.be
         B, n = masks.shape
-        d, c, m = be.put(packed), be.put(card), be.put(np.ascontiguousarray(masks, U64))
-        L, T, status = be.put(np.full((B, n), -7.0)), be.put(np.full((B, n, n), -7.0)), be.put(np.zeros(1, np.int32))
+        suffix, args = self._scorer_args(packed, card, masks, typ, arg, rows, set_of)
+        L, T = be.put(np.full((B, n), -7.0)), be.put(np.full((B, n, n), -7.0))
         wl = None if worklist is None else be.put(np.ascontiguousarray(worklist, np.int32))
-        head = (B, n, packed.shape[0], be.ptr(d), be.ptr(c), be.ptr(m), bn.TYPE_CODE[typ], NAN if arg is None else float(arg),
-                self._p(wl), be.ptr(L), B * n * 8, be.ptr(T), B * n * n * 8, be.ptr(status))
-        if rows is None:
-            rc = self.lib.dvs_bn_toggle_scores(*head, be.stream)
-        else:
-            hr, hs, ra = self._row_args(rows, set_of)
-            rc = self.lib.dvs_bn_toggle_scores_rows(*head, *ra, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
-        return be.get(L).copy(), be.get(T).copy(), int(be.get(status)[0])
+        call(be, "dvs_bn_toggle_scores" + suffix, **args, worklist=wl, local=L, local_bytes=B * n * 8, toggles=T,
+             toggles_bytes=B * n * n * 8)
+        return be.get(L).copy(), be.get(T).copy(), int(be.get(args["status"])[0])
 
     def bootstrap(self, n_sets, set_size, n_samples, seed, set_offset=0):
         be = self.be
         rows = be.put(np.full((n_sets, set_size), -7, np.int32))
-        rc = self.lib.dvs_bootstrap_rows(n_sets, set_size, n_samples, seed, set_offset, be.ptr(rows), be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_bootstrap_rows", n_sets=n_sets, set_size=set_size, n_samples=n_samples, seed=seed, set_offset=set_offset,
+             rows=rows)
         return be.get(rows).copy()
 
     def arc_strength(self, P, counts=None):
@@ -93,8 +83,7 @@ class Driver:
         B, n = P.shape
         hP = be.put(P)
         hc = be.put(np.zeros((n, n, 2), np.int32) if counts is None else np.ascontiguousarray(counts, np.int32))
-        rc = self.lib.dvs_arc_strength(B, n, be.ptr(hP), be.ptr(hc), n * n * 8, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_arc_strength", batch=B, n_vars=n, pdag=hP, counts=hc, counts_bytes=n * n * 8)
         assert be.get(hP).tobytes() == P.tobytes()
         return be.get(hc).copy()
 
@@ -105,9 +94,8 @@ class Driver:
         G, n = counts.shape[:2]
         hc, hn, hm = be.put(counts), be.put(np.asarray(n_networks, np.int32)), be.put(np.asarray(min_any, np.int32))
         par, info = be.put(np.full((G, n), 0xA5A5A5A5A5A5A5A5, U64)), be.put(np.full((G, 4), -7, np.int32))
-        rc = self.lib.dvs_averaged_network(G, n, be.ptr(hc), be.ptr(hn), be.ptr(hm), be.ptr(par), G * n * 8, be.ptr(info),
-                                           be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_averaged_network", groups=G, n_vars=n, counts=hc, n_networks=hn, min_any=hm, parents=par,
+             parents_bytes=G * n * 8, info=info)
         return be.get(par).copy(), be.get(info).copy()
 
 
@@ -255,21 +243,22 @@ def check_rows_refusals(drv):
     L, T = be.put(np.full((B, n), -7.0)), be.put(np.full((B, n, n), -7.0))
     BIC = bn.TYPE_CODE["bic"]
 
-    def score(set_size=64, n_sets=5, set_of=None, rows_ptr=be.ptr(r)):
-        return lib.dvs_bn_scores_rows(B, n, len(data), be.ptr(d), be.ptr(c), be.ptr(m), BIC, NAN, be.ptr(scratch), be.ptr(out),
-                                      be.ptr(status), rows_ptr, set_size, n_sets, set_of, be.stream)
+    head = dict(batch=B, n_vars=n, n_samples=len(data), data=d, card=c, parents=m, score_type=BIC, score_arg=NAN, status=status)
+
+    def score(set_size=64, n_sets=5, set_of=None, rows=r):
+        return call_rc(be, "dvs_bn_scores_rows", **head, scratch=scratch, out=out, rows=rows, set_size=set_size, n_sets=n_sets,
+                       set_of=set_of)
 
     def toggle(set_size=64, n_sets=5, set_of=None, local_bytes=B * n * 8, toggles_bytes=B * n * n * 8):
-        return lib.dvs_bn_toggle_scores_rows(B, n, len(data), be.ptr(d), be.ptr(c), be.ptr(m), BIC, NAN, None, be.ptr(L),
-                                             local_bytes, be.ptr(T), toggles_bytes, be.ptr(status), be.ptr(r), set_size, n_sets,
-                                             set_of, be.stream)
+        return call_rc(be, "dvs_bn_toggle_scores_rows", **head, worklist=None, local=L, local_bytes=local_bytes, toggles=T,
+                       toggles_bytes=toggles_bytes, rows=r, set_size=set_size, n_sets=n_sets, set_of=set_of)
     for fn, name in ((score, "dvs_bn_scores_rows"), (toggle, "dvs_bn_toggle_scores_rows")):
         for kw, text in ((dict(set_size=0), "set_size and n_sets must be >= 1"), (dict(n_sets=0), "set_size and n_sets must be >= 1"),
                          (dict(n_sets=B - 1), "n_sets must be >= batch")):
             assert fn(**kw) == 13, (name, kw)
             msg = lib.dvs_last_error().decode()
             assert msg.startswith(name + ":") and text in msg, msg
-    assert score(rows_ptr=None) == 10
+    assert score(rows=None) == 10
     assert toggle(local_bytes=B * n * 8 - 1) == 14 and str(B * n * 8) in lib.dvs_last_error().decode()
     assert toggle(toggles_bytes=B * n * n * 8 - 1) == 14 and str(B * n * n * 8) in lib.dvs_last_error().decode()
     assert toggle(set_size=0, local_bytes=0) == 13                                   # the row-set check before the sizes

@@ -23,9 +23,9 @@ from types import SimpleNamespace
 import numpy as np
 
 from oracle import rng as orng
-from tests import bn_score_corpus as bn
 from tests import scoring_corpus as sc
-from tests.hillclimb_corpus import (HAND_N, MIN_DELTA, NAN, TAU_RTOL, U64, EmuDriver, GpuDriver, _neighbourhood, apply_move,
+from tests.abi_cases import call, call_rc
+from tests.hillclimb_corpus import (HAND_N, MIN_DELTA, NAN, TAU_RTOL, U64, Driver, GpuDriver, _neighbourhood, apply_move,
                                     closure, hand_tables, has_cycle, hc_case, legal_moves, move_delta, oracle_local, select_ref)
 
 INF = float("inf")
@@ -96,43 +96,31 @@ def tabu_select_ref(P, L, T, st, max_stall, max_parents=None, forbidden=None, mi
 TabuClimb = namedtuple("TabuClimb", "parents best_parents best_score steps converged flags codes deltas stall visited ring")
 
 
-class TabuOps:
-    def _data(self):
-        if not hasattr(self, "_dc"):
-            self._dc = (self.be.put(sc.pack(self.case.data)), self.be.put(np.ascontiguousarray(self.case.card)))
-        return self._dc
-
-    def _toggle_on(self, B, hP, hwl, hL, hT, hstatus):
-        d, c = self._data()
-        be, (S, n) = self.be, self.case.data.shape
-        rc = self.lib.dvs_bn_toggle_scores(B, n, S, be.ptr(d), be.ptr(c), be.ptr(hP), bn.TYPE_CODE[self.typ],
-                                           NAN if self.arg is None else float(self.arg), None if hwl is None else be.ptr(hwl),
-                                           be.ptr(hL), B * n * 8, be.ptr(hT), B * n * n * 8, be.ptr(hstatus), be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+class TabuDriver(Driver):
+    def _tabu_args(self, P, L, T, worklist_fill, step_cap, tabu_len, max_stall, max_parents, forbidden, min_delta, ring=None,
+                   visited=0, stall=0, best_score=-INF, best_parents=None, steps=0):
+        """the named arguments of one dvs_tabu_step on fresh handles: those of dvs_hc_step and the state; `active` is the caller's"""
+        be = self.be
+        B, n = np.shape(P)
+        full = lambda x, dt: be.put(np.full(B, x, dt) if np.isscalar(x) else np.array(x, dt))
+        return dict(
+            self._step_args(P, L, T, max_parents, forbidden, min_delta, step_cap, worklist_fill), steps=full(steps, np.int32),
+            tabu_len=tabu_len, ring_bytes=B * tabu_len * n * 8, max_stall=max_stall, best_bytes=B * n * 8,
+            ring=be.put(np.zeros((B, tabu_len, n), U64) if ring is None else np.array(ring, U64).reshape(B, tabu_len, n)),
+            visited=full(visited, np.int32), stall=full(stall, np.int32), best_score=full(best_score, np.float64),
+            best_parents=be.put(np.zeros((B, n), U64) if best_parents is None else np.array(best_parents, U64).reshape(B, n)))
 
     def tabu_step(self, P, L, T, *, tabu_len, max_stall, ring=None, visited=0, stall=0, best_score=-INF, best_parents=None,
                   max_parents=None, forbidden=None, min_delta=0.0, step_cap=4, steps=0):
         """one dvs_tabu_step on given tables and state -> everything it writes"""
         be = self.be
-        P, L, T = np.array(P, U64), np.array(L, np.float64), np.ascontiguousarray(T, np.float64)
-        B, n = P.shape
-        full = lambda x, dt: np.full(B, x, dt) if np.isscalar(x) else np.array(x, dt)
-        h = SimpleNamespace(
-            P=be.put(P), L=be.put(L), T=be.put(T), wl=be.put(np.full(2 * B, 5, np.int32)), steps=be.put(full(steps, np.int32)),
-            converged=be.put(np.zeros(B, np.int32)), flags=be.put(np.zeros(B, np.int32)),
-            trace=be.put(np.zeros((B, step_cap, 2), np.int64)), active=be.put(np.zeros(1, np.int32)),
-            ring=be.put(np.zeros((B, tabu_len, n), U64) if ring is None else np.array(ring, U64).reshape(B, tabu_len, n)),
-            visited=be.put(full(visited, np.int32)), stall=be.put(full(stall, np.int32)),
-            best_score=be.put(full(best_score, np.float64)),
-            best_parents=be.put(np.zeros((B, n), U64) if best_parents is None else np.array(best_parents, U64).reshape(B, n)))
-        forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
-        rc = self.lib.dvs_tabu_step(B, n, be.ptr(h.P), be.ptr(h.L), be.ptr(h.T), T.nbytes, max_parents or 0, float(min_delta),
-                                    None if forb is None else be.ptr(forb), step_cap, be.ptr(h.wl), be.ptr(h.steps),
-                                    be.ptr(h.converged), be.ptr(h.flags), be.ptr(h.trace), B * step_cap * 16, be.ptr(h.active),
-                                    tabu_len, be.ptr(h.ring), B * tabu_len * n * 8, be.ptr(h.visited), max_stall,
-                                    be.ptr(h.stall), be.ptr(h.best_score), be.ptr(h.best_parents), B * n * 8, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
-        return SimpleNamespace(**{k: be.get(v).copy() for k, v in vars(h).items()})
+        a = self._tabu_args(P, L, T, 5, step_cap, tabu_len, max_stall, max_parents, forbidden, min_delta, ring, visited, stall,
+                            best_score, best_parents, steps)
+        a["active"] = be.put(np.zeros(1, np.int32))
+        call(be, "dvs_tabu_step", **a)
+        g = lambda k: be.get(a[k]).copy()
+        return SimpleNamespace(P=g("parents"), L=g("local"), T=g("toggles"), wl=g("worklist"), **{k: g(k) for k in (
+            "steps", "converged", "flags", "trace", "active", "ring", "visited", "stall", "best_score", "best_parents")})
 
     def perturb(self, P, L, T, seed, draw_index, max_parents=None, forbidden=None, flags=None):
         """one dvs_hc_perturb -> (P, L, worklist, flags)"""
@@ -142,49 +130,31 @@ class TabuOps:
         hP, hL, hT, wl = be.put(P), be.put(L), be.put(T), be.put(np.full(2 * B, 5, np.int32))
         fl = be.put(np.zeros(B, np.int32) if flags is None else np.array(flags, np.int32))
         forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
-        rc = self.lib.dvs_hc_perturb(B, n, be.ptr(hP), be.ptr(hL), be.ptr(hT), T.nbytes, max_parents or 0,
-                                     None if forb is None else be.ptr(forb), be.ptr(wl), be.ptr(fl), seed, draw_index, be.stream)
-        assert rc == 0, self.lib.dvs_last_error()
+        call(be, "dvs_hc_perturb", batch=B, n_vars=n, parents=hP, local=hL, toggles=hT, toggles_bytes=T.nbytes,
+             max_parents=max_parents or 0, forbidden=forb, worklist=wl, flags=fl, seed=seed, draw_index=draw_index)
         g = lambda x: be.get(x).copy()
         return g(hP), g(hL), g(wl), g(fl)
 
     def tabu_climb(self, starts, max_steps, tabu_len, max_stall, max_parents=None, forbidden=None, min_delta=0.0, check_every=8):
         """the launch sequence of tabu.tabu_search (restarts = 0) on the raw ABI"""
         be = self.be
-        P = np.array(starts, U64)
-        B, n = P.shape
-        h = SimpleNamespace(
-            P=be.put(P), L=be.put(np.full((B, n), -7.0)), T=be.put(np.full((B, n, n), -7.0)),
-            wl=be.put(np.full(2 * B, -1, np.int32)), steps=be.put(np.zeros(B, np.int32)), converged=be.put(np.zeros(B, np.int32)),
-            flags=be.put(np.zeros(B, np.int32)), trace=be.put(np.zeros((B, max_steps, 2), np.int64)),
-            ring=be.put(np.zeros((B, tabu_len, n), U64)), visited=be.put(np.zeros(B, np.int32)),
-            stall=be.put(np.zeros(B, np.int32)), best_score=be.put(np.full(B, -INF)), best_parents=be.put(np.zeros((B, n), U64)),
-            status=be.put(np.zeros(1, np.int32)))
-        act = [be.put(np.zeros(1, np.int32)) for _ in range(max_steps)]
-        forb = None if forbidden is None else be.put(np.ascontiguousarray(forbidden, U64))
-        self._toggle_on(B, h.P, None, h.L, h.T, h.status)
+        B, n = np.shape(starts)
+        a = self._tabu_args(starts, np.full((B, n), -7.0), np.full((B, n, n), -7.0), -1, max_steps, tabu_len, max_stall,
+                            max_parents, forbidden, min_delta)
+        act, status = [be.put(np.zeros(1, np.int32)) for _ in range(max_steps)], be.put(np.zeros(1, np.int32))
+        self._toggle_on(B, a["parents"], None, a["local"], a["toggles"], status)
         for t in range(max_steps):
-            rc = self.lib.dvs_tabu_step(B, n, be.ptr(h.P), be.ptr(h.L), be.ptr(h.T), B * n * n * 8, max_parents or 0,
-                                        float(min_delta), None if forb is None else be.ptr(forb), max_steps, be.ptr(h.wl),
-                                        be.ptr(h.steps), be.ptr(h.converged), be.ptr(h.flags), be.ptr(h.trace),
-                                        B * max_steps * 16, be.ptr(act[t]), tabu_len, be.ptr(h.ring), B * tabu_len * n * 8,
-                                        be.ptr(h.visited), max_stall, be.ptr(h.stall), be.ptr(h.best_score),
-                                        be.ptr(h.best_parents), B * n * 8, be.stream)
-            assert rc == 0, self.lib.dvs_last_error()
-            self._toggle_on(B, h.P, h.wl, h.L, h.T, h.status)
+            call(be, "dvs_tabu_step", **a, active=act[t])
+            self._toggle_on(B, a["parents"], a["worklist"], a["local"], a["toggles"], status)
             if (t + 1) % check_every == 0 and int(be.get(act[t])[0]) == 0:
                 break
-        g = lambda x: be.get(x).copy()
-        tr = g(h.trace)
-        return TabuClimb(g(h.P), g(h.best_parents), g(h.best_score), g(h.steps), g(h.converged), g(h.flags), tr[..., 0].copy(),
-                         tr[..., 1].copy().view(np.float64), g(h.stall), g(h.visited), g(h.ring))
+        g = lambda k: be.get(a[k]).copy()
+        tr = g("trace")
+        return TabuClimb(g("parents"), g("best_parents"), g("best_score"), g("steps"), g("converged"), g("flags"), tr[..., 0].copy(),
+                         tr[..., 1].copy().view(np.float64), g("stall"), g("visited"), g("ring"))
 
 
-class EmuTabuDriver(TabuOps, EmuDriver):
-    pass
-
-
-class GpuTabuDriver(TabuOps, GpuDriver):
+class GpuTabuDriver(TabuDriver, GpuDriver):
     def search(self, starts, **kw):
         """the package's own tabu_search on the same evaluator -> TabuResult"""
         from dags_vae_search_amd import tabu_search
@@ -606,11 +576,14 @@ def check_perturb_hand_made(drv):
 # 6. Argument refusals (no device needed: everything is checked before anything is enqueued)
 # ---------------------------------------------------------------------------------------------------------------------
 def check_argument_refusals(lib, ptr):
-    p = ptr
+    be, p = sc.EmuBackend(lib), ptr                          # nothing is moved: dummy pointers as they are, the null stream
     last = lambda: lib.dvs_last_error().decode()
     tb, trb, rb, bb = 4 * 8 * 8 * 8, 4 * 10 * 16, 4 * 3 * 8 * 8, 4 * 8 * 8
     ts = lambda B=4, n=8, tb=tb, md=0.0, cap=10, tr=p, trb=trb, P=p, act=p, tl=3, ring=p, rb=rb, ms=5, best=p, bb=bb, vis=p: \
-        lib.dvs_tabu_step(B, n, P, p, p, tb, 0, md, None, cap, p, p, p, p, tr, trb, act, tl, ring, rb, vis, ms, p, p, best, bb, None)
+        call_rc(be, "dvs_tabu_step", batch=B, n_vars=n, parents=P, local=p, toggles=p, toggles_bytes=tb, max_parents=0, min_delta=md,
+                forbidden=None, step_cap=cap, worklist=p, steps=p, converged=p, flags=p, trace=tr, trace_bytes=trb, active=act,
+                tabu_len=tl, ring=ring, ring_bytes=rb, visited=vis, max_stall=ms, stall=p, best_score=p, best_parents=best,
+                best_bytes=bb)
     assert ts(tb=tb - 1) == 14 and "toggles_bytes" in last() and str(tb) in last()
     assert ts(trb=trb - 1) == 14 and "trace_bytes" in last() and str(trb) in last()
     assert ts(rb=rb - 1) == 14 and "ring_bytes" in last() and str(rb) in last()
@@ -623,7 +596,9 @@ def check_argument_refusals(lib, ptr):
     assert ts(B=0) == 2 and ts(n=0) == 3 and ts(n=49) == 3
     assert ts(B=1 << 20, n=48, tb=1 << 40, trb=1 << 40, rb=1 << 40, bb=1 << 40) == 2
     assert ts(P=None) == 10 and ts(act=None) == 10 and ts(ring=None) == 10 and ts(best=None) == 10 and ts(vis=None) == 10
-    pt = lambda B=4, n=8, tb=tb, P=p, wl=p, fl=p: lib.dvs_hc_perturb(B, n, P, p, p, tb, 0, None, wl, fl, 1, 0, None)
+    pt = lambda B=4, n=8, tb=tb, P=p, wl=p, fl=p: call_rc(
+        be, "dvs_hc_perturb", batch=B, n_vars=n, parents=P, local=p, toggles=p, toggles_bytes=tb, max_parents=0, forbidden=None,
+        worklist=wl, flags=fl, seed=1, draw_index=0)
     assert pt(tb=tb - 1) == 14 and "toggles_bytes" in last() and str(tb) in last()
     assert pt(B=0) == 2 and pt(n=0) == 3 and pt(n=49) == 3 and pt(B=1 << 20, n=48, tb=1 << 40) == 2
     assert pt(P=None) == 10 and pt(wl=None) == 10 and pt(fl=None) == 10

@@ -6,7 +6,7 @@ import re
 import pytest
 
 from dags_vae_search_amd import _lib as dl
-from tests.abi_cases import entry, run
+from tests.abi_cases import call, call_rc, entry, run
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -350,3 +350,71 @@ def test_search_entry_points_validate_in_a_fixed_order_before_anything_is_enqueu
     assert len({fn for fn, *_ in cases}) == 16
     assert lib.dvs_structset_filter(0, 12, None, None, None, 0, None, 0, None, None, 0, None, None) == 0   # an empty batch
     run(lib, cases)
+
+
+# ---- tests/abi_cases.py: call / call_rc against a recording stand-in library (no device, no emulator build)
+FN = "dvs_tabu_step"
+NAMES = [name for name, _ in dl.SIGNATURES[FN][1]]
+POINTERS = [name for name, ctype in dl.SIGNATURES[FN][1] if ctype is ctypes.c_void_p and name != "stream"]
+
+
+class Backend:
+    """its own recording library: every dvs_* call returns `rc`; a handle is ("h", k), at address 0x1000 + k"""
+    stream = ctypes.c_void_p(0x5000)
+
+    def __init__(self, rc=0):
+        self.lib, self.rc, self.calls = self, rc, []
+
+    def __getattr__(self, fn):
+        return lambda *args: self.calls.append((fn, args)) or self.rc
+
+    def dvs_last_error(self):
+        return b"dvs_tabu_step: ring_bytes < 768"
+
+    def ptr(self, h):
+        assert h[0] == "h"
+        return ctypes.c_void_p(0x1000 + h[1])
+
+
+def full_args():
+    """every argument of FN but the stream: the k-th a handle if it is a pointer, else the scalar 100 + k"""
+    return {name: ("h", k) if name in POINTERS else 100 + k for k, name in enumerate(NAMES) if name != "stream"}
+
+
+def test_arguments_go_in_the_order_of_the_header():
+    assert len(NAMES) > 20
+    be, raw = Backend(), ctypes.c_void_p(4096)
+    args = {**full_args(), "forbidden": None, "ring": raw}
+    assert call(be, FN, **dict(reversed(args.items()))) is None              # the order they are named in does not matter
+    (fn, got), = be.calls
+    assert fn == FN and len(got) == len(NAMES)
+    for k, (name, value) in enumerate(zip(NAMES, got)):
+        if name in ("stream", "forbidden", "ring"):                          # from the backend; NULL; a c_void_p as it is
+            assert value is {"stream": be.stream, "forbidden": None, "ring": raw}[name]
+        elif name in POINTERS:
+            assert isinstance(value, ctypes.c_void_p) and value.value == 0x1000 + k, name      # a handle goes through be.ptr
+        else:
+            assert value == 100 + k, name
+    shape = ctypes.byref(dl.make_shape(2, 8, 4))                             # a struct pointer and a given stream are kept
+    call(be, "dvs_decode", s=shape, params=("h", 1), n_params=7, workspace=("h", 2), workspace_bytes=64, records=("h", 3),
+         records_bytes=192, z=("h", 4), uniforms=None, state_out=("h", 5), state_bytes=880, stream=raw)
+    assert be.calls[1][1][0] is shape and be.calls[1][1][1].value == 0x1001 and be.calls[1][1][-1] is raw
+
+
+@pytest.mark.parametrize("change,listed", [({"ring_bytes": None}, "missing ['ring_bytes'], unknown []"),
+                                           ({"ring_size": 1}, "missing [], unknown ['ring_size']")])
+def test_a_missing_or_unknown_name_is_a_type_error(change, listed):
+    be = Backend()
+    args = {k: v for k, v in {**full_args(), **change}.items() if v is not None}
+    for fn in (lambda: call(be, FN, **args), lambda: call_rc(be, FN, **args), lambda: entry(FN, [], stream=None, **args)):
+        with pytest.raises(TypeError, match=FN) as e:                        # entry() shares the check
+            fn()
+        assert listed in str(e.value)
+    assert be.calls == []
+
+
+def test_a_refusal_fails_call_with_the_message_and_is_returned_by_call_rc():
+    be = Backend(rc=14)
+    with pytest.raises(AssertionError, match="dvs_tabu_step: ring_bytes < 768"):
+        call(be, FN, **full_args())
+    assert call_rc(be, FN, **full_args()) == 14 and len(be.calls) == 2

@@ -14,7 +14,7 @@ CASES = [(name, typ, arg) for name in hc.CASE_NAMES for typ, arg in hc.case_type
 @functools.lru_cache(maxsize=None)
 def make_driver(name, typ, arg):
     from tests.emu.harness import emu
-    return hc.EmuDriver(emu(), hc.any_case(name), typ, arg)
+    return hc.Driver(hc.sc.EmuBackend(emu()), hc.any_case(name), typ, arg)
 
 
 @pytest.mark.parametrize("name", hc.TOGGLE_CASES)

@@ -11,7 +11,7 @@ from tests import tabu_corpus as tb
 @functools.lru_cache(maxsize=None)
 def make_driver(name, typ, arg):
     from tests.emu.harness import emu
-    return tb.EmuTabuDriver(emu(), tb.hc_case(name), typ, arg)
+    return tb.TabuDriver(tb.sc.EmuBackend(emu()), tb.hc_case(name), typ, arg)
 
 
 @pytest.mark.parametrize("name", tb.TABU_CASES)

@@ -17,7 +17,7 @@ CASES = [(name, typ, arg) for name in hc.CASE_NAMES for typ, arg in hc.case_type
 @functools.lru_cache(maxsize=None)
 def make_driver(name, typ, arg):
     from dags_vae_search_amd import _lib as dl
-    return hc.GpuDriver(dl.load(), hc.any_case(name), typ, arg)
+    return hc.GpuDriver(hc.sc.GpuBackend(dl.load()), hc.any_case(name), typ, arg)
 
 
 @pytest.mark.parametrize("name", hc.TOGGLE_CASES)

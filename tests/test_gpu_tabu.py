@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 @functools.lru_cache(maxsize=None)
 def make_driver(name, typ, arg):
     from dags_vae_search_amd import _lib as dl
-    return tb.GpuTabuDriver(dl.load(), tb.hc_case(name), typ, arg)
+    return tb.GpuTabuDriver(tb.sc.GpuBackend(dl.load()), tb.hc_case(name), typ, arg)
 
 
 @pytest.mark.parametrize("name", tb.TABU_CASES)
