@@ -29,5 +29,7 @@ from .posterior import ArcPosterior, arc_posterior, arc_posterior_from_tables  #
 # ordermc.py is named after no function it exports, so it needs no such care
 from .ordermc import FamilyScores, OrderMCMCResult, family_scores, order_mcmc  # noqa: F401
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
+from .eliminate import (EliminationPlan, elimination_plan, evidence_probability, exact_cpquery, exact_joint,  # noqa: F401
+                        exact_posterior)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

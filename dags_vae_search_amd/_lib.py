@@ -17,6 +17,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libdvs_hip.so"
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs.h")
+EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_eliminate.h")   # the companion header: dvs_bn_eliminate
 
 
 class DvsShape(Structure):
@@ -70,15 +71,28 @@ def parse_header(text: str):
     return signatures, constants
 
 
-def _read_header():
-    if not os.path.exists(HEADER):
-        raise RuntimeError(f"include/dvs.h not found at {HEADER}: the binding of {LIB_NAME} is read from it")
-    with open(HEADER) as f:
+def _read_header(path=None):
+    """parse_header of include/dvs.h, or of the companion header at ``path``; a missing file is an error that gives its path"""
+    path = HEADER if path is None else path
+    if not os.path.exists(path):
+        raise RuntimeError(f"include/{os.path.basename(path)} not found at {path}: the binding of {LIB_NAME} is read from it")
+    with open(path) as f:
         return parse_header(f.read())
 
 
 SIGNATURES, _H = _read_header()
 EXPORTS = list(SIGNATURES)
+# include/dvs_eliminate.h declares what was added beside the 64 entry points of include/dvs.h; SIGNATURES and EXPORTS stay those
+EXT_SIGNATURES, _X = _read_header(EXT_HEADER)
+
+
+def signature(fn: str):
+    """(restype, [(argument name, ctype), ...]) of an entry point of include/dvs.h or of the companion header"""
+    if fn in SIGNATURES:
+        return SIGNATURES[fn]
+    if fn in EXT_SIGNATURES:
+        return EXT_SIGNATURES[fn]
+    raise KeyError(f"{fn} is declared neither in include/dvs.h nor in include/dvs_eliminate.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -110,11 +124,14 @@ STATUS_LABELS = 32            # bit 5 (dvs_bic_parent_masks): a DAG's labels are
 STATUS_NOT_PROBABILITY = 64   # bit 6 (dvs_bn_sample, dvs_bn_lw): a table row is not a probability vector
 LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
 SCORE_TYPES = _by_bnlearn_name("DVS_SCORE_", ("loglik", "aic", "bic", "bde", "bds", "k2", "bdj"))   # dvs_score_type
+# dvs_bn_eliminate (include/dvs_eliminate.h): the arena and table cap in fp64 cells, the plan words' tag and limits
+ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
+    _X["DVS_BN_ELIM_" + k] for k in ("MAX_CELLS", "MAX_WORDS", "MAX_SCOPE", "MAX_INPUTS", "TAG"))
 
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
-    """Declare argument/return types of every entry point of include/dvs.h on a loaded library."""
-    for name, (restype, args) in SIGNATURES.items():
+    """Declare argument/return types of every entry point of include/dvs.h and of its companion header on a loaded library."""
+    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

@@ -1,5 +1,5 @@
 // Search-side entry points (included by dvs_api.hip): reconstruction matching, search candidates, the graph generator, the
-// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference, exact search, the exact arc posterior, order MCMC, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
+// BN scorers, hill climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters and inference (likelihood weighting, variable elimination), exact search, the exact arc posterior, order MCMC, arc strengths and the GP predictor.  Each validates, fills one argument block of dvs_search_args.h by
 // field name and calls that block's launcher between call_begin() and call_end().
 
 static int failf(int code, const char* fmt, ...) {
@@ -747,6 +747,54 @@ extern "C" int dvs_bn_blanket_posterior(int32_t batch, int32_t n_vars, int64_t n
     call_begin();
     dvs_launch_bn_blanket(a, (dvs_stream_t)stream);
     return call_end("dvs_bn_blanket_posterior");
+}
+
+// ---- exact inference by variable elimination (dvs_eliminate.h) ---------------------------------------------------------
+extern "C" int dvs_bn_eliminate(int32_t n_vars, int32_t n_plans, int64_t n_rows, const uint8_t* card, const uint64_t* parents,
+                                const int64_t* offsets, const double* cpt, int64_t n_cells, const int32_t* plans,
+                                size_t plans_bytes, const int64_t* plan_offsets, int32_t plan_words, int32_t arena_cells,
+                                int32_t step_cells, const uint16_t* masks, int32_t rows_per_group, int32_t out_stride,
+                                double* out, size_t out_bytes, double* z, int32_t* plan_flags, int32_t* status, void* stream) {
+    if (int e = bn_sample_dims("dvs_bn_eliminate", n_cells, n_vars)) return e;
+    if (n_plans < 1 || n_rows < 1 || n_rows > (int64_t)0x7fffffff || (int64_t)n_plans * n_rows > (int64_t)0x7fffffff)
+        return fail(2, "dvs_bn_eliminate: n_plans and n_rows must be in [1, 2^31 - 1] and n_plans * n_rows < 2^31");
+    if (plan_words < 7 || plan_words > DVS_BN_ELIM_MAX_WORDS)
+        return fail(12, "dvs_bn_eliminate: plan_words must be in [7, DVS_BN_ELIM_MAX_WORDS = 4096]");
+    if (arena_cells < 1 || arena_cells > DVS_BN_ELIM_MAX_CELLS || step_cells < 1 || step_cells > DVS_BN_ELIM_MAX_CELLS)
+        return fail(12, "dvs_bn_eliminate: arena_cells and step_cells must be in [1, DVS_BN_ELIM_MAX_CELLS = 16384]");
+    if (out_stride < 1 || out_stride > DVS_BN_ELIM_MAX_CELLS)
+        return fail(12, "dvs_bn_eliminate: out_stride must be in [1, DVS_BN_ELIM_MAX_CELLS = 16384]");
+    if (rows_per_group < 0 || rows_per_group > 64) return fail(12, "dvs_bn_eliminate: rows_per_group must be in [0, 64]");
+    if (!card || !parents || !offsets || !cpt || !plans || !plan_offsets || !masks || !out || !z || !plan_flags || !status)
+        return fail(10, "dvs_bn_eliminate: null pointer");
+    if (plans_bytes < (size_t)n_plans * 28) return fail_size("dvs_bn_eliminate: plans_bytes < n_plans * 28", (size_t)n_plans * 28);
+    const size_t need = (size_t)n_plans * (size_t)n_rows * (size_t)out_stride * 8;
+    if (out_bytes < need) return fail_size("dvs_bn_eliminate: out_bytes < n_plans * n_rows * out_stride * 8", need);
+    BnElimArgs a = {};
+    a.n = n_vars;
+    a.P = n_plans;
+    a.plan_words = plan_words;
+    a.arena_cells = arena_cells;
+    a.step_cells = step_cells;
+    a.rows_per_group = rows_per_group;
+    a.out_stride = out_stride;
+    a.rows = n_rows;
+    a.n_cells = n_cells;
+    a.plans_words = (long long)(plans_bytes / 4);
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.cpt = cpt;
+    a.plans = plans;
+    a.plan_offsets = (const long long*)plan_offsets;
+    a.masks = masks;
+    a.out = out;
+    a.z = z;
+    a.plan_flags = plan_flags;
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_eliminate(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_eliminate");
 }
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------

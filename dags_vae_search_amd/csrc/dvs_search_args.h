@@ -2,12 +2,13 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
 #pragma once
 #include "dvs_kernels.h"
+#include "../../include/dvs_eliminate.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -328,6 +329,25 @@ struct BnBlanketArgs {
     int* status;
 };
 void dvs_launch_bn_blanket(const BnBlanketArgs& a, dvs_stream_t st);
+
+// ---- exact inference by variable elimination (dvs_eliminate.h; the plan words: include/dvs_eliminate.h) ---------------
+struct BnElimArgs {
+    int n, P, G, groups;         // G, groups: launcher (rows per workgroup, workgroups per plan)
+    int plan_words, arena_cells, step_cells, rows_per_group, out_stride;
+    long long rows, n_cells, plans_words;        // plans_words: plans_bytes / 4: a plan that ends beyond it is malformed
+    const uint8_t* card;         // [n]
+    const uint64_t* parents;     // [n]
+    const long long* offsets;    // [n + 1]
+    const double* cpt;
+    const int* plans;            // the words of every plan
+    const long long* plan_offsets;   // [P + 1]
+    const uint16_t* masks;       // [rows][n]
+    double* out;                 // [P][rows][out_stride]
+    double* z;                   // [P][rows]
+    int* plan_flags;             // [P], written by k_bn_elim_check
+    int* status;
+};
+void dvs_launch_bn_eliminate(const BnElimArgs& a, dvs_stream_t st);
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 // The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.

@@ -664,6 +664,7 @@ int dvs_bn_blanket_posterior(int32_t batch, int32_t n_vars, int64_t n_rows, cons
                              const uint64_t* parents, const int64_t* offsets, const double* cpt, size_t cpt_bytes,
                              int32_t target, int32_t use_children, double* posterior, uint8_t* pred, int32_t* status,
                              void* stream);
+/* Exact inference by variable elimination is declared in the companion header dvs_eliminate.h, which includes this one. */
 
 /* Exact structure search: the DAG with the largest decomposable score, by the subset dynamic programme of
  * Silander and Myllymaki (2006).  table (device f64 [batch][2^n_vars][n_vars]): cell [t][S][v] is the local score of
