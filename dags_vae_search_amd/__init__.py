@@ -31,5 +31,7 @@ from .ordermc import FamilyScores, OrderMCMCResult, family_scores, order_mcmc  #
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
 from .eliminate import (EliminationPlan, elimination_plan, evidence_probability, exact_cpquery, exact_joint,  # noqa: F401
                         exact_posterior)
+from .incomplete import (EMResult, ExpectedCounts, em_fit, expected_counts, family_plans, fit_counts, impute,  # noqa: F401
+                         incomplete_rows, target_plans)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libdvs_hip.so"
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs.h")
 EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_eliminate.h")   # the companion header: dvs_bn_eliminate
+INC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_incomplete.h")  # the second: expected counts, fit_counts, impute
 
 
 class DvsShape(Structure):
@@ -84,6 +85,8 @@ SIGNATURES, _H = _read_header()
 EXPORTS = list(SIGNATURES)
 # include/dvs_eliminate.h declares what was added beside the 64 entry points of include/dvs.h; SIGNATURES and EXPORTS stay those
 EXT_SIGNATURES, _X = _read_header(EXT_HEADER)
+# include/dvs_incomplete.h, the second companion: learning from incomplete data; EXT_SIGNATURES stays the one entry it has
+INC_SIGNATURES, _ = _read_header(INC_HEADER)
 
 
 def signature(fn: str):
@@ -92,7 +95,9 @@ def signature(fn: str):
         return SIGNATURES[fn]
     if fn in EXT_SIGNATURES:
         return EXT_SIGNATURES[fn]
-    raise KeyError(f"{fn} is declared neither in include/dvs.h nor in include/dvs_eliminate.h")
+    if fn in INC_SIGNATURES:
+        return INC_SIGNATURES[fn]
+    raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h and include/dvs_incomplete.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -130,8 +135,8 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
-    """Declare argument/return types of every entry point of include/dvs.h and of its companion header on a loaded library."""
-    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
+    """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
+    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

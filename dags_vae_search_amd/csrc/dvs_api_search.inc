@@ -797,6 +797,155 @@ extern "C" int dvs_bn_eliminate(int32_t n_vars, int32_t n_plans, int64_t n_rows,
     return call_end("dvs_bn_eliminate");
 }
 
+// ---- incomplete data: expected counts, tables from counts, exact imputation (dvs_incomplete.h) -------------------------
+static int bn_inc_dims(const char* fn, int64_t n_cells, int n_vars, int64_t n_rows, bool counts) {
+    if (int e = bn_sample_dims(fn, n_cells, n_vars)) return e;
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn);
+    if (counts && ((n_rows + 255) / 256) * n_cells >= ((int64_t)1 << 40))
+        return failf(2, "%s: ceil(n_rows / 256) * n_cells must be < 2^40", fn);
+    return 0;
+}
+
+// impute: out_cells is the 16 levels a variable can have, not an argument
+static int bn_inc_plans(const char* fn, int plan_words, int arena_cells, int out_cells, int step_cells, int rows_per_group, bool impute) {
+    if (plan_words < 7 || plan_words > DVS_BN_ELIM_MAX_WORDS)
+        return failf(12, "%s: plan_words must be in [7, DVS_BN_ELIM_MAX_WORDS = 4096]", fn);
+    if (arena_cells < 1 || arena_cells > DVS_BN_ELIM_MAX_CELLS || out_cells < 1 || out_cells > DVS_BN_ELIM_MAX_CELLS ||
+        step_cells < 1 || step_cells > DVS_BN_ELIM_MAX_CELLS)
+        return failf(12, "%s: arena_cells%s and step_cells must be in [1, DVS_BN_ELIM_MAX_CELLS = 16384]", fn, impute ? "" : ", out_cells");
+    if (arena_cells + out_cells > DVS_BN_ELIM_MAX_CELLS)
+        return impute ? failf(12, "%s: arena_cells + 16 = %d exceeds DVS_BN_ELIM_MAX_CELLS = 16384", fn, arena_cells + 16)
+                      : failf(12, "%s: arena_cells + out_cells = %d exceeds DVS_BN_ELIM_MAX_CELLS = 16384", fn, arena_cells + out_cells);
+    if (rows_per_group < 0 || rows_per_group > 64) return failf(12, "%s: rows_per_group must be in [0, 64]", fn);
+    return 0;
+}
+
+extern "C" size_t dvs_bn_expected_counts_workspace_bytes(int64_t n_cells, int32_t n_vars, int64_t n_rows) {
+    if (bn_inc_dims("dvs_bn_expected_counts_workspace_bytes", n_cells, n_vars, n_rows, true)) return 0;
+    return dvs_bn_inc_layout(n_cells, n_vars, n_rows, false).total;
+}
+
+extern "C" size_t dvs_bn_impute_workspace_bytes(int32_t n_vars, int64_t n_rows) {
+    // no n_cells here: n_vars stands in its place, the least value bn_inc_dims accepts, so only n_vars and n_rows are judged
+    if (bn_inc_dims("dvs_bn_impute_workspace_bytes", n_vars, n_vars, n_rows, false)) return 0;
+    return dvs_bn_inc_layout(0, n_vars, n_rows, true).total;
+}
+
+static void bn_inc_fill(BnIncArgs& a, int n_vars, int n_plans, int64_t n_rows, const uint8_t* card, const uint64_t* parents,
+                        const int64_t* offsets, const double* cpt, int64_t n_cells, const int32_t* plans, size_t plans_bytes,
+                        const int64_t* plan_offsets, int plan_words, int arena_cells, int out_cells, int step_cells,
+                        int rows_per_group, int32_t* plan_flags, int32_t* status) {
+    a.e.n = n_vars;
+    a.e.P = n_plans;
+    a.e.plan_words = plan_words;
+    a.e.arena_cells = arena_cells;
+    a.e.step_cells = step_cells;
+    a.e.rows_per_group = rows_per_group;
+    a.e.out_stride = out_cells;
+    a.e.rows = n_rows;
+    a.e.n_cells = n_cells;
+    a.e.plans_words = (long long)(plans_bytes / 4);
+    a.e.card = card;
+    a.e.parents = parents;
+    a.e.offsets = (const long long*)offsets;
+    a.e.cpt = cpt;
+    a.e.plans = plans;
+    a.e.plan_offsets = (const long long*)plan_offsets;
+    a.e.plan_flags = plan_flags;
+    a.e.status = status;
+    a.chunks = (int)((n_rows + 255) / 256);
+}
+
+extern "C" int dvs_bn_expected_counts(int32_t n_vars, int64_t n_rows, const uint8_t* card, const uint64_t* parents,
+                                      const int64_t* offsets, const double* cpt, int64_t n_cells, const int32_t* plans,
+                                      size_t plans_bytes, const int64_t* plan_offsets, int32_t plan_words, int32_t arena_cells,
+                                      int32_t out_cells, int32_t step_cells, const uint64_t* data, const uint64_t* observed,
+                                      int32_t rows_per_group, double* counts, double* row_z, double* loglik, int64_t* skipped,
+                                      int32_t* plan_flags, void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_bn_expected_counts";
+    if (int e = bn_inc_dims(fn, n_cells, n_vars, n_rows, true)) return e;
+    if (int e = bn_inc_plans(fn, plan_words, arena_cells, out_cells, step_cells, rows_per_group, false)) return e;
+    if (!card || !parents || !offsets || !cpt || !plans || !plan_offsets || !data || !observed || !counts || !row_z || !loglik ||
+        !skipped || !plan_flags || !workspace || !status)
+        return fail(10, "dvs_bn_expected_counts: null pointer");
+    const size_t words = (size_t)(n_vars + 1) * 28;
+    if (plans_bytes < words) return fail_size("dvs_bn_expected_counts: plans_bytes < (n_vars + 1) * 28", words);
+    const BnIncLayout l = dvs_bn_inc_layout(n_cells, n_vars, n_rows, false);
+    if (workspace_bytes < l.total)
+        return fail_size("dvs_bn_expected_counts: workspace_bytes < dvs_bn_expected_counts_workspace_bytes", l.total);
+    BnIncArgs a = {};
+    bn_inc_fill(a, n_vars, n_vars + 1, n_rows, card, parents, offsets, cpt, n_cells, plans, plans_bytes, plan_offsets, plan_words,
+                arena_cells, out_cells, step_cells, rows_per_group, plan_flags, status);
+    a.data = data;
+    a.observed = observed;
+    a.counts = counts;
+    a.row_z = row_z;
+    a.loglik = loglik;
+    a.skipped = (long long*)skipped;
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.icounts = (int*)((char*)workspace + l.icounts);
+    a.ll_partials = (double*)((char*)workspace + l.ll);
+    a.skip_partials = (int*)((char*)workspace + l.skip);
+    a.row_ok = (unsigned char*)workspace + l.row_ok;
+    call_begin();
+    dvs_launch_bn_expected_counts(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_expected_counts");
+}
+
+extern "C" int dvs_bn_fit_counts(int32_t n_vars, const uint8_t* card, const uint64_t* parents, const int64_t* offsets,
+                                 const double* counts, int64_t n_cells, int32_t method, double iss, int32_t unobserved,
+                                 double* cpt_out, int32_t* status, void* stream) {
+    if (int e = bn_sample_dims("dvs_bn_fit_counts", n_cells, n_vars)) return e;
+    if (method != DVS_FIT_MLE && method != DVS_FIT_BAYES) return fail(12, "dvs_bn_fit_counts: method is not a dvs_fit_method");
+    if (method == DVS_FIT_BAYES && !(iss > 0.0 && isfinite(iss))) return fail(13, "dvs_bn_fit_counts: iss must be finite and > 0");
+    if (unobserved != 0 && unobserved != 1) return fail(12, "dvs_bn_fit_counts: unobserved must be 0 (NaN) or 1 (uniform)");
+    if (!card || !parents || !offsets || !counts || !cpt_out || !status) return fail(10, "dvs_bn_fit_counts: null pointer");
+    BnFitCountsArgs a = {};
+    a.n = n_vars;
+    a.method = method;
+    a.unobserved = unobserved;
+    a.n_cells = n_cells;
+    a.iss = iss;
+    a.card = card;
+    a.parents = parents;
+    a.offsets = (const long long*)offsets;
+    a.counts = counts;
+    a.cpt = cpt_out;
+    a.status = status;
+    call_begin();
+    dvs_launch_bn_fit_counts(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_fit_counts");
+}
+
+extern "C" int dvs_bn_impute(int32_t n_vars, int64_t n_rows, const uint8_t* card, const uint64_t* parents, const int64_t* offsets,
+                             const double* cpt, int64_t n_cells, const int32_t* plans, size_t plans_bytes,
+                             const int64_t* plan_offsets, int32_t plan_words, int32_t arena_cells, int32_t step_cells,
+                             const uint64_t* data, const uint64_t* observed, int32_t rows_per_group, uint64_t* data_out,
+                             uint64_t* observed_out, int32_t* plan_flags, void* workspace, size_t workspace_bytes, int32_t* status,
+                             void* stream) {
+    const char* fn = "dvs_bn_impute";
+    if (int e = bn_inc_dims(fn, n_cells, n_vars, n_rows, false)) return e;
+    if (int e = bn_inc_plans(fn, plan_words, arena_cells, 16, step_cells, rows_per_group, true)) return e;
+    if (!card || !parents || !offsets || !cpt || !plans || !plan_offsets || !data || !observed || !data_out || !observed_out ||
+        !plan_flags || !workspace || !status)
+        return fail(10, "dvs_bn_impute: null pointer");
+    const size_t words = (size_t)n_vars * 28;
+    if (plans_bytes < words) return fail_size("dvs_bn_impute: plans_bytes < n_vars * 28", words);
+    const BnIncLayout l = dvs_bn_inc_layout(0, n_vars, n_rows, true);
+    if (workspace_bytes < l.total) return fail_size("dvs_bn_impute: workspace_bytes < dvs_bn_impute_workspace_bytes", l.total);
+    BnIncArgs a = {};
+    bn_inc_fill(a, n_vars, n_vars, n_rows, card, parents, offsets, cpt, n_cells, plans, plans_bytes, plan_offsets, plan_words,
+                arena_cells, 16, step_cells, rows_per_group, plan_flags, status);
+    a.data = data;
+    a.observed = observed;
+    a.levels = (unsigned char*)workspace + l.levels;
+    a.data_out = data_out;
+    a.observed_out = observed_out;
+    call_begin();
+    dvs_launch_bn_impute(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_impute");
+}
+
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 static int exact_dims(const char* fn, int batch, int n_vars) {
     if (batch <= 0) return failf(2, "%s: batch must be > 0", fn);

@@ -13,6 +13,8 @@
 //                     barrier separates steps.  The tables are read from global memory through the cache (a copy in LDS
 //                     measured no faster on asia and 42 % slower on a 48-variable network).  z is the fixed
 //                     tree over the cells of the last step, BN_ELIM_ZBATCH rows per pass.
+//   bn_elim_family_ok, bn_elim_plan_ok, bn_elim_steps   the family check, the word walk and the step executor as device functions:
+//                     dvs_incomplete.h builds its kernels on the same three.
 #pragma once
 #include "dvs_infer.h"
 
@@ -86,12 +88,10 @@ __device__ inline bool bn_elim_plan_ok(const BnElimArgs& a, const int p, const l
     return cur == len;
 }
 
-__global__ __launch_bounds__(256) void k_bn_elim_check(BnElimArgs a) {
-    __shared__ int s_ok;
-    __shared__ long long s_size[48];
-    const int tid = threadIdx.x, n = a.n, p = blockIdx.x;
-    if (tid == 0) s_ok = 1;
-    __syncthreads();
+// the network's families, one lane each (as k_bn_blanket checks them): a family that fails clears *s_ok; size[v] = the cells of
+// variable v's table.  The caller sets *s_ok and puts a barrier on either side.
+__device__ __forceinline__ void bn_elim_family_ok(const BnElimArgs& a, const int tid, long long* size, int* s_ok) {
+    const int n = a.n;
     if (tid < n) {
         const long long lo = a.offsets[tid], hi = a.offsets[tid + 1], r = a.card[tid], first = a.offsets[0];
         const uint64_t pm = a.parents[tid] & ~(1ull << tid);
@@ -101,14 +101,73 @@ __global__ __launch_bounds__(256) void k_bn_elim_check(BnElimArgs a) {
             q *= a.card[dvs_ctz64(m)];
             ok = q * r <= 0x7fffffffLL;
         }
-        if (!ok || hi - lo != q * r) s_ok = 0;
-        s_size[tid] = hi - lo;
+        if (!ok || hi - lo != q * r) *s_ok = 0;
+        size[tid] = hi - lo;
     }
+}
+
+__global__ __launch_bounds__(256) void k_bn_elim_check(BnElimArgs a) {
+    __shared__ int s_ok;
+    __shared__ long long s_size[48];
+    const int tid = threadIdx.x, p = blockIdx.x;
+    if (tid == 0) s_ok = 1;
+    __syncthreads();
+    bn_elim_family_ok(a, tid, s_size, &s_ok);
     __syncthreads();
     if (tid == 0) {
         const bool ok = s_ok != 0 && bn_elim_plan_ok(a, p, s_size);
         a.plan_flags[p] = ok ? 0 : 1;
         if (!ok) atomicOr(a.status, 16);
+    }
+}
+
+// The step executor, shared with dvs_incomplete.h: every thread of the 256-thread workgroup calls it with the plan's checked
+// words `w` (in LDS) and their step count, `rows` rows whose arenas lie `arena_cells` apart behind `arena`, their level masks [rows][n] and the
+// staged level counts and table bases.  The last step writes row r's cells to out[r * out_stride + c]: global memory for
+// k_bn_eliminate, LDS for the kernels of dvs_incomplete.h.  It ends with the barrier behind the last step.
+__device__ __forceinline__ void bn_elim_steps(const int* w, const int steps, const int rows, const int arena_cells, double* arena, const uint16_t* masks,
+                                              const int n, const unsigned char* s_card, const long long* s_base, const double* cpt,
+                                              double* out, const int out_stride, const int tid) {
+    int cur = 6 + w[5];
+    for (int s = 0; s < steps; ++s) {
+        const int x = w[cur], off = w[cur + 1], cells = w[cur + 2], ns = w[cur + 3], ni = w[cur + 4], width = 4 + ns;
+        const int* sc = w + cur + 5;
+        const int* in0 = sc + ns;
+        const int cx = x >= 0 ? s_card[x] : 1;
+        for (int idx = tid; idx < rows * cells; idx += 256) {
+            const int r = idx / cells, c = idx - r * cells;
+            const uint16_t* m = masks + (size_t)r * n;
+            const double* mine = arena + (size_t)r * arena_cells;
+            uint64_t lv = 0ull;                              // the cell's levels, 4 bits per scope variable
+            bool allowed = true;
+            for (int i = 0, rem = c; i < ns; ++i) {
+                const int cd = s_card[sc[i]], l = rem % cd;
+                rem /= cd;
+                lv |= (uint64_t)l << (4 * i);
+                if (x < 0 && !((m[sc[i]] >> l) & 1)) allowed = false;      // the last step: a kept level the row does not allow
+            }
+            const unsigned mx = x >= 0 ? m[x] : 1u;
+            double acc = 0.0;
+            {
+#pragma clang fp contract(off)
+                for (int k = 0; k < cx && allowed; ++k) {
+                    if (!((mx >> k) & 1u)) continue;
+                    double pr = 0.0;
+                    for (int j = 0; j < ni; ++j) {
+                        const int* in = in0 + j * width;
+                        int at = k * in[3];
+                        for (int i = 0; i < ns; ++i) at += (int)((lv >> (4 * i)) & 15ull) * in[4 + i];
+                        const double val = in[0] >= 0 ? cpt[s_base[in[0]] + at] : mine[in[1] + at];
+                        pr = j == 0 ? val : pr * val;
+                    }
+                    acc += pr;
+                }
+            }
+            if (x >= 0) arena[(size_t)r * arena_cells + off + c] = acc;
+            else out[(size_t)r * out_stride + c] = acc;
+        }
+        cur += 5 + ns + ni * width;
+        __syncthreads();
     }
 }
 
@@ -141,48 +200,7 @@ __global__ __launch_bounds__(256) void k_bn_eliminate(BnElimArgs a) {
     }
     __syncthreads();
     const int steps = w[2], outc = w[4];
-    const uint16_t* masks = a.masks + (size_t)row0 * n;
-    int cur = 6 + w[5];
-    for (int s = 0; s < steps; ++s) {
-        const int x = w[cur], off = w[cur + 1], cells = w[cur + 2], ns = w[cur + 3], ni = w[cur + 4], width = 4 + ns;
-        const int* sc = w + cur + 5;
-        const int* in0 = sc + ns;
-        const int cx = x >= 0 ? s_card[x] : 1;
-        for (int idx = tid; idx < rows * cells; idx += 256) {
-            const int r = idx / cells, c = idx - r * cells;
-            const uint16_t* m = masks + (size_t)r * n;
-            const double* mine = arena + (size_t)r * a.arena_cells;
-            uint64_t lv = 0ull;                              // the cell's levels, 4 bits per scope variable
-            bool allowed = true;
-            for (int i = 0, rem = c; i < ns; ++i) {
-                const int cd = s_card[sc[i]], l = rem % cd;
-                rem /= cd;
-                lv |= (uint64_t)l << (4 * i);
-                if (x < 0 && !((m[sc[i]] >> l) & 1)) allowed = false;      // the last step: a kept level the row does not allow
-            }
-            const unsigned mx = x >= 0 ? m[x] : 1u;
-            double acc = 0.0;
-            {
-#pragma clang fp contract(off)
-                for (int k = 0; k < cx && allowed; ++k) {
-                    if (!((mx >> k) & 1u)) continue;
-                    double pr = 0.0;
-                    for (int j = 0; j < ni; ++j) {
-                        const int* in = in0 + j * width;
-                        int at = k * in[3];
-                        for (int i = 0; i < ns; ++i) at += (int)((lv >> (4 * i)) & 15ull) * in[4 + i];
-                        const double val = in[0] >= 0 ? a.cpt[s_base[in[0]] + at] : mine[in[1] + at];
-                        pr = j == 0 ? val : pr * val;
-                    }
-                    acc += pr;
-                }
-            }
-            if (x >= 0) arena[(size_t)r * a.arena_cells + off + c] = acc;
-            else out[(size_t)r * a.out_stride + c] = acc;
-        }
-        cur += 5 + ns + ni * width;
-        __syncthreads();
-    }
+    bn_elim_steps(w, steps, rows, a.arena_cells, arena, a.masks + (size_t)row0 * n, n, s_card, s_base, a.cpt, out, a.out_stride, tid);
     const int pad = a.out_stride - outc;                     // the cells behind the last step's: +0
     for (int idx = tid; idx < rows * pad; idx += 256) {
         const int r = idx / pad;

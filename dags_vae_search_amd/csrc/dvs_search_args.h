@@ -2,13 +2,14 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
 #pragma once
 #include "dvs_kernels.h"
 #include "../../include/dvs_eliminate.h"
+#include "../../include/dvs_incomplete.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -348,6 +349,63 @@ struct BnElimArgs {
     int* status;
 };
 void dvs_launch_bn_eliminate(const BnElimArgs& a, dvs_stream_t st);
+
+// ---- incomplete data: expected counts, tables from counts, exact imputation (dvs_incomplete.h; include/dvs_incomplete.h) ----
+// The workspace of dvs_bn_expected_counts: the chunk partials f64 [chunks][n_cells], the integer counts i32 [n_cells], the
+// chunks' log-likelihood partials f64 [chunks] and skipped rows i32 [chunks], the rows' ok flags u8 [n_rows]; the workspace of
+// dvs_bn_impute: the levels u8 [n_rows][n_vars] and nothing else.  Each array starts at a multiple of 256 bytes.
+struct BnIncLayout {
+    size_t partials, icounts, ll, skip, row_ok, levels, total, chunks;
+};
+inline BnIncLayout dvs_bn_inc_layout(long long n_cells, int n_vars, long long rows, bool impute) {
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    BnIncLayout l = {};
+    l.chunks = (size_t)((rows + 255) / 256);
+    if (impute) {
+        l.total = up((size_t)rows * n_vars);
+        return l;
+    }
+    l.icounts = up(l.chunks * (size_t)n_cells * 8);
+    l.ll = l.icounts + up((size_t)n_cells * 4);
+    l.skip = l.ll + up(l.chunks * 8);
+    l.row_ok = l.skip + up(l.chunks * 4);
+    l.total = l.row_ok + up((size_t)rows);
+    return l;
+}
+struct BnIncArgs {
+    BnElimArgs e;                // the network, the plans and their limits; e.out_stride = out_cells, e.masks / e.out / e.z unused;
+                                 // e.G: launcher (rows per group); e.P = n + 1 (expected counts) or n (impute)
+    int words, chunks, impute;   // words: launcher
+    const uint64_t* data;        // [rows][words]
+    const uint64_t* observed;    // [rows]
+    double* counts;              // [n_cells]
+    double* row_z;               // [rows]
+    double* loglik;              // [1]
+    long long* skipped;          // [1]
+    double* partials;            // workspace [chunks][n_cells]
+    int* icounts;                // workspace [n_cells]
+    double* ll_partials;         // workspace [chunks]
+    int* skip_partials;          // workspace [chunks]
+    unsigned char* row_ok;       // workspace [rows]
+    unsigned char* levels;       // impute workspace [rows][n]: the level, or 255 for "stays missing"
+    uint64_t* data_out;          // impute [rows][words]
+    uint64_t* observed_out;      // impute [rows]
+};
+void dvs_launch_bn_expected_counts(const BnIncArgs& a, dvs_stream_t st);
+void dvs_launch_bn_impute(const BnIncArgs& a, dvs_stream_t st);
+
+struct BnFitCountsArgs {
+    int n, method, unobserved;
+    long long n_cells;
+    double iss;
+    const uint8_t* card;         // [n]
+    const uint64_t* parents;     // [n]
+    const long long* offsets;    // [n + 1]
+    const double* counts;        // [n_cells]: the cell of offsets[v] + i is counts[offsets[v] - offsets[0] + i]
+    double* cpt;                 // [n_cells], indexed as counts
+    int* status;
+};
+void dvs_launch_bn_fit_counts(const BnFitCountsArgs& a, dvs_stream_t st);
 
 // ---- exact search (dvs_exact.h) --------------------------------------------------------------------------------------
 // The workspace of dvs_exact_search (include/dvs.h): four arrays, each starting at a multiple of 256 bytes.

@@ -262,6 +262,7 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
 #include "dvs_params.h"
 #include "dvs_infer.h"
 #include "dvs_eliminate.h"
+#include "dvs_incomplete.h"
 #include "dvs_exact.h"
 #include "dvs_posterior.h"
 #include "dvs_ordermc.h"
