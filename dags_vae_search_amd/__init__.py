@@ -9,7 +9,7 @@ from .pace import PaceVaeV3  # noqa: F401
 from .train import batch_test, load_model_state, model_test, train_batch, train_model  # noqa: F401
 from . import optim  # noqa: F401
 from .records import CompactBatch, CompactDagDataset, encode_graphs  # noqa: F401
-from .bic import BNLearnWrapper  # noqa: F401
+from .bic import AvailableCaseEvaluator, BNLearnWrapper  # noqa: F401
 from .predictor_data import create_predictor_dataset, generate_predictor_graphs_batch, prepare_predictor_data  # noqa: F401
 from .datasets import LabeledDagDatasetInMemory, LabeledDagDatasetInMemoryTest  # noqa: F401
 from .search import (SearchResult, StructureSet, decoded_structures, generation_metrics, latent_bo_search,  # noqa: F401
@@ -31,7 +31,7 @@ from .ordermc import FamilyScores, OrderMCMCResult, family_scores, order_mcmc  #
 from .infer import cpdist, cpquery, posterior, predict  # noqa: F401
 from .eliminate import (EliminationPlan, elimination_plan, evidence_probability, exact_cpquery, exact_joint,  # noqa: F401
                         exact_posterior)
-from .incomplete import (EMResult, ExpectedCounts, em_fit, expected_counts, family_plans, fit_counts, impute,  # noqa: F401
-                         incomplete_rows, target_plans)
+from .incomplete import (EMResult, ExpectedCounts, StructuralEMResult, available_case_evaluator, em_fit,  # noqa: F401
+                         expected_counts, family_plans, fit_counts, impute, incomplete_rows, structural_em, target_plans)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

@@ -19,6 +19,7 @@ LIB_NAME = "libdvs_hip.so"
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs.h")
 EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_eliminate.h")   # the companion header: dvs_bn_eliminate
 INC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_incomplete.h")  # the second: expected counts, fit_counts, impute
+AVAIL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_available.h")  # the third: available-case scoring (nal / pnal)
 
 
 class DvsShape(Structure):
@@ -87,6 +88,8 @@ EXPORTS = list(SIGNATURES)
 EXT_SIGNATURES, _X = _read_header(EXT_HEADER)
 # include/dvs_incomplete.h, the second companion: learning from incomplete data; EXT_SIGNATURES stays the one entry it has
 INC_SIGNATURES, _ = _read_header(INC_HEADER)
+# include/dvs_available.h, the third: the available-case scorer and its toggle pass; the three tables above stay what they are
+AVAIL_SIGNATURES, _ = _read_header(AVAIL_HEADER)
 
 
 def signature(fn: str):
@@ -97,7 +100,10 @@ def signature(fn: str):
         return EXT_SIGNATURES[fn]
     if fn in INC_SIGNATURES:
         return INC_SIGNATURES[fn]
-    raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h and include/dvs_incomplete.h")
+    if fn in AVAIL_SIGNATURES:
+        return AVAIL_SIGNATURES[fn]
+    raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h and "
+                   f"include/dvs_available.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -128,6 +134,7 @@ STATUS_REFUSED = 16           # bit 4: a family, test, row or query was refused 
 STATUS_LABELS = 32            # bit 5 (dvs_bic_parent_masks): a DAG's labels are not a permutation of 0..n_vars-1
 STATUS_NOT_PROBABILITY = 64   # bit 6 (dvs_bn_sample, dvs_bn_lw): a table row is not a probability vector
 LW_STATUS_ZERO_WEIGHT = 128   # dvs_bn_lw status bit 7: a query whose weights sum to zero (information, not an error)
+STATUS_NO_ROWS = 128          # dvs_bn_scores_avail status bit 7: a family that no row observes whole (-inf; information as well)
 SCORE_TYPES = _by_bnlearn_name("DVS_SCORE_", ("loglik", "aic", "bic", "bde", "bds", "k2", "bdj"))   # dvs_score_type
 # dvs_bn_eliminate (include/dvs_eliminate.h): the arena and table cap in fp64 cells, the plan words' tag and limits
 ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
@@ -136,7 +143,7 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
-    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items()):
+    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

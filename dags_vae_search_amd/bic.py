@@ -40,17 +40,34 @@ PENALISED_SCORES = ("aic", "bic")        # take k
 DIRICHLET_SCORES = ("bde", "bds")        # take iss
 
 
-class _Scorer:
-    """The scorer launches of both evaluators.  ``_source(B)`` names the evaluator that holds the data set and the
-    arguments that follow ``status``: none (dvs_bic_scores / dvs_bn_scores, dvs_bn_toggle_scores) or the row sets of the
-    ``_rows`` entry points, which take the same arguments up to there (include/dvs.h)."""
+class _AvailableCase:
+    """what ``AvailableCaseEvaluator._source`` names instead of row sets: the observed words and k of the ``_avail`` entry points"""
 
-    def launch_scores(self, parents, scratch, out, status):
+    def __init__(self, observed, k):
+        self.observed, self.k = observed, float(k)
+
+
+class _Scorer:
+    """The scorer launches of the evaluators.  ``_source(B)`` names the evaluator that holds the data set and the
+    arguments that follow ``status``: none (dvs_bic_scores / dvs_bn_scores, dvs_bn_toggle_scores), the row sets of the
+    ``_rows`` entry points, which take the same arguments up to there (include/dvs.h), or an ``_AvailableCase`` for the
+    ``_avail`` entry points (include/dvs_available.h)."""
+
+    def launch_scores(self, parents, scratch, out, status, used=None):
         """The scorer on the caller's buffers, unchecked: ``parents`` int64 [B, n_vars] contiguous on the device ->
         ``scratch`` f64 [B, n_vars] (the local scores), ``out`` f64 [B], ``status`` int32 [1] (bit 4: a family was refused).
-        The default-penalty bic of a plain evaluator is dvs_bic_scores; everything else dvs_bn_scores."""
+        The default-penalty bic of a plain evaluator is dvs_bic_scores; everything else dvs_bn_scores.  An available-case
+        view (dvs_bn_scores_avail) also fills ``used`` int32 [B, n_vars], the rows that counted per family."""
         base, row_args = self._source(parents.shape[0])
         p = dl.ptr
+        if isinstance(row_args, _AvailableCase):
+            name = "dvs_bn_scores_avail"
+            dl.check(self.lib, self.lib.dvs_bn_scores_avail(
+                parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(row_args.observed), p(base.card), p(parents),
+                row_args.k, p(scratch), p(out), p(used), p(status), dl.stream()), name)
+            return
+        if used is not None:
+            raise ValueError("used= is what an available-case view counts (BNLearnWrapper.available_case)")
         head = (parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(base.card), p(parents))
         tail = (p(scratch), p(out), p(status), *row_args, dl.stream())
         if self.metric_name == "bic" and self.k is None and not row_args:
@@ -92,6 +109,12 @@ class _Scorer:
         L, T = out
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         p = dl.ptr
+        if isinstance(row_args, _AvailableCase):
+            name = "dvs_bn_toggle_scores_avail"
+            dl.check(self.lib, self.lib.dvs_bn_toggle_scores_avail(
+                B, n, base.n_samples, p(base.packed), p(row_args.observed), p(base.card), p(parents), row_args.k, p(worklist),
+                p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()), name)
+            return (L, T, status) if return_status else (L, T)
         name = "dvs_bn_toggle_scores_rows" if row_args else "dvs_bn_toggle_scores"
         dl.check(self.lib, getattr(self.lib, name)(
             B, n, base.n_samples, p(base.packed), p(base.card), p(parents), dl.SCORE_TYPES[self.metric_name], base.score_arg,
@@ -217,6 +240,14 @@ class BNLearnWrapper(_Scorer):
         ``tabu_search`` take to climb one bootstrap replicate per structure (strength.py)."""
         return RowSetEvaluator(self, rows, set_of)
 
+    def available_case(self, observed: torch.Tensor, metric: str = "pnal", k=None) -> "AvailableCaseEvaluator":
+        """A view of this evaluator's rows as incomplete data (dvs_bn_scores_avail / dvs_bn_toggle_scores_avail, DESIGN.md
+        §26): ``observed`` int64 [n_samples] on the device, bit v set where variable v is observed in that row (what
+        ``incomplete_rows`` returns next to the rows).  ``metric``: ``"nal"``, the node-average likelihood, or ``"pnal"``
+        with the penalty coefficient ``k`` (default ``n_samples ** -0.25``).  This evaluator's own score type plays no part.
+        What ``hill_climb`` and ``tabu_search`` take to learn a structure without dropping incomplete rows."""
+        return AvailableCaseEvaluator(self, observed, metric, k)
+
     def score(self, labeled_graph, label_key: str = LABEL_KEY) -> float:
         return self.score_batch([labeled_graph], label_key)[0]
 
@@ -257,3 +288,57 @@ class RowSetEvaluator(_Scorer):
         elif self.set_of.numel() != B:
             raise ValueError(f"{B} structures but set_of names {self.set_of.numel()}")
         return self.base, (dl.ptr(self.rows), self.n_samples, self.n_sets, dl.ptr(self.set_of))
+
+
+AVAILABLE_CASE_SCORES = ("nal", "pnal")
+
+
+class AvailableCaseEvaluator(_Scorer):
+    """``BNLearnWrapper.available_case``: the base evaluator's rows, level counts and device, each family scored on exactly
+    the rows that observe it whole: local = LL / m - k (r - 1) q (include/dvs_available.h).  ``nal`` is k = 0; the default k of
+    ``pnal``, ``n_samples ** -0.25``, is computed here and is the alpha = 1/4 of Bodewes and Scutari (2021) as recalled: parity
+    with bnlearn's ``nal`` / ``pnal`` is unpinned against an R run.  A family that no row observes whole scores -inf (status
+    bit 7, which does not raise); a refused family raises as it does for the plain evaluator.  ``observed`` is checked here,
+    once."""
+
+    def __init__(self, base: BNLearnWrapper, observed, metric="pnal", k=None):
+        if metric not in AVAILABLE_CASE_SCORES:
+            raise NotImplementedError(f"available-case scores: {', '.join(AVAILABLE_CASE_SCORES)} (got {metric!r})")
+        if k is not None and metric != "pnal":
+            raise ValueError(f"k is the argument of pnal, not of {metric!r}")
+        if k is not None and not (math.isfinite(k) and k >= 0):
+            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
+        self.base = base
+        self.lib, self.device, self.n_vars, self.n_samples = base.lib, base.device, base.n_vars, base.n_samples
+        self.card, self.card_host = base.card, base.card_host       # no ``packed``: what reads rows off an evaluator must not take these as complete
+        self.dataset_name, self.metric_name, self.iss, self.k = base.dataset_name, metric, None, k
+        self.penalty = 0.0 if metric == "nal" else float(base.n_samples) ** -0.25 if k is None else float(k)
+        if not torch.is_tensor(observed) or observed.dtype != torch.int64 or observed.shape != (base.n_samples,):
+            raise ValueError(f"observed must be an int64 tensor [{base.n_samples}]: bit v set where variable v is observed")
+        dl.require_cuda(observed, "observed")
+        self.observed = observed.to(self.device).contiguous()
+        seen = int(np.bitwise_or.reduce(self.observed.cpu().numpy().view(np.uint64)))
+        never = [v for v in range(self.n_vars) if not (seen >> v) & 1]
+        if never:
+            raise ValueError(f"available_case: no row observes variable(s) {never}: nothing could score them")
+
+    def _source(self, B):
+        return self.base, _AvailableCase(self.observed, self.penalty)
+
+    def compact_parent_masks(self, batch) -> torch.Tensor:
+        return self.base.compact_parent_masks(batch)
+
+    def used(self, parents: torch.Tensor) -> torch.Tensor:
+        """the rows that count for every family of ``parents`` (int64 [B, n_vars]) -> int32 [B, n_vars]; 0 where no row does
+        and where the family is refused"""
+        parents = parents.to(self.device).contiguous()
+        B = parents.shape[0]
+        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        used = torch.empty(B, self.n_vars, dtype=torch.int32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.launch_scores(parents, scratch, out, status, used=used)
+        return used
+
+    def with_rows(self, rows, set_of=None):
+        raise NotImplementedError("row sets over an available-case view (bootstrap on incomplete data) are not built")

@@ -1154,6 +1154,50 @@ extern "C" int dvs_bn_toggle_scores_rows(int32_t batch, int32_t n_vars, int32_t 
     return call_end("dvs_bn_toggle_scores_rows");
 }
 
+// ---- available-case scoring on incomplete data (dvs_available.h; include/dvs_available.h) ------------------------------
+// k of the two *_avail entry points, checked where the plain ones check score_arg; the block then holds loglik with arg = k
+static int avail_args(const char* fn, BicArgs& a, int batch, int n_vars, int n_samples, const uint64_t* data, const uint8_t* card,
+                      const uint64_t* parents, double k, double* local, double* out, int32_t* status) {
+    if (!(k >= 0.0 && isfinite(k))) return failf(13, "%s: k must be finite and >= 0", fn);
+    if (int e = scorer_args(fn, a, batch, n_vars, n_samples, data, card, parents, DVS_SCORE_LOGLIK, __builtin_nan(""), local, out, status))
+        return e;
+    a.arg = k;
+    return 0;
+}
+
+extern "C" int dvs_bn_scores_avail(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint64_t* observed,
+                                   const uint8_t* card, const uint64_t* parents, double k, double* local, double* out,
+                                   int32_t* used, int32_t* status, void* stream) {
+    const char* fn = "dvs_bn_scores_avail";
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, false, !data || !observed || !card || !parents || !local || !out || !status))
+        return e;
+    BicAvailArgs a = {};
+    if (int e = avail_args(fn, a.s, batch, n_vars, n_samples, data, card, parents, k, local, out, status)) return e;
+    a.observed = observed;
+    a.used = used;
+    call_begin();
+    dvs_launch_bn_avail(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_scores_avail");
+}
+
+extern "C" int dvs_bn_toggle_scores_avail(int32_t batch, int32_t n_vars, int32_t n_samples, const uint64_t* data,
+                                          const uint64_t* observed, const uint8_t* card, const uint64_t* parents, double k,
+                                          const int32_t* worklist, double* local, size_t local_bytes, double* toggles,
+                                          size_t toggles_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_bn_toggle_scores_avail";
+    if (int e = scorer_check(fn, batch, n_vars, n_samples, true, !data || !observed || !card || !parents || !local || !toggles || !status))
+        return e;
+    ToggleAvailArgs a = {};
+    if (int e = avail_args(fn, a.t.s, batch, n_vars, n_samples, data, card, parents, k, local, nullptr, status)) return e;
+    if (int e = toggle_buffers({fn, batch, n_vars}, local_bytes, toggles_bytes)) return e;
+    a.observed = observed;
+    a.t.worklist = worklist;
+    a.t.toggles = toggles;
+    call_begin();
+    dvs_launch_bn_toggle_avail(a, (dvs_stream_t)stream);
+    return call_end("dvs_bn_toggle_scores_avail");
+}
+
 extern "C" int dvs_bootstrap_rows(int32_t n_sets, int32_t set_size, int32_t n_samples, uint64_t seed, int64_t set_offset,
                                   int32_t* rows, void* stream) {
     if (n_sets <= 0) return fail(2, "dvs_bootstrap_rows: n_sets must be > 0");

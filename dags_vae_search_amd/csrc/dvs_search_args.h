@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -10,6 +10,7 @@
 #include "dvs_kernels.h"
 #include "../../include/dvs_eliminate.h"
 #include "../../include/dvs_incomplete.h"
+#include "../../include/dvs_available.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -536,6 +537,20 @@ struct ToggleRowsArgs {
     RowSetArgs r;
 };
 void dvs_launch_bn_toggle_rows(const ToggleRowsArgs& a, dvs_stream_t st);
+
+// ---- available-case scoring on incomplete data (dvs_available.h; include/dvs_available.h) -----------------------------------
+// Beside BicArgs / ToggleArgs, as the row sets are.  s.type is DVS_SCORE_LOGLIK and s.arg the penalty coefficient k.
+struct BicAvailArgs {
+    BicArgs s;
+    const uint64_t* observed;    // [S]: bit v set <=> variable v is observed in that row
+    int* used;                   // null or [B][n]: the rows that counted for the family
+};
+void dvs_launch_bn_avail(const BicAvailArgs& a, dvs_stream_t st);
+struct ToggleAvailArgs {
+    ToggleArgs t;
+    const uint64_t* observed;    // [S]
+};
+void dvs_launch_bn_toggle_avail(const ToggleAvailArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

@@ -267,6 +267,7 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
 #include "dvs_posterior.h"
 #include "dvs_ordermc.h"
 #include "dvs_strength.h"
+#include "dvs_available.h"
 
 void dvs_launch_bic(const BicArgs& in, dvs_stream_t st) {
     BicArgs a = in;

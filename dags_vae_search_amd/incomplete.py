@@ -11,6 +11,10 @@ with P(observed part) of every row and the log-likelihood of the incomplete data
 of ``bn_fit`` on such counts.  ``em_fit`` alternates them.  ``impute`` fills every missing value with the most probable level
 given the row's observed values (ties to the lowest level; bnlearn breaks them at random).
 
+Structure learning on the same data: ``available_case_evaluator`` wraps the pair in the available-case scorer
+(``BNLearnWrapper.available_case``: nal / pnal, which ``hill_climb`` and ``tabu_search`` take as they are), and
+``structural_em`` is bnlearn's ``structural.em``: impute, maximise the structure on the completed rows, fit, repeated.
+
 Everything is fp64 in the linear domain with stated summation orders: two runs give equal bytes.  The limits are those of
 ``elimination_plan``; here the arena and the family's cells share LDS, so ``arena_cells + out_cells`` must fit
 ``DVS_BN_ELIM_MAX_CELLS``.  Parity with bnlearn is unpinned against an R run.
@@ -18,6 +22,7 @@ Everything is fp64 in the linear domain with stated summation orders: two runs g
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import List, Optional
 
 import numpy as np
@@ -309,3 +314,99 @@ def impute(fitted: FittedBN, data, index: int = 0, *, plans=None):
             raise ValueError(f"{what}: a row has an observed level at or above its variable's level count or an observed bit at or "
                              f"above n_vars, a plan is malformed, or the tables do not match the structure")
     return out, seen
+
+
+def available_case_evaluator(data, card, metric: str = "pnal", k=None, name: str = "incomplete"):
+    """The ``(rows, observed)`` pair of ``incomplete_rows`` as an available-case evaluator (``AvailableCaseEvaluator``, bic.py):
+    every family is scored on exactly the rows that observe it whole.  ``metric`` "nal" or "pnal" with the penalty coefficient
+    ``k`` (default ``n_samples ** -0.25``; parity with bnlearn's pnal is unpinned against an R run).  ``hill_climb`` and
+    ``tabu_search`` take the result as they take any evaluator."""
+    from .bic import BNLearnWrapper
+    if not (isinstance(data, tuple) and len(data) == 2 and torch.is_tensor(data[0]) and torch.is_tensor(data[1])):
+        raise ValueError("available_case_evaluator: data must be (rows, observed) tensors, as incomplete_rows gives them")
+    return BNLearnWrapper.from_packed(name, "loglik", data[0], card).available_case(data[1], metric, k)
+
+
+@dataclass
+class StructuralEMResult:
+    parents: torch.Tensor          # int64 [n] on the device: the last iteration's parent masks
+    fitted: FittedBN               # its tables
+    iterations: int                # iterations done
+    converged: bool                # the last iteration's masks equal the one before's
+    trace: list                    # per iteration: dict(parents=[n ints], score, left_out, log_likelihood)
+
+
+def structural_em(data, card, *, start=None, maximize: str = "hc", maximize_args=None, score: str = "bic", score_args=None,
+                  fit: str = "bayes", iss=None, refit: str = "completed", max_iter: int = 5, max_parents: Optional[int] = 3) -> StructuralEMResult:
+    """bnlearn's ``structural.em`` as a composition of what the package has: from the empty graph (or the parent masks
+    ``start``), whose tables come from ``em_fit``, every iteration runs ``impute`` with the current network, builds
+    ``BNLearnWrapper.from_packed("completed", score, completed rows, card, **score_args)``, runs ``hill_climb`` (``maximize="hc"``) or
+    ``tabu_search`` ("tabu") from the current structure with ``max_parents`` and ``maximize_args`` (``max_steps`` defaults to
+    max(16, n^2)), and fits the new structure: ``bn_fit`` on the completed rows (``refit="completed"``, bnlearn's way) or
+    ``em_fit`` on the incomplete rows (``refit="em"``), with ``fit`` ("bayes" or "mle"; an unobserved configuration is uniform)
+    and ``iss``.  A row in which ``impute`` leaves a value missing is left out of that iteration's completed rows and counted.
+    It stops when the parent masks equal the previous iteration's (``converged``) or after ``max_iter`` iterations.
+
+    ``trace`` holds per iteration the parent masks, the search's score, the rows left out and the log-likelihood of the
+    incomplete data under the new network.  This is hard EM: none of them need be monotone.  The defaults ``max_iter=5``
+    (bnlearn's), ``fit="bayes"`` (no table zero leaves a value unimputable) and ``max_parents=3`` (the plans stay within the
+    16 384-cell cap) are unmeasured choices.  A structure whose plans exceed the cap raises the ValueError of ``check_cells``
+    with the iteration number (0: the start) in front."""
+    from .bic import BNLearnWrapper
+    from .hillclimb import hill_climb
+    from .params import bn_fit
+    from .tabu import tabu_search
+    what = "structural_em"
+    if maximize not in ("hc", "tabu"):
+        raise ValueError(f"{what}: maximize must be 'hc' or 'tabu' (got {maximize!r})")
+    if refit not in ("completed", "em"):
+        raise ValueError(f"{what}: refit must be 'completed' or 'em' (got {refit!r})")
+    if fit not in dl.FIT_METHODS:
+        raise ValueError(f"{what}: fit must be one of {sorted(dl.FIT_METHODS)} (got {fit!r})")
+    if int(max_iter) < 1:
+        raise ValueError(f"{what}: max_iter must be >= 1")
+    if not (isinstance(data, tuple) and len(data) == 2 and torch.is_tensor(data[0]) and torch.is_tensor(data[1])):
+        raise ValueError(f"{what}: data must be (rows, observed) tensors, as incomplete_rows gives them")
+    card = dl.level_counts(card)
+    n, dev = len(card), data[0].device
+    dl.need_cuda(what, dev)
+    if start is None:
+        current = [0] * n
+    else:
+        current = [int(m) & ~(1 << v) for v, m in enumerate(start.reshape(-1).tolist() if torch.is_tensor(start) else start)]
+        if len(current) != n:
+            raise ValueError(f"{what}: start must hold one parent row per variable ({n})")
+    search = hill_climb if maximize == "hc" else tabu_search
+    search_args = {"max_steps": max(16, n * n), **(maximize_args or {})}
+    full = (1 << n) - 1
+
+    def at_iteration(it, fn, *args, **kw):
+        try:
+            return fn(*args, **kw)
+        except ValueError as e:
+            raise ValueError(f"{what}: iteration {it}: {e}") from e
+
+    fitted = at_iteration(0, em_fit, current, card, data, method=fit, iss=iss).fitted
+    trace, converged = [], False
+    for it in range(1, int(max_iter) + 1):
+        rows, seen = at_iteration(it, impute, fitted, data)
+        whole = (seen & full) == full
+        left_out = int(whole.numel() - int(whole.sum()))
+        if left_out == whole.numel():
+            raise ValueError(f"{what}: iteration {it}: impute left a value missing in every row")
+        completed = rows[whole].contiguous() if left_out else rows
+        ev = BNLearnWrapper.from_packed("completed", score, completed, card, **(score_args or {}))
+        starts = torch.tensor([current], dtype=torch.int64, device=dev)
+        found = at_iteration(it, search, ev, starts, max_parents=max_parents, **search_args)
+        new = [int(m) for m in found.parents[0].tolist()]
+        if refit == "completed":
+            fitted = at_iteration(it, bn_fit, ev, found.parents[0], method=fit, iss=iss, unobserved="uniform")
+        else:
+            fitted = at_iteration(it, em_fit, new, card, data, method=fit, iss=iss).fitted
+        ll = float(at_iteration(it, expected_counts, fitted, data).log_likelihood.item())
+        trace.append(dict(parents=new, score=float(found.scores[0].item()), left_out=left_out, log_likelihood=ll))
+        converged = new == current
+        current = new
+        if converged:
+            break
+    return StructuralEMResult(torch.tensor(current, dtype=torch.int64, device=dev), fitted, len(trace), converged, trace)
