@@ -21,6 +21,7 @@ from .tabu import TabuResult, tabu_search  # noqa: F401
 from .compare import StructureComparison, compare_structures, cpdag, equivalence_classes, shd  # noqa: F401
 from .exact import ExactResult, exact_from_tables, exact_search, local_score_table  # noqa: F401
 from .pc import PCResult, ci_test, ci_tests, pc_stable, skeleton_blacklist  # noqa: F401
+from .local import MMPCResult, RSMAX2Result, ci_tests_group, mmhc, mmpc, rsmax2  # noqa: F401
 from .params import FittedBN, bn_fit, cross_validate, cv_folds, log_likelihood, sample  # noqa: F401
 # posterior.py is imported before infer.py: loading a submodule binds its name in the package, and the name `posterior` must end
 # up as infer.posterior, the function it has always been (the module stays reachable as dags_vae_search_amd.posterior in

@@ -20,6 +20,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs.h")
 EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_eliminate.h")   # the companion header: dvs_bn_eliminate
 INC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_incomplete.h")  # the second: expected counts, fit_counts, impute
 AVAIL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_available.h")  # the third: available-case scoring (nal / pnal)
+LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_local.h")      # the fourth: grouped CI tests, the MMPC round
 
 
 class DvsShape(Structure):
@@ -90,6 +91,8 @@ EXT_SIGNATURES, _X = _read_header(EXT_HEADER)
 INC_SIGNATURES, _ = _read_header(INC_HEADER)
 # include/dvs_available.h, the third: the available-case scorer and its toggle pass; the three tables above stay what they are
 AVAIL_SIGNATURES, _ = _read_header(AVAIL_HEADER)
+# include/dvs_local.h, the fourth: dvs_ci_tests_group and dvs_mmpc_update; the four tables above stay what they are
+LOCAL_SIGNATURES, _ = _read_header(LOCAL_HEADER)
 
 
 def signature(fn: str):
@@ -102,8 +105,10 @@ def signature(fn: str):
         return INC_SIGNATURES[fn]
     if fn in AVAIL_SIGNATURES:
         return AVAIL_SIGNATURES[fn]
-    raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h and "
-                   f"include/dvs_available.h")
+    if fn in LOCAL_SIGNATURES:
+        return LOCAL_SIGNATURES[fn]
+    raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
+                   f"include/dvs_available.h and include/dvs_local.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -143,7 +148,8 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
-    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items()):
+    for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
+                                  *LOCAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

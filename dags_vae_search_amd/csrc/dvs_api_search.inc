@@ -460,6 +460,81 @@ extern "C" int dvs_ci_tests(int32_t n_tests, int32_t n_vars, int32_t n_samples, 
     return call_end("dvs_ci_tests");
 }
 
+// ---- grouped CI tests and the MMPC round (dvs_local.h; include/dvs_local.h) ----------------------------------------------
+extern "C" int dvs_ci_tests_group(int32_t n_groups, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                                  const int32_t* target, const uint64_t* cond, const uint64_t* candidates, int32_t test_type,
+                                  int32_t lds_cells, double* out, size_t out_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_ci_tests_group";
+    if (n_groups <= 0 || n_samples <= 0) return failf(2, "%s: n_groups and n_samples must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (test_type < DVS_CI_MI || test_type > DVS_CI_X2_ADF) return failf(12, "%s: test_type is not a dvs_ci_type", fn);
+    if (lds_cells < 1 || lds_cells > DVS_CI_MAX_CELLS) return failf(13, "%s: lds_cells must be in [1, 36864]", fn);
+    if ((int64_t)n_groups * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: n_groups * n_vars must be < 2^31", fn);
+    if (!data || !card || !target || !cond || !candidates || !out || !status) return failf(10, "%s: null pointer", fn);
+    if (out_bytes < (size_t)n_groups * n_vars * 24)
+        return fail_size("dvs_ci_tests_group: out_bytes < n_groups * n_vars * 24", (size_t)n_groups * n_vars * 24);
+    CiGroupArgs a = {};
+    a.G = n_groups;
+    a.n = n_vars;
+    a.S = n_samples;
+    a.type = test_type;
+    a.lds_cells = lds_cells;
+    a.data = data;
+    a.card = card;
+    a.target = target;
+    a.cond = cond;
+    a.candidates = candidates;
+    a.out = out;
+    a.status = status;
+    call_begin();
+    dvs_launch_ci_tests_group(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_mmpc_update(int32_t n_vars, int32_t n_groups, int32_t phase, const int32_t* target, const uint64_t* cond,
+                               const uint64_t* candidates, const int64_t* group_offsets, const double* out, size_t out_bytes,
+                               double alpha, const uint64_t* cpc, const uint64_t* cand, uint64_t* cpc_next, uint64_t* cand_next,
+                               int32_t* last, double* pmax, double* smin, uint64_t* sepset, size_t state_bytes, int32_t* refused,
+                               int64_t* result, size_t result_bytes, void* stream) {
+    const char* fn = "dvs_mmpc_update";
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (n_groups <= 0) return failf(2, "%s: n_groups must be > 0", fn);
+    if ((int64_t)n_groups * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: n_groups * n_vars must be < 2^31", fn);
+    if (phase != 0 && phase != 1) return failf(13, "%s: phase must be 0 (forward) or 1 (backward)", fn);
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return failf(13, "%s: alpha must be in [0, 1]", fn);
+    if (!target || !cond || !candidates || !group_offsets || !out || !cpc || !cand || !cpc_next || !cand_next || !last || !pmax ||
+        !smin || !sepset || !refused || !result)
+        return failf(10, "%s: null pointer", fn);
+    if (out_bytes < (size_t)n_groups * n_vars * 24)
+        return fail_size("dvs_mmpc_update: out_bytes < n_groups * n_vars * 24", (size_t)n_groups * n_vars * 24);
+    if (state_bytes < (size_t)n_vars * n_vars * 8)
+        return fail_size("dvs_mmpc_update: state_bytes < n_vars^2 * 8", (size_t)n_vars * n_vars * 8);
+    if (result_bytes < (size_t)n_vars * 16) return fail_size("dvs_mmpc_update: result_bytes < n_vars * 16", (size_t)n_vars * 16);
+    MmpcUpdateArgs a = {};
+    a.n = n_vars;
+    a.G = n_groups;
+    a.phase = phase;
+    a.alpha = alpha;
+    a.target = target;
+    a.cond = cond;
+    a.candidates = candidates;
+    a.offsets = (const long long*)group_offsets;
+    a.out = out;
+    a.cpc = cpc;
+    a.cand = cand;
+    a.cpc_next = cpc_next;
+    a.cand_next = cand_next;
+    a.last = last;
+    a.pmax = pmax;
+    a.smin = smin;
+    a.sepset = sepset;
+    a.refused = refused;
+    a.result = (long long*)result;
+    call_begin();
+    dvs_launch_mmpc_update(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

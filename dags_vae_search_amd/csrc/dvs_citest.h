@@ -52,6 +52,60 @@ __device__ inline double ci_gamma_q(const double a, const double x) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The partial sums of one configuration z of a test: `cell` is its [rx][ry] block of counts, acc the statistic's sum and adf
+// the adjusted degrees of freedom.  k_ci_tests and k_ci_group (dvs_local.h) both call it, and dvs_ci_tests_group promises the
+// bytes of dvs_ci_tests, so what the compiler may or may not contract is stated: the G^2 term enters its sum by one fma on the
+// device (the emulator build contracts nothing and has two roundings), whichever kernel it is inlined into.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double ci_g2_add(const double acc, const double c, const double l) {
+#ifdef DVS_EMU
+    return acc + c * l;
+#else
+    return fma(c, l, acc);
+#endif
+}
+
+__device__ __forceinline__ void ci_config_sums(const unsigned* cell, const int rx, const int ry, const bool g2, double& acc, int& adf) {
+    unsigned col[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) col[k] = 0u;
+    unsigned n_z = 0u;
+    for (int i = 0; i < rx; ++i) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < ry) {
+                const unsigned c = cell[i * ry + k];
+                col[k] += c;
+                n_z += c;
+            }
+    }
+    if (n_z == 0u) return;
+    int rows_z = 0, cols_z = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) cols_z += (k < ry && col[k] != 0u) ? 1 : 0;
+    const double dz = (double)n_z;
+    for (int i = 0; i < rx; ++i) {
+        unsigned n_xz = 0u;
+        for (int k = 0; k < ry; ++k) n_xz += cell[i * ry + k];
+        if (n_xz == 0u) continue;
+        ++rows_z;
+        const double dxz = (double)n_xz;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < ry && col[k] != 0u) {
+                const double c = (double)cell[i * ry + k], dyz = (double)col[k];
+                if (g2) {
+                    if (c > 0.0) acc = ci_g2_add(acc, c, log((c * dz) / (dxz * dyz)));
+                } else {
+                    const double e = dxz * dyz / dz, d = c - e;
+                    acc += d * d / e;
+                }
+            }
+    }
+    adf += (rows_z > 1 ? rows_z - 1 : 0) * (cols_z > 1 ? cols_z - 1 : 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_ci_tests
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ci_tests(CiArgs a) {
@@ -95,46 +149,7 @@ __global__ __launch_bounds__(256) void k_ci_tests(CiArgs a) {
     const bool g2 = a.type == DVS_CI_MI || a.type == DVS_CI_MI_ADF;
     double acc = 0.0;
     int adf = 0;
-    for (int j = tid; j < q; j += blockDim.x) {
-        const unsigned* cell = hist + (size_t)j * plane;
-        unsigned col[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) col[k] = 0u;
-        unsigned n_z = 0u;
-        for (int i = 0; i < rx; ++i) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < ry) {
-                    const unsigned c = cell[i * ry + k];
-                    col[k] += c;
-                    n_z += c;
-                }
-        }
-        if (n_z == 0u) continue;
-        int rows_z = 0, cols_z = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) cols_z += (k < ry && col[k] != 0u) ? 1 : 0;
-        const double dz = (double)n_z;
-        for (int i = 0; i < rx; ++i) {
-            unsigned n_xz = 0u;
-            for (int k = 0; k < ry; ++k) n_xz += cell[i * ry + k];
-            if (n_xz == 0u) continue;
-            ++rows_z;
-            const double dxz = (double)n_xz;
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < ry && col[k] != 0u) {
-                    const double c = (double)cell[i * ry + k], dyz = (double)col[k];
-                    if (g2) {
-                        if (c > 0.0) acc += c * log((c * dz) / (dxz * dyz));
-                    } else {
-                        const double e = dxz * dyz / dz, d = c - e;
-                        acc += d * d / e;
-                    }
-                }
-        }
-        adf += (rows_z > 1 ? rows_z - 1 : 0) * (cols_z > 1 ? cols_z - 1 : 0);
-    }
+    for (int j = tid; j < q; j += blockDim.x) ci_config_sums(hist + (size_t)j * plane, rx, ry, g2, acc, adf);
     red[tid] = acc;
     redi[tid] = adf;
     __syncthreads();

@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -11,6 +11,7 @@
 #include "../../include/dvs_eliminate.h"
 #include "../../include/dvs_incomplete.h"
 #include "../../include/dvs_available.h"
+#include "../../include/dvs_local.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -551,6 +552,40 @@ struct ToggleAvailArgs {
     const uint64_t* observed;    // [S]
 };
 void dvs_launch_bn_toggle_avail(const ToggleAvailArgs& a, dvs_stream_t st);
+
+// ---- grouped CI tests and the MMPC round (dvs_local.h; include/dvs_local.h) ------------------------------------------------
+struct CiGroupArgs {
+    int G, n, S, words, type, lds_cells;         // words: launcher
+    const uint64_t* data;        // [S][words]
+    const uint8_t* card;         // [n]
+    const int* target;           // [G]: y
+    const uint64_t* cond;        // [G]: bit z <=> z is in the conditioning set
+    const uint64_t* candidates;  // [G]: bit x <=> x is tested against y
+    double* out;                 // [G][n][3]: statistic, df, p-value; NaN where not asked or refused
+    int* status;
+};
+void dvs_launch_ci_tests_group(const CiGroupArgs& a, dvs_stream_t st);
+
+struct MmpcUpdateArgs {
+    int n, G, phase;
+    double alpha;
+    const int* target;           // [G]
+    const uint64_t* cond;        // [G]
+    const uint64_t* candidates;  // [G]
+    const long long* offsets;    // [n + 1]: groups of target t are offsets[t] .. offsets[t + 1] - 1
+    const double* out;           // [G][n][3]
+    const uint64_t* cpc;         // [n]
+    const uint64_t* cand;        // [n]
+    uint64_t* cpc_next;          // [n], written whole
+    uint64_t* cand_next;         // [n], written whole
+    int* last;                   // [n], written in the forward phase
+    double* pmax;                // [n][n]
+    double* smin;                // [n][n]
+    uint64_t* sepset;            // [n][n], cell [t][x] of an x that left written
+    int* refused;                // [1], written
+    long long* result;           // [n][2]: (the member added or -1, candidates that left)
+};
+void dvs_launch_mmpc_update(const MmpcUpdateArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;
