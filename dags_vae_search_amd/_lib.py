@@ -21,6 +21,7 @@ EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_eliminate.h") 
 INC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_incomplete.h")  # the second: expected counts, fit_counts, impute
 AVAIL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_available.h")  # the third: available-case scoring (nal / pnal)
 LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_local.h")      # the fourth: grouped CI tests, the MMPC round
+PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_permtest.h")    # the fifth: Monte Carlo permutation CI tests
 
 
 class DvsShape(Structure):
@@ -93,6 +94,8 @@ INC_SIGNATURES, _ = _read_header(INC_HEADER)
 AVAIL_SIGNATURES, _ = _read_header(AVAIL_HEADER)
 # include/dvs_local.h, the fourth: dvs_ci_tests_group and dvs_mmpc_update; the four tables above stay what they are
 LOCAL_SIGNATURES, _ = _read_header(LOCAL_HEADER)
+# include/dvs_permtest.h, the fifth: dvs_ci_perm_tests and its workspace size; the five tables above stay what they are
+PERM_SIGNATURES, _P = _read_header(PERM_HEADER)
 
 
 def signature(fn: str):
@@ -107,8 +110,10 @@ def signature(fn: str):
         return AVAIL_SIGNATURES[fn]
     if fn in LOCAL_SIGNATURES:
         return LOCAL_SIGNATURES[fn]
+    if fn in PERM_SIGNATURES:
+        return PERM_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
-                   f"include/dvs_available.h and include/dvs_local.h")
+                   f"include/dvs_available.h, include/dvs_local.h and include/dvs_permtest.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -131,6 +136,8 @@ def _by_bnlearn_name(prefix, keys):
 
 CI_TYPES = _by_bnlearn_name("DVS_CI_", ("mi", "x2", "mi-adf", "x2-adf"))   # dvs_ci_type
 CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
+CI_PERM_TYPES = {k: _P["DVS_CI_" + k.upper().replace("-", "_")]      # dvs_ci_perm_type (include/dvs_permtest.h)
+                 for k in ("mc-mi", "mc-x2", "smc-mi", "smc-x2", "sp-mi", "sp-x2")}
 FIT_METHODS = _by_bnlearn_name("DVS_FIT_", ("mle", "bayes"))   # dvs_fit_method
 FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
 # bits of the BN entry points' status word (device int32, zeroed by the caller), as include/dvs.h defines them
@@ -149,7 +156,7 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
-                                  *LOCAL_SIGNATURES.items()):
+                                  *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

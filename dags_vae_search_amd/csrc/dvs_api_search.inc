@@ -535,6 +535,63 @@ extern "C" int dvs_mmpc_update(int32_t n_vars, int32_t n_groups, int32_t phase, 
     return call_end(fn);
 }
 
+// ---- Monte Carlo permutation CI tests (dvs_permtest.h; include/dvs_permtest.h) -------------------------------------------
+static bool ci_perm_too_many(int n_tests, int n_perm) { return (int64_t)n_tests * ((n_perm + 255) / 256) > (int64_t)0x7fffffff; }
+
+extern "C" size_t dvs_ci_perm_workspace_bytes(int32_t n_tests, int32_t n_perm) {
+    const char* fn = "dvs_ci_perm_workspace_bytes";
+    if (n_tests <= 0) return failf(2, "%s: n_tests must be > 0", fn), 0;
+    if (n_perm < 1 || n_perm > DVS_CI_PERM_MAX) return failf(13, "%s: n_perm must be in [1, 2^20]", fn), 0;
+    if (ci_perm_too_many(n_tests, n_perm)) return failf(2, "%s: n_tests * blocks must be < 2^31", fn), 0;
+    return dvs_ci_perm_layout(n_tests, n_perm).total;
+}
+
+extern "C" int dvs_ci_perm_tests(int32_t n_tests, int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card,
+                                 const int32_t* pairs, const uint64_t* cond, int32_t perm_type, int32_t n_perm, double alpha,
+                                 uint64_t seed, uint32_t test_offset, int32_t slices, int32_t max_cells, void* workspace,
+                                 size_t workspace_bytes, double* out, size_t out_bytes, int32_t* used, int32_t* status, void* stream) {
+    const char* fn = "dvs_ci_perm_tests";
+    if (n_tests <= 0 || n_samples <= 0) return failf(2, "%s: n_tests and n_samples must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (perm_type < DVS_CI_MC_MI || perm_type > DVS_CI_SP_X2) return failf(12, "%s: perm_type is not a dvs_ci_perm_type", fn);
+    if (n_perm < 1 || n_perm > DVS_CI_PERM_MAX) return failf(13, "%s: n_perm must be in [1, 2^20]", fn);
+    const bool smc = perm_type == DVS_CI_SMC_MI || perm_type == DVS_CI_SMC_X2;
+    if (smc && !(alpha > 0.0 && alpha < 1.0)) return failf(13, "%s: alpha must be in (0, 1)", fn);
+    const CiPermLayout l = dvs_ci_perm_layout(n_tests, n_perm);
+    if (slices < 1 || (size_t)slices > l.blocks) return failf(13, "%s: slices must be in [1, ceil(n_perm / 256)]", fn);
+    if (max_cells < 1 || max_cells > DVS_CI_MAX_CELLS) return failf(13, "%s: max_cells must be in [1, 36864]", fn);
+    if (ci_perm_too_many(n_tests, n_perm)) return failf(2, "%s: n_tests * blocks must be < 2^31", fn);
+    if (!data || !card || !pairs || !cond || !workspace || !out || !used || !status) return failf(10, "%s: null pointer", fn);
+    if (workspace_bytes < l.total) return fail_size("dvs_ci_perm_tests: workspace_bytes < dvs_ci_perm_workspace_bytes", l.total);
+    if (out_bytes < (size_t)n_tests * 24) return fail_size("dvs_ci_perm_tests: out_bytes < n_tests * 24", (size_t)n_tests * 24);
+    CiPermArgs a = {};
+    a.g2 = (perm_type & 1) == 0;
+    a.sp = perm_type == DVS_CI_SP_MI || perm_type == DVS_CI_SP_X2;
+    a.c.T = n_tests;
+    a.c.n = n_vars;
+    a.c.S = n_samples;
+    a.c.type = a.g2 ? DVS_CI_MI : DVS_CI_X2;
+    a.c.max_cells = max_cells;
+    a.c.data = data;
+    a.c.card = card;
+    a.c.pairs = pairs;
+    a.c.cond = cond;
+    a.c.out = out;
+    a.c.status = status;
+    a.B = n_perm;
+    a.E = smc ? (int)floor(alpha * (double)n_perm) + 1 : 0;
+    a.slices = slices;
+    a.blocks = (int)l.blocks;
+    a.test_offset = test_offset;
+    a.counts = (int*)((char*)workspace + l.counts);
+    a.sums = (double*)((char*)workspace + l.sums);
+    a.masks = (unsigned long long*)((char*)workspace + l.masks);
+    a.used = used;
+    call_begin();
+    dvs_launch_ci_perm(a, seed, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

@@ -422,7 +422,8 @@ __device__ __forceinline__ void dvs_block_sum256(const int tid, T*... x) {
 // draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw),
 // 600 the bootstrap row sets of dvs_bootstrap_rows (dvs_strength.h; keyed by the global set index, element = position),
 // 700 / 701 the proposals and the start order of dvs_order_mcmc (dvs_ordermc.h; keyed by the global chain index; step t draws
-// elements 3 t, 3 t + 1, 3 t + 2, the shuffle draws element k for position k).
+// elements 3 t, 3 t + 1, 3 t + 2, the shuffle draws element k for position k),
+// 800 the permutation CI tests (dvs_permtest.h; keyed by the global test index, then permutation, draw ordinal and attempt).
 constexpr uint32_t DVS_SITE_GEN_EDGES = 300u, DVS_SITE_GEN_LABELS = 301u, DVS_SITE_GEN_COUNTS = 302u;
 constexpr uint32_t DVS_SITE_HC_PERTURB = 400u;
 constexpr uint32_t DVS_SITE_BN_SAMPLE = 500u;

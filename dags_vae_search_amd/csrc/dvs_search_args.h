@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -12,6 +12,7 @@
 #include "../../include/dvs_incomplete.h"
 #include "../../include/dvs_available.h"
 #include "../../include/dvs_local.h"
+#include "../../include/dvs_permtest.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -586,6 +587,35 @@ struct MmpcUpdateArgs {
     long long* result;           // [n][2]: (the member added or -1, candidates that left)
 };
 void dvs_launch_mmpc_update(const MmpcUpdateArgs& a, dvs_stream_t st);
+
+// ---- Monte Carlo permutation CI tests (dvs_permtest.h; include/dvs_permtest.h) ---------------------------------------------
+constexpr int DVS_CI_PERM_MAX = 1 << 20;         // n_perm
+constexpr size_t DVS_CI_PERM_LDS = 159744;       // dynamic LDS a k_ci_perm workgroup may ask for: 160 KiB less 4 KiB of static
+// The workspace of dvs_ci_perm_tests (include/dvs_permtest.h): three arrays, each starting at a multiple of 256 bytes.
+struct CiPermLayout {
+    size_t counts, sums, masks, total, blocks;
+};
+inline CiPermLayout dvs_ci_perm_layout(long long n_tests, int n_perm) {
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    CiPermLayout l;
+    l.blocks = (size_t)((n_perm + 255) / 256);
+    const size_t cells = (size_t)n_tests * l.blocks;
+    l.counts = 0;
+    l.sums = up(cells * 4);
+    l.masks = l.sums + up(cells * 8);
+    l.total = l.masks + up(cells * 32);
+    return l;
+}
+struct CiPermArgs {
+    CiArgs c;                    // the tests; c.type is DVS_CI_MI or DVS_CI_X2, c.out [T][3]
+    int g2, sp, B, E, slices, blocks, lnk_cells;     // E: smc's stopping count, 0 otherwise; lnk_cells: launcher
+    uint32_t seed_lo, seed_hi, test_offset;      // seed_lo / seed_hi: launcher, from `seed`
+    int* counts;                 // workspace [T][blocks]
+    double* sums;                // workspace [T][blocks]
+    unsigned long long* masks;   // workspace [T][blocks][4]
+    int* used;                   // [T]
+};
+void dvs_launch_ci_perm(const CiPermArgs& a, uint64_t seed, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

@@ -27,10 +27,19 @@ import torch
 
 from . import _lib as dl
 from .hillclimb import hill_climb
-from .pc import _evaluator, _test_type, pc_stable, skeleton_blacklist
+from .pc import _evaluator, pc_stable, skeleton_blacklist
+from .pc import _test_type as _any_test_type
 from .tabu import tabu_search
 
 INDEX_RANGE = (1 << 31) - 1                # groups of one round: dvs_ci_tests_group's n_groups
+
+
+def _test_type(what, test):
+    """the dvs_ci_type of ``test``; the permutation tests (dvs_ci_perm_tests) are not built for the grouped kernel"""
+    if test in dl.CI_PERM_TYPES:
+        raise ValueError(f"{what}: permutation tests are not built for the grouped kernel (got {test!r}): "
+                         f"ci_tests and pc_stable take them, and rsmax2(restrict=\"pc.stable\") through pc_stable")
+    return _any_test_type(test)
 
 
 class MMPCResult(NamedTuple):
@@ -76,7 +85,7 @@ def ci_tests_group(evaluator, targets, cond, candidates, test: str = "mi", *, ld
     in as many passes over the rows as their tables need)."""
     what = "ci_tests_group"
     _evaluator(what, evaluator)
-    typ = _test_type(test)
+    typ = _test_type(what, test)
     targets = _tensor_arg(what, "targets", targets, torch.int32, "int32 [G >= 1]", lambda t: t.ndim == 1 and t.numel() >= 1)
     G = targets.numel()
     cond = _tensor_arg(what, "cond", cond, torch.int64, f"int64 [{G}] bit masks", lambda t: t.shape == (G,))
@@ -175,7 +184,7 @@ def _mmpc(evaluator, alpha, test, max_cond, targets, rounds=None):
     (bench_mmpc.py replays them)"""
     what = "mmpc"
     card = _evaluator(what, evaluator)
-    typ = _test_type(test)
+    typ = _test_type(what, test)
     if not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("alpha must be in [0, 1]")
     if int(max_cond) < 0:

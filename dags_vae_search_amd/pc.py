@@ -1,13 +1,15 @@
 """Constraint-based structure learning on the device (csrc/dvs_citest.h): bnlearn's ``ci.test`` and
 ``pc.stable`` for discrete data, next to the score-based searches.
 
-``ci_tests`` evaluates a batch of conditional-independence tests (G^2 ``mi``, Pearson ``x2`` and their ``-adf`` variants) on the
+``ci_tests`` evaluates a batch of conditional-independence tests (G^2 ``mi``, Pearson ``x2`` and their ``-adf`` variants, and
+the Monte Carlo permutation family ``mc-``, ``smc-``, ``sp-`` ``mi`` / ``x2`` of csrc/dvs_permtest.h) on the
 evaluator's packed data set; ``pc_stable`` runs the order-independent PC skeleton search level by level (one read-back of the
 48 adjacency words per level) and orients the result into a PDAG; ``skeleton_blacklist`` turns a learned skeleton into the
 ``forbidden`` rows that ``hill_climb``, ``tabu_search`` and ``exact_search`` accept — the restrict-then-maximise hybrid.
 
 The definitions are those of include/dvs.h (dvs_ci_tests, dvs_pc_expand, dvs_pc_reduce, dvs_pc_orient).  Parity with
-bnlearn's ``ci.test`` / ``pc.stable`` rests on them and is not pinned against an R run.
+bnlearn's ``ci.test`` / ``pc.stable`` rests on them and is not pinned against an R run.  The permutation tests are defined in
+include/dvs_permtest.h; their p-value is count / B, bnlearn's convention as recalled, and that too is not pinned against R.
 """
 from __future__ import annotations
 
@@ -21,6 +23,9 @@ from . import _lib as dl
 
 MAX_VARS = 48
 INDEX_RANGE = (1 << 31) - 1                # tests of one level: dvs_pc_expand's n_tests
+PERM_MAX = 1 << 20                         # permutations of one test: dvs_ci_perm_tests' n_perm
+PERM_FILL = 4                              # a permutation launch is sliced until tests * slices reaches PERM_FILL workgroups per
+                                           # CU: chosen before anything was measured; DESIGN.md §28 has what it costs
 
 
 class PCResult(NamedTuple):
@@ -39,9 +44,30 @@ def _evaluator(what, evaluator):
 
 
 def _test_type(test):
+    """the dvs_ci_type of an asymptotic test, or the name itself for a permutation test (dl.CI_PERM_TYPES)"""
+    if test in dl.CI_PERM_TYPES:
+        return test
     if test not in dl.CI_TYPES:
-        raise ValueError(f"test must be one of {sorted(dl.CI_TYPES)} (got {test!r})")
+        raise ValueError(f"test must be one of {sorted(dl.CI_TYPES) + sorted(dl.CI_PERM_TYPES)} (got {test!r})")
     return dl.CI_TYPES[test]
+
+
+class _Perm(NamedTuple):
+    """what a permutation test takes beyond the tests themselves"""
+    B: int
+    seed: int
+    alpha: float
+    test_offset: int
+
+    @staticmethod
+    def of(what, test, B, seed, alpha, test_offset=0):
+        if not 1 <= int(B) <= PERM_MAX:
+            raise ValueError(f"{what}: B must be in [1, 2^20]")
+        if test.startswith("smc-") and not 0.0 < float(alpha) < 1.0:
+            raise ValueError(f"{what}: alpha must be in (0, 1) for {test}")
+        if not 0 <= int(test_offset) < 1 << 32:
+            raise ValueError(f"{what}: test_offset must be in [0, 2^32)")
+        return _Perm(int(B), dl.seed64(seed), float(alpha), int(test_offset))
 
 
 def _max_cells(card, level):
@@ -52,7 +78,28 @@ def _max_cells(card, level):
     return max(1, min(cells, dl.CI_MAX_CELLS))
 
 
-def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk):
+def _run_perm_tests(evaluator, pairs, cond, test, perm, max_cells, out, status, used, chunk):
+    """dvs_ci_perm_tests in chunks; test t of the batch draws as global test perm.test_offset + t (mod 2^32)"""
+    lib, T, p = evaluator.lib, cond.numel(), dl.ptr
+    blocks = (perm.B + 255) // 256
+    chunk = max(1, min(chunk, INDEX_RANGE // blocks))
+    cus = torch.cuda.get_device_properties(evaluator.device).multi_processor_count
+    work = torch.empty(dl.workspace_bytes(lib, "dvs_ci_perm_workspace_bytes", min(chunk, T), perm.B), dtype=torch.uint8,
+                       device=evaluator.device)                  # sized for the largest chunk: a smaller one needs less
+    for t0 in range(0, T, chunk):
+        m = min(chunk, T - t0)
+        slices = max(1, min(blocks, -(-PERM_FILL * cus // m)))
+        dl.check(lib, lib.dvs_ci_perm_tests(m, evaluator.n_vars, evaluator.n_samples, p(evaluator.packed), p(evaluator.card),
+                                            p(pairs[t0:]), p(cond[t0:]), dl.CI_PERM_TYPES[test], perm.B, perm.alpha, perm.seed,
+                                            (perm.test_offset + t0) & 0xFFFFFFFF, slices, max_cells, p(work), dl.nbytes(work),
+                                            p(out[t0:]), m * 24, p(used[t0:]), p(status), dl.stream()), "dvs_ci_perm_tests")
+
+
+def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk, perm=None, used=None):
+    if perm is not None:
+        if used is None:
+            used = torch.empty(cond.numel(), dtype=torch.int32, device=evaluator.device)
+        return _run_perm_tests(evaluator, pairs, cond, typ, perm, max_cells, out, status, used, chunk)
     lib, T, p = evaluator.lib, cond.numel(), dl.ptr
     for t0 in range(0, T, chunk):
         m = min(chunk, T - t0)
@@ -61,14 +108,26 @@ def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk):
                  "dvs_ci_tests")
 
 
-def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = False, chunk: int = 65536):
+def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = False, chunk: int = 65536, B: int = 5000,
+             seed: int = 0, alpha: float = 0.05, test_offset: int = 0, return_used: bool = False):
     """``pairs`` int32 [T, 2] (x, y) and ``cond`` int64 [T] (bit z: z is conditioned on), both on the evaluator's device ->
     float64 [T, 3] on the device: (statistic, df, p-value) of ``test`` in {"mi", "x2", "mi-adf", "x2-adf"}.  A test whose
     table exceeds 36 864 cells, with x = y, with x or y in its conditioning set or with an index outside the data set comes
-    back as three NaNs (``return_status=True`` also returns the status word: bit 4 says that some test was refused)."""
+    back as three NaNs (``return_status=True`` also returns the status word: bit 4 says that some test was refused).
+
+    ``test`` in {"mc-mi", "mc-x2", "smc-mi", "smc-x2", "sp-mi", "sp-x2"} is a permutation test (include/dvs_permtest.h) with
+    ``B`` permutations (5000 is bnlearn's default as recalled: an unmeasured choice) drawn from ``seed``; test t of the batch
+    draws as global test ``test_offset + t``, so a batch cut into calls gives the bytes of the whole.  ``alpha`` is the
+    threshold of the sequential ``smc-`` tests' early stop and is not read otherwise.  p = count / B follows bnlearn's
+    convention as recalled; parity with an R run is not pinned.  ``return_used=True`` (permutation tests only) also returns
+    int32 [T], the permutations each test counted: B, fewer where an ``smc-`` test stopped early, 0 for a refused test.  The
+    returns come in the order (out, status, used)."""
     what = "ci_tests"
     card = _evaluator(what, evaluator)
     typ = _test_type(test)
+    perm = _Perm.of(what, test, B, seed, alpha, test_offset) if test in dl.CI_PERM_TYPES else None
+    if return_used and perm is None:
+        raise ValueError(f"{what}: return_used goes with a permutation test (got {test!r})")
     for name, t in (("pairs", pairs), ("cond", cond)):
         if not torch.is_tensor(t):
             raise TypeError(f"{what}: {name} must be a torch tensor")
@@ -91,12 +150,17 @@ def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = 
         level = int(((x * 0x0101010101010101) >> 56).max())
         out = torch.empty(cond.numel(), 3, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk)
-    return (out, status) if return_status else out
+        used = torch.empty(cond.numel(), dtype=torch.int32, device=dev) if perm is not None else None
+        _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk, perm, used)
+    ret = (out,) + ((status,) if return_status else ()) + ((used,) if return_used else ())
+    return ret if len(ret) > 1 else out
 
 
-def ci_test(evaluator, x: int, y: int, cond=(), test: str = "mi") -> torch.Tensor:
-    """one test of x against y given the variables in ``cond`` -> float64 [3] on the device: (statistic, df, p-value)"""
+def ci_test(evaluator, x: int, y: int, cond=(), test: str = "mi", *, B: int = 5000, seed: int = 0, alpha: float = 0.05,
+            test_offset: int = 0, return_used: bool = False):
+    """one test of x against y given the variables in ``cond`` -> float64 [3] on the device: (statistic, df, p-value); the
+    keywords are those of ``ci_tests`` for a permutation test (with ``return_used`` the result is (float64 [3], int32 [], the
+    permutations counted))"""
     _evaluator("ci_test", evaluator)
     mask = 0
     for z in cond:
@@ -105,7 +169,9 @@ def ci_test(evaluator, x: int, y: int, cond=(), test: str = "mi") -> torch.Tenso
         mask |= 1 << int(z)
     dev = evaluator.device
     pairs = torch.tensor([[int(x), int(y)]], dtype=torch.int32, device=dev)
-    return ci_tests(evaluator, pairs, torch.tensor([mask], dtype=torch.int64, device=dev), test)[0]
+    got = ci_tests(evaluator, pairs, torch.tensor([mask], dtype=torch.int64, device=dev), test, B=B, seed=seed, alpha=alpha,
+                   test_offset=test_offset, return_used=return_used)
+    return (got[0][0], got[1][0]) if return_used else got[0]
 
 
 def level_tests(adj: List[int], level: int):
@@ -125,11 +191,15 @@ def level_tests(adj: List[int], level: int):
     return pair_xy, offsets
 
 
-def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Optional[int] = None, chunk: int = 65536) -> PCResult:
+def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Optional[int] = None, chunk: int = 65536,
+              B: int = 5000, seed: int = 0) -> PCResult:
     """The PC-stable algorithm (Colombo and Maathuis 2014) on the evaluator's data set: the skeleton by levels of conditional
     independence tests of growing conditioning-set size, every level working on the adjacency rows frozen at its start, then
     colliders from the separating sets and Meek's rules.  ``max_cond`` caps the size of the conditioning sets (None: no cap,
-    the search stops at the first level where no adjacent pair has enough neighbours left).  ``chunk``: tests per launch."""
+    the search stops at the first level where no adjacent pair has enough neighbours left).  ``chunk``: tests per launch.
+    With a permutation ``test`` (``ci_tests``), ``B`` permutations per test are drawn from ``seed``, ``alpha`` is also the
+    ``smc-`` tests' stopping threshold, and the tests are numbered on across the levels (test t of a level draws as global test
+    ``tests of the earlier levels + t``), so the result is a function of the seed alone, not of ``chunk``."""
     what = "pc_stable"
     card = _evaluator(what, evaluator)
     typ = _test_type(test)
@@ -139,6 +209,7 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
         raise ValueError("chunk must be >= 1")
     if max_cond is not None and int(max_cond) < 0:
         raise ValueError("max_cond must be >= 0 or None")
+    perm = _Perm.of(what, test, B, seed, alpha) if test in dl.CI_PERM_TYPES else None
     dev, n, lib, p = evaluator.device, evaluator.n_vars, evaluator.lib, dl.ptr
     full = (1 << n) - 1
     adj = [full & ~(1 << v) for v in range(n)]
@@ -170,7 +241,8 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
             result = torch.empty(P, 2, dtype=torch.int64, device=dev)
             dl.check(lib, lib.dvs_pc_expand(P, n, level, p(d_adj), p(d_xy), p(d_off), T, p(pairs), p(cond), T * 8, dl.stream()),
                      "dvs_pc_expand")
-            _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk)
+            _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk,
+                       perm and perm._replace(test_offset=sum(tests_per_level) & 0xFFFFFFFF))
             dl.check(lib, lib.dvs_pc_reduce(P, n, p(d_xy), p(d_off), T, p(cond), p(out), float(alpha), p(d_adj), p(d_next),
                                             p(sepsets), n * n * 8, p(result), P * 16, p(refused), dl.stream()), "dvs_pc_reduce")
             adj = [int(a) for a in d_next.cpu().numpy().view(np.uint64)]        # the level's one read-back
