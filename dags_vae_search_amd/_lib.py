@@ -22,6 +22,7 @@ INC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_incomplete.h")
 AVAIL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_available.h")  # the third: available-case scoring (nal / pnal)
 LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_local.h")      # the fourth: grouped CI tests, the MMPC round
 PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_permtest.h")    # the fifth: Monte Carlo permutation CI tests
+GAUSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian.h")   # the sixth: Gaussian networks on real-valued data
 
 
 class DvsShape(Structure):
@@ -96,6 +97,8 @@ AVAIL_SIGNATURES, _ = _read_header(AVAIL_HEADER)
 LOCAL_SIGNATURES, _ = _read_header(LOCAL_HEADER)
 # include/dvs_permtest.h, the fifth: dvs_ci_perm_tests and its workspace size; the five tables above stay what they are
 PERM_SIGNATURES, _P = _read_header(PERM_HEADER)
+# include/dvs_gaussian.h, the sixth: moments, Gaussian scores, their toggle pass and the fit; the six tables above stay what they are
+GAUSS_SIGNATURES, _G = _read_header(GAUSS_HEADER)
 
 
 def signature(fn: str):
@@ -112,8 +115,10 @@ def signature(fn: str):
         return LOCAL_SIGNATURES[fn]
     if fn in PERM_SIGNATURES:
         return PERM_SIGNATURES[fn]
+    if fn in GAUSS_SIGNATURES:
+        return GAUSS_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
-                   f"include/dvs_available.h, include/dvs_local.h and include/dvs_permtest.h")
+                   f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h and include/dvs_gaussian.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -138,6 +143,16 @@ CI_TYPES = _by_bnlearn_name("DVS_CI_", ("mi", "x2", "mi-adf", "x2-adf"))   # dvs
 CI_MAX_CELLS = 36864      # the dense (z, x, y) table of dvs_ci_tests that fits LDS
 CI_PERM_TYPES = {k: _P["DVS_CI_" + k.upper().replace("-", "_")]      # dvs_ci_perm_type (include/dvs_permtest.h)
                  for k in ("mc-mi", "mc-x2", "smc-mi", "smc-x2", "sp-mi", "sp-x2")}
+GSCORE_TYPES = {k: _G["DVS_GSCORE_" + k.upper()[:-2] if k.endswith("-g") else "DVS_GSCORE_" + k.upper()]     # dvs_gscore_type
+                for k in ("loglik-g", "aic-g", "bic-g", "bge")}
+GBN_CHUNK, GBN_MAX_PARENTS = _G["DVS_GBN_CHUNK"], _G["DVS_GBN_MAX_PARENTS"]      # include/dvs_gaussian.h
+
+
+def gbn_stride(n: int) -> int:
+    """DVS_GBN_STRIDE(n): the doubles of one set's moments (m, mean [n], C [n][n])"""
+    return 1 + n + n * n
+
+
 FIT_METHODS = _by_bnlearn_name("DVS_FIT_", ("mle", "bayes"))   # dvs_fit_method
 FIT_MAX_CELLS = 36864     # the dense (configuration, level) table of dvs_bn_fit that fits LDS
 # bits of the BN entry points' status word (device int32, zeroed by the caller), as include/dvs.h defines them
@@ -156,7 +171,7 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
-                                  *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items()):
+                                  *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]
@@ -232,6 +247,13 @@ def require_cuda(t, what: str):
     if not t.is_cuda:
         raise RuntimeError(f"dags_vae_search_amd: {what} must live on the GPU (got device {t.device}); "
                            f"this package has no CPU path")
+
+
+def need_discrete(what, evaluator):
+    """the entry points that read ``packed`` / ``card`` refuse an evaluator over real-valued data (gaussian.py)"""
+    if getattr(evaluator, "continuous", False):
+        raise ValueError(f"{what}: the evaluator holds real-valued data and {what} reads discrete levels: its Gaussian "
+                         f"counterpart is not built")
 
 
 def workspace_bytes(lib, name: str, *args) -> int:

@@ -592,6 +592,149 @@ extern "C" int dvs_ci_perm_tests(int32_t n_tests, int32_t n_vars, int32_t n_samp
     return call_end(fn);
 }
 
+// ---- Gaussian networks (dvs_gaussian.h; include/dvs_gaussian.h) ----------------------------------------------------------------
+static int gbn_moment_dims(const char* fn, int n_vars, int n_sets, int set_size) {
+    if (n_sets <= 0 || set_size <= 0) return failf(2, "%s: n_sets and set_size must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    return 0;
+}
+static bool gbn_moment_too_many(const GbnMomentLayout& l, int n_sets) {
+    return (double)n_sets * (double)l.chunks * (double)l.tri > 2147483647.0;
+}
+
+extern "C" size_t dvs_gbn_moments_workspace_bytes(int32_t n_vars, int32_t n_sets, int32_t set_size) {
+    const char* fn = "dvs_gbn_moments_workspace_bytes";
+    if (gbn_moment_dims(fn, n_vars, n_sets, set_size)) return 0;
+    const GbnMomentLayout l = dvs_gbn_moment_layout(n_vars, n_sets, set_size);
+    if (gbn_moment_too_many(l, n_sets)) return failf(2, "%s: n_sets * chunks * n (n + 1) / 2 must be < 2^31", fn), 0;
+    return l.total;
+}
+
+extern "C" int dvs_gbn_moments(int32_t n_vars, int32_t n_samples, const double* data, const int32_t* rows, int32_t n_sets,
+                               int32_t set_size, void* workspace, size_t workspace_bytes, double* moments, size_t moments_bytes,
+                               void* stream) {
+    const char* fn = "dvs_gbn_moments";
+    if (n_samples <= 0) return failf(2, "%s: n_samples must be > 0", fn);
+    if (int e = gbn_moment_dims(fn, n_vars, n_sets, set_size)) return e;
+    if (!rows && (n_sets != 1 || set_size != n_samples))
+        return failf(13, "%s: without rows there is one set of n_samples rows", fn);
+    const GbnMomentLayout l = dvs_gbn_moment_layout(n_vars, n_sets, set_size);
+    if (gbn_moment_too_many(l, n_sets)) return failf(2, "%s: n_sets * chunks * n (n + 1) / 2 must be < 2^31", fn);
+    if (!data || !workspace || !moments) return failf(10, "%s: null pointer", fn);
+    if (workspace_bytes < l.total) return fail_size("dvs_gbn_moments: workspace_bytes < dvs_gbn_moments_workspace_bytes", l.total);
+    const size_t need = (size_t)n_sets * DVS_GBN_STRIDE(n_vars) * 8;
+    if (moments_bytes < need) return fail_size("dvs_gbn_moments: moments_bytes < n_sets * DVS_GBN_STRIDE(n_vars) * 8", need);
+    GbnMomentArgs a = {};
+    a.n = n_vars;
+    a.n_sets = n_sets;
+    a.set_size = set_size;
+    a.data = data;
+    a.rows = rows;
+    a.sums = (double*)workspace;
+    a.cells = (double*)((char*)workspace + l.cells);
+    a.moments = moments;
+    call_begin();
+    dvs_launch_gbn_moments(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+// score_type and its arguments -> the fields the kernels read (include/dvs_gaussian.h)
+static int gbn_score_args(const char* fn, GbnScoreArgs& a, int n_vars, int score_type, double arg, double arg2) {
+    const bool dflt = arg != arg, dflt2 = arg2 != arg2;
+    a.type = score_type;
+    a.arg = arg;
+    a.arg2 = arg2;
+    a.t = 0.0;
+    switch (score_type) {
+        case DVS_GSCORE_LOGLIK:
+            if (!dflt || !dflt2) return failf(13, "%s: loglik-g takes no argument (score_arg and score_arg2 must be NaN)", fn);
+            return 0;
+        case DVS_GSCORE_AIC:
+        case DVS_GSCORE_BIC:
+            if (!dflt && !(arg >= 0.0 && isfinite(arg))) return failf(13, "%s: k must be finite and >= 0", fn);
+            if (!dflt2) return failf(13, "%s: score_arg2 is bge's alpha_w (must be NaN)", fn);
+            if (dflt && score_type == DVS_GSCORE_AIC) a.arg = 1.0;       // bic's default, log(m) / 2, is taken on the device
+            return 0;
+        case DVS_GSCORE_BGE:
+            if (dflt) a.arg = 1.0;
+            if (dflt2) a.arg2 = (double)n_vars + 2.0;
+            if (!(a.arg > 0.0 && isfinite(a.arg))) return failf(13, "%s: alpha_mu must be finite and > 0", fn);
+            if (!(a.arg2 > (double)n_vars + 1.0 && isfinite(a.arg2))) return failf(13, "%s: alpha_w must be finite and > n_vars + 1", fn);
+            a.t = a.arg * (a.arg2 - (double)n_vars - 1.0) / (a.arg + 1.0);
+            return 0;
+        default:
+            return failf(12, "%s: score_type is not a dvs_gscore_type", fn);
+    }
+}
+// what the three family entry points check first: sizes (2), n_vars (3; the table's index range with it)
+static int gbn_dims(const char* fn, int batch, int n_vars, int n_sets, bool table) {
+    if (batch <= 0 || n_sets <= 0) return failf(2, "%s: batch and n_sets must be > 0", fn);
+    if (table) return HcCheck{fn, batch, n_vars}.dims();
+    return n_vars < 1 || n_vars > DVS_WTOK ? failf(3, "%s: n_vars must be in [1, 48]", fn) : 0;
+}
+static void gbn_fill(GbnScoreArgs& a, int batch, int n_vars, const double* moments, const int32_t* set_of, const uint64_t* parents,
+                     double* local, double* out, int32_t* status) {
+    a.B = batch;
+    a.n = n_vars;
+    a.moments = moments;
+    a.set_of = set_of;
+    a.parents = parents;
+    a.local = local;
+    a.out = out;
+    a.status = status;
+}
+
+extern "C" int dvs_gbn_scores(int32_t batch, int32_t n_vars, const double* moments, int32_t n_sets, const int32_t* set_of,
+                              const uint64_t* parents, int32_t score_type, double score_arg, double score_arg2, double* local,
+                              double* out, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_scores";
+    if (int e = gbn_dims(fn, batch, n_vars, n_sets, false)) return e;
+    GbnScoreArgs a = {};
+    if (int e = gbn_score_args(fn, a, n_vars, score_type, score_arg, score_arg2)) return e;
+    if (!moments || !parents || !local || !out || !status) return failf(10, "%s: null pointer", fn);
+    gbn_fill(a, batch, n_vars, moments, set_of, parents, local, out, status);
+    call_begin();
+    dvs_launch_gbn_scores(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_gbn_toggle_scores(int32_t batch, int32_t n_vars, const double* moments, int32_t n_sets, const int32_t* set_of,
+                                     const uint64_t* parents, int32_t score_type, double score_arg, double score_arg2,
+                                     const int32_t* worklist, double* local, size_t local_bytes, double* toggles,
+                                     size_t toggles_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_toggle_scores";
+    if (int e = gbn_dims(fn, batch, n_vars, n_sets, true)) return e;
+    GbnToggleArgs t = {};
+    if (int e = gbn_score_args(fn, t.s, n_vars, score_type, score_arg, score_arg2)) return e;
+    if (!moments || !parents || !local || !toggles || !status) return failf(10, "%s: null pointer", fn);
+    if (int e = toggle_buffers({fn, batch, n_vars}, local_bytes, toggles_bytes)) return e;
+    gbn_fill(t.s, batch, n_vars, moments, set_of, parents, local, nullptr, status);
+    t.worklist = worklist;
+    t.toggles = toggles;
+    call_begin();
+    dvs_launch_gbn_toggle(t, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_gbn_fit(int32_t batch, int32_t n_vars, const double* moments, int32_t n_sets, const int32_t* set_of,
+                           const uint64_t* parents, double* coef, size_t coef_bytes, double* intercept, double* sd,
+                           int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_fit";
+    if (int e = gbn_dims(fn, batch, n_vars, n_sets, true)) return e;
+    if (!moments || !parents || !coef || !intercept || !sd || !status) return failf(10, "%s: null pointer", fn);
+    const size_t need = (size_t)batch * n_vars * n_vars * 8;
+    if (coef_bytes < need) return fail_size("dvs_gbn_fit: coef_bytes < batch * n_vars^2 * 8", need);
+    GbnFitArgs t = {};
+    t.s.type = DVS_GSCORE_LOGLIK;
+    gbn_fill(t.s, batch, n_vars, moments, set_of, parents, nullptr, nullptr, status);
+    t.coef = coef;
+    t.intercept = intercept;
+    t.sd = sd;
+    call_begin();
+    dvs_launch_gbn_fit(t, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -13,6 +13,7 @@
 #include "../../include/dvs_available.h"
 #include "../../include/dvs_local.h"
 #include "../../include/dvs_permtest.h"
+#include "../../include/dvs_gaussian.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -616,6 +617,54 @@ struct CiPermArgs {
     int* used;                   // [T]
 };
 void dvs_launch_ci_perm(const CiPermArgs& a, uint64_t seed, dvs_stream_t st);
+
+// ---- Gaussian networks (dvs_gaussian.h; include/dvs_gaussian.h) ----------------------------------------------------------------
+// The workspace of dvs_gbn_moments: the chunk column sums [n_sets][chunks][n], then the chunk cells [n_sets][chunks][n (n + 1) / 2].
+struct GbnMomentLayout {
+    size_t chunks, tri, cells, total;            // cells: byte offset of the chunk cells
+};
+inline GbnMomentLayout dvs_gbn_moment_layout(long long n, long long n_sets, long long set_size) {
+    GbnMomentLayout l;
+    l.chunks = (size_t)((set_size + DVS_GBN_CHUNK - 1) / DVS_GBN_CHUNK);
+    l.tri = (size_t)(n * (n + 1) / 2);
+    l.cells = (size_t)n_sets * l.chunks * (size_t)n * 8;
+    l.total = l.cells + (size_t)n_sets * l.chunks * l.tri * 8;
+    return l;
+}
+struct GbnMomentArgs {
+    int n, n_sets, set_size, chunks, tri;        // chunks, tri: launcher
+    const double* data;          // [n_samples][n]
+    const int* rows;             // [n_sets][set_size] or null: the one set is the data in order
+    double* sums;                // workspace [n_sets][chunks][n]
+    double* cells;               // workspace [n_sets][chunks][tri]
+    double* moments;             // [n_sets][DVS_GBN_STRIDE(n)]
+};
+void dvs_launch_gbn_moments(const GbnMomentArgs& a, dvs_stream_t st);
+
+struct GbnScoreArgs {
+    int B, n, type;              // type: dvs_gscore_type; the fit takes DVS_GSCORE_LOGLIK's refusals
+    double arg, arg2, t;         // aic / bic: k (NaN: log(m) / 2 on the device); bge: alpha_mu, alpha_w and t
+    const double* moments;       // [n_sets][DVS_GBN_STRIDE(n)]
+    const int* set_of;           // [B] or null: set 0
+    const uint64_t* parents;     // [B][n]
+    double* local;               // [B][n]
+    double* out;                 // [B]; unused by the toggle pass
+    int* status;
+};
+void dvs_launch_gbn_scores(const GbnScoreArgs& a, dvs_stream_t st);
+struct GbnToggleArgs {
+    GbnScoreArgs s;
+    const int* worklist;         // null: full pass; else i32 [2 B]
+    double* toggles;             // T [B][n][n]
+};
+void dvs_launch_gbn_toggle(const GbnToggleArgs& a, dvs_stream_t st);
+struct GbnFitArgs {
+    GbnScoreArgs s;              // s.local, s.out unused
+    double* coef;                // [B][n][n]
+    double* intercept;           // [B][n]
+    double* sd;                  // [B][n]
+};
+void dvs_launch_gbn_fit(const GbnFitArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

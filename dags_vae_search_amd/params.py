@@ -102,6 +102,7 @@ def bn_fit(evaluator, parents, *, method: str = "mle", iss=None, unobserved: str
     (N_jk + a) / (N_j + r a), a = iss / (r q); ``iss`` defaults to 1).  The rows are read back once to lay out the tables; a
     family of more than 36 864 cells raises ValueError before anything is launched."""
     what = "bn_fit"
+    dl.need_discrete(what, evaluator)
     dl.need_cuda(what, evaluator.device)
     if method not in dl.FIT_METHODS:
         raise ValueError(f"method must be one of {sorted(dl.FIT_METHODS)} (got {method!r})")
@@ -221,6 +222,7 @@ def cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 0, method
     is the argument of "pred-lw" alone; a row that predicts 255 counts as wrong).  "pred-lw" runs one likelihood-weighting call
     per structure and part; the other two take the whole batch of structures in one call per part.  bnlearn has "pred" and "pred-lw"; "pred-exact" is what "pred-lw" approximates."""
     what = "cross_validate"
+    dl.need_discrete(what, evaluator)
     dl.need_cuda(what, evaluator.device)
     S = evaluator.n_samples
     if not 2 <= int(folds) <= S:

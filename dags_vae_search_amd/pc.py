@@ -39,6 +39,7 @@ class PCResult(NamedTuple):
 
 
 def _evaluator(what, evaluator):
+    dl.need_discrete(what, evaluator)
     dl.need_cuda(what, evaluator.device)
     return evaluator.card_host
 
