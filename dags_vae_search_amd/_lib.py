@@ -23,6 +23,7 @@ AVAIL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_available.h"
 LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_local.h")      # the fourth: grouped CI tests, the MMPC round
 PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_permtest.h")    # the fifth: Monte Carlo permutation CI tests
 GAUSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian.h")   # the sixth: Gaussian networks on real-valued data
+GCI_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_ci.h")  # the seventh: CI tests on real-valued data
 
 
 class DvsShape(Structure):
@@ -99,6 +100,8 @@ LOCAL_SIGNATURES, _ = _read_header(LOCAL_HEADER)
 PERM_SIGNATURES, _P = _read_header(PERM_HEADER)
 # include/dvs_gaussian.h, the sixth: moments, Gaussian scores, their toggle pass and the fit; the six tables above stay what they are
 GAUSS_SIGNATURES, _G = _read_header(GAUSS_HEADER)
+# include/dvs_gaussian_ci.h, the seventh: dvs_gbn_ci_tests and dvs_gbn_ci_tests_group; the seven tables above stay what they are
+GCI_SIGNATURES, _GC = _read_header(GCI_HEADER)
 
 
 def signature(fn: str):
@@ -117,8 +120,11 @@ def signature(fn: str):
         return PERM_SIGNATURES[fn]
     if fn in GAUSS_SIGNATURES:
         return GAUSS_SIGNATURES[fn]
+    if fn in GCI_SIGNATURES:
+        return GCI_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
-                   f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h and include/dvs_gaussian.h")
+                   f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h and "
+                   f"include/dvs_gaussian_ci.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -146,6 +152,8 @@ CI_PERM_TYPES = {k: _P["DVS_CI_" + k.upper().replace("-", "_")]      # dvs_ci_pe
 GSCORE_TYPES = {k: _G["DVS_GSCORE_" + k.upper()[:-2] if k.endswith("-g") else "DVS_GSCORE_" + k.upper()]     # dvs_gscore_type
                 for k in ("loglik-g", "aic-g", "bic-g", "bge")}
 GBN_CHUNK, GBN_MAX_PARENTS = _G["DVS_GBN_CHUNK"], _G["DVS_GBN_MAX_PARENTS"]      # include/dvs_gaussian.h
+GCI_TYPES = {k: _GC["DVS_GCI_" + k.upper().replace("-", "_")] for k in ("cor", "zf", "mi-g")}      # dvs_gci_type
+GCI_MAX_COND = _GC["DVS_GCI_MAX_COND"]     # the largest conditioning set of a Gaussian CI test (include/dvs_gaussian_ci.h)
 
 
 def gbn_stride(n: int) -> int:
@@ -171,7 +179,8 @@ ELIM_MAX_CELLS, ELIM_MAX_WORDS, ELIM_MAX_SCOPE, ELIM_MAX_INPUTS, ELIM_TAG = (
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
-                                  *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items()):
+                                  *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items(),
+                                  *GCI_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]
@@ -249,10 +258,14 @@ def require_cuda(t, what: str):
                            f"this package has no CPU path")
 
 
+GCI_ENTRY_POINTS = ("ci_tests", "ci_test", "pc_stable", "mmpc", "ci_tests_group", "rsmax2", "mmhc")
+
+
 def need_discrete(what, evaluator):
     """the entry points that read ``packed`` / ``card`` refuse an evaluator over real-valued data (gaussian.py)"""
     if getattr(evaluator, "continuous", False):
-        raise ValueError(f"{what}: the evaluator holds real-valued data and {what} reads discrete levels: its Gaussian "
+        gci = " (its tests on real-valued data are test=\"cor\", \"zf\" and \"mi-g\")" if what in GCI_ENTRY_POINTS else ""
+        raise ValueError(f"{what}: the evaluator holds real-valued data and {what} reads discrete levels{gci}: its Gaussian "
                          f"counterpart is not built")
 
 

@@ -735,6 +735,63 @@ extern "C" int dvs_gbn_fit(int32_t batch, int32_t n_vars, const double* moments,
     return call_end(fn);
 }
 
+// ---- Gaussian CI tests (dvs_gaussian_ci.h; include/dvs_gaussian_ci.h) -----------------------------------------------------------
+// what the two entry points check first: counts (2), n_vars (3), the range of the cell index (2), test_type (12)
+static int gci_dims(const char* fn, const char* count, const char* cells_text, int items, int n_vars, int n_sets, bool per_var, int test_type) {
+    if (items <= 0 || n_sets <= 0) return failf(2, "%s: %s and n_sets must be > 0", fn, count);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if ((int64_t)items * (per_var ? n_vars : 1) * 3 > (int64_t)0x7fffffff) return failf(2, "%s: %s must be < 2^31", fn, cells_text);
+    if (test_type < DVS_GCI_COR || test_type > DVS_GCI_MI_G) return failf(12, "%s: test_type is not a dvs_gci_type", fn);
+    return 0;
+}
+
+extern "C" int dvs_gbn_ci_tests(int32_t n_tests, int32_t n_vars, const double* moments, int32_t n_sets, const int32_t* set_of,
+                                const int32_t* pairs, const uint64_t* cond, int32_t test_type, double* out, size_t out_bytes,
+                                int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_ci_tests";
+    if (int e = gci_dims(fn, "n_tests", "n_tests * 3", n_tests, n_vars, n_sets, false, test_type)) return e;
+    if (!moments || !pairs || !cond || !out || !status) return failf(10, "%s: null pointer", fn);
+    if (out_bytes < (size_t)n_tests * 24) return fail_size("dvs_gbn_ci_tests: out_bytes < n_tests * 24", (size_t)n_tests * 24);
+    GbnCiArgs a = {};
+    a.T = n_tests;
+    a.n = n_vars;
+    a.type = test_type;
+    a.moments = moments;
+    a.set_of = set_of;
+    a.pairs = pairs;
+    a.cond = cond;
+    a.out = out;
+    a.status = status;
+    call_begin();
+    dvs_launch_gbn_ci(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_gbn_ci_tests_group(int32_t n_groups, int32_t n_vars, const double* moments, int32_t n_sets, const int32_t* set_of,
+                                      const int32_t* target, const uint64_t* cond, const uint64_t* candidates, int32_t test_type,
+                                      double* out, size_t out_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_ci_tests_group";
+    if (int e = gci_dims(fn, "n_groups", "n_groups * n_vars * 3", n_groups, n_vars, n_sets, true, test_type))
+        return e;
+    if (!moments || !target || !cond || !candidates || !out || !status) return failf(10, "%s: null pointer", fn);
+    const size_t need = (size_t)n_groups * n_vars * 24;
+    if (out_bytes < need) return fail_size("dvs_gbn_ci_tests_group: out_bytes < n_groups * n_vars * 24", need);
+    GbnCiGroupArgs a = {};
+    a.G = n_groups;
+    a.n = n_vars;
+    a.type = test_type;
+    a.moments = moments;
+    a.set_of = set_of;
+    a.target = target;
+    a.cond = cond;
+    a.candidates = candidates;
+    a.out = out;
+    a.status = status;
+    call_begin();
+    dvs_launch_gbn_ci_group(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

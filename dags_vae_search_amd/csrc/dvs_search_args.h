@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -14,6 +14,7 @@
 #include "../../include/dvs_local.h"
 #include "../../include/dvs_permtest.h"
 #include "../../include/dvs_gaussian.h"
+#include "../../include/dvs_gaussian_ci.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -665,6 +666,29 @@ struct GbnFitArgs {
     double* sd;                  // [B][n]
 };
 void dvs_launch_gbn_fit(const GbnFitArgs& a, dvs_stream_t st);
+
+// ---- Gaussian CI tests (dvs_gaussian_ci.h; include/dvs_gaussian_ci.h) -----------------------------------------------------------
+struct GbnCiArgs {
+    int T, n, type;              // type: dvs_gci_type
+    const double* moments;       // [n_sets][DVS_GBN_STRIDE(n)]
+    const int* set_of;           // [T] or null: set 0
+    const int* pairs;            // [T][2]: x, y
+    const uint64_t* cond;        // [T]: bit z <=> z is in the conditioning set
+    double* out;                 // [T][3]: statistic, df, p-value; NaN where refused
+    int* status;
+};
+void dvs_launch_gbn_ci(const GbnCiArgs& a, dvs_stream_t st);
+struct GbnCiGroupArgs {
+    int G, n, type;
+    const double* moments;       // [n_sets][DVS_GBN_STRIDE(n)]
+    const int* set_of;           // [G] or null: set 0
+    const int* target;           // [G]: x, factored once with Z
+    const uint64_t* cond;        // [G]
+    const uint64_t* candidates;  // [G]: bit c <=> c is tested against the target
+    double* out;                 // [G][n][3]; NaN where not asked or refused
+    int* status;
+};
+void dvs_launch_gbn_ci_group(const GbnCiGroupArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

@@ -11,8 +11,11 @@ The definitions are those of include/dvs_gaussian.h.  Three things follow bnlear
 run: the unbiased residual variance RSS / (m - p - 1) in the likelihood, the defaults alpha_mu = 1 (``iss_mu``) and alpha_w =
 n + 2 (``iss_w``) of ``bge``, and its prior mean, the sample mean.  A family whose Cholesky pivot is within rounding of zero (a
 duplicated or collinear column) and a family of more than ``_lib.GBN_MAX_PARENTS`` parents are refused: NaN in their cell.
-The entry points that read discrete levels (``ci_tests``, ``pc_stable``, ``mmpc``, ``ci_tests_group``, ``bn_fit``,
-``cross_validate``, ``available_case``) raise ``ValueError`` on this evaluator: their Gaussian counterparts are not built.
+``ci_tests``, ``ci_test``, ``pc_stable``, ``ci_tests_group``, ``mmpc``, ``rsmax2`` and ``mmhc`` take this evaluator with
+``test`` "cor", "zf" or "mi-g" (include/dvs_gaussian_ci.h, DESIGN.md §30: the tests read ``moments``); with a discrete or
+permutation test name, their default "mi" included, they raise ``ValueError``.  The entry points that read discrete levels
+alone (``bn_fit``, ``cross_validate``, ``available_case``) raise ``ValueError`` on this evaluator: their Gaussian counterparts
+are not built.
 """
 from __future__ import annotations
 

@@ -1,5 +1,6 @@
 """Local and hybrid structure learning on the device (csrc/dvs_local.h): bnlearn's ``mmpc``, ``mmhc`` and
-``rsmax2`` for discrete data, next to ``pc.py`` and the score-based searches.
+``rsmax2`` for discrete data and, with ``test`` in {"cor", "zf", "mi-g"} on a ``GaussianEvaluator``, for real-valued data
+(csrc/dvs_gaussian_ci.h), next to ``pc.py`` and the score-based searches.
 
 ``ci_tests_group`` evaluates conditional-independence tests grouped by (target, conditioning set): one workgroup scans the
 rows once for every candidate of its group, and each cell is byte for byte what ``ci_tests`` gives for the same test.
@@ -27,7 +28,7 @@ import torch
 
 from . import _lib as dl
 from .hillclimb import hill_climb
-from .pc import _evaluator, pc_stable, skeleton_blacklist
+from .pc import _evaluator, _gaussian, _one_set, pc_stable, skeleton_blacklist
 from .pc import _test_type as _any_test_type
 from .tabu import tabu_search
 
@@ -48,7 +49,8 @@ class MMPCResult(NamedTuple):
     forward: torch.Tensor                  # int64 [n]: the same after the forward phase alone
     sepsets: torch.Tensor                  # int64 [n, n]: cell [t, x] the conditioning set that separated x from target t
     groups_per_round: List[int]            # (target, conditioning set) groups of forward round 0, 1, ..., then of the backward pass
-    refused: int                           # tests that were refused (table too large): never counted as independence
+    refused: int                           # tests that were refused (table too large; on real-valued data a conditioning set
+                                           # beyond dl.GCI_MAX_COND or a collinear one): never counted as independence
     asymmetric: int                        # members removed by the symmetry correction (x in cpc(t), t not in cpc(x))
 
 
@@ -68,8 +70,14 @@ def _tensor_arg(what, name, t, dtype, shape_text, ok):
     return t.contiguous()
 
 
-def _launch_group(evaluator, target, cond, candidates, typ, lds_cells, out, status):
+def _launch_group(evaluator, target, cond, candidates, typ, lds_cells, out, status, sets=None):
     lib, p, G = evaluator.lib, dl.ptr, target.numel()
+    if _gaussian(evaluator):
+        n_sets, set_of = (evaluator.moments.shape[0], None) if sets is None else sets
+        dl.check(lib, lib.dvs_gbn_ci_tests_group(G, evaluator.n_vars, p(evaluator.moments), n_sets, p(set_of), p(target), p(cond),
+                                                 p(candidates), typ, p(out), dl.nbytes(out), p(status), dl.stream()),
+                 "dvs_gbn_ci_tests_group")
+        return
     dl.check(lib, lib.dvs_ci_tests_group(G, evaluator.n_vars, evaluator.n_samples, p(evaluator.packed), p(evaluator.card), p(target),
                                          p(cond), p(candidates), typ, lds_cells, p(out), dl.nbytes(out), p(status), dl.stream()),
              "dvs_ci_tests_group")
@@ -82,10 +90,14 @@ def ci_tests_group(evaluator, targets, cond, candidates, test: str = "mi", *, ld
     variables in ``cond[g]`` for every x in ``candidates[g]``, byte for byte what ``ci_tests`` returns for it, and three NaNs
     for every other x.  A candidate is refused (three NaNs, bit 4 of the status word) by the rules of ``ci_tests``, its table
     against ``lds_cells`` (None: 36 864, all of the LDS a workgroup can count in; the workgroup takes a group's candidates
-    in as many passes over the rows as their tables need)."""
+    in as many passes over the rows as their tables need).
+
+    On a ``GaussianEvaluator`` with ``test`` in {"cor", "zf", "mi-g"} (include/dvs_gaussian_ci.h) one lane factors the
+    conditioning set and the target once and appends a row per candidate; the cells are ``ci_tests``' bytes for the pair
+    (``targets[g]``, x), ``lds_cells`` is not read, and on a row-set view group g reads set g, or ``set_of[g]``."""
     what = "ci_tests_group"
-    _evaluator(what, evaluator)
     typ = _test_type(what, test)
+    gaussian = _evaluator(what, evaluator, test) is None
     targets = _tensor_arg(what, "targets", targets, torch.int32, "int32 [G >= 1]", lambda t: t.ndim == 1 and t.numel() >= 1)
     G = targets.numel()
     cond = _tensor_arg(what, "cond", cond, torch.int64, f"int64 [{G}] bit masks", lambda t: t.shape == (G,))
@@ -99,7 +111,7 @@ def ci_tests_group(evaluator, targets, cond, candidates, test: str = "mi", *, ld
     with torch.cuda.device(dev):
         out = torch.empty(G, evaluator.n_vars, 3, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _launch_group(evaluator, targets, cond, candidates, typ, lds_cells, out, status)
+        _launch_group(evaluator, targets, cond, candidates, typ, lds_cells, out, status, evaluator._sets(G) if gaussian else None)
     return (out, status) if return_status else out
 
 
@@ -175,7 +187,11 @@ def mmpc(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: int = 3,
 
     ``max_cond=3`` is a choice, not a measurement: bnlearn's ``max.sx`` is unbounded.  ``targets`` (None: all) restricts the
     search to those targets; the symmetry correction then leaves edges among them only.  A refused test (a table beyond
-    36 864 cells) is counted in ``refused`` and never read as independence."""
+    36 864 cells) is counted in ``refused`` and never read as independence.
+
+    On a ``GaussianEvaluator`` ``test`` is "cor", "zf" or "mi-g" (``pc.ci_tests``).  ``cor`` and ``zf`` are signed, so the
+    statistic column is replaced by its absolute value before the round's update reads it.  ``max_cond`` may exceed
+    ``_lib.GCI_MAX_COND``: the tests beyond it, and those on a collinear conditioning set, are counted in ``refused``."""
     return _mmpc(evaluator, alpha, test, max_cond, targets)
 
 
@@ -183,8 +199,10 @@ def _mmpc(evaluator, alpha, test, max_cond, targets, rounds=None):
     """``mmpc``; ``rounds``, a list, receives (phase, target, cond, candidates, lds_cells) of every round as it is launched
     (bench_mmpc.py replays them)"""
     what = "mmpc"
-    card = _evaluator(what, evaluator)
     typ = _test_type(what, test)
+    card = _evaluator(what, evaluator, test)
+    _one_set(what, evaluator)
+    gaussian = card is None
     if not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("alpha must be in [0, 1]")
     if int(max_cond) < 0:
@@ -194,7 +212,7 @@ def _mmpc(evaluator, alpha, test, max_cond, targets, rounds=None):
     chosen = list(range(n)) if targets is None else sorted({int(t) for t in targets})
     if not chosen or chosen[0] < 0 or chosen[-1] >= n:
         raise ValueError(f"{what}: targets must name variables in [0, {n})")
-    card = [int(c) for c in card]
+    card = None if gaussian else [int(c) for c in card]
     full = (1 << n) - 1
 
     def dev_u64(values):
@@ -231,10 +249,12 @@ def _mmpc(evaluator, alpha, test, max_cond, targets, rounds=None):
             d_z, d_c = dev_u64(cond), dev_u64(candidates)
             d_off = torch.tensor(offsets, dtype=torch.int64, device=dev)
             out = torch.empty(G, n, 3, dtype=torch.float64, device=dev)
-            lds_cells = _lds_cells(card, target, cond, candidates)
+            lds_cells = 0 if gaussian else _lds_cells(card, target, cond, candidates)
             if rounds is not None:
                 rounds.append((phase, target, cond, candidates, lds_cells))
             _launch_group(evaluator, d_t, d_z, d_c, typ, lds_cells, out, status)
+            if gaussian:
+                out[:, :, 0].abs_()              # cor and zf are signed; the tie rule takes the larger minimum statistic
             dl.check(lib, lib.dvs_mmpc_update(n, G, phase, p(d_t), p(d_z), p(d_c), p(d_off), p(out), dl.nbytes(out), float(alpha),
                                               p(cur[0]), p(cur[1]), p(nxt[0]), p(nxt[1]), p(last), p(pmax), p(smin), p(sepsets),
                                               n * n * 8, p(refused), p(result), n * 16, dl.stream()), "dvs_mmpc_update")
@@ -265,7 +285,8 @@ def _mmpc(evaluator, alpha, test, max_cond, targets, rounds=None):
 def rsmax2(evaluator, *, restrict: str = "mmpc", maximize: str = "hc", restrict_args: Optional[Dict] = None,
            maximize_args: Optional[Dict] = None) -> RSMAX2Result:
     """Restrict, then maximise (bnlearn's ``rsmax2``): learn a skeleton with ``mmpc`` ("mmpc") or ``pc_stable`` ("pc.stable") on
-    the evaluator's packed data with ``restrict_args``, then run ``hill_climb`` ("hc") or ``tabu_search`` ("tabu") on the
+    the evaluator's packed data (on a ``GaussianEvaluator``: its moments, ``restrict_args`` naming ``test`` "cor", "zf" or
+    "mi-g") with ``restrict_args``, then run ``hill_climb`` ("hc") or ``tabu_search`` ("tabu") on the
     evaluator's metric with ``maximize_args`` and ``forbidden=skeleton_blacklist(skeleton)``, so that every learned arc lies in
     the skeleton.  ``max_steps`` defaults to max(16, n^2); ``maximize_args`` may not name ``forbidden``.  A composition: it
     launches what its two halves launch."""
@@ -278,7 +299,8 @@ def rsmax2(evaluator, *, restrict: str = "mmpc", maximize: str = "hc", restrict_
         raise ValueError(f"{what}: maximize must be one of {sorted(searches)} (got {maximize!r})")
     if "forbidden" in (maximize_args or {}):
         raise ValueError(f"{what}: forbidden is the learned skeleton's blacklist and cannot be given in maximize_args")
-    _evaluator(what, evaluator)
+    if not _gaussian(evaluator):             # a Gaussian evaluator is judged by the restrict step against the test it is given
+        _evaluator(what, evaluator)
     restricted = restrictors[restrict](evaluator, **(restrict_args or {}))
     n = evaluator.n_vars
     search_args = {"max_steps": max(16, n * n), **(maximize_args or {})}

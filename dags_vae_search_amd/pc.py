@@ -1,5 +1,6 @@
 """Constraint-based structure learning on the device (csrc/dvs_citest.h): bnlearn's ``ci.test`` and
-``pc.stable`` for discrete data, next to the score-based searches.
+``pc.stable`` for discrete data and, with ``test`` in {"cor", "zf", "mi-g"} on a ``GaussianEvaluator``, for real-valued data
+(csrc/dvs_gaussian_ci.h), next to the score-based searches.
 
 ``ci_tests`` evaluates a batch of conditional-independence tests (G^2 ``mi``, Pearson ``x2`` and their ``-adf`` variants, and
 the Monte Carlo permutation family ``mc-``, ``smc-``, ``sp-`` ``mi`` / ``x2`` of csrc/dvs_permtest.h) on the
@@ -10,6 +11,9 @@ evaluator's packed data set; ``pc_stable`` runs the order-independent PC skeleto
 The definitions are those of include/dvs.h (dvs_ci_tests, dvs_pc_expand, dvs_pc_reduce, dvs_pc_orient).  Parity with
 bnlearn's ``ci.test`` / ``pc.stable`` rests on them and is not pinned against an R run.  The permutation tests are defined in
 include/dvs_permtest.h; their p-value is count / B, bnlearn's convention as recalled, and that too is not pinned against R.
+The Gaussian tests are defined in include/dvs_gaussian_ci.h: one Cholesky factor of the moments per test, no pass over the
+rows; Student's t for ``cor``, Fisher's z for ``zf``, the chi-square form for ``mi-g``, as bnlearn's are recalled and unpinned
+against R as well.  A discrete test name on a Gaussian evaluator and a Gaussian test name on a discrete one raise ``ValueError``.
 """
 from __future__ import annotations
 
@@ -33,24 +37,48 @@ class PCResult(NamedTuple):
     skeleton: torch.Tensor                 # int64 [n]: symmetric adjacency rows
     sepsets: torch.Tensor                  # int64 [n, n]: the separating set of every separated pair, as a bit mask
     tests_per_level: List[int]             # tests evaluated at level 0, 1, ...
-    refused: int                           # tests that were refused (table too large): never counted as independence
+    refused: int                           # tests that were refused (table too large; on real-valued data a conditioning set
+                                           # beyond dl.GCI_MAX_COND or a collinear one): never counted as independence
     conflicts: int                         # edges that colliders claimed in both directions (left undirected)
     flags: int                             # 0, or 1 when the directed part of ``pdag`` has a cycle
 
 
-def _evaluator(what, evaluator):
+def _gaussian(evaluator):
+    """whether the evaluator holds real-valued data (gaussian.py): its tests are dl.GCI_TYPES over ``evaluator.moments``"""
+    return getattr(evaluator, "continuous", False)
+
+
+def _evaluator(what, evaluator, test=None):
+    """the level counts of a discrete evaluator, or None for a Gaussian one asked for one of its own tests (dl.GCI_TYPES); a
+    test of the other kind of data is a ValueError"""
+    if test in dl.GCI_TYPES:
+        if not _gaussian(evaluator):
+            raise ValueError(f"{what}: test {test!r} reads real-valued data and the evaluator holds discrete levels: pass a "
+                             f"GaussianEvaluator, or one of {sorted(dl.CI_TYPES) + sorted(dl.CI_PERM_TYPES)}")
+        dl.need_cuda(what, evaluator.device)
+        return None
     dl.need_discrete(what, evaluator)
     dl.need_cuda(what, evaluator.device)
     return evaluator.card_host
 
 
 def _test_type(test):
-    """the dvs_ci_type of an asymptotic test, or the name itself for a permutation test (dl.CI_PERM_TYPES)"""
+    """the dvs_ci_type of an asymptotic test, the dvs_gci_type of a Gaussian one (dl.GCI_TYPES), or the name itself for a
+    permutation test (dl.CI_PERM_TYPES)"""
     if test in dl.CI_PERM_TYPES:
         return test
+    if test in dl.GCI_TYPES:
+        return dl.GCI_TYPES[test]
     if test not in dl.CI_TYPES:
-        raise ValueError(f"test must be one of {sorted(dl.CI_TYPES) + sorted(dl.CI_PERM_TYPES)} (got {test!r})")
+        raise ValueError(f"test must be one of {sorted(dl.CI_TYPES) + sorted(dl.CI_PERM_TYPES) + sorted(dl.GCI_TYPES)} (got {test!r})")
     return dl.CI_TYPES[test]
+
+
+def _one_set(what, evaluator):
+    """pc_stable and mmpc learn one structure: a row-set view of several sets has no single data set to learn it from"""
+    if _gaussian(evaluator) and evaluator.moments.shape[0] != 1:
+        raise ValueError(f"{what}: the evaluator is a view of {evaluator.moments.shape[0]} row sets and {what} learns from one: "
+                         f"pass the base evaluator or a view of one set")
 
 
 class _Perm(NamedTuple):
@@ -96,7 +124,20 @@ def _run_perm_tests(evaluator, pairs, cond, test, perm, max_cells, out, status, 
                                             p(out[t0:]), m * 24, p(used[t0:]), p(status), dl.stream()), "dvs_ci_perm_tests")
 
 
+def _run_gaussian_tests(evaluator, pairs, cond, typ, out, status, chunk, sets=None):
+    """dvs_gbn_ci_tests over the evaluator's moments in chunks; ``sets`` = (n_sets, set_of int32 [T] or None: set 0)"""
+    lib, T, p = evaluator.lib, cond.numel(), dl.ptr
+    n_sets, set_of = (evaluator.moments.shape[0], None) if sets is None else sets
+    for t0 in range(0, T, chunk):
+        m = min(chunk, T - t0)
+        dl.check(lib, lib.dvs_gbn_ci_tests(m, evaluator.n_vars, p(evaluator.moments), n_sets, None if set_of is None else p(set_of[t0:]),
+                                           p(pairs[t0:]), p(cond[t0:]), typ, p(out[t0:]), m * 24, p(status), dl.stream()),
+                 "dvs_gbn_ci_tests")
+
+
 def _run_tests(evaluator, pairs, cond, typ, max_cells, out, status, chunk, perm=None, used=None):
+    if _gaussian(evaluator):
+        return _run_gaussian_tests(evaluator, pairs, cond, typ, out, status, chunk)
     if perm is not None:
         if used is None:
             used = torch.empty(cond.numel(), dtype=torch.int32, device=evaluator.device)
@@ -122,10 +163,16 @@ def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = 
     threshold of the sequential ``smc-`` tests' early stop and is not read otherwise.  p = count / B follows bnlearn's
     convention as recalled; parity with an R run is not pinned.  ``return_used=True`` (permutation tests only) also returns
     int32 [T], the permutations each test counted: B, fewer where an ``smc-`` test stopped early, 0 for a refused test.  The
-    returns come in the order (out, status, used)."""
+    returns come in the order (out, status, used).
+
+    On a ``GaussianEvaluator``, ``test`` in {"cor", "zf", "mi-g"} (include/dvs_gaussian_ci.h) reads the evaluator's moments:
+    (Student's t, m - k - 2, two-sided p), (Fisher's z, m - k - 3, two-sided p) or (-m log(1 - r^2), 1, p) with r the partial
+    correlation of x and y given the k conditioning variables and m the rows.  Refused (three NaNs): x = y, x or y in the
+    conditioning set, an index outside the data, more than ``_lib.GCI_MAX_COND`` conditioning variables, df < 1, and a
+    collinear set (a Cholesky pivot within rounding of zero).  On a row-set view test t reads set t, or ``set_of[t]``."""
     what = "ci_tests"
-    card = _evaluator(what, evaluator)
     typ = _test_type(test)
+    card = _evaluator(what, evaluator, test)
     perm = _Perm.of(what, test, B, seed, alpha, test_offset) if test in dl.CI_PERM_TYPES else None
     if return_used and perm is None:
         raise ValueError(f"{what}: return_used goes with a permutation test (got {test!r})")
@@ -143,6 +190,11 @@ def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = 
     dev = evaluator.device
     with torch.cuda.device(dev):
         pairs, cond = pairs.contiguous(), cond.contiguous()
+        if card is None:
+            out = torch.empty(cond.numel(), 3, dtype=torch.float64, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            _run_gaussian_tests(evaluator, pairs, cond, typ, out, status, chunk, evaluator._sets(cond.numel()))
+            return (out, status) if return_status else out
         # the largest conditioning set sizes the LDS table: a popcount of the bits below n_vars (a higher bit is refused anyway)
         x = cond & ((1 << evaluator.n_vars) - 1)
         x = x - ((x >> 1) & 0x5555555555555555)
@@ -162,7 +214,7 @@ def ci_test(evaluator, x: int, y: int, cond=(), test: str = "mi", *, B: int = 50
     """one test of x against y given the variables in ``cond`` -> float64 [3] on the device: (statistic, df, p-value); the
     keywords are those of ``ci_tests`` for a permutation test (with ``return_used`` the result is (float64 [3], int32 [], the
     permutations counted))"""
-    _evaluator("ci_test", evaluator)
+    _evaluator("ci_test", evaluator, test)
     mask = 0
     for z in cond:
         if not 0 <= int(z) < 63:
@@ -200,10 +252,13 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
     the search stops at the first level where no adjacent pair has enough neighbours left).  ``chunk``: tests per launch.
     With a permutation ``test`` (``ci_tests``), ``B`` permutations per test are drawn from ``seed``, ``alpha`` is also the
     ``smc-`` tests' stopping threshold, and the tests are numbered on across the levels (test t of a level draws as global test
-    ``tests of the earlier levels + t``), so the result is a function of the seed alone, not of ``chunk``."""
+    ``tests of the earlier levels + t``), so the result is a function of the seed alone, not of ``chunk``.
+    On a ``GaussianEvaluator`` ``test`` is "cor", "zf" or "mi-g" (``ci_tests``); ``max_cond`` may exceed
+    ``_lib.GCI_MAX_COND``: the tests beyond it come back refused and are counted in ``refused``, never as independence."""
     what = "pc_stable"
-    card = _evaluator(what, evaluator)
     typ = _test_type(test)
+    card = _evaluator(what, evaluator, test)
+    _one_set(what, evaluator)
     if not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("alpha must be in [0, 1]")
     if chunk < 1:
@@ -242,7 +297,7 @@ def pc_stable(evaluator, *, alpha: float = 0.05, test: str = "mi", max_cond: Opt
             result = torch.empty(P, 2, dtype=torch.int64, device=dev)
             dl.check(lib, lib.dvs_pc_expand(P, n, level, p(d_adj), p(d_xy), p(d_off), T, p(pairs), p(cond), T * 8, dl.stream()),
                      "dvs_pc_expand")
-            _run_tests(evaluator, pairs, cond, typ, _max_cells(card, level), out, status, chunk,
+            _run_tests(evaluator, pairs, cond, typ, 0 if card is None else _max_cells(card, level), out, status, chunk,
                        perm and perm._replace(test_offset=sum(tests_per_level) & 0xFFFFFFFF))
             dl.check(lib, lib.dvs_pc_reduce(P, n, p(d_xy), p(d_off), T, p(cond), p(out), float(alpha), p(d_adj), p(d_next),
                                             p(sepsets), n * n * 8, p(result), P * 16, p(refused), dl.stream()), "dvs_pc_reduce")
