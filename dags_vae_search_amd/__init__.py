@@ -34,6 +34,7 @@ from .eliminate import (EliminationPlan, elimination_plan, evidence_probability,
                         exact_posterior)
 from .incomplete import (EMResult, ExpectedCounts, StructuralEMResult, available_case_evaluator, em_fit,  # noqa: F401
                          expected_counts, family_plans, fit_counts, impute, incomplete_rows, structural_em, target_plans)
-from .gaussian import FittedGBN, GaussianEvaluator, gaussian_fit  # noqa: F401
+from .gaussian import (FittedGBN, GaussianEvaluator, gaussian_cross_validate, gaussian_fit, gaussian_joint,  # noqa: F401
+                       gaussian_log_likelihood, gaussian_predict, gaussian_sample)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

@@ -24,6 +24,7 @@ LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_local.h")   
 PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_permtest.h")    # the fifth: Monte Carlo permutation CI tests
 GAUSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian.h")   # the sixth: Gaussian networks on real-valued data
 GCI_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_ci.h")  # the seventh: CI tests on real-valued data
+GPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_params.h")  # the eighth: a fitted Gaussian network
 
 
 class DvsShape(Structure):
@@ -102,6 +103,8 @@ PERM_SIGNATURES, _P = _read_header(PERM_HEADER)
 GAUSS_SIGNATURES, _G = _read_header(GAUSS_HEADER)
 # include/dvs_gaussian_ci.h, the seventh: dvs_gbn_ci_tests and dvs_gbn_ci_tests_group; the seven tables above stay what they are
 GCI_SIGNATURES, _GC = _read_header(GCI_HEADER)
+# include/dvs_gaussian_params.h, the eighth: joint, quantiles, sample, loglik, predict; the eight tables above stay what they are
+GPAR_SIGNATURES, _GP = _read_header(GPAR_HEADER)
 
 
 def signature(fn: str):
@@ -122,9 +125,11 @@ def signature(fn: str):
         return GAUSS_SIGNATURES[fn]
     if fn in GCI_SIGNATURES:
         return GCI_SIGNATURES[fn]
+    if fn in GPAR_SIGNATURES:
+        return GPAR_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
-                   f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h and "
-                   f"include/dvs_gaussian_ci.h")
+                   f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h, "
+                   f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -154,6 +159,7 @@ GSCORE_TYPES = {k: _G["DVS_GSCORE_" + k.upper()[:-2] if k.endswith("-g") else "D
 GBN_CHUNK, GBN_MAX_PARENTS = _G["DVS_GBN_CHUNK"], _G["DVS_GBN_MAX_PARENTS"]      # include/dvs_gaussian.h
 GCI_TYPES = {k: _GC["DVS_GCI_" + k.upper().replace("-", "_")] for k in ("cor", "zf", "mi-g")}      # dvs_gci_type
 GCI_MAX_COND = _GC["DVS_GCI_MAX_COND"]     # the largest conditioning set of a Gaussian CI test (include/dvs_gaussian_ci.h)
+GBN_PREDICT_MODES = {"parents": _GP["DVS_GBN_PREDICT_PARENTS"], "exact": _GP["DVS_GBN_PREDICT_EXACT"]}      # include/dvs_gaussian_params.h
 
 
 def gbn_stride(n: int) -> int:
@@ -180,7 +186,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
                                   *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items(),
-                                  *GCI_SIGNATURES.items()):
+                                  *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

@@ -792,6 +792,134 @@ extern "C" int dvs_gbn_ci_tests_group(int32_t n_groups, int32_t n_vars, const do
     return call_end(fn);
 }
 
+// ---- a fitted Gaussian network (dvs_gaussian_params.h; include/dvs_gaussian_params.h) -------------------------------------------
+static void gpar_net(GbnNet& net, int batch, int n_vars, const uint64_t* parents, const double* coef, const double* intercept,
+                     const double* sd, int32_t* status) {
+    net.B = batch;
+    net.n = n_vars;
+    net.parents = parents;
+    net.coef = coef;
+    net.intercept = intercept;
+    net.sd = sd;
+    net.status = status;
+}
+
+extern "C" int dvs_gbn_joint(int32_t batch, int32_t n_vars, const uint64_t* parents, const double* coef, const double* intercept,
+                             const double* sd, double* mean, double* cov, size_t cov_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_joint";
+    if (batch <= 0) return failf(2, "%s: batch must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if ((int64_t)batch * n_vars * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: batch * n_vars^2 must be < 2^31", fn);
+    if (!parents || !coef || !intercept || !sd || !mean || !cov || !status) return failf(10, "%s: null pointer", fn);
+    const size_t need = (size_t)batch * n_vars * n_vars * 8;
+    if (cov_bytes < need) return fail_size("dvs_gbn_joint: cov_bytes < batch * n_vars^2 * 8", need);
+    GbnJointArgs a = {};
+    gpar_net(a.net, batch, n_vars, parents, coef, intercept, sd, status);
+    a.mean = mean;
+    a.cov = cov;
+    call_begin();
+    dvs_launch_gbn_joint(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_gbn_quantiles(int64_t count, const uint64_t* k, double* z, void* stream) {
+    const char* fn = "dvs_gbn_quantiles";
+    if (count < 1 || count > (int64_t)0x7fffffff) return failf(2, "%s: count must be in [1, 2^31 - 1]", fn);
+    if (!k || !z) return failf(10, "%s: null pointer", fn);
+    GbnQuantileArgs a = {};
+    a.count = count;
+    a.k = k;
+    a.z = z;
+    call_begin();
+    dvs_launch_gbn_quantiles(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" size_t dvs_gbn_sample_workspace_bytes(int32_t n_vars) {
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", "dvs_gbn_sample_workspace_bytes"), 0;
+    return DVS_GBN_SAMPLE_WORKSPACE;
+}
+
+extern "C" int dvs_gbn_sample(int32_t n_vars, int64_t n_rows, const uint64_t* parents, const double* coef, const double* intercept,
+                              const double* sd, uint64_t seed, int64_t row_offset, void* workspace, size_t workspace_bytes,
+                              double* data_out, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_sample";
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (row_offset < 0) return failf(12, "%s: row_offset must be >= 0", fn);
+    if (!parents || !coef || !intercept || !sd || !workspace || !data_out || !status) return failf(10, "%s: null pointer", fn);
+    if (workspace_bytes < DVS_GBN_SAMPLE_WORKSPACE)
+        return fail_size("dvs_gbn_sample: workspace_bytes < dvs_gbn_sample_workspace_bytes", DVS_GBN_SAMPLE_WORKSPACE);
+    GbnSampleArgs a = {};
+    gpar_net(a.net, 1, n_vars, parents, coef, intercept, sd, status);
+    a.rows = n_rows;
+    a.row_offset = (uint32_t)row_offset;
+    a.header = (int*)workspace;
+    a.out = data_out;
+    call_begin();
+    dvs_launch_gbn_sample(a, seed, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+// what dvs_gbn_loglik and dvs_gbn_predict check first: batch, n_rows (2), n_vars (3), the index ranges (2)
+static int gpar_row_dims(const char* fn, int batch, int n_vars, int64_t n_rows) {
+    if (batch <= 0) return failf(2, "%s: batch must be > 0", fn);
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if ((int64_t)batch * n_vars > (int64_t)0x7fffffff || (int64_t)batch * ((n_rows + 255) / 256) > (int64_t)0x7fffffff)
+        return failf(2, "%s: batch * n_vars and batch * ceil(n_rows / 256) must be < 2^31", fn);
+    return 0;
+}
+
+extern "C" int dvs_gbn_loglik(int32_t batch, int32_t n_vars, int64_t n_rows, const double* data, const uint64_t* parents,
+                              const double* coef, const double* intercept, const double* sd, double* per_row, double* out,
+                              void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_loglik";
+    if (int e = gpar_row_dims(fn, batch, n_vars, n_rows)) return e;
+    if (!data || !parents || !coef || !intercept || !sd || !out || !workspace || !status) return failf(10, "%s: null pointer", fn);
+    const BnLoglikLayout l = dvs_bn_loglik_layout(batch, n_vars, n_rows);
+    const size_t need = l.logs + (size_t)batch * n_vars * 8;
+    if (workspace_bytes < need) return fail_size("dvs_gbn_loglik: workspace_bytes < partials + flags + batch * n_vars * 8", need);
+    GbnRowArgs a = {};
+    gpar_net(a.net, batch, n_vars, parents, coef, intercept, sd, status);
+    a.chunks = (int)l.chunks;
+    a.rows = n_rows;
+    a.data = data;
+    a.per_row = per_row;
+    a.out = out;
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.ok = (int*)((char*)workspace + l.fam_ok);
+    a.c = (double*)((char*)workspace + l.logs);
+    call_begin();
+    dvs_launch_gbn_loglik(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_gbn_predict(int32_t batch, int32_t n_vars, int64_t n_rows, const double* data, const uint64_t* parents,
+                               const double* coef, const double* intercept, const double* sd, int32_t target, int32_t mode,
+                               double* pred, double* var, void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_predict";
+    if (int e = gpar_row_dims(fn, batch, n_vars, n_rows)) return e;
+    if (target < 0 || target >= n_vars) return failf(13, "%s: target must be in [0, n_vars)", fn);
+    if (mode != DVS_GBN_PREDICT_PARENTS && mode != DVS_GBN_PREDICT_EXACT) return failf(12, "%s: mode must be 0 (parents) or 1 (exact)", fn);
+    if (!data || !parents || !coef || !intercept || !sd || !pred || !var || !workspace || !status) return failf(10, "%s: null pointer", fn);
+    const size_t need = ((size_t)batch * 4 + 255) & ~(size_t)255;
+    if (workspace_bytes < need) return fail_size("dvs_gbn_predict: workspace_bytes < batch * 4 rounded up to 256", need);
+    GbnRowArgs a = {};
+    gpar_net(a.net, batch, n_vars, parents, coef, intercept, sd, status);
+    a.chunks = (int)((n_rows + 255) / 256);
+    a.target = target;
+    a.mode = mode;
+    a.rows = n_rows;
+    a.data = data;
+    a.per_row = pred;
+    a.out = var;
+    a.ok = (int*)workspace;
+    call_begin();
+    dvs_launch_gbn_predict(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

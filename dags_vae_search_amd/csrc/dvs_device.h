@@ -420,6 +420,8 @@ __device__ __forceinline__ void dvs_block_sum256(const int tid, T*... x) {
 // 500 the forward sampler of dvs_bn_sample (dvs_params.h; keyed by the global row index, element = variable),
 // 501 the likelihood-weighting sampler of dvs_bn_lw (dvs_infer.h; keyed by the global query index; variable v of particle p
 // draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw),
+// 510 the forward sampler of dvs_gbn_sample (dvs_gaussian_params.h; keyed by the global row index; variable v draws elements
+// 2 v and 2 v + 1),
 // 600 the bootstrap row sets of dvs_bootstrap_rows (dvs_strength.h; keyed by the global set index, element = position),
 // 700 / 701 the proposals and the start order of dvs_order_mcmc (dvs_ordermc.h; keyed by the global chain index; step t draws
 // elements 3 t, 3 t + 1, 3 t + 2, the shuffle draws element k for position k),
@@ -428,6 +430,7 @@ constexpr uint32_t DVS_SITE_GEN_EDGES = 300u, DVS_SITE_GEN_LABELS = 301u, DVS_SI
 constexpr uint32_t DVS_SITE_HC_PERTURB = 400u;
 constexpr uint32_t DVS_SITE_BN_SAMPLE = 500u;
 constexpr uint32_t DVS_SITE_BN_LW = 501u;
+constexpr uint32_t DVS_SITE_GBN_SAMPLE = 510u;
 constexpr uint32_t DVS_SITE_BOOTSTRAP = 600u;
 constexpr uint32_t DVS_SITE_ORDER_MCMC = 700u, DVS_SITE_ORDER_MCMC_INIT = 701u;
 __device__ __forceinline__ uint32_t dvs_fmix32(uint32_t x) {

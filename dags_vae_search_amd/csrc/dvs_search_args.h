@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -15,6 +15,7 @@
 #include "../../include/dvs_permtest.h"
 #include "../../include/dvs_gaussian.h"
 #include "../../include/dvs_gaussian_ci.h"
+#include "../../include/dvs_gaussian_params.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -689,6 +690,52 @@ struct GbnCiGroupArgs {
     int* status;
 };
 void dvs_launch_gbn_ci_group(const GbnCiGroupArgs& a, dvs_stream_t st);
+
+// ---- a fitted Gaussian network (dvs_gaussian_params.h; include/dvs_gaussian_params.h) -------------------------------------------
+struct GbnNet {
+    int B, n;
+    const uint64_t* parents;     // [B][n]
+    const double* coef;          // [B][n][n], read at parent bits
+    const double* intercept;     // [B][n]
+    const double* sd;            // [B][n]
+    int* status;
+};
+struct GbnJointArgs {
+    GbnNet net;
+    double* mean;                // [B][n]
+    double* cov;                 // [B][n][n]
+};
+void dvs_launch_gbn_joint(const GbnJointArgs& a, dvs_stream_t st);
+struct GbnQuantileArgs {
+    long long count;
+    const uint64_t* k;           // [count]
+    double* z;                   // [count]
+};
+void dvs_launch_gbn_quantiles(const GbnQuantileArgs& a, dvs_stream_t st);
+// The workspace of dvs_gbn_sample: a header of 64 i32, order [48] then the "drawable" word at index 48 (dvs_bn_sample's header).
+constexpr size_t DVS_GBN_SAMPLE_WORKSPACE = 256;
+struct GbnSampleArgs {
+    GbnNet net;                  // net.B = 1
+    long long rows;
+    uint32_t seed_lo, seed_hi, row_offset;       // seed_lo / seed_hi: launcher, from `seed`
+    int* header;                 // workspace: order [48], drawable at [48]
+    double* out;                 // [rows][n]
+};
+void dvs_launch_gbn_sample(const GbnSampleArgs& a, uint64_t seed, dvs_stream_t st);
+// dvs_gbn_loglik's workspace is dvs_bn_loglik_layout's: partials f64 [B][chunks], flags i32 (the first B of [B][n]), c f64 [B][n]
+struct GbnRowArgs {
+    GbnNet net;
+    int chunks, bsplit, target, mode;            // bsplit: launcher, the parts the batch is cut into; target, mode: the prediction
+    long long rows;
+    const double* data;          // [rows][n]
+    double* per_row;             // loglik: null or [B][rows]; predict: pred [B][rows]
+    double* out;                 // loglik: [B]; predict: var [B]
+    double* partials;            // loglik workspace [B][chunks]
+    int* ok;                     // workspace [B]
+    double* c;                   // loglik workspace [B][n]
+};
+void dvs_launch_gbn_loglik(const GbnRowArgs& a, dvs_stream_t st);
+void dvs_launch_gbn_predict(const GbnRowArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;
