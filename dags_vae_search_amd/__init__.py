@@ -1,7 +1,8 @@
 """dags_vae_search_amd — MI355X-native DAG-VAE (PACE) train-step hot path of rlog58/dags-vae-search.
 
 Drop-in surface for that path: PaceVaeV3, train_batch, pace_collate_fn, collate_graph_batch, load_model_state,
-LabeledDag (row codec).  latent_bo_search: Bayesian optimisation of the BIC in the VAE's latent space.  evaluate_reconstruction: model_test with
+LabeledDag (row codec).  Structure learning next to it, on three kinds of data: BNLearnWrapper (discrete), GaussianEvaluator
+(real-valued) and MixedEvaluator (factors and real columns) under hill_climb and tabu_search.  latent_bo_search: Bayesian optimisation of the BIC in the VAE's latent space.  evaluate_reconstruction: model_test with
 the isomorphism judging on the device.  All arithmetic runs in libdvs_hip.so (hand-written HIP for gfx950); there is no CPU path.
 """
 from .features import LabeledDag, LabeledGraph, collate_graph_batch, pace_collate_fn, prepare_features  # noqa: F401
@@ -34,6 +35,7 @@ from .eliminate import (EliminationPlan, elimination_plan, evidence_probability,
                         exact_posterior)
 from .incomplete import (EMResult, ExpectedCounts, StructuralEMResult, available_case_evaluator, em_fit,  # noqa: F401
                          expected_counts, family_plans, fit_counts, impute, incomplete_rows, structural_em, target_plans)
+from .mixed import FittedCGBN, MixedEvaluator, cg_fit  # noqa: F401
 from .gaussian import (FittedGBN, GaussianEvaluator, gaussian_cross_validate, gaussian_fit, gaussian_joint,  # noqa: F401
                        gaussian_log_likelihood, gaussian_predict, gaussian_sample)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401

@@ -25,6 +25,7 @@ PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_permtest.h") 
 GAUSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian.h")   # the sixth: Gaussian networks on real-valued data
 GCI_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_ci.h")  # the seventh: CI tests on real-valued data
 GPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_params.h")  # the eighth: a fitted Gaussian network
+MIXED_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_mixed.h")       # the ninth: conditional Gaussian networks on mixed data
 
 
 class DvsShape(Structure):
@@ -105,6 +106,8 @@ GAUSS_SIGNATURES, _G = _read_header(GAUSS_HEADER)
 GCI_SIGNATURES, _GC = _read_header(GCI_HEADER)
 # include/dvs_gaussian_params.h, the eighth: joint, quantiles, sample, loglik, predict; the eight tables above stay what they are
 GPAR_SIGNATURES, _GP = _read_header(GPAR_HEADER)
+# include/dvs_mixed.h, the ninth: partition, ragged moments, the cg scores, their toggle pass and the fit; the nine tables above stay what they are
+MIXED_SIGNATURES, _M = _read_header(MIXED_HEADER)
 
 
 def signature(fn: str):
@@ -127,9 +130,11 @@ def signature(fn: str):
         return GCI_SIGNATURES[fn]
     if fn in GPAR_SIGNATURES:
         return GPAR_SIGNATURES[fn]
+    if fn in MIXED_SIGNATURES:
+        return MIXED_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
                    f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h, "
-                   f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h")
+                   f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h, nor in include/dvs_mixed.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -160,6 +165,8 @@ GBN_CHUNK, GBN_MAX_PARENTS = _G["DVS_GBN_CHUNK"], _G["DVS_GBN_MAX_PARENTS"]     
 GCI_TYPES = {k: _GC["DVS_GCI_" + k.upper().replace("-", "_")] for k in ("cor", "zf", "mi-g")}      # dvs_gci_type
 GCI_MAX_COND = _GC["DVS_GCI_MAX_COND"]     # the largest conditioning set of a Gaussian CI test (include/dvs_gaussian_ci.h)
 GBN_PREDICT_MODES = {"parents": _GP["DVS_GBN_PREDICT_PARENTS"], "exact": _GP["DVS_GBN_PREDICT_EXACT"]}      # include/dvs_gaussian_params.h
+CGSCORE_TYPES = {k: _M["DVS_CGSCORE_" + k.upper()[:-3]] for k in ("loglik-cg", "aic-cg", "bic-cg")}      # dvs_cgscore_type (include/dvs_mixed.h)
+CG_MAX_CONFIGS = _M["DVS_CG_MAX_CONFIGS"]      # the configurations of the discrete parents of one continuous family
 
 
 def gbn_stride(n: int) -> int:
@@ -186,7 +193,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
                                   *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items(),
-                                  *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items()):
+                                  *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items(), *MIXED_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]
@@ -267,8 +274,16 @@ def require_cuda(t, what: str):
 GCI_ENTRY_POINTS = ("ci_tests", "ci_test", "pc_stable", "mmpc", "ci_tests_group", "rsmax2", "mmhc")
 
 
+def need_unmixed(what, evaluator):
+    """the entry points that are not built on mixed data refuse a MixedEvaluator (mixed.py)"""
+    if getattr(evaluator, "mixed", False):
+        raise ValueError(f"{what}: the evaluator holds mixed data (factors and real columns) and mixed data is not built for "
+                         f"{what}: hill_climb, tabu_search, score_masks and cg_fit are")
+
+
 def need_discrete(what, evaluator):
     """the entry points that read ``packed`` / ``card`` refuse an evaluator over real-valued data (gaussian.py)"""
+    need_unmixed(what, evaluator)
     if getattr(evaluator, "continuous", False):
         gci = " (its tests on real-valued data are test=\"cor\", \"zf\" and \"mi-g\")" if what in GCI_ENTRY_POINTS else ""
         raise ValueError(f"{what}: the evaluator holds real-valued data and {what} reads discrete levels{gci}: its Gaussian "
@@ -294,6 +309,7 @@ def level_counts(card):
 def packed_rows(what, data, n):
     """``data``: an evaluator over n variables (bic.py) or packed int64 rows [S >= 1, ceil(n / 16)] -> the rows, contiguous"""
     if not torch.is_tensor(data) and hasattr(data, "packed"):
+        need_unmixed(what, data)
         if data.n_vars != n:
             raise ValueError(f"{what}: the evaluator has {data.n_vars} variables, the network {n}")
         data = data.packed

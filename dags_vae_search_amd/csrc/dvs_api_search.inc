@@ -735,6 +735,215 @@ extern "C" int dvs_gbn_fit(int32_t batch, int32_t n_vars, const double* moments,
     return call_end(fn);
 }
 
+// ---- conditional Gaussian networks on mixed data (dvs_mixed.h; include/dvs_mixed.h) ----------------------------------------------
+static int cg_pitch(const char* fn, int q_pitch) {
+    return q_pitch < 1 || q_pitch > DVS_CG_MAX_CONFIGS ? failf(13, "%s: q_pitch must be in [1, %d]", fn, DVS_CG_MAX_CONFIGS) : 0;
+}
+
+extern "C" int dvs_cg_partition(int32_t n_vars, int32_t n_samples, const uint64_t* data, const uint8_t* card, int32_t n_requests,
+                                const uint64_t* masks, int32_t q_pitch, int32_t* count, size_t count_bytes, int32_t* start,
+                                int32_t* order, size_t order_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_cg_partition";
+    if (n_requests <= 0 || n_samples <= 0) return failf(2, "%s: n_requests and n_samples must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (int e = cg_pitch(fn, q_pitch)) return e;
+    if ((int64_t)n_requests * (q_pitch > n_samples ? q_pitch : n_samples) > (int64_t)0x7fffffff)
+        return failf(2, "%s: n_requests * max(q_pitch, n_samples) must be < 2^31", fn);
+    if (!data || !card || !masks || !count || !start || !order || !status) return failf(10, "%s: null pointer", fn);
+    const size_t need = (size_t)n_requests * q_pitch * 4, need_order = (size_t)n_requests * n_samples * 4;
+    if (count_bytes < need) return fail_size("dvs_cg_partition: count_bytes < n_requests * q_pitch * 4", need);
+    if (order_bytes < need_order) return fail_size("dvs_cg_partition: order_bytes < n_requests * n_samples * 4", need_order);
+    CgPartitionArgs a = {};
+    a.n = n_vars;
+    a.S = n_samples;
+    a.n_req = n_requests;
+    a.q_pitch = q_pitch;
+    a.data = data;
+    a.card = card;
+    a.masks = masks;
+    a.count = count;
+    a.start = start;
+    a.order = order;
+    a.status = status;
+    call_begin();
+    dvs_launch_cg_partition(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+static int cg_moment_dims(const char* fn, int n_cont, int n_samples, int n_requests, int q_pitch) {
+    if (n_requests <= 0 || n_samples <= 0) return failf(2, "%s: n_requests and n_samples must be > 0", fn);
+    if (n_cont < 1 || n_cont > DVS_WTOK) return failf(3, "%s: n_cont must be in [1, 48]", fn);
+    if (int e = cg_pitch(fn, q_pitch)) return e;
+    const CgMomentLayout l = dvs_cg_moment_layout(n_cont, n_samples, n_requests, q_pitch);
+    const double tri = (double)l.tri;
+    if ((double)n_requests * (double)l.slots * tri > 2147483647.0 || (double)n_requests * (double)q_pitch * tri > 2147483647.0)
+        return failf(2, "%s: n_requests * slots * n (n + 1) / 2 and n_requests * q_pitch * n (n + 1) / 2 must be < 2^31", fn);
+    return 0;
+}
+
+extern "C" size_t dvs_cg_moments_workspace_bytes(int32_t n_cont, int32_t n_samples, int32_t n_requests, int32_t q_pitch) {
+    if (cg_moment_dims("dvs_cg_moments_workspace_bytes", n_cont, n_samples, n_requests, q_pitch)) return 0;
+    return dvs_cg_moment_layout(n_cont, n_samples, n_requests, q_pitch).total;
+}
+
+extern "C" int dvs_cg_moments(int32_t n_cont, int32_t n_samples, const double* x, int32_t n_requests, int32_t q_pitch,
+                              const int32_t* count, const int32_t* start, const int32_t* order, void* workspace,
+                              size_t workspace_bytes, double* moments, size_t moments_bytes, void* stream) {
+    const char* fn = "dvs_cg_moments";
+    if (int e = cg_moment_dims(fn, n_cont, n_samples, n_requests, q_pitch)) return e;
+    if (!x || !count || !start || !order || !workspace || !moments) return failf(10, "%s: null pointer", fn);
+    const CgMomentLayout l = dvs_cg_moment_layout(n_cont, n_samples, n_requests, q_pitch);
+    if (workspace_bytes < l.total) return fail_size("dvs_cg_moments: workspace_bytes < dvs_cg_moments_workspace_bytes", l.total);
+    const size_t need = (size_t)n_requests * q_pitch * DVS_GBN_STRIDE(n_cont) * 8;
+    if (moments_bytes < need) return fail_size("dvs_cg_moments: moments_bytes < n_requests * q_pitch * DVS_GBN_STRIDE(n_cont) * 8", need);
+    CgMomentArgs a = {};
+    a.n = n_cont;
+    a.S = n_samples;
+    a.n_req = n_requests;
+    a.q_pitch = q_pitch;
+    a.x = x;
+    a.count = count;
+    a.start = start;
+    a.order = order;
+    a.pre = (int*)workspace;
+    a.sums = (double*)((char*)workspace + l.sums);
+    a.cells = (double*)((char*)workspace + l.cells);
+    a.moments = moments;
+    call_begin();
+    dvs_launch_cg_moments(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+// what dvs_cg_scores and dvs_cg_toggle_scores check alike and the two blocks they fill: a for the continuous and the illegal
+// cells, bn for the discrete scorer on the workspace's copy of the structures
+static int cg_score_check(const char* fn, int batch, int n_vars, int n_cont, int n_samples, bool table) {
+    if (batch <= 0 || n_samples <= 0) return failf(2, "%s: batch and n_samples must be > 0", fn);
+    if (table) {
+        if (int e = HcCheck{fn, batch, n_vars}.dims()) return e;
+    } else if (n_vars < 1 || n_vars > DVS_WTOK) {
+        return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    }
+    return n_cont < 0 || n_cont > n_vars ? failf(3, "%s: n_cont must be in [0, n_vars]", fn) : 0;
+}
+static size_t cg_workspace(int batch, int n_vars, bool toggle) {
+    return (size_t)batch * n_vars * 8 + 64 + (toggle ? (size_t)batch * 8 : 0);
+}
+static int cg_fill(const char* fn, CgScoreArgs& a, BicArgs& bn, int batch, int n_vars, int n_cont, int n_samples, const uint64_t* data,
+                   const uint8_t* card, const uint64_t* tables, const int32_t* table_of, const uint64_t* parents, int score_type,
+                   double score_arg, void* workspace, double* local, double* out, int32_t* status) {
+    a.B = batch;
+    a.n = n_vars;
+    a.nc = n_cont;
+    a.S = n_samples;
+    a.type = score_type;
+    a.card = card;
+    a.tables = tables;
+    a.table_of = table_of;
+    a.parents = parents;
+    a.local = local;
+    a.out = out;
+    a.status = status;
+    a.bn_parents = (uint64_t*)workspace;
+    a.bn_card = (uint8_t*)workspace + (size_t)batch * n_vars * 8;
+    a.bn_worklist = (int*)(a.bn_card + 64);
+    // dvs_cgscore_type and dvs_score_type agree on loglik, aic, bic: the discrete scorer's own argument rules
+    if (int e = scorer_args(fn, bn, batch, n_vars, n_samples, data, a.bn_card, a.bn_parents, score_type, score_arg, local, out, status))
+        return e;
+    a.arg = bn.arg;
+    return 0;
+}
+static_assert(DVS_CGSCORE_LOGLIK == (int)DVS_SCORE_LOGLIK && DVS_CGSCORE_AIC == (int)DVS_SCORE_AIC && DVS_CGSCORE_BIC == (int)DVS_SCORE_BIC,
+              "the mixed scores hand their type to the discrete scorer");
+
+extern "C" size_t dvs_cg_scores_workspace_bytes(int32_t batch, int32_t n_vars) {
+    if (cg_score_check("dvs_cg_scores_workspace_bytes", batch, n_vars, 0, 1, false)) return 0;
+    return cg_workspace(batch, n_vars, false);
+}
+extern "C" size_t dvs_cg_toggle_workspace_bytes(int32_t batch, int32_t n_vars) {
+    if (cg_score_check("dvs_cg_toggle_workspace_bytes", batch, n_vars, 0, 1, true)) return 0;
+    return cg_workspace(batch, n_vars, true);
+}
+
+extern "C" int dvs_cg_scores(int32_t batch, int32_t n_vars, int32_t n_cont, int32_t n_samples, const uint64_t* data,
+                             const uint8_t* card, const uint64_t* tables, const int32_t* table_of, const uint64_t* parents,
+                             int32_t score_type, double score_arg, void* workspace, size_t workspace_bytes, double* local,
+                             double* out, int32_t* status, void* stream) {
+    const char* fn = "dvs_cg_scores";
+    if (int e = cg_score_check(fn, batch, n_vars, n_cont, n_samples, false)) return e;
+    if (score_type < DVS_CGSCORE_LOGLIK || score_type > DVS_CGSCORE_BIC) return failf(12, "%s: score_type is not a dvs_cgscore_type", fn);
+    CgScoreArgs a = {};
+    BicArgs bn = {};
+    if (int e = cg_fill(fn, a, bn, batch, n_vars, n_cont, n_samples, data, card, tables, table_of, parents, score_type, score_arg,
+                        workspace, local, out, status))
+        return e;
+    if (!data || !card || !parents || !workspace || !local || !out || !status || (n_cont > 0 && (!tables || !table_of)))
+        return failf(10, "%s: null pointer", fn);
+    const size_t need = cg_workspace(batch, n_vars, false);
+    if (workspace_bytes < need) return fail_size("dvs_cg_scores: workspace_bytes < dvs_cg_scores_workspace_bytes", need);
+    call_begin();
+    dvs_launch_cg_scores(a, bn, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_cg_toggle_scores(int32_t batch, int32_t n_vars, int32_t n_cont, int32_t n_samples, const uint64_t* data,
+                                    const uint8_t* card, const uint64_t* tables, const int32_t* table_of, const uint64_t* parents,
+                                    int32_t score_type, double score_arg, const int32_t* worklist, void* workspace,
+                                    size_t workspace_bytes, double* local, size_t local_bytes, double* toggles, size_t toggles_bytes,
+                                    int32_t* status, void* stream) {
+    const char* fn = "dvs_cg_toggle_scores";
+    if (int e = cg_score_check(fn, batch, n_vars, n_cont, n_samples, true)) return e;
+    if (score_type < DVS_CGSCORE_LOGLIK || score_type > DVS_CGSCORE_BIC) return failf(12, "%s: score_type is not a dvs_cgscore_type", fn);
+    CgScoreArgs a = {};
+    ToggleArgs bn = {};
+    if (int e = cg_fill(fn, a, bn.s, batch, n_vars, n_cont, n_samples, data, card, tables, table_of, parents, score_type, score_arg,
+                        workspace, local, nullptr, status))
+        return e;
+    if (!data || !card || !parents || !workspace || !local || !toggles || !status || (n_cont > 0 && (!tables || !table_of)))
+        return failf(10, "%s: null pointer", fn);
+    const size_t need = cg_workspace(batch, n_vars, true);
+    if (workspace_bytes < need) return fail_size("dvs_cg_toggle_scores: workspace_bytes < dvs_cg_toggle_workspace_bytes", need);
+    if (int e = toggle_buffers({fn, batch, n_vars}, local_bytes, toggles_bytes)) return e;
+    a.worklist = worklist;
+    a.toggles = toggles;
+    bn.worklist = worklist ? a.bn_worklist : nullptr;
+    bn.toggles = toggles;
+    call_begin();
+    dvs_launch_cg_toggle(a, bn, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" int dvs_cg_fit(int32_t n_families, int32_t n_cells, int32_t n_vars, int32_t n_cont, const uint8_t* card,
+                          const int32_t* var, const uint64_t* parents, const uint64_t* table, const int64_t* offset, double* coef,
+                          size_t coef_bytes, double* intercept, double* sd, double* count, int32_t* status, void* stream) {
+    const char* fn = "dvs_cg_fit";
+    if (n_families <= 0 || n_cells <= 0) return failf(2, "%s: n_families and n_cells must be > 0", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (n_cont < 1 || n_cont > n_vars) return failf(3, "%s: n_cont must be in [1, n_vars]", fn);
+    if ((int64_t)n_cells * n_vars > (int64_t)0x7fffffff) return failf(2, "%s: n_cells * n_vars must be < 2^31", fn);
+    if (!card || !var || !parents || !table || !offset || !coef || !intercept || !sd || !count || !status)
+        return failf(10, "%s: null pointer", fn);
+    const size_t need = (size_t)n_cells * n_vars * 8;
+    if (coef_bytes < need) return fail_size("dvs_cg_fit: coef_bytes < n_cells * n_vars * 8", need);
+    CgFitArgs t = {};
+    t.F = n_families;
+    t.cells = n_cells;
+    t.n = n_vars;
+    t.nc = n_cont;
+    t.card = card;
+    t.var = var;
+    t.parents = parents;
+    t.table = table;
+    t.offset = (const long long*)offset;
+    t.coef = coef;
+    t.intercept = intercept;
+    t.sd = sd;
+    t.count = count;
+    t.status = status;
+    call_begin();
+    dvs_launch_cg_fit(t, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // ---- Gaussian CI tests (dvs_gaussian_ci.h; include/dvs_gaussian_ci.h) -----------------------------------------------------------
 // what the two entry points check first: counts (2), n_vars (3), the range of the cell index (2), test_type (12)
 static int gci_dims(const char* fn, const char* count, const char* cells_text, int items, int n_vars, int n_sets, bool per_var, int test_type) {

@@ -27,30 +27,74 @@ static_assert((size_t)DVS_GBN_CHUNK * DVS_WTOK * sizeof(double) <= 64 * 1024, "a
 // ---------------------------------------------------------------------------------------------------------
 // Moments
 // ---------------------------------------------------------------------------------------------------------
-// stages the chunk's rows [len][n] into x; returns len.  Every thread of the workgroup calls it; a barrier follows.
-__device__ __forceinline__ int gbn_stage_chunk(const GbnMomentArgs& a, int set, int chunk, double* x) {
-    const int n = a.n, p0 = chunk * DVS_GBN_CHUNK;
-    const int len = a.set_size - p0 < DVS_GBN_CHUNK ? a.set_size - p0 : DVS_GBN_CHUNK;
-    const int* rows = a.rows != nullptr ? a.rows + (size_t)set * (size_t)a.set_size + p0 : nullptr;
+// The chunk routines.  dvs_mixed.h runs the same ones over the segments of a partition (a segment list instead of a set), so
+// a block of dvs_cg_moments and a row set of dvs_gbn_moments are one summation.
+// stages `len` rows [len][n] into x: row r is data row rows[r], or p0 + r with rows null.  Every thread of the workgroup calls
+// it; a barrier follows.
+__device__ __forceinline__ void gbn_stage_rows(const double* data, int n, const int* rows, int p0, int len, double* x) {
     for (int e = threadIdx.x; e < len * n; e += blockDim.x) {
         const int r = e / n, c = e - r * n;
         const size_t src = rows != nullptr ? (size_t)rows[r] : (size_t)(p0 + r);
-        x[e] = a.data[src * n + c];
+        x[e] = data[src * n + c];
     }
     __syncthreads();
+}
+// stages chunk `chunk` of set `set`; returns its length
+__device__ __forceinline__ int gbn_stage_chunk(const GbnMomentArgs& a, int set, int chunk, double* x) {
+    const int p0 = chunk * DVS_GBN_CHUNK;
+    const int len = a.set_size - p0 < DVS_GBN_CHUNK ? a.set_size - p0 : DVS_GBN_CHUNK;
+    gbn_stage_rows(a.data, a.n, a.rows != nullptr ? a.rows + (size_t)set * (size_t)a.set_size + p0 : nullptr, p0, len, x);
     return len;
 }
-
-__global__ __launch_bounds__(256) void k_gbn_colsum(GbnMomentArgs a) {
+// pass 1 of a staged chunk: thread i < n adds column i in position order -> out[i]
+__device__ __forceinline__ void gbn_chunk_colsum(const double* x, int len, int n, double* out) {
 #pragma clang fp contract(off)
-    __shared__ double s_x[DVS_GBN_CHUNK * DVS_WTOK];
-    const int set = blockIdx.x / a.chunks, chunk = blockIdx.x - set * a.chunks, n = a.n;
-    const int len = gbn_stage_chunk(a, set, chunk, s_x);
     const int i = threadIdx.x;
     if (i >= n) return;
     double s = 0.0;
-    for (int r = 0; r < len; ++r) s = s + s_x[r * n + i];
-    a.sums[(size_t)blockIdx.x * n + i] = s;
+    for (int r = 0; r < len; ++r) s = s + x[r * n + i];
+    out[i] = s;
+}
+// `chunks` chunk values, `stride` doubles apart, added in chunk order from +0
+__device__ __forceinline__ double gbn_fold_chunks(const double* part, int chunks, size_t stride) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s = s + part[(size_t)c * stride];
+    return s;
+}
+// cell q of the upper triangle in row-major order: row i holds n - i cells (i, i) .. (i, n - 1)
+__device__ __forceinline__ void gbn_tri_cell(int q, int n, int* i_out, int* j_out) {
+    int i = 0, at = q;
+    while (at >= n - i) {
+        at -= n - i;
+        ++i;
+    }
+    *i_out = i;
+    *j_out = i + at;
+}
+// pass 2 of a staged chunk: centres it in place, then every thread owns cells of the upper triangle -> out[tri].  Every thread
+// of the 256-thread workgroup calls it (it holds a barrier).
+__device__ __forceinline__ void gbn_chunk_cross(double* x, int len, int n, int tri, const double* mean, double* out) {
+#pragma clang fp contract(off)
+    for (int e = threadIdx.x; e < len * n; e += 256) x[e] = x[e] - mean[e % n];
+    __syncthreads();
+    for (int q = threadIdx.x; q < tri; q += 256) {
+        int i, j;
+        gbn_tri_cell(q, n, &i, &j);
+        double s = 0.0;
+        for (int r = 0; r < len; ++r) {
+            const double prod = x[r * n + i] * x[r * n + j];
+            s = s + prod;
+        }
+        out[q] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gbn_colsum(GbnMomentArgs a) {
+    __shared__ double s_x[DVS_GBN_CHUNK * DVS_WTOK];
+    const int set = blockIdx.x / a.chunks, chunk = blockIdx.x - set * a.chunks;
+    const int len = gbn_stage_chunk(a, set, chunk, s_x);
+    gbn_chunk_colsum(s_x, len, a.n, a.sums + (size_t)blockIdx.x * a.n);
 }
 
 __global__ __launch_bounds__(256) void k_gbn_mean(GbnMomentArgs a) {
@@ -58,9 +102,7 @@ __global__ __launch_bounds__(256) void k_gbn_mean(GbnMomentArgs a) {
     const int idx = blockIdx.x * 256 + threadIdx.x, n = a.n;
     if (idx >= a.n_sets * n) return;
     const int set = idx / n, i = idx - set * n;
-    const double* part = a.sums + (size_t)set * a.chunks * n + i;
-    double s = 0.0;
-    for (int c = 0; c < a.chunks; ++c) s = s + part[(size_t)c * n];
+    const double s = gbn_fold_chunks(a.sums + (size_t)set * a.chunks * n + i, a.chunks, (size_t)n);
     double* mom = a.moments + (size_t)set * DVS_GBN_STRIDE(n);
     const double m = (double)a.set_size;
     if (i == 0) mom[0] = m;
@@ -68,44 +110,19 @@ __global__ __launch_bounds__(256) void k_gbn_mean(GbnMomentArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_gbn_cross(GbnMomentArgs a) {
-#pragma clang fp contract(off)
     __shared__ double s_x[DVS_GBN_CHUNK * DVS_WTOK];
     const int set = blockIdx.x / a.chunks, chunk = blockIdx.x - set * a.chunks, n = a.n;
     const int len = gbn_stage_chunk(a, set, chunk, s_x);
-    const double* mean = a.moments + (size_t)set * DVS_GBN_STRIDE(n) + 1;
-    for (int e = threadIdx.x; e < len * n; e += 256) s_x[e] = s_x[e] - mean[e % n];
-    __syncthreads();
-    // cell q of the upper triangle in row-major order: row i holds n - i cells (i, i) .. (i, n - 1)
-    for (int q = threadIdx.x; q < a.tri; q += 256) {
-        int i = 0, at = q;
-        while (at >= n - i) {
-            at -= n - i;
-            ++i;
-        }
-        const int j = i + at;
-        double s = 0.0;
-        for (int r = 0; r < len; ++r) {
-            const double prod = s_x[r * n + i] * s_x[r * n + j];
-            s = s + prod;
-        }
-        a.cells[(size_t)blockIdx.x * a.tri + q] = s;
-    }
+    gbn_chunk_cross(s_x, len, n, a.tri, a.moments + (size_t)set * DVS_GBN_STRIDE(n) + 1, a.cells + (size_t)blockIdx.x * a.tri);
 }
 
 __global__ __launch_bounds__(256) void k_gbn_fold(GbnMomentArgs a) {
-#pragma clang fp contract(off)
     const int idx = blockIdx.x * 256 + threadIdx.x, n = a.n;
     if (idx >= a.n_sets * a.tri) return;
     const int set = idx / a.tri, q = idx - set * a.tri;
-    int i = 0, at = q;
-    while (at >= n - i) {
-        at -= n - i;
-        ++i;
-    }
-    const int j = i + at;
-    const double* part = a.cells + (size_t)set * a.chunks * a.tri + q;
-    double s = 0.0;
-    for (int c = 0; c < a.chunks; ++c) s = s + part[(size_t)c * a.tri];
+    int i, j;
+    gbn_tri_cell(q, n, &i, &j);
+    const double s = gbn_fold_chunks(a.cells + (size_t)set * a.chunks * a.tri + q, a.chunks, (size_t)a.tri);
     double* C = a.moments + (size_t)set * DVS_GBN_STRIDE(n) + 1 + n;
     C[i * n + j] = s;
     C[j * n + i] = s;
@@ -285,6 +302,19 @@ void dvs_launch_gbn_toggle(const GbnToggleArgs& t, dvs_stream_t st) {
     DVS_LAUNCH(k_gbn_toggle, dim3((unsigned)((rows * t.s.n + GBN_LANES - 1) / GBN_LANES)), dim3(GBN_LANES), 0, st, t);
 }
 
+// the backward solve of include/dvs_gaussian.h over the last row of a factored family, in place: L[p][i] becomes beta_i
+__device__ __forceinline__ void gbn_backsolve(double* L, int p) {
+#pragma clang fp contract(off)
+    for (int i = p - 1; i >= 0; --i) {
+        double s = gbn_L(L, p, i);
+        for (int k = i + 1; k < p; ++k) {
+            const double prod = gbn_L(L, k, i) * gbn_L(L, p, k);
+            s = s - prod;
+        }
+        gbn_L(L, p, i) = s / gbn_L(L, i, i);
+    }
+}
+
 // One lane per family: the factor, then the backward solve over the last row in place.
 __global__ __launch_bounds__(GBN_LANES) void k_gbn_fit(GbnFitArgs t) {
 #pragma clang fp contract(off)
@@ -307,14 +337,7 @@ __global__ __launch_bounds__(GBN_LANES) void k_gbn_fit(GbnFitArgs t) {
         return;
     }
     const int p = f.p;
-    for (int i = p - 1; i >= 0; --i) {
-        double s = gbn_L(L, p, i);
-        for (int k = i + 1; k < p; ++k) {
-            const double prod = gbn_L(L, k, i) * gbn_L(L, p, k);
-            s = s - prod;
-        }
-        gbn_L(L, p, i) = s / gbn_L(L, i, i);
-    }
+    gbn_backsolve(L, p);
     for (int u = 0; u < n; ++u) coef[u] = 0.0;
     double c0 = mom[1 + v];
     uint64_t mi = pm;

@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h / dvs_mixed.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -16,6 +16,7 @@
 #include "../../include/dvs_gaussian.h"
 #include "../../include/dvs_gaussian_ci.h"
 #include "../../include/dvs_gaussian_params.h"
+#include "../../include/dvs_mixed.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -736,6 +737,82 @@ struct GbnRowArgs {
 };
 void dvs_launch_gbn_loglik(const GbnRowArgs& a, dvs_stream_t st);
 void dvs_launch_gbn_predict(const GbnRowArgs& a, dvs_stream_t st);
+
+// ---- conditional Gaussian networks on mixed data (dvs_mixed.h; include/dvs_mixed.h) ----------------------------------------------
+struct CgPartitionArgs {
+    int n, S, n_req, q_pitch, words;             // words: launcher
+    const uint64_t* data;        // [S][words]
+    const uint8_t* card;         // [n], 0: continuous
+    const uint64_t* masks;       // [n_req]
+    int* count;                  // [n_req][q_pitch]
+    int* start;                  // [n_req][q_pitch]
+    int* order;                  // [n_req][S]
+    int* status;
+};
+void dvs_launch_cg_partition(const CgPartitionArgs& a, dvs_stream_t st);
+// The workspace of dvs_cg_moments: the exclusive prefix of every request's chunks per configuration, i32 [n_req][q_pitch + 1]
+// (rows padded to 8 bytes), then the chunk column sums [n_req][slots][n] and the chunk cells [n_req][slots][n (n + 1) / 2].
+struct CgMomentLayout {
+    size_t slots, tri, pre_pitch, sums, cells, total;        // pre_pitch in i32; sums, cells: byte offsets
+};
+inline CgMomentLayout dvs_cg_moment_layout(long long n, long long S, long long n_req, long long q_pitch) {
+    CgMomentLayout l;
+    l.slots = (size_t)((S + DVS_GBN_CHUNK - 1) / DVS_GBN_CHUNK + q_pitch);
+    l.tri = (size_t)(n * (n + 1) / 2);
+    l.pre_pitch = (size_t)(2 * ((q_pitch + 2) / 2));
+    l.sums = l.pre_pitch * 4 * (size_t)n_req;
+    l.cells = l.sums + (size_t)n_req * l.slots * (size_t)n * 8;
+    l.total = l.cells + (size_t)n_req * l.slots * l.tri * 8;
+    return l;
+}
+struct CgMomentArgs {
+    int n, S, n_req, q_pitch, slots, tri, pre_pitch;         // n: the continuous columns; slots, tri, pre_pitch: launcher
+    const double* x;             // [S][n]
+    const int* count;            // [n_req][q_pitch]
+    const int* start;            // [n_req][q_pitch]
+    const int* order;            // [n_req][S]
+    int* pre;                    // workspace [n_req][pre_pitch]
+    double* sums;                // workspace [n_req][slots][n]
+    double* cells;               // workspace [n_req][slots][tri]
+    double* moments;             // [n_req][q_pitch][DVS_GBN_STRIDE(n)]
+};
+void dvs_launch_cg_moments(const CgMomentArgs& a, dvs_stream_t st);
+
+// dvs_cg_scores and dvs_cg_toggle_scores: the discrete cells come from the discrete scorer on `bn` (its parents, card and
+// worklist are the copies k_cg_prep writes into the workspace); the continuous and the illegal ones are written after it
+struct CgScoreArgs {
+    int B, n, nc, S, type;       // type: dvs_cgscore_type
+    double arg;                  // k; NaN: log(S) / 2 on the device
+    const uint8_t* card;         // [n], 0: continuous
+    const uint64_t* tables;      // [n_tables] addresses of moment blocks [q][DVS_GBN_STRIDE(nc)]
+    const int* table_of;         // scores [B][n]; toggle pass [rows][n]
+    const uint64_t* parents;     // [B][n]
+    double* local;               // [B][n]
+    double* out;                 // [B]; unused by the toggle pass
+    int* status;
+    uint64_t* bn_parents;        // workspace [B][n]
+    uint8_t* bn_card;            // workspace [64]
+    const int* worklist;         // toggle pass: null or [2 B]
+    int* bn_worklist;            // workspace [2 B] (toggle pass with a worklist)
+    double* toggles;             // toggle pass: T [B][n][n]
+};
+void dvs_launch_cg_scores(const CgScoreArgs& a, const BicArgs& bn, dvs_stream_t st);
+void dvs_launch_cg_toggle(const CgScoreArgs& a, const ToggleArgs& bn, dvs_stream_t st);
+
+struct CgFitArgs {
+    int F, cells, n, nc;
+    const uint8_t* card;
+    const int* var;              // [F]
+    const uint64_t* parents;     // [F]
+    const uint64_t* table;       // [F]
+    const long long* offset;     // [F + 1]
+    double* coef;                // [cells][n]
+    double* intercept;           // [cells]
+    double* sd;                  // [cells]
+    double* count;               // [cells]
+    int* status;
+};
+void dvs_launch_cg_fit(const CgFitArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

@@ -83,6 +83,7 @@ def local_score_table(evaluator, *, max_parents: Optional[int] = None, chunk: in
     that parent set is not available).  With ``max_parents = k`` only the rows with ``popcount(S) <= k + 1`` are scored and
     the rest of the table is NaN."""
     what = "local_score_table"
+    dl.need_unmixed(what, evaluator)
     dev, n = evaluator.device, evaluator.n_vars
     dl.need_cuda(what, dev)
     _refuse_size(what, n)
@@ -117,6 +118,7 @@ def exact_search(evaluator, *, max_parents: Optional[int] = None, forbidden=None
     """The optimal DAG for the evaluator's score and data under ``max_parents`` and ``forbidden`` (B = 1):
     ``local_score_table`` then ``exact_from_tables``.  ``scores`` is the dynamic programme's own value (the local scores
     added in sink order); ``rescored`` is ``evaluator.score_masks(parents)``, the same n terms added by variable index."""
+    dl.need_unmixed("exact_search", evaluator)
     table = local_score_table(evaluator, max_parents=max_parents)
     res = exact_from_tables(table[None], max_parents=max_parents, forbidden=forbidden, lib=evaluator.lib)
     with torch.cuda.device(evaluator.device):

@@ -17,6 +17,9 @@ permutation test name, their default "mi" included, they raise ``ValueError``.  
 alone (``bn_fit``, ``cross_validate``, ``available_case``) raise ``ValueError`` on this evaluator; the counterparts of the first
 two have names of their own, ``gaussian_fit`` and ``gaussian_cross_validate``.
 
+A data set that holds factors next to real columns has an evaluator of its own, ``MixedEvaluator`` (mixed.py),
+whose cells on all-real data are this one's bytes.
+
 A ``FittedGBN`` goes to ``gaussian_joint`` (bnlearn's gbn2mvnorm), ``gaussian_sample`` (rbn), ``gaussian_log_likelihood`` (logLik
 on held-out rows) and ``gaussian_predict`` (from the parents, or the exact conditional given every other variable):
 include/dvs_gaussian_params.h, DESIGN.md §31.
@@ -252,6 +255,7 @@ class FittedGBN:
 
 def _fit(what, evaluator, parents):
     """dvs_gbn_fit -> (FittedGBN, status); the checks of gaussian_fit"""
+    dl.need_unmixed(what, evaluator)
     if not getattr(evaluator, "continuous", False):
         raise ValueError(f"{what}: the evaluator holds discrete data: bn_fit fits its tables")
     if not torch.is_tensor(parents) or parents.dtype != torch.int64 or parents.ndim not in (1, 2):
@@ -449,6 +453,7 @@ def gaussian_cross_validate(evaluator, parents, *, folds: int = 10, seed: int = 
     + ``gaussian_log_likelihood``.  A family ``gaussian_fit`` refuses on some fold raises its ``ValueError``, naming the fold."""
     from .params import cv_folds
     what = "gaussian_cross_validate"
+    dl.need_unmixed(what, evaluator)
     if not getattr(evaluator, "continuous", False):
         raise ValueError(f"{what}: the evaluator holds discrete data: cross_validate is its counterpart")
     if not isinstance(evaluator, GaussianEvaluator):

@@ -143,7 +143,7 @@ def hill_climb(evaluator, starts=None, *, batch: Optional[int] = None, max_steps
                trace: bool = False) -> HillClimbResult:
     """Climb from every start at once.
 
-    ``evaluator``: a ``BNLearnWrapper``.  ``starts``: int64 [B, n] parent masks in data-set variable indices, a
+    ``evaluator``: a ``BNLearnWrapper``, a ``GaussianEvaluator`` or a ``MixedEvaluator``.  ``starts``: int64 [B, n] parent masks in data-set variable indices, a
     ``CompactBatch`` (e.g. from ``generate_dags``), or None with ``batch=`` for that many empty graphs.  ``max_parents``:
     no add or reversal gives a variable more parents than this (None: no cap).  ``forbidden``: int64 [n], bit u of
     ``forbidden[v]`` bars the edge u -> v (bnlearn's blacklist).  A move is taken only if it gains more than ``min_delta``.

@@ -312,4 +312,5 @@ def rsmax2(evaluator, *, restrict: str = "mmpc", maximize: str = "hc", restrict_
 
 def mmhc(evaluator, *, restrict_args: Optional[Dict] = None, maximize_args: Optional[Dict] = None) -> RSMAX2Result:
     """Max-min hill climbing (Tsamardinos, Brown and Aliferis 2006; bnlearn's ``mmhc``): ``rsmax2(restrict="mmpc", maximize="hc")``"""
+    dl.need_unmixed("mmhc", evaluator)
     return rsmax2(evaluator, restrict="mmpc", maximize="hc", restrict_args=restrict_args, maximize_args=maximize_args)

@@ -1,0 +1,396 @@
+"""Conditional Gaussian networks on data sets that hold factors and real columns (csrc/dvs_mixed.h).
+
+The reference hands ``metric_name`` to ``bnlearn::score`` unseen; on a mixed data frame that means ``loglik-cg``, ``aic-cg`` and
+``bic-cg``.  ``MixedEvaluator`` is their evaluator.  A discrete variable takes discrete parents only and is scored as
+``BNLearnWrapper`` scores it (``loglik`` / ``aic`` / ``bic``, equal bytes); a continuous variable has one linear regression on
+its continuous parents for every configuration of its discrete parents D.  What the scorer reads for D is a *table*: the
+moments of the real columns of every configuration (``dvs_cg_partition`` sorts the rows by configuration, ``dvs_cg_moments`` runs
+``dvs_gbn_moments``' summation over every segment).  The evaluator keeps tables in a cache keyed by D under a byte budget
+(``table_bytes=``, default 1 GiB): a pass collects its distinct masks (``torch.unique``), reads them back (the cache's one
+synchronisation per pass), builds the misses and hands the kernels a table index per cell.
+
+``hill_climb`` and ``tabu_search`` run on it unchanged: a continuous -> discrete arc is a NaN toggle cell, which the move
+selection treats as "not available"; ``illegal`` holds the same arcs as ``forbidden=`` rows.  ``cg_fit`` gives the parameters of
+a structure (``dvs_cg_fit``, and ``bn_fit`` on the discrete columns).  Not built on mixed data, each raising ``ValueError`` that
+says so: ``with_rows`` / ``boot_strength``, ``exact_search``, ``arc_posterior``, ``order_mcmc``, ``bn_fit``, ``gaussian_fit``, the
+CI-test family, ``cross_validate`` and ``available_case``.
+
+The definitions are those of include/dvs_mixed.h.  Three things follow bnlearn as recalled and are unpinned against an R run:
+the unbiased residual variance of every configuration, the parameter count q (p + 2), and the treatment of sparse
+configurations (an empty one adds nothing and counts in q; one with 1 .. p + 1 rows refuses the family).
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib as dl
+from .bic import BNLearnWrapper
+from .gaussian import load_real_csv
+
+PENALISED = ("aic-cg", "bic-cg")           # take k
+DISCRETE_METRIC = {"loglik-cg": "loglik", "aic-cg": "aic", "bic-cg": "bic"}      # what a discrete node's cell is, as bytes
+
+
+def _kinds(discrete, n):
+    """``discrete``: n entries (a level count 1..16 for a factor; 0 or None for a real column) or {column: level count} -> [n] ints"""
+    if isinstance(discrete, dict):
+        if any(not 0 <= int(c) < n for c in discrete):
+            raise ValueError(f"discrete names a column outside [0, {n})")
+        card = [int(discrete.get(i, 0) or 0) for i in range(n)]
+    else:
+        card = [int(c or 0) for c in discrete]
+    if len(card) != n or any(not 0 <= c <= 16 for c in card):
+        raise ValueError(f"discrete must give {n} entries: a level count in 1..16 for a factor, 0 for a real column")
+    return card
+
+
+def _pack(codes: np.ndarray, cols, n) -> np.ndarray:
+    """level codes [S, len(cols)] of the variables ``cols`` -> the packed int64 rows [S, ceil(n / 16)] (the other nibbles zero)"""
+    packed = np.zeros((codes.shape[0], (n + 15) // 16), np.uint64)
+    for j, v in enumerate(cols):
+        packed[:, v // 16] |= codes[:, j].astype(np.uint64) << np.uint64(4 * (v % 16))
+    return packed.view(np.int64)
+
+
+class MixedEvaluator:
+    """``packed`` (int64 [S, ceil(n / 16)]: the level codes of the factors), ``x`` (f64 [S, n_cont]: the real columns in ascending
+    variable order) and ``card`` (uint8 [n]: a factor's level count, 0 for a real column) are the data set."""
+    mixed = True                           # what _lib.need_discrete and _lib.need_unmixed look at
+
+    def __init__(self, dataset_name: str, metric_name: str = "bic-cg", data=None, discrete=None, device="cuda", *, k=None,
+                 table_bytes: int = 1 << 30):
+        """``data``: path of a CSV with a header row, or a real array [S, n <= 48] whose factor columns hold level codes 0 ..
+        levels - 1.  ``discrete``: n entries, a level count (1..16) for a factor and 0 for a real column, or {column: level
+        count}.  ``metric_name``: ``loglik-cg``, ``aic-cg`` or ``bic-cg``; ``k``: the penalty coefficient of aic-cg (default 1) /
+        bic-cg (default log(S) / 2).  ``table_bytes``: the budget of the table cache."""
+        if data is None or discrete is None:
+            raise ValueError("pass data=<csv path or real array [S, n]> and discrete=<level counts, 0 for a real column>")
+        arr = load_real_csv(data)[1] if isinstance(data, str) else np.asarray(data)
+        if arr.ndim != 2 or arr.shape[0] < 1 or not 1 <= arr.shape[1] <= dl.MAX_TOKENS or arr.dtype.kind not in "fiu":
+            raise ValueError("data must be a real array [samples >= 1, 1 <= n_vars <= 48]")
+        n = arr.shape[1]
+        card = _kinds(discrete, n)
+        dcols = [v for v in range(n) if card[v]]
+        ccols = [v for v in range(n) if not card[v]]
+        codes = arr[:, dcols]
+        if dcols and (not np.array_equal(codes, np.floor(codes)) or codes.min() < 0 or (codes.max(0) >= np.asarray([card[v] for v in dcols])).any()):
+            raise ValueError("a factor column must hold integer level codes in [0, its level count)")
+        device = torch.device(device)
+        dl.need_cuda("MixedEvaluator", device)
+        packed = torch.from_numpy(_pack(codes.astype(np.int64), dcols, n)).to(device)
+        x = torch.from_numpy(np.array(arr[:, ccols], np.float64, order="C")).to(device)
+        self._set(dataset_name, metric_name, k, table_bytes, packed, x, card)
+
+    @classmethod
+    def from_device(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, x: Optional[torch.Tensor], card, *, k=None,
+                    table_bytes: int = 1 << 30):
+        """An evaluator around rows that are already on the device: ``packed`` int64 [S, ceil(n / 16)] (the nibbles of real
+        columns are not read), ``x`` float64 or float32 [S, n_cont] (None without real columns), ``card`` as ``discrete``."""
+        card = _kinds(card, len(card))
+        n, nc = len(card), sum(1 for c in card if not c)
+        if not torch.is_tensor(packed) or packed.device.type != "cuda":
+            raise RuntimeError("dags_vae_search_amd: from_device takes rows on the GPU; this package has no CPU path")
+        if not 1 <= n <= dl.MAX_TOKENS or packed.dtype != torch.int64 or packed.ndim != 2 or packed.shape[0] < 1 or packed.shape[1] != (n + 15) // 16:
+            raise ValueError(f"packed must be int64 [S >= 1, {(n + 15) // 16}] for {n} variables")
+        S = packed.shape[0]
+        if x is None:
+            x = torch.empty(S, 0, dtype=torch.float64, device=packed.device)
+        if not torch.is_tensor(x) or x.device != packed.device or x.dtype not in (torch.float32, torch.float64) or tuple(x.shape) != (S, nc):
+            raise ValueError(f"x must be float64 or float32 [{S}, {nc}] on {packed.device}")
+        self = cls.__new__(cls)
+        self._set(dataset_name, metric_name, k, table_bytes, packed.contiguous(), x.to(torch.float64).contiguous(), card)
+        return self
+
+    def _set(self, dataset_name, metric_name, k, table_bytes, packed, x, card):
+        if metric_name not in dl.CGSCORE_TYPES:
+            raise NotImplementedError(f"built mixed-data scores: {', '.join(sorted(dl.CGSCORE_TYPES))} (got {metric_name!r})")
+        if k is not None and metric_name not in PENALISED:
+            raise ValueError(f"k is the argument of {' / '.join(PENALISED)}, not of {metric_name!r}")
+        if k is not None and not (math.isfinite(k) and k >= 0):
+            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
+        if int(table_bytes) < 1:
+            raise ValueError("table_bytes must be >= 1")
+        self.dataset_name, self.metric_name, self.k = dataset_name, metric_name, k
+        self.score_arg = float("nan") if k is None else float(k)          # NaN: the type's default (include/dvs_mixed.h)
+        self.lib, self.device, self.packed, self.x = dl.load(), packed.device, packed, x
+        self.n_samples, self.n_vars, self.n_cont = int(packed.shape[0]), len(card), int(x.shape[1])
+        self.card_host = card
+        self.kind = ["discrete" if c else "continuous" for c in card]
+        self.disc_mask = sum(1 << v for v in range(self.n_vars) if card[v])
+        self.cont_mask = sum(1 << v for v in range(self.n_vars) if not card[v])
+        self.table_bytes = int(table_bytes)
+        self._cache: "OrderedDict[int, torch.Tensor]" = OrderedDict()
+        self._cached_bytes = 0
+        self.cache_stats = {"passes": 0, "hits": 0, "misses": 0, "built": 0, "evicted": 0}
+        with torch.cuda.device(self.device):
+            dev = self.device
+            self.card = torch.tensor(card, dtype=torch.uint8, device=dev)
+            self.illegal = torch.tensor([self.cont_mask if c else 0 for c in card], dtype=torch.int64, device=dev)
+            self._is_cont = torch.tensor([not c for c in card], dtype=torch.bool, device=dev)
+            # bit u for a discrete u, 0 for a continuous one: what flipping u does to a family's D
+            self._flip = torch.tensor([(1 << v) if card[v] else 0 for v in range(self.n_vars)], dtype=torch.int64, device=dev)
+
+    # the relabelling of a CompactBatch (dvs_bic_parent_masks) reads no data: BNLearnWrapper's own, unbound from its class
+    _compact_parent_masks = BNLearnWrapper._compact_parent_masks
+    compact_parent_masks = BNLearnWrapper.compact_parent_masks
+
+    # ---- tables ------------------------------------------------------------------------------------------------------------
+    def configurations(self, mask: int) -> int:
+        """q of the set D = ``mask`` of discrete variables: the product of their level counts"""
+        q = 1
+        for v in range(self.n_vars):
+            if (mask >> v) & 1:
+                q *= self.card_host[v]
+        return q
+
+    def _table_nbytes(self, q):
+        return q * dl.gbn_stride(self.n_cont) * 8
+
+    def build_tables(self, masks: List[int]) -> List[torch.Tensor]:
+        """dvs_cg_partition + dvs_cg_moments for the sets ``masks`` (each within ``_lib.CG_MAX_CONFIGS`` configurations) ->
+        their tables f64 [q, stride], each its own allocation.  The requests run in launches of equal q_pitch whose buffers
+        stay within a quarter of the budget."""
+        lib, p, dev, S, nc = self.lib, dl.ptr, self.device, self.n_samples, self.n_cont
+        stride = dl.gbn_stride(nc)
+        order_of = sorted(range(len(masks)), key=lambda i: self.configurations(masks[i]))
+        out: List[Optional[torch.Tensor]] = [None] * len(masks)
+        at = 0
+        while at < len(order_of):
+            # the requests are sorted by q: a launch takes requests while its buffers at the last one's pitch stay in the slice
+            take = 1
+            while at + take < len(order_of):
+                pitch = self.configurations(masks[order_of[at + take]])
+                per = pitch * stride * 8 + 8 * pitch + 4 * S + ((S + dl.GBN_CHUNK - 1) // dl.GBN_CHUNK + pitch) * (nc + nc * (nc + 1) // 2) * 8
+                slots, tri = (S + dl.GBN_CHUNK - 1) // dl.GBN_CHUNK + pitch, nc * (nc + 1) // 2
+                if (take + 1) * per > max(self.table_bytes // 4, per) or (take + 1) * max(pitch, S, slots * tri) >= 1 << 30:
+                    break                                    # the buffers' slice of the budget; the index ranges of the two calls
+                take += 1
+            mine = order_of[at:at + take]
+            at += take
+            pitch = self.configurations(masks[mine[-1]])
+            R = len(mine)
+            req = torch.tensor([masks[i] for i in mine], dtype=torch.int64, device=dev)
+            count = torch.empty(R, pitch, dtype=torch.int32, device=dev)
+            start = torch.empty(R, pitch, dtype=torch.int32, device=dev)
+            order = torch.empty(R, S, dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            dl.check(lib, lib.dvs_cg_partition(self.n_vars, S, p(self.packed), p(self.card), R, p(req), pitch, p(count), dl.nbytes(count),
+                                               p(start), p(order), dl.nbytes(order), p(status), dl.stream()), "dvs_cg_partition")
+            ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_moments_workspace_bytes", nc, S, R, pitch), dtype=torch.uint8, device=dev)
+            mom = torch.empty(R, pitch, stride, dtype=torch.float64, device=dev)
+            dl.check(lib, lib.dvs_cg_moments(nc, S, p(self.x), R, pitch, p(count), p(start), p(order), p(ws), dl.nbytes(ws), p(mom),
+                                             dl.nbytes(mom), dl.stream()), "dvs_cg_moments")
+            for j, i in enumerate(mine):
+                out[i] = mom[j, :self.configurations(masks[i])].clone()
+        self.cache_stats["built"] += len(masks)
+        return out
+
+    def _tables_of(self, cell_masks: torch.Tensor):
+        """``cell_masks``: int64, the set D of every continuous family a pass scores, -1 where no table is read -> (tables int64
+        [T] device addresses, table_of int32 like cell_masks; -1: none, or D beyond ``_lib.CG_MAX_CONFIGS`` configurations:
+        refused on the device).  Reads the distinct masks back: the pass's one synchronisation."""
+        dev = self.device
+        uniq = torch.unique(cell_masks)
+        host = [int(m) for m in uniq.cpu().tolist()]
+        self.cache_stats["passes"] += 1
+        wanted = [m for m in host if m >= 0 and self.configurations(m) <= dl.CG_MAX_CONFIGS]
+        misses = [m for m in wanted if m not in self._cache]
+        self.cache_stats["hits"] += len(wanted) - len(misses)
+        self.cache_stats["misses"] += len(misses)
+        need = sum(self._table_nbytes(self.configurations(m)) for m in wanted)
+        if need > self.table_bytes:
+            raise ValueError(f"MixedEvaluator: the {len(wanted)} tables of one pass take {need:,} bytes, beyond table_bytes = "
+                             f"{self.table_bytes:,}: raise the budget or score fewer structures per call")
+        for m in wanted:
+            if m in self._cache:
+                self._cache.move_to_end(m)
+        incoming = sum(self._table_nbytes(self.configurations(m)) for m in misses)
+        keep = set(wanted)
+        for m in list(self._cache):
+            if self._cached_bytes + incoming <= self.table_bytes:
+                break
+            if m not in keep:
+                self._cached_bytes -= dl.nbytes(self._cache.pop(m))
+                self.cache_stats["evicted"] += 1
+        if misses:
+            for m, t in zip(misses, self.build_tables(misses)):
+                self._cache[m] = t
+                self._cached_bytes += dl.nbytes(t)
+        slot, addresses = {}, []
+        for m in wanted:
+            slot[m] = len(addresses)
+            addresses.append(self._cache[m].data_ptr())
+        tables = torch.tensor(addresses or [0], dtype=torch.int64, device=dev)
+        lookup = torch.tensor([slot.get(m, -1) for m in host], dtype=torch.int32, device=dev)
+        return tables, lookup[torch.searchsorted(uniq, cell_masks)].contiguous()
+
+    def clear_cache(self):
+        self._cache.clear()
+        self._cached_bytes = 0
+
+    def _family_masks(self, parents):
+        """D of every family [B, n]; -1 on the rows of discrete variables"""
+        return torch.where(self._is_cont[None, :], parents & self.disc_mask, torch.full_like(parents, -1))
+
+    def _score_args(self):
+        return dl.CGSCORE_TYPES[self.metric_name], self.score_arg
+
+    # ---- the scorer's surface ------------------------------------------------------------------------------------------------
+    def launch_scores(self, parents, scratch, out, status, used=None):
+        """``dvs_cg_scores`` on the caller's buffers: ``parents`` int64 [B, n_vars] contiguous on the device -> ``scratch`` f64
+        [B, n_vars] (the local scores), ``out`` f64 [B], ``status`` int32 [1] (bit 4: a family was refused)."""
+        if used is not None:
+            raise ValueError("used= is what an available-case view counts (BNLearnWrapper.available_case)")
+        B, n, lib, p = parents.shape[0], self.n_vars, self.lib, dl.ptr
+        tables = table_of = None
+        if self.n_cont:
+            tables, table_of = self._tables_of(self._family_masks(parents))
+        ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_scores_workspace_bytes", B, n), dtype=torch.uint8, device=self.device)
+        dl.check(lib, lib.dvs_cg_scores(B, n, self.n_cont, self.n_samples, p(self.packed), p(self.card), p(tables), p(table_of),
+                                        p(parents), *self._score_args(), p(ws), dl.nbytes(ws), p(scratch), p(out), p(status),
+                                        dl.stream()), "dvs_cg_scores")
+
+    def score_masks(self, parents: torch.Tensor, local: bool = False):
+        """parents: int64 [B, n_vars] bit rows (bit u of [b, v] <=> u -> v) -> f64 [B], or with ``local`` (scores f64 [B],
+        local scores f64 [B, n_vars]).  A refused family raises."""
+        parents = parents.to(self.device).contiguous()
+        B = parents.shape[0]
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
+            out = torch.empty(B, dtype=torch.float64, device=self.device)
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.launch_scores(parents, scratch, out, status)
+            if int(status.item()) & dl.STATUS_REFUSED:
+                bad = torch.nonzero(torch.isnan(scratch)).cpu().tolist()
+                raise ValueError(f"refused families (structure, variable): {bad[:8]}: {self._refusals()}")
+        return (out, scratch) if local else out
+
+    def _refusals(self):
+        return (f"a continuous parent of a discrete variable, more than {dl.CG_MAX_CONFIGS} configurations of the discrete parents, "
+                f"more than {dl.GBN_MAX_PARENTS} continuous parents, a parent bit >= {self.n_vars}, a configuration with 1 .. p + 1 "
+                f"rows, a Cholesky pivot within rounding of zero (a duplicated or collinear column) in some configuration, or a "
+                f"discrete family the counting paths cannot hold")
+
+    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
+        """The single-edge neighbourhood of every structure (dvs_cg_toggle_scores) -> (L f64 [B, n_vars], T f64 [B, n_vars,
+        n_vars]), with the meaning, the ``worklist`` / ``out`` pass and ``return_status`` of ``BNLearnWrapper.toggle_scores``; a
+        cell (v, u) with a discrete v and a continuous u is NaN: the move is not available."""
+        parents = parents.to(self.device).contiguous()
+        B, n = parents.shape
+        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
+        if out is None:
+            if worklist is not None:
+                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
+            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
+                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
+        L, T = out
+        lib, p = self.lib, dl.ptr
+        with torch.cuda.device(self.device):
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            tables = table_of = None
+            if self.n_cont:
+                if worklist is None:
+                    D = self._family_masks(parents).reshape(B * n)
+                else:
+                    wl = worklist.to(torch.int64)
+                    v = wl.clamp(0, n - 1)
+                    rows = parents[torch.arange(2 * B, device=self.device) // 2, v]
+                    live = (wl >= 0) & (wl < n) & self._is_cont[v]
+                    D = torch.where(live, rows & self.disc_mask, torch.full_like(rows, -1))
+                cells = torch.where(D[:, None] >= 0, D[:, None] ^ self._flip[None, :], D[:, None].expand(-1, n))
+                tables, table_of = self._tables_of(cells.contiguous())
+            ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_toggle_workspace_bytes", B, n), dtype=torch.uint8, device=self.device)
+            dl.check(lib, lib.dvs_cg_toggle_scores(B, n, self.n_cont, self.n_samples, p(self.packed), p(self.card), p(tables),
+                                                   p(table_of), p(parents), *self._score_args(), p(worklist), p(ws), dl.nbytes(ws),
+                                                   p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()),
+                     "dvs_cg_toggle_scores")
+        return (L, T, status) if return_status else (L, T)
+
+    def with_rows(self, *args, **kwargs):
+        dl.need_unmixed("with_rows / boot_strength", self)
+
+    def available_case(self, *args, **kwargs):
+        dl.need_unmixed("available_case", self)
+
+
+@dataclass
+class FittedCGBN:
+    parents: torch.Tensor                  # int64 [n]: the structure
+    kind: List[str]                        # "discrete" / "continuous" per variable
+    card: List[int]                        # a factor's level count, 0 for a real column
+    coef: List[Optional[torch.Tensor]]     # per continuous v: f64 [q_v, n], coef[v][z, u] the coefficient of u in configuration z, 0 off the continuous parents
+    intercept: List[Optional[torch.Tensor]]    # per continuous v: f64 [q_v]
+    sd: List[Optional[torch.Tensor]]       # per continuous v: f64 [q_v], sqrt(RSS_z / (m_z - p - 1))
+    count: List[Optional[torch.Tensor]]    # per continuous v: f64 [q_v], the rows of every configuration
+    discrete: object                       # params.FittedBN over the discrete columns in ascending order (None without factors)
+    discrete_vars: List[int]               # the variable of every column of ``discrete``
+
+
+def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
+    """bnlearn's ``bn.fit`` on a conditional Gaussian network: ``parents`` int64 [n] parent masks -> for every continuous
+    variable one regression per configuration of its discrete parents (dvs_cg_fit: NaN in an empty configuration), for the
+    discrete ones the tables of ``bn_fit`` on the discrete columns.  A refusal raises ``ValueError`` naming (variable,
+    configuration)."""
+    from .params import bn_fit
+    what = "cg_fit"
+    if not isinstance(evaluator, MixedEvaluator):
+        raise ValueError(f"{what}: takes a MixedEvaluator (bn_fit and gaussian_fit fit discrete and real-valued data)")
+    ev, n, dev = evaluator, evaluator.n_vars, evaluator.device
+    if not torch.is_tensor(parents) or parents.dtype != torch.int64 or tuple(parents.shape) != (n,):
+        raise ValueError(f"{what}: parents must be an int64 tensor [{n}] of parent masks")
+    host = [int(m) & ~(1 << v) for v, m in enumerate(parents.cpu().tolist())]
+    for v, m in enumerate(host):
+        if m >> n or m < 0:
+            raise ValueError(f"{what}: variable {v} has a parent bit >= {n}")
+        if ev.card_host[v] and m & ev.cont_mask:
+            raise ValueError(f"{what}: the discrete variable {v} has a continuous parent")
+    cvars = [v for v in range(n) if not ev.card_host[v]]
+    dvars = [v for v in range(n) if ev.card_host[v]]
+    coef: List[Optional[torch.Tensor]] = [None] * n
+    icpt, sd, cnt = list(coef), list(coef), list(coef)
+    with torch.cuda.device(dev):
+        if cvars:
+            qs = [ev.configurations(host[v] & ev.disc_mask) for v in cvars]
+            for v, q in zip(cvars, qs):
+                if q > dl.CG_MAX_CONFIGS:
+                    raise ValueError(f"{what}: variable {v} has {q} configurations of its discrete parents, beyond {dl.CG_MAX_CONFIGS}")
+            masks = torch.tensor([host[v] & ev.disc_mask for v in cvars], dtype=torch.int64, device=dev)
+            tables, table_of = ev._tables_of(masks)
+            offset = np.concatenate([[0], np.cumsum(qs)]).astype(np.int64)
+            cells, F, p = int(offset[-1]), len(cvars), dl.ptr
+            var = torch.tensor(cvars, dtype=torch.int32, device=dev)
+            par = torch.tensor([host[v] for v in cvars], dtype=torch.int64, device=dev)
+            table = tables[table_of.to(torch.int64)].contiguous()
+            off = torch.from_numpy(offset).to(dev)
+            c = torch.empty(cells, n, dtype=torch.float64, device=dev)
+            i0, s0, m0 = (torch.empty(cells, dtype=torch.float64, device=dev) for _ in range(3))
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            dl.check(ev.lib, ev.lib.dvs_cg_fit(F, cells, n, ev.n_cont, p(ev.card), p(var), p(par), p(table), p(off), p(c), dl.nbytes(c),
+                                               p(i0), p(s0), p(m0), p(status), dl.stream()), "dvs_cg_fit")
+            if int(status.item()) & dl.STATUS_REFUSED:
+                bad_cells = torch.nonzero(torch.isnan(s0) & (m0 != 0)).flatten().cpu().tolist()
+                bad = [(cvars[int(np.searchsorted(offset, b, side="right")) - 1], int(b - offset[int(np.searchsorted(offset, b, side="right")) - 1]))
+                       for b in bad_cells]
+                raise ValueError(f"{what}: refused (variable, configuration): {bad[:8]}: more than {dl.GBN_MAX_PARENTS} continuous "
+                                 f"parents, a configuration with 1 .. p + 1 rows, or collinear columns in that configuration")
+            for j, v in enumerate(cvars):
+                a, b = int(offset[j]), int(offset[j + 1])
+                coef[v], icpt[v], sd[v], cnt[v] = c[a:b], i0[a:b], s0[a:b], m0[a:b]
+        fitted = None
+        if dvars:
+            # the discrete columns as a data set of their own, in ascending variable order
+            codes = torch.stack([(ev.packed[:, v // 16] >> (4 * (v % 16))) & 15 for v in dvars], dim=1)
+            packed = torch.zeros(ev.n_samples, (len(dvars) + 15) // 16, dtype=torch.int64, device=dev)
+            for j in range(len(dvars)):
+                packed[:, j // 16] |= codes[:, j] << (4 * (j % 16))
+            sub = BNLearnWrapper.from_packed(ev.dataset_name, DISCRETE_METRIC[ev.metric_name], packed, [ev.card_host[v] for v in dvars])
+            rank = {v: j for j, v in enumerate(dvars)}
+            fitted = bn_fit(sub, torch.tensor([sum(1 << rank[u] for u in dvars if (host[v] >> u) & 1) for v in dvars],
+                                              dtype=torch.int64, device=dev))
+    return FittedCGBN(parents.to(dev), list(ev.kind), list(ev.card_host), coef, icpt, sd, cnt, fitted, dvars)

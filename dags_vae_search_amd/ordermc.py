@@ -108,6 +108,7 @@ def family_scores(evaluator, max_parents: int = 3, candidates=None, forbidden=No
     ``"koivisto"`` or a float64 [n] tensor, as in ``arc_posterior``) is added by set size.  Over DAGs the resulting prior is
     order-modular, not uniform (see the module docstring)."""
     what = "family_scores"
+    dl.need_unmixed(what, evaluator)
     dev, n = evaluator.device, evaluator.n_vars
     dl.need_cuda(what, dev)
     cap = int(max_parents)
@@ -207,6 +208,7 @@ def order_mcmc(families_or_evaluator, *, chains: int = 256, steps: int, burn_in:
     what = "order_mcmc"
     fam = families_or_evaluator
     if not isinstance(fam, FamilyScores):
+        dl.need_unmixed(what, fam)
         fam = family_scores(fam, **family_args)
     elif family_args:
         raise TypeError(f"{what}: {sorted(family_args)} apply to an evaluator, not to a FamilyScores")

@@ -51,6 +51,7 @@ def _gaussian(evaluator):
 def _evaluator(what, evaluator, test=None):
     """the level counts of a discrete evaluator, or None for a Gaussian one asked for one of its own tests (dl.GCI_TYPES); a
     test of the other kind of data is a ValueError"""
+    dl.need_unmixed(what, evaluator)
     if test in dl.GCI_TYPES:
         if not _gaussian(evaluator):
             raise ValueError(f"{what}: test {test!r} reads real-valued data and the evaluator holds discrete levels: pass a "

@@ -127,6 +127,7 @@ def arc_posterior(evaluator, *, max_parents: Optional[int] = None, forbidden=Non
     """The exact arc posterior for the evaluator's score and data (B = 1): ``local_score_table`` then
     ``arc_posterior_from_tables``.  Use a marginal-likelihood score (``bde``, ``k2``) for Bayesian model averaging; with a
     penalised likelihood (``bic``) the result is the same sum over exp(score), an approximation of it."""
+    dl.need_unmixed("arc_posterior", evaluator)
     table = local_score_table(evaluator, max_parents=max_parents)
     return arc_posterior_from_tables(table[None], max_parents=max_parents, forbidden=forbidden, parent_prior=parent_prior,
                                      families=families, lib=evaluator.lib)

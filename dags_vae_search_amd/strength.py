@@ -105,6 +105,7 @@ def boot_strength(evaluator, *, replicates: int = 200, m: Optional[int] = None, 
     for every ``chunk``, and shards with different ``set_offset`` add up (``+``).  With ``restarts`` the perturbation is
     keyed by the replicate's index within its batch (``dvs_hc_perturb``, as in ``hill_climb``), so the result then
     depends on ``chunk``.  ``exhausted`` counts the replicates whose search ran out of ``max_steps``."""
+    dl.need_unmixed("boot_strength", evaluator)
     if algorithm not in ("hc", "tabu"):
         raise ValueError(f"algorithm must be 'hc' or 'tabu' (got {algorithm!r})")
     args = dict(algorithm_args or {})
