@@ -11,6 +11,7 @@ from .train import batch_test, load_model_state, model_test, train_batch, train_
 from . import optim  # noqa: F401
 from .records import CompactBatch, CompactDagDataset, encode_graphs  # noqa: F401
 from .bic import AvailableCaseEvaluator, BNLearnWrapper  # noqa: F401
+from .evaluator import Evaluator  # noqa: F401
 from .predictor_data import create_predictor_dataset, generate_predictor_graphs_batch, prepare_predictor_data  # noqa: F401
 from .datasets import LabeledDagDatasetInMemory, LabeledDagDatasetInMemoryTest  # noqa: F401
 from .search import (SearchResult, StructureSet, decoded_structures, generation_metrics, latent_bo_search,  # noqa: F401

@@ -274,9 +274,14 @@ def require_cuda(t, what: str):
 GCI_ENTRY_POINTS = ("ci_tests", "ci_test", "pc_stable", "mmpc", "ci_tests_group", "rsmax2", "mmhc")
 
 
+def data_kind(evaluator) -> str:
+    """"discrete", "continuous" or "mixed" (``Evaluator.data_kind``, evaluator.py); what does not say holds discrete data"""
+    return getattr(evaluator, "data_kind", "discrete")
+
+
 def need_unmixed(what, evaluator):
     """the entry points that are not built on mixed data refuse a MixedEvaluator (mixed.py)"""
-    if getattr(evaluator, "mixed", False):
+    if data_kind(evaluator) == "mixed":
         raise ValueError(f"{what}: the evaluator holds mixed data (factors and real columns) and mixed data is not built for "
                          f"{what}: hill_climb, tabu_search, score_masks and cg_fit are")
 
@@ -284,7 +289,7 @@ def need_unmixed(what, evaluator):
 def need_discrete(what, evaluator):
     """the entry points that read ``packed`` / ``card`` refuse an evaluator over real-valued data (gaussian.py)"""
     need_unmixed(what, evaluator)
-    if getattr(evaluator, "continuous", False):
+    if data_kind(evaluator) == "continuous":
         gci = " (its tests on real-valued data are test=\"cor\", \"zf\" and \"mi-g\")" if what in GCI_ENTRY_POINTS else ""
         raise ValueError(f"{what}: the evaluator holds real-valued data and {what} reads discrete levels{gci}: its Gaussian "
                          f"counterpart is not built")

@@ -9,18 +9,19 @@ R's ``data(asia)``; its CSV copies are data/bn_asia/target.csv, data/bn_sachs/ta
 The reference hands ``metric_name`` to bnlearn unseen (bnlearn_scripts/bnlearn_score.R); built here are ``bic`` (the
 default, dvs_bic_scores) and, through dvs_bn_scores, ``loglik``, ``aic``, ``bde`` (BDeu), ``bds``, ``k2`` and ``bdj`` with
 bnlearn's arguments ``k`` (aic, bic) and ``iss`` (bde, bds) — definitions in include/dvs.h.  All of them are to be
-maximised, as the search (search.py) and the predictor data (predictor_data.py) assume.
+maximised, as the search (search.py) and the predictor data (predictor_data.py) assume.  The three classes here are
+``Evaluator``s (evaluator.py holds ``score_masks`` / ``toggle_scores`` / ``compact_parent_masks``); each names its entry points.
 """
 from __future__ import annotations
 
 import csv
-import math
 from typing import List, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib as dl
+from .evaluator import Evaluator, RowSets, check_k, check_positive, pack_levels, score_arg
 from .features import LABEL_KEY, _as_labels_edges
 
 
@@ -40,89 +41,15 @@ PENALISED_SCORES = ("aic", "bic")        # take k
 DIRICHLET_SCORES = ("bde", "bds")        # take iss
 
 
-class _AvailableCase:
-    """what ``AvailableCaseEvaluator._source`` names instead of row sets: the observed words and k of the ``_avail`` entry points"""
+class _DiscreteEvaluator(Evaluator):
+    """the refusal the evaluator of a discrete data set and its views share"""
 
-    def __init__(self, observed, k):
-        self.observed, self.k = observed, float(k)
-
-
-class _Scorer:
-    """The scorer launches of the evaluators.  ``_source(B)`` names the evaluator that holds the data set and the
-    arguments that follow ``status``: none (dvs_bic_scores / dvs_bn_scores, dvs_bn_toggle_scores), the row sets of the
-    ``_rows`` entry points, which take the same arguments up to there (include/dvs.h), or an ``_AvailableCase`` for the
-    ``_avail`` entry points (include/dvs_available.h)."""
-
-    def launch_scores(self, parents, scratch, out, status, used=None):
-        """The scorer on the caller's buffers, unchecked: ``parents`` int64 [B, n_vars] contiguous on the device ->
-        ``scratch`` f64 [B, n_vars] (the local scores), ``out`` f64 [B], ``status`` int32 [1] (bit 4: a family was refused).
-        The default-penalty bic of a plain evaluator is dvs_bic_scores; everything else dvs_bn_scores.  An available-case
-        view (dvs_bn_scores_avail) also fills ``used`` int32 [B, n_vars], the rows that counted per family."""
-        base, row_args = self._source(parents.shape[0])
-        p = dl.ptr
-        if isinstance(row_args, _AvailableCase):
-            name = "dvs_bn_scores_avail"
-            dl.check(self.lib, self.lib.dvs_bn_scores_avail(
-                parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(row_args.observed), p(base.card), p(parents),
-                row_args.k, p(scratch), p(out), p(used), p(status), dl.stream()), name)
-            return
-        if used is not None:
-            raise ValueError("used= is what an available-case view counts (BNLearnWrapper.available_case)")
-        head = (parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(base.card), p(parents))
-        tail = (p(scratch), p(out), p(status), *row_args, dl.stream())
-        if self.metric_name == "bic" and self.k is None and not row_args:
-            name = "dvs_bic_scores"
-        else:
-            name = "dvs_bn_scores_rows" if row_args else "dvs_bn_scores"
-            head += (dl.SCORE_TYPES[self.metric_name], base.score_arg)
-        dl.check(self.lib, getattr(self.lib, name)(*head, *tail), name)
-
-    def score_masks(self, parents: torch.Tensor, local: bool = False):
-        """parents: int64 [B, n_vars] bit rows in data-set variable indices (bit u of [b, v] <=> u -> v); -> f64 [B], or
-        with ``local`` (scores f64 [B], per-variable local scores f64 [B, n_vars])."""
-        parents = parents.to(self.device).contiguous()
-        B = parents.shape[0]
-        scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
-        out = torch.empty(B, dtype=torch.float64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.launch_scores(parents, scratch, out, status)
-        if int(status.item()) & dl.STATUS_REFUSED:
-            raise ValueError("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
-                             "cells; sorted samples: 16 384 samples, 63 key bits)")
-        return (out, scratch) if local else out
-
-    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
-        """The single-edge neighbourhood of every structure (dvs_bn_toggle_scores) -> (L f64 [B, n_vars],
-        T f64 [B, n_vars, n_vars]) on the device: L the local scores as ``score_masks(local=True)`` gives them, T[b, v, u]
-        the local score of v with bit u of ``parents[b, v]`` flipped (NaN on the diagonal and where the family is refused:
-        that move is not available).  ``worklist`` (int32 [2 B], ``hill_climb``'s) with ``out=(L, T)`` recomputes only
-        the rows it names, in place.  ``return_status`` appends the status word (bit 4: some family was refused)."""
-        parents = parents.to(self.device).contiguous()
-        B, n = parents.shape
-        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
-        base, row_args = self._source(B)
-        if out is None:
-            if worklist is not None:
-                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
-            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
-                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
-        L, T = out
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = dl.ptr
-        if isinstance(row_args, _AvailableCase):
-            name = "dvs_bn_toggle_scores_avail"
-            dl.check(self.lib, self.lib.dvs_bn_toggle_scores_avail(
-                B, n, base.n_samples, p(base.packed), p(row_args.observed), p(base.card), p(parents), row_args.k, p(worklist),
-                p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()), name)
-            return (L, T, status) if return_status else (L, T)
-        name = "dvs_bn_toggle_scores_rows" if row_args else "dvs_bn_toggle_scores"
-        dl.check(self.lib, getattr(self.lib, name)(
-            B, n, base.n_samples, p(base.packed), p(base.card), p(parents), dl.SCORE_TYPES[self.metric_name], base.score_arg,
-            p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), *row_args, dl.stream()), name)
-        return (L, T, status) if return_status else (L, T)
+    def _refusal(self, scratch):
+        return ("a variable's parent set is too large for the on-chip counting paths (dense table: 36 864 "
+                "cells; sorted samples: 16 384 samples, 63 key bits)")
 
 
-class BNLearnWrapper(_Scorer):
+class BNLearnWrapper(_DiscreteEvaluator):
     """``packed`` (int64 [S, ceil(n / 16)], 4-bit level codes), ``card`` (uint8 [n]) and its host copy ``card_host`` are the
     data set on the device; ``score_arg`` is the score type's argument as the library takes it."""
 
@@ -136,13 +63,10 @@ class BNLearnWrapper(_Scorer):
         arr = load_discrete_csv(data)[1] if isinstance(data, str) else np.asarray(data)
         if arr.ndim != 2 or arr.shape[1] > dl.MAX_TOKENS or arr.min() < 0 or arr.max() > 15:
             raise ValueError("data must be [samples, n_vars <= 48] with level codes 0..15")
-        words = (arr.shape[1] + 15) // 16
-        packed = np.zeros((arr.shape[0], words), np.uint64)
-        for i in range(arr.shape[1]):
-            packed[:, i // 16] |= arr[:, i].astype(np.uint64) << np.uint64(4 * (i % 16))
+        packed = pack_levels(arr, range(arr.shape[1]), arr.shape[1])
         # card_host: pc.py sizes the CI tables' LDS from it
         device = torch.device(device)
-        self._set_data(torch.from_numpy(packed.view(np.int64)).to(device), [int(c) for c in arr.max(0) + 1], device)
+        self._set_data(torch.from_numpy(packed).to(device), [int(c) for c in arr.max(0) + 1], device)
 
     @classmethod
     def from_packed(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, card, *, iss=None, k=None):
@@ -163,18 +87,10 @@ class BNLearnWrapper(_Scorer):
     def _set_score(self, dataset_name, metric_name, iss, k):
         if metric_name not in dl.SCORE_TYPES:
             raise NotImplementedError(f"built scores: {', '.join(sorted(dl.SCORE_TYPES))} (got {metric_name!r})")
-        if iss is not None and metric_name not in DIRICHLET_SCORES:
-            raise ValueError(f"iss is the argument of {' / '.join(DIRICHLET_SCORES)}, not of {metric_name!r}")
-        if k is not None and metric_name not in PENALISED_SCORES:
-            raise ValueError(f"k is the argument of {' / '.join(PENALISED_SCORES)}, not of {metric_name!r}")
-        if iss is not None and not (math.isfinite(iss) and iss > 0):
-            raise ValueError(f"iss must be finite and > 0 (got {iss!r})")
-        if k is not None and not (math.isfinite(k) and k >= 0):
-            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
-        self.dataset_name, self.metric_name = dataset_name, metric_name
-        self.iss, self.k = iss, k
-        arg = iss if iss is not None else k
-        self.score_arg = float("nan") if arg is None else float(arg)       # NaN: the type's default (include/dvs.h)
+        check_positive("iss", iss, metric_name, DIRICHLET_SCORES)
+        check_k(k, metric_name, PENALISED_SCORES)
+        self.dataset_name, self.metric_name, self.iss, self.k = dataset_name, metric_name, iss, k
+        self.score_arg = score_arg(iss if iss is not None else k)
 
     def _set_data(self, packed, card_host, device):
         self.lib = dl.load()
@@ -183,8 +99,28 @@ class BNLearnWrapper(_Scorer):
         self.packed, self.card_host = packed, card_host
         self.card = torch.tensor(card_host, dtype=torch.uint8, device=self.device)
 
-    def _source(self, B):
-        return self, ()
+    def _head(self, parents):
+        """what every scorer entry point over these rows starts with (include/dvs.h), a row-set view's included"""
+        p = dl.ptr
+        return parents.shape[0], self.n_vars, self.n_samples, p(self.packed), p(self.card), p(parents)
+
+    def _score_args(self):
+        return dl.SCORE_TYPES[self.metric_name], self.score_arg
+
+    def _launch_scores(self, parents, scratch, out, status, used):
+        """the default-penalty bic is dvs_bic_scores; everything else dvs_bn_scores"""
+        p, lib = dl.ptr, self.lib
+        if self.metric_name == "bic" and self.k is None:
+            dl.check(lib, lib.dvs_bic_scores(*self._head(parents), p(scratch), p(out), p(status), dl.stream()), "dvs_bic_scores")
+        else:
+            dl.check(lib, lib.dvs_bn_scores(*self._head(parents), *self._score_args(), p(scratch), p(out), p(status), dl.stream()),
+                     "dvs_bn_scores")
+
+    def _launch_toggles(self, parents, worklist, L, T, status):
+        p = dl.ptr
+        dl.check(self.lib, self.lib.dvs_bn_toggle_scores(
+            *self._head(parents), *self._score_args(), p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status),
+            dl.stream()), "dvs_bn_toggle_scores")
 
     def _parent_masks(self, graphs: Sequence, label_key: str) -> np.ndarray:
         n = self.n_vars
@@ -200,28 +136,6 @@ class BNLearnWrapper(_Scorer):
     def score_batch(self, labeled_graphs: Sequence, label_key: str = LABEL_KEY) -> List[float]:
         masks = self._parent_masks(labeled_graphs, label_key)
         return self.score_masks(torch.from_numpy(masks.view(np.int64))).cpu().tolist()
-
-    def _compact_parent_masks(self, batch):
-        """(parent masks, the relabelling's status word), both on the device and unchecked"""
-        labels =batch.labels.to(self.device).contiguous()
-        preds = batch.preds.to(self.device).contiguous()
-        B, n = labels.shape
-        assert n == self.n_vars, f"Expected {self.n_vars} vertices, but got {n}"                             # bnlearn.py:34
-        parents = torch.empty(B, n, dtype=torch.int64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = dl.ptr
-        dl.check(self.lib, self.lib.dvs_bic_parent_masks(B, n, 1 if preds.dtype == torch.int64 else 0, p(labels), p(preds),
-                                                         p(parents), p(status), dl.stream()), "dvs_bic_parent_masks")
-        return parents, status
-
-    def compact_parent_masks(self, batch) -> torch.Tensor:
-        """Parent masks (int64 [B, n_vars], data-set variable indices) of a ``CompactBatch`` that lives on the device: the
-        relabelling of bnlearn.py:34-45 as one HIP launch (dvs_bic_parent_masks).  What ``score_masks``, ``toggle_scores``
-        and ``hill_climb`` take."""
-        parents, status = self._compact_parent_masks(batch)
-        if int(status.item()) & dl.STATUS_LABELS:
-            raise AssertionError(f"Expected graph labels from 0 to {self.n_vars - 1}")                        # bnlearn.py:35
-        return parents
 
     def score_compact(self, batch) -> torch.Tensor:
         """Score of a ``CompactBatch`` (records.py) that lives on the device -> float64 [B] on the device: the relabelling
@@ -252,7 +166,7 @@ class BNLearnWrapper(_Scorer):
         return self.score_batch([labeled_graph], label_key)[0]
 
 
-class RowSetEvaluator(_Scorer):
+class RowSetEvaluator(_DiscreteEvaluator):
     """``BNLearnWrapper.with_rows``: the base evaluator's data, score and device, with structure b counted over the rows
     ``rows[set_of[b]]``.  ``n_samples`` is the set size: every score is, bit for bit, the base score type on the gathered
     data set (bic's default penalty is log(set_size) / 2).  The indices are checked here, once: the device does not."""
@@ -261,53 +175,45 @@ class RowSetEvaluator(_Scorer):
         self.base = base
         self.lib, self.device, self.n_vars, self.metric_name = base.lib, base.device, base.n_vars, base.metric_name
         self.dataset_name, self.iss, self.k = base.dataset_name, base.iss, base.k
-        if not torch.is_tensor(rows) or rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1 or \
-                rows.dtype not in (torch.int32, torch.int64):
-            raise ValueError("rows must be an integer tensor [n_sets >= 1, set_size >= 1]")
-        rows = rows.to(self.device)
-        if int(torch.amin(rows)) < 0 or int(torch.amax(rows)) >= base.n_samples:
-            raise ValueError(f"rows must lie in [0, {base.n_samples})")
-        self.rows = rows.to(torch.int32).contiguous()
-        self.n_sets, self.n_samples = int(rows.shape[0]), int(rows.shape[1])
-        self.set_of = None
-        if set_of is not None:
-            set_of = torch.as_tensor(set_of).to(self.device)
-            if set_of.ndim != 1 or set_of.numel() < 1 or set_of.dtype not in (torch.int32, torch.int64):
-                raise ValueError("set_of must be an integer tensor [B]")
-            if int(torch.amin(set_of)) < 0 or int(torch.amax(set_of)) >= self.n_sets:
-                raise ValueError(f"set_of must lie in [0, {self.n_sets})")
-            self.set_of = set_of.to(torch.int32).contiguous()
+        self.sets = sets = RowSets(rows, set_of, base.n_samples, self.device)
+        self.rows, self.set_of, self.n_sets, self.n_samples = sets.rows, sets.set_of, sets.n_sets, sets.set_size
 
-    def compact_parent_masks(self, batch) -> torch.Tensor:
-        return self.base.compact_parent_masks(batch)
+    def row_sets(self, B):
+        return self.sets.of(B)
 
-    def _source(self, B):
-        if self.set_of is None:
-            if B > self.n_sets:
-                raise ValueError(f"{B} structures but {self.n_sets} row sets: pass set_of")
-        elif self.set_of.numel() != B:
-            raise ValueError(f"{B} structures but set_of names {self.set_of.numel()}")
-        return self.base, (dl.ptr(self.rows), self.n_samples, self.n_sets, dl.ptr(self.set_of))
+    def _tail(self, B):
+        """what follows ``status`` in the ``_rows`` entry points, which take the plain ones' arguments up to there"""
+        n_sets, set_of = self.sets.of(B)
+        return dl.ptr(self.rows), self.n_samples, n_sets, dl.ptr(set_of), dl.stream()
+
+    def _launch_scores(self, parents, scratch, out, status, used):
+        p, base = dl.ptr, self.base
+        dl.check(self.lib, self.lib.dvs_bn_scores_rows(*base._head(parents), *base._score_args(), p(scratch), p(out), p(status),
+                                                       *self._tail(parents.shape[0])), "dvs_bn_scores_rows")
+
+    def _launch_toggles(self, parents, worklist, L, T, status):
+        p, base = dl.ptr, self.base
+        dl.check(self.lib, self.lib.dvs_bn_toggle_scores_rows(
+            *base._head(parents), *base._score_args(), p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status),
+            *self._tail(parents.shape[0])), "dvs_bn_toggle_scores_rows")
 
 
 AVAILABLE_CASE_SCORES = ("nal", "pnal")
 
 
-class AvailableCaseEvaluator(_Scorer):
+class AvailableCaseEvaluator(_DiscreteEvaluator):
     """``BNLearnWrapper.available_case``: the base evaluator's rows, level counts and device, each family scored on exactly
     the rows that observe it whole: local = LL / m - k (r - 1) q (include/dvs_available.h).  ``nal`` is k = 0; the default k of
     ``pnal``, ``n_samples ** -0.25``, is computed here and is the alpha = 1/4 of Bodewes and Scutari (2021) as recalled: parity
     with bnlearn's ``nal`` / ``pnal`` is unpinned against an R run.  A family that no row observes whole scores -inf (status
     bit 7, which does not raise); a refused family raises as it does for the plain evaluator.  ``observed`` is checked here,
     once."""
+    counts_used = True
 
     def __init__(self, base: BNLearnWrapper, observed, metric="pnal", k=None):
         if metric not in AVAILABLE_CASE_SCORES:
             raise NotImplementedError(f"available-case scores: {', '.join(AVAILABLE_CASE_SCORES)} (got {metric!r})")
-        if k is not None and metric != "pnal":
-            raise ValueError(f"k is the argument of pnal, not of {metric!r}")
-        if k is not None and not (math.isfinite(k) and k >= 0):
-            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
+        check_k(k, metric, ("pnal",))
         self.base = base
         self.lib, self.device, self.n_vars, self.n_samples = base.lib, base.device, base.n_vars, base.n_samples
         self.card, self.card_host = base.card, base.card_host       # no ``packed``: what reads rows off an evaluator must not take these as complete
@@ -322,11 +228,22 @@ class AvailableCaseEvaluator(_Scorer):
         if never:
             raise ValueError(f"available_case: no row observes variable(s) {never}: nothing could score them")
 
-    def _source(self, B):
-        return self.base, _AvailableCase(self.observed, self.penalty)
+    def _head(self, parents):
+        """what the ``_avail`` entry points start with (include/dvs_available.h)"""
+        p, base = dl.ptr, self.base
+        return (parents.shape[0], self.n_vars, base.n_samples, p(base.packed), p(self.observed), p(base.card), p(parents),
+                self.penalty)
 
-    def compact_parent_masks(self, batch) -> torch.Tensor:
-        return self.base.compact_parent_masks(batch)
+    def _launch_scores(self, parents, scratch, out, status, used):
+        p = dl.ptr
+        dl.check(self.lib, self.lib.dvs_bn_scores_avail(*self._head(parents), p(scratch), p(out), p(used), p(status), dl.stream()),
+                 "dvs_bn_scores_avail")
+
+    def _launch_toggles(self, parents, worklist, L, T, status):
+        p = dl.ptr
+        dl.check(self.lib, self.lib.dvs_bn_toggle_scores_avail(
+            *self._head(parents), p(worklist), p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()),
+            "dvs_bn_toggle_scores_avail")
 
     def used(self, parents: torch.Tensor) -> torch.Tensor:
         """the rows that count for every family of ``parents`` (int64 [B, n_vars]) -> int32 [B, n_vars]; 0 where no row does

@@ -111,7 +111,7 @@ def ci_tests_group(evaluator, targets, cond, candidates, test: str = "mi", *, ld
     with torch.cuda.device(dev):
         out = torch.empty(G, evaluator.n_vars, 3, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _launch_group(evaluator, targets, cond, candidates, typ, lds_cells, out, status, evaluator._sets(G) if gaussian else None)
+        _launch_group(evaluator, targets, cond, candidates, typ, lds_cells, out, status, evaluator.row_sets(G) if gaussian else None)
     return (out, status) if return_status else out
 
 

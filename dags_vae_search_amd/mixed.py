@@ -9,7 +9,7 @@ moments of the real columns of every configuration (``dvs_cg_partition`` sorts t
 (``table_bytes=``, default 1 GiB): a pass collects its distinct masks (``torch.unique``), reads them back (the cache's one
 synchronisation per pass), builds the misses and hands the kernels a table index per cell.
 
-``hill_climb`` and ``tabu_search`` run on it unchanged: a continuous -> discrete arc is a NaN toggle cell, which the move
+It is an ``Evaluator`` (evaluator.py), so ``hill_climb`` and ``tabu_search`` run on it unchanged: a continuous -> discrete arc is a NaN toggle cell, which the move
 selection treats as "not available"; ``illegal`` holds the same arcs as ``forbidden=`` rows.  ``cg_fit`` gives the parameters of
 a structure (``dvs_cg_fit``, and ``bn_fit`` on the discrete columns).  Not built on mixed data, each raising ``ValueError`` that
 says so: ``with_rows`` / ``boot_strength``, ``exact_search``, ``arc_posterior``, ``order_mcmc``, ``bn_fit``, ``gaussian_fit``, the
@@ -21,7 +21,6 @@ configurations (an empty one adds nothing and counts in q; one with 1 .. p + 1 r
 """
 from __future__ import annotations
 
-import math
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import List, Optional
@@ -31,6 +30,7 @@ import torch
 
 from . import _lib as dl
 from .bic import BNLearnWrapper
+from .evaluator import Evaluator, check_k, pack_levels, score_arg
 from .gaussian import load_real_csv
 
 PENALISED = ("aic-cg", "bic-cg")           # take k
@@ -50,18 +50,10 @@ def _kinds(discrete, n):
     return card
 
 
-def _pack(codes: np.ndarray, cols, n) -> np.ndarray:
-    """level codes [S, len(cols)] of the variables ``cols`` -> the packed int64 rows [S, ceil(n / 16)] (the other nibbles zero)"""
-    packed = np.zeros((codes.shape[0], (n + 15) // 16), np.uint64)
-    for j, v in enumerate(cols):
-        packed[:, v // 16] |= codes[:, j].astype(np.uint64) << np.uint64(4 * (v % 16))
-    return packed.view(np.int64)
-
-
-class MixedEvaluator:
+class MixedEvaluator(Evaluator):
     """``packed`` (int64 [S, ceil(n / 16)]: the level codes of the factors), ``x`` (f64 [S, n_cont]: the real columns in ascending
     variable order) and ``card`` (uint8 [n]: a factor's level count, 0 for a real column) are the data set."""
-    mixed = True                           # what _lib.need_discrete and _lib.need_unmixed look at
+    data_kind = "mixed"
 
     def __init__(self, dataset_name: str, metric_name: str = "bic-cg", data=None, discrete=None, device="cuda", *, k=None,
                  table_bytes: int = 1 << 30):
@@ -83,9 +75,10 @@ class MixedEvaluator:
             raise ValueError("a factor column must hold integer level codes in [0, its level count)")
         device = torch.device(device)
         dl.need_cuda("MixedEvaluator", device)
-        packed = torch.from_numpy(_pack(codes.astype(np.int64), dcols, n)).to(device)
+        self._set_score(dataset_name, metric_name, k, table_bytes)
+        packed = torch.from_numpy(pack_levels(codes.astype(np.int64), dcols, n)).to(device)
         x = torch.from_numpy(np.array(arr[:, ccols], np.float64, order="C")).to(device)
-        self._set(dataset_name, metric_name, k, table_bytes, packed, x, card)
+        self._set_data(packed, x, card)
 
     @classmethod
     def from_device(cls, dataset_name: str, metric_name: str, packed: torch.Tensor, x: Optional[torch.Tensor], card, *, k=None,
@@ -104,27 +97,26 @@ class MixedEvaluator:
         if not torch.is_tensor(x) or x.device != packed.device or x.dtype not in (torch.float32, torch.float64) or tuple(x.shape) != (S, nc):
             raise ValueError(f"x must be float64 or float32 [{S}, {nc}] on {packed.device}")
         self = cls.__new__(cls)
-        self._set(dataset_name, metric_name, k, table_bytes, packed.contiguous(), x.to(torch.float64).contiguous(), card)
+        self._set_score(dataset_name, metric_name, k, table_bytes)
+        self._set_data(packed.contiguous(), x.to(torch.float64).contiguous(), card)
         return self
 
-    def _set(self, dataset_name, metric_name, k, table_bytes, packed, x, card):
+    def _set_score(self, dataset_name, metric_name, k, table_bytes):
         if metric_name not in dl.CGSCORE_TYPES:
             raise NotImplementedError(f"built mixed-data scores: {', '.join(sorted(dl.CGSCORE_TYPES))} (got {metric_name!r})")
-        if k is not None and metric_name not in PENALISED:
-            raise ValueError(f"k is the argument of {' / '.join(PENALISED)}, not of {metric_name!r}")
-        if k is not None and not (math.isfinite(k) and k >= 0):
-            raise ValueError(f"k must be finite and >= 0 (got {k!r})")
+        check_k(k, metric_name, PENALISED)
         if int(table_bytes) < 1:
             raise ValueError("table_bytes must be >= 1")
         self.dataset_name, self.metric_name, self.k = dataset_name, metric_name, k
-        self.score_arg = float("nan") if k is None else float(k)          # NaN: the type's default (include/dvs_mixed.h)
+        self.score_arg, self.table_bytes = score_arg(k), int(table_bytes)
+
+    def _set_data(self, packed, x, card):
         self.lib, self.device, self.packed, self.x = dl.load(), packed.device, packed, x
         self.n_samples, self.n_vars, self.n_cont = int(packed.shape[0]), len(card), int(x.shape[1])
         self.card_host = card
         self.kind = ["discrete" if c else "continuous" for c in card]
         self.disc_mask = sum(1 << v for v in range(self.n_vars) if card[v])
         self.cont_mask = sum(1 << v for v in range(self.n_vars) if not card[v])
-        self.table_bytes = int(table_bytes)
         self._cache: "OrderedDict[int, torch.Tensor]" = OrderedDict()
         self._cached_bytes = 0
         self.cache_stats = {"passes": 0, "hits": 0, "misses": 0, "built": 0, "evicted": 0}
@@ -135,10 +127,6 @@ class MixedEvaluator:
             self._is_cont = torch.tensor([not c for c in card], dtype=torch.bool, device=dev)
             # bit u for a discrete u, 0 for a continuous one: what flipping u does to a family's D
             self._flip = torch.tensor([(1 << v) if card[v] else 0 for v in range(self.n_vars)], dtype=torch.int64, device=dev)
-
-    # the relabelling of a CompactBatch (dvs_bic_parent_masks) reads no data: BNLearnWrapper's own, unbound from its class
-    _compact_parent_masks = BNLearnWrapper._compact_parent_masks
-    compact_parent_masks = BNLearnWrapper.compact_parent_masks
 
     # ---- tables ------------------------------------------------------------------------------------------------------------
     def configurations(self, mask: int) -> int:
@@ -191,7 +179,7 @@ class MixedEvaluator:
         self.cache_stats["built"] += len(masks)
         return out
 
-    def _tables_of(self, cell_masks: torch.Tensor):
+    def tables_of(self, cell_masks: torch.Tensor):
         """``cell_masks``: int64, the set D of every continuous family a pass scores, -1 where no table is read -> (tables int64
         [T] device addresses, table_of int32 like cell_masks; -1: none, or D beyond ``_lib.CG_MAX_CONFIGS`` configurations:
         refused on the device).  Reads the distinct masks back: the pass's one synchronisation."""
@@ -242,75 +230,44 @@ class MixedEvaluator:
         return dl.CGSCORE_TYPES[self.metric_name], self.score_arg
 
     # ---- the scorer's surface ------------------------------------------------------------------------------------------------
-    def launch_scores(self, parents, scratch, out, status, used=None):
-        """``dvs_cg_scores`` on the caller's buffers: ``parents`` int64 [B, n_vars] contiguous on the device -> ``scratch`` f64
-        [B, n_vars] (the local scores), ``out`` f64 [B], ``status`` int32 [1] (bit 4: a family was refused)."""
-        if used is not None:
-            raise ValueError("used= is what an available-case view counts (BNLearnWrapper.available_case)")
+    def _launch_scores(self, parents, scratch, out, status, used):
         B, n, lib, p = parents.shape[0], self.n_vars, self.lib, dl.ptr
         tables = table_of = None
         if self.n_cont:
-            tables, table_of = self._tables_of(self._family_masks(parents))
+            tables, table_of = self.tables_of(self._family_masks(parents))
         ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_scores_workspace_bytes", B, n), dtype=torch.uint8, device=self.device)
         dl.check(lib, lib.dvs_cg_scores(B, n, self.n_cont, self.n_samples, p(self.packed), p(self.card), p(tables), p(table_of),
                                         p(parents), *self._score_args(), p(ws), dl.nbytes(ws), p(scratch), p(out), p(status),
                                         dl.stream()), "dvs_cg_scores")
 
-    def score_masks(self, parents: torch.Tensor, local: bool = False):
-        """parents: int64 [B, n_vars] bit rows (bit u of [b, v] <=> u -> v) -> f64 [B], or with ``local`` (scores f64 [B],
-        local scores f64 [B, n_vars]).  A refused family raises."""
-        parents = parents.to(self.device).contiguous()
-        B = parents.shape[0]
-        with torch.cuda.device(self.device):
-            scratch = torch.empty(B, self.n_vars, dtype=torch.float64, device=self.device)
-            out = torch.empty(B, dtype=torch.float64, device=self.device)
-            status = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.launch_scores(parents, scratch, out, status)
-            if int(status.item()) & dl.STATUS_REFUSED:
-                bad = torch.nonzero(torch.isnan(scratch)).cpu().tolist()
-                raise ValueError(f"refused families (structure, variable): {bad[:8]}: {self._refusals()}")
-        return (out, scratch) if local else out
-
-    def _refusals(self):
-        return (f"a continuous parent of a discrete variable, more than {dl.CG_MAX_CONFIGS} configurations of the discrete parents, "
+    def _refusal(self, scratch):
+        bad = torch.nonzero(torch.isnan(scratch)).cpu().tolist()
+        return (f"refused families (structure, variable): {bad[:8]}: "
+                f"a continuous parent of a discrete variable, more than {dl.CG_MAX_CONFIGS} configurations of the discrete parents, "
                 f"more than {dl.GBN_MAX_PARENTS} continuous parents, a parent bit >= {self.n_vars}, a configuration with 1 .. p + 1 "
                 f"rows, a Cholesky pivot within rounding of zero (a duplicated or collinear column) in some configuration, or a "
                 f"discrete family the counting paths cannot hold")
 
-    def toggle_scores(self, parents: torch.Tensor, *, worklist=None, out=None, return_status: bool = False):
-        """The single-edge neighbourhood of every structure (dvs_cg_toggle_scores) -> (L f64 [B, n_vars], T f64 [B, n_vars,
-        n_vars]), with the meaning, the ``worklist`` / ``out`` pass and ``return_status`` of ``BNLearnWrapper.toggle_scores``; a
-        cell (v, u) with a discrete v and a continuous u is NaN: the move is not available."""
-        parents = parents.to(self.device).contiguous()
-        B, n = parents.shape
-        assert n == self.n_vars, f"Expected {self.n_vars} variables, but got {n}"
-        if out is None:
-            if worklist is not None:
-                raise ValueError("an incremental pass (worklist=) updates a table in place: pass out=(L, T)")
-            out = (torch.empty(B, n, dtype=torch.float64, device=self.device),
-                   torch.empty(B, n, n, dtype=torch.float64, device=self.device))
-        L, T = out
-        lib, p = self.lib, dl.ptr
-        with torch.cuda.device(self.device):
-            status = torch.zeros(1, dtype=torch.int32, device=self.device)
-            tables = table_of = None
-            if self.n_cont:
-                if worklist is None:
-                    D = self._family_masks(parents).reshape(B * n)
-                else:
-                    wl = worklist.to(torch.int64)
-                    v = wl.clamp(0, n - 1)
-                    rows = parents[torch.arange(2 * B, device=self.device) // 2, v]
-                    live = (wl >= 0) & (wl < n) & self._is_cont[v]
-                    D = torch.where(live, rows & self.disc_mask, torch.full_like(rows, -1))
-                cells = torch.where(D[:, None] >= 0, D[:, None] ^ self._flip[None, :], D[:, None].expand(-1, n))
-                tables, table_of = self._tables_of(cells.contiguous())
-            ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_toggle_workspace_bytes", B, n), dtype=torch.uint8, device=self.device)
-            dl.check(lib, lib.dvs_cg_toggle_scores(B, n, self.n_cont, self.n_samples, p(self.packed), p(self.card), p(tables),
-                                                   p(table_of), p(parents), *self._score_args(), p(worklist), p(ws), dl.nbytes(ws),
-                                                   p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()),
-                     "dvs_cg_toggle_scores")
-        return (L, T, status) if return_status else (L, T)
+    def _launch_toggles(self, parents, worklist, L, T, status):
+        """dvs_cg_toggle_scores; a cell (v, u) with a discrete v and a continuous u is NaN: the move is not available"""
+        (B, n), lib, p = parents.shape, self.lib, dl.ptr
+        tables = table_of = None
+        if self.n_cont:
+            if worklist is None:
+                D = self._family_masks(parents).reshape(B * n)
+            else:
+                wl = worklist.to(torch.int64)
+                v = wl.clamp(0, n - 1)
+                rows = parents[torch.arange(2 * B, device=self.device) // 2, v]
+                live = (wl >= 0) & (wl < n) & self._is_cont[v]
+                D = torch.where(live, rows & self.disc_mask, torch.full_like(rows, -1))
+            cells = torch.where(D[:, None] >= 0, D[:, None] ^ self._flip[None, :], D[:, None].expand(-1, n))
+            tables, table_of = self.tables_of(cells.contiguous())
+        ws = torch.empty(dl.workspace_bytes(lib, "dvs_cg_toggle_workspace_bytes", B, n), dtype=torch.uint8, device=self.device)
+        dl.check(lib, lib.dvs_cg_toggle_scores(B, n, self.n_cont, self.n_samples, p(self.packed), p(self.card), p(tables),
+                                               p(table_of), p(parents), *self._score_args(), p(worklist), p(ws), dl.nbytes(ws),
+                                               p(L), L.numel() * 8, p(T), T.numel() * 8, p(status), dl.stream()),
+                 "dvs_cg_toggle_scores")
 
     def with_rows(self, *args, **kwargs):
         dl.need_unmixed("with_rows / boot_strength", self)
@@ -361,7 +318,7 @@ def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
                 if q > dl.CG_MAX_CONFIGS:
                     raise ValueError(f"{what}: variable {v} has {q} configurations of its discrete parents, beyond {dl.CG_MAX_CONFIGS}")
             masks = torch.tensor([host[v] & ev.disc_mask for v in cvars], dtype=torch.int64, device=dev)
-            tables, table_of = ev._tables_of(masks)
+            tables, table_of = ev.tables_of(masks)
             offset = np.concatenate([[0], np.cumsum(qs)]).astype(np.int64)
             cells, F, p = int(offset[-1]), len(cvars), dl.ptr
             var = torch.tensor(cvars, dtype=torch.int32, device=dev)
@@ -384,7 +341,8 @@ def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
                 coef[v], icpt[v], sd[v], cnt[v] = c[a:b], i0[a:b], s0[a:b], m0[a:b]
         fitted = None
         if dvars:
-            # the discrete columns as a data set of their own, in ascending variable order
+            # the discrete columns as a data set of their own, in ascending variable order; repacked on the device and not
+            # by evaluator.pack_levels, which would take the rows through the host
             codes = torch.stack([(ev.packed[:, v // 16] >> (4 * (v % 16))) & 15 for v in dvars], dim=1)
             packed = torch.zeros(ev.n_samples, (len(dvars) + 15) // 16, dtype=torch.int64, device=dev)
             for j in range(len(dvars)):

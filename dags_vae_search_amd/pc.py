@@ -45,7 +45,7 @@ class PCResult(NamedTuple):
 
 def _gaussian(evaluator):
     """whether the evaluator holds real-valued data (gaussian.py): its tests are dl.GCI_TYPES over ``evaluator.moments``"""
-    return getattr(evaluator, "continuous", False)
+    return dl.data_kind(evaluator) == "continuous"
 
 
 def _evaluator(what, evaluator, test=None):
@@ -194,7 +194,7 @@ def ci_tests(evaluator, pairs, cond, test: str = "mi", *, return_status: bool = 
         if card is None:
             out = torch.empty(cond.numel(), 3, dtype=torch.float64, device=dev)
             status = torch.zeros(1, dtype=torch.int32, device=dev)
-            _run_gaussian_tests(evaluator, pairs, cond, typ, out, status, chunk, evaluator._sets(cond.numel()))
+            _run_gaussian_tests(evaluator, pairs, cond, typ, out, status, chunk, evaluator.row_sets(cond.numel()))
             return (out, status) if return_status else out
         # the largest conditioning set sizes the LDS table: a popcount of the bits below n_vars (a higher bit is refused anyway)
         x = cond & ((1 << evaluator.n_vars) - 1)
