@@ -36,7 +36,8 @@ from .eliminate import (EliminationPlan, elimination_plan, evidence_probability,
                         exact_posterior)
 from .incomplete import (EMResult, ExpectedCounts, StructuralEMResult, available_case_evaluator, em_fit,  # noqa: F401
                          expected_counts, family_plans, fit_counts, impute, incomplete_rows, structural_em, target_plans)
-from .mixed import FittedCGBN, MixedEvaluator, cg_fit  # noqa: F401
+from .mixed import (FittedCGBN, MixedEvaluator, cg_cross_validate, cg_fit, cg_log_likelihood, cg_predict,  # noqa: F401
+                    cg_sample)
 from .gaussian import (FittedGBN, GaussianEvaluator, gaussian_cross_validate, gaussian_fit, gaussian_joint,  # noqa: F401
                        gaussian_log_likelihood, gaussian_predict, gaussian_sample)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401

@@ -26,6 +26,7 @@ GAUSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian.h")
 GCI_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_ci.h")  # the seventh: CI tests on real-valued data
 GPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_params.h")  # the eighth: a fitted Gaussian network
 MIXED_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_mixed.h")       # the ninth: conditional Gaussian networks on mixed data
+MPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_mixed_params.h")  # the tenth: a fitted conditional Gaussian network
 
 
 class DvsShape(Structure):
@@ -108,6 +109,8 @@ GCI_SIGNATURES, _GC = _read_header(GCI_HEADER)
 GPAR_SIGNATURES, _GP = _read_header(GPAR_HEADER)
 # include/dvs_mixed.h, the ninth: partition, ragged moments, the cg scores, their toggle pass and the fit; the nine tables above stay what they are
 MIXED_SIGNATURES, _M = _read_header(MIXED_HEADER)
+# include/dvs_mixed_params.h, the tenth: sample, loglik and predict on a fitted CG network; the ten tables above stay what they are
+MPAR_SIGNATURES, _MP = _read_header(MPAR_HEADER)
 
 
 def signature(fn: str):
@@ -132,9 +135,12 @@ def signature(fn: str):
         return GPAR_SIGNATURES[fn]
     if fn in MIXED_SIGNATURES:
         return MIXED_SIGNATURES[fn]
+    if fn in MPAR_SIGNATURES:
+        return MPAR_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
                    f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h, "
-                   f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h, nor in include/dvs_mixed.h")
+                   f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h, nor in include/dvs_mixed.h or "
+                   f"include/dvs_mixed_params.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -167,6 +173,9 @@ GCI_MAX_COND = _GC["DVS_GCI_MAX_COND"]     # the largest conditioning set of a G
 GBN_PREDICT_MODES = {"parents": _GP["DVS_GBN_PREDICT_PARENTS"], "exact": _GP["DVS_GBN_PREDICT_EXACT"]}      # include/dvs_gaussian_params.h
 CGSCORE_TYPES = {k: _M["DVS_CGSCORE_" + k.upper()[:-3]] for k in ("loglik-cg", "aic-cg", "bic-cg")}      # dvs_cgscore_type (include/dvs_mixed.h)
 CG_MAX_CONFIGS = _M["DVS_CG_MAX_CONFIGS"]      # the configurations of the discrete parents of one continuous family
+CGBN_PREDICT_MODES = {"parents": _MP["DVS_CGBN_PREDICT_PARENTS"], "exact": _MP["DVS_CGBN_PREDICT_EXACT"],
+                      "class": _MP["DVS_CGBN_PREDICT_CLASS"]}      # include/dvs_mixed_params.h
+STATUS_EMPTY_CONFIG = 128     # dvs_cgbn_* status bit 7: a row met an empty configuration (NaN in its cell; information)
 
 
 def gbn_stride(n: int) -> int:
@@ -193,7 +202,8 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Declare argument/return types of every entry point of include/dvs.h and of its companion headers on a loaded library."""
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
                                   *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items(),
-                                  *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items(), *MIXED_SIGNATURES.items()):
+                                  *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items(), *MIXED_SIGNATURES.items(),
+                                  *MPAR_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

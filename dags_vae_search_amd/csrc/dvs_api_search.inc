@@ -944,6 +944,123 @@ extern "C" int dvs_cg_fit(int32_t n_families, int32_t n_cells, int32_t n_vars, i
     return call_end(fn);
 }
 
+// ---- a fitted conditional Gaussian network (dvs_mixed_params.h; include/dvs_mixed_params.h) ---------------------------------------
+// what the entry points check first: n_rows, n_cells (2), n_vars, n_cont (3)
+static int cgbn_dims(const char* fn, int n_vars, int n_cont, int64_t n_rows, int64_t n_cells) {
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn);
+    if (n_cells < 1 || n_cells * (n_vars > 0 ? n_vars : 1) > (int64_t)0x7fffffff || n_cells > (int64_t)0x7fffffff)
+        return failf(2, "%s: n_cells must be >= 1 and n_cells * n_vars < 2^31", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (n_cont < 1 || n_cont > n_vars) return failf(3, "%s: n_cont must be in [1, n_vars]", fn);
+    return 0;
+}
+static void cgbn_fill(CgbnRowArgs& a, int n_vars, int n_cont, int64_t n_rows, int64_t n_cells, const uint8_t* card, const uint64_t* parents,
+                      const int64_t* offset, const double* coef, const double* intercept, const double* sd, const uint64_t* packed,
+                      void* workspace, int32_t* status) {
+    a.net.n = n_vars;
+    a.net.nc = n_cont;
+    a.net.cells = n_cells;
+    a.net.card = card;
+    a.net.parents = parents;
+    a.net.offset = (const long long*)offset;
+    a.net.coef = coef;
+    a.net.intercept = intercept;
+    a.net.sd = sd;
+    a.net.status = status;
+    a.rows = n_rows;
+    a.chunks = (int)((n_rows + 255) / 256);
+    a.target = -1;
+    a.packed = packed;
+    a.header = (int*)workspace;
+}
+
+extern "C" size_t dvs_cgbn_sample_workspace_bytes(int32_t n_vars) {
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", "dvs_cgbn_sample_workspace_bytes"), 0;
+    return DVS_CGBN_HEADER;
+}
+
+extern "C" int dvs_cgbn_sample(int32_t n_vars, int32_t n_cont, int64_t n_rows, int64_t n_cells, const uint8_t* card,
+                               const uint64_t* parents, const int64_t* offset, const double* coef, const double* intercept,
+                               const double* sd, const uint64_t* packed, uint64_t seed, int64_t row_offset, void* workspace,
+                               size_t workspace_bytes, double* x_out, int32_t* status, void* stream) {
+    const char* fn = "dvs_cgbn_sample";
+    if (int e = cgbn_dims(fn, n_vars, n_cont, n_rows, n_cells)) return e;
+    if (row_offset < 0) return failf(12, "%s: row_offset must be >= 0", fn);
+    if (!card || !parents || !offset || !coef || !intercept || !sd || !packed || !workspace || !x_out || !status)
+        return failf(10, "%s: null pointer", fn);
+    if (workspace_bytes < DVS_CGBN_HEADER) return fail_size("dvs_cgbn_sample: workspace_bytes < dvs_cgbn_sample_workspace_bytes", DVS_CGBN_HEADER);
+    CgbnRowArgs a = {};
+    cgbn_fill(a, n_vars, n_cont, n_rows, n_cells, card, parents, offset, coef, intercept, sd, packed, workspace, status);
+    a.row_offset = (uint32_t)row_offset;
+    a.per_row = x_out;
+    call_begin();
+    dvs_launch_cgbn_sample(a, seed, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" size_t dvs_cgbn_loglik_workspace_bytes(int32_t n_vars, int64_t n_rows, int64_t n_cells) {
+    if (cgbn_dims("dvs_cgbn_loglik_workspace_bytes", n_vars, 1, n_rows, n_cells)) return 0;
+    return dvs_cgbn_loglik_c_offset(n_rows) + (size_t)n_cells * 8;
+}
+
+extern "C" int dvs_cgbn_loglik(int32_t n_vars, int32_t n_cont, int64_t n_rows, int64_t n_cells, const uint8_t* card,
+                               const uint64_t* parents, const int64_t* offset, const double* coef, const double* intercept,
+                               const double* sd, const uint64_t* packed, const double* x, double* per_row, double* out,
+                               void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_cgbn_loglik";
+    if (int e = cgbn_dims(fn, n_vars, n_cont, n_rows, n_cells)) return e;
+    if (!card || !parents || !offset || !coef || !intercept || !sd || !packed || !x || !out || !workspace || !status)
+        return failf(10, "%s: null pointer", fn);
+    const size_t c_at = dvs_cgbn_loglik_c_offset(n_rows), need = c_at + (size_t)n_cells * 8;
+    if (workspace_bytes < need) return fail_size("dvs_cgbn_loglik: workspace_bytes < dvs_cgbn_loglik_workspace_bytes", need);
+    CgbnRowArgs a = {};
+    cgbn_fill(a, n_vars, n_cont, n_rows, n_cells, card, parents, offset, coef, intercept, sd, packed, workspace, status);
+    a.x = x;
+    a.per_row = per_row;
+    a.out = out;
+    a.partials = (double*)((char*)workspace + DVS_CGBN_HEADER);
+    a.c = (double*)((char*)workspace + c_at);
+    call_begin();
+    dvs_launch_cgbn_loglik(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
+extern "C" size_t dvs_cgbn_predict_workspace_bytes(int32_t n_vars, int64_t n_cells) {
+    if (cgbn_dims("dvs_cgbn_predict_workspace_bytes", n_vars, 1, 1, n_cells)) return 0;
+    return DVS_CGBN_HEADER + (size_t)n_cells * 8;
+}
+
+extern "C" int dvs_cgbn_predict(int32_t n_vars, int32_t n_cont, int64_t n_rows, int64_t n_cells, const uint8_t* card,
+                                const uint64_t* parents, const int64_t* offset, const double* coef, const double* intercept,
+                                const double* sd, const uint64_t* packed, const double* x, int32_t target, int32_t mode,
+                                const double* prior, void* pred, double* var, double* posterior, void* workspace,
+                                size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_cgbn_predict";
+    if (int e = cgbn_dims(fn, n_vars, n_cont, n_rows, n_cells)) return e;
+    if (mode < DVS_CGBN_PREDICT_PARENTS || mode > DVS_CGBN_PREDICT_CLASS)
+        return failf(12, "%s: mode must be 0 (parents), 1 (exact) or 2 (class)", fn);
+    if (target < 0 || target >= n_vars) return failf(13, "%s: target must be in [0, n_vars)", fn);
+    if (!card || !parents || !offset || !coef || !intercept || !sd || !packed || !x || !pred || !workspace || !status ||
+        (mode != DVS_CGBN_PREDICT_CLASS && !var))
+        return failf(10, "%s: null pointer", fn);
+    const size_t need = DVS_CGBN_HEADER + (size_t)n_cells * 8;
+    if (workspace_bytes < need) return fail_size("dvs_cgbn_predict: workspace_bytes < dvs_cgbn_predict_workspace_bytes", need);
+    CgbnRowArgs a = {};
+    cgbn_fill(a, n_vars, n_cont, n_rows, n_cells, card, parents, offset, coef, intercept, sd, packed, workspace, status);
+    a.x = x;
+    a.target = target;
+    a.mode = mode;
+    a.prior = prior;
+    a.per_row = (double*)pred;
+    a.label = (uint8_t*)pred;
+    a.out = var;
+    a.posterior = posterior;
+    a.c = (double*)((char*)workspace + DVS_CGBN_HEADER);
+    call_begin();
+    dvs_launch_cgbn_predict(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // ---- Gaussian CI tests (dvs_gaussian_ci.h; include/dvs_gaussian_ci.h) -----------------------------------------------------------
 // what the two entry points check first: counts (2), n_vars (3), the range of the cell index (2), test_type (12)
 static int gci_dims(const char* fn, const char* count, const char* cells_text, int items, int n_vars, int n_sets, bool per_var, int test_type) {

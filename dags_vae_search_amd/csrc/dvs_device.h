@@ -421,7 +421,7 @@ __device__ __forceinline__ void dvs_block_sum256(const int tid, T*... x) {
 // 501 the likelihood-weighting sampler of dvs_bn_lw (dvs_infer.h; keyed by the global query index; variable v of particle p
 // draws dvs_draw(dvs_draw(key, v), p): for a fixed (query, variable) a bijection of p, so no two particles share a draw),
 // 510 the forward sampler of dvs_gbn_sample (dvs_gaussian_params.h; keyed by the global row index; variable v draws elements
-// 2 v and 2 v + 1),
+// 2 v and 2 v + 1) and, on purpose, of dvs_cgbn_sample (dvs_mixed_params.h: the same draws for the real columns of a mixed row),
 // 600 the bootstrap row sets of dvs_bootstrap_rows (dvs_strength.h; keyed by the global set index, element = position),
 // 700 / 701 the proposals and the start order of dvs_order_mcmc (dvs_ordermc.h; keyed by the global chain index; step t draws
 // elements 3 t, 3 t + 1, 3 t + 2, the shuffle draws element k for position k),

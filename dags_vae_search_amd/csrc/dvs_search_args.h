@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h / dvs_mixed.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h / dvs_mixed.h / dvs_mixed_params.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -17,6 +17,7 @@
 #include "../../include/dvs_gaussian_ci.h"
 #include "../../include/dvs_gaussian_params.h"
 #include "../../include/dvs_mixed.h"
+#include "../../include/dvs_mixed_params.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -813,6 +814,43 @@ struct CgFitArgs {
     int* status;
 };
 void dvs_launch_cg_fit(const CgFitArgs& a, dvs_stream_t st);
+
+// ---- a fitted conditional Gaussian network (dvs_mixed_params.h; include/dvs_mixed_params.h) ---------------------------------------
+struct CgbnNet {
+    int n, nc;
+    long long cells;
+    const uint8_t* card;         // [n], 0: continuous
+    const uint64_t* parents;     // [n]
+    const long long* offset;     // [n + 1]
+    const double* coef;          // [cells][n], read at continuous parent bits
+    const double* intercept;     // [cells]
+    const double* sd;            // [cells]
+    int* status;
+};
+// The workspace of the three entry points starts with a header of 64 i32: order [48], the "sound" word at index 48 (as
+// dvs_bn_sample's header), the "a cell broke bit 6" word at index 49.  loglik: then the chunk sums f64 [chunks] (rounded up to 256
+// bytes) and c f64 [cells]; predict: then c f64 [cells].
+constexpr size_t DVS_CGBN_HEADER = 256;
+inline size_t dvs_cgbn_loglik_c_offset(long long rows) { return DVS_CGBN_HEADER + ((((size_t)rows + 255) / 256 * 8 + 255) & ~(size_t)255); }
+struct CgbnRowArgs {
+    CgbnNet net;
+    long long rows;
+    int chunks, words, target, mode;             // chunks, words: launcher; target < 0: no target (sample, loglik)
+    uint32_t seed_lo, seed_hi, row_offset;       // the sampler; seed_lo / seed_hi: launcher, from `seed`
+    const uint64_t* packed;      // [rows][words]
+    const double* x;             // [rows][nc]; unused by the sampler
+    const double* prior;         // predict mode 2: null or [rows][r]
+    double* per_row;             // sample: x_out [rows][nc]; loglik: null or [rows]; predict modes 0, 1: pred [rows]
+    uint8_t* label;              // predict mode 2: pred [rows]
+    double* out;                 // loglik: [1]; predict modes 0, 1: var [rows]
+    double* posterior;           // predict mode 2: null or [rows][r]
+    int* header;                 // workspace
+    double* partials;            // loglik workspace [chunks]
+    double* c;                   // loglik, predict workspace [cells]; null: the sampler
+};
+void dvs_launch_cgbn_sample(const CgbnRowArgs& a, uint64_t seed, dvs_stream_t st);
+void dvs_launch_cgbn_loglik(const CgbnRowArgs& a, dvs_stream_t st);
+void dvs_launch_cgbn_predict(const CgbnRowArgs& a, dvs_stream_t st);
 
 struct BootRowsArgs {
     int n_sets, set_size, n_samples;

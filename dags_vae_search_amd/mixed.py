@@ -11,19 +11,24 @@ synchronisation per pass), builds the misses and hands the kernels a table index
 
 It is an ``Evaluator`` (evaluator.py), so ``hill_climb`` and ``tabu_search`` run on it unchanged: a continuous -> discrete arc is a NaN toggle cell, which the move
 selection treats as "not available"; ``illegal`` holds the same arcs as ``forbidden=`` rows.  ``cg_fit`` gives the parameters of
-a structure (``dvs_cg_fit``, and ``bn_fit`` on the discrete columns).  Not built on mixed data, each raising ``ValueError`` that
-says so: ``with_rows`` / ``boot_strength``, ``exact_search``, ``arc_posterior``, ``order_mcmc``, ``bn_fit``, ``gaussian_fit``, the
-CI-test family, ``cross_validate`` and ``available_case``.
+a structure (``dvs_cg_fit``, and ``bn_fit`` on the discrete columns).  What is done with the fitted network (csrc/dvs_mixed_params.h,
+DESIGN.md §33): ``cg_sample`` draws mixed rows (bnlearn's ``rbn``), ``cg_log_likelihood`` scores rows the parameters were not
+fitted on (``logLik``), ``cg_predict`` predicts a real column or a class (``predict``) and ``cg_cross_validate`` composes them
+(``bn.cv``); the discrete half of each is the discrete entry point on ``fitted.discrete``, the continuous half one ``dvs_cgbn_*``
+call.  Not built on mixed data, each raising ``ValueError`` that says so: ``with_rows`` / ``boot_strength``, ``exact_search``,
+``arc_posterior``, ``order_mcmc``, ``bn_fit``, ``gaussian_fit``, the CI-test family, ``cross_validate`` (the discrete one) and
+``available_case``; nor are a batch of CG networks per call, likelihood weighting on a ``FittedCGBN`` and incomplete mixed data.
 
 The definitions are those of include/dvs_mixed.h.  Three things follow bnlearn as recalled and are unpinned against an R run:
 the unbiased residual variance of every configuration, the parameter count q (p + 2), and the treatment of sparse
-configurations (an empty one adds nothing and counts in q; one with 1 .. p + 1 rows refuses the family).
+configurations (an empty one adds nothing and counts in q; one with 1 .. p + 1 rows refuses the family).  Parity of the four
+functions on a fitted network with bnlearn's ``rbn``, ``logLik``, ``predict`` and ``bn.cv`` on mixed data is unpinned as well.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -287,6 +292,88 @@ class FittedCGBN:
     count: List[Optional[torch.Tensor]]    # per continuous v: f64 [q_v], the rows of every configuration
     discrete: object                       # params.FittedBN over the discrete columns in ascending order (None without factors)
     discrete_vars: List[int]               # the variable of every column of ``discrete``
+    # the layout of include/dvs_mixed_params.h, kept so that nothing is concatenated per call (None: built on first use)
+    offset: Optional[torch.Tensor] = None          # int64 [n + 1]: the exclusive prefix of q_v, 0 for a discrete v
+    coef_flat: Optional[torch.Tensor] = None       # f64 [cells, n]: the rows of ``coef`` in ascending variable order
+    intercept_flat: Optional[torch.Tensor] = None  # f64 [cells]
+    sd_flat: Optional[torch.Tensor] = None         # f64 [cells]
+
+    @property
+    def n_vars(self) -> int:
+        return len(self.card)
+
+    @property
+    def continuous_vars(self) -> List[int]:
+        return [v for v, c in enumerate(self.card) if not c]
+
+    def flat(self):
+        """(card uint8 [n], offset int64 [n + 1], coef [cells, n], intercept [cells], sd [cells]) on the device"""
+        dev = self.parents.device
+        if self.offset is None:
+            qs = [0 if c else int(self.sd[v].shape[0]) for v, c in enumerate(self.card)]
+            self.offset = torch.tensor(np.concatenate([[0], np.cumsum(qs)]).astype(np.int64), device=dev)
+            cv = self.continuous_vars
+            self.coef_flat = torch.cat([self.coef[v].reshape(-1, self.n_vars) for v in cv]).contiguous()
+            self.intercept_flat = torch.cat([self.intercept[v].reshape(-1) for v in cv]).contiguous()
+            self.sd_flat = torch.cat([self.sd[v].reshape(-1) for v in cv]).contiguous()
+        if getattr(self, "_card_dev", None) is None:
+            self._card_dev = torch.tensor(self.card, dtype=torch.uint8, device=dev)
+        return self._card_dev, self.offset, self.coef_flat, self.intercept_flat, self.sd_flat
+
+    @classmethod
+    def from_parameters(cls, parents: Sequence[int], card: Sequence[int], coef, intercept, sd, tables, device="cuda") -> "FittedCGBN":
+        """A hand-written network.  ``parents``: n parent masks (ints); ``card``: a factor's level count, 0 for a real column;
+        ``coef[v]`` [q_v, n], ``intercept[v]`` and ``sd[v]`` [q_v] for a real v (None for a factor), configuration z of the
+        discrete parents with the lowest variable id fastest, ``coef[v][z, u]`` read at the real parents u; a configuration
+        whose sd is NaN is empty.  ``tables[v]``: the [q, r] table of a factor v (None for a real column), rows the
+        configurations of its parents.  A ``ValueError`` names the rule a network breaks."""
+        what = "FittedCGBN.from_parameters"
+        dl.need_cuda(what, device)
+        dev = torch.device(device)
+        card = _kinds(card, len(card))
+        n = len(card)
+        host = [int(m) & ~(1 << v) for v, m in enumerate(parents)]
+        if not 1 <= n <= dl.MAX_TOKENS or len(host) != n or any(len(a) != n for a in (coef, intercept, sd, tables)):
+            raise ValueError(f"{what}: parents, card, coef, intercept, sd and tables must have one entry per variable (1 .. 48)")
+        dvars = [v for v in range(n) if card[v]]
+        cvars = [v for v in range(n) if not card[v]]
+        cont_mask = sum(1 << v for v in cvars)
+        cf: List[Optional[torch.Tensor]] = [None] * n
+        ic, s0, cnt = list(cf), list(cf), list(cf)
+        for v, m in enumerate(host):
+            if m >> n or m < 0:
+                raise ValueError(f"{what}: variable {v} has a parent bit >= {n}")
+            if card[v] and m & cont_mask:
+                raise ValueError(f"{what}: the discrete variable {v} has a continuous parent")
+            if card[v]:
+                continue
+            q = int(np.prod([card[u] for u in range(n) if (m >> u) & 1 and card[u]], dtype=np.int64))
+            if q > dl.CG_MAX_CONFIGS:
+                raise ValueError(f"{what}: variable {v} has {q} configurations of its discrete parents, beyond {dl.CG_MAX_CONFIGS}")
+            c, i, s = (np.asarray(a[v], np.float64) for a in (coef, intercept, sd))
+            if c.shape != (q, n) or i.shape != (q,) or s.shape != (q,):
+                raise ValueError(f"{what}: variable {v} needs coef [{q}, {n}], intercept [{q}] and sd [{q}] (got {c.shape}, {i.shape}, {s.shape})")
+            live = ~np.isnan(s)
+            pa = [u for u in cvars if (m >> u) & 1]
+            if not (np.isfinite(i[live]).all() and np.isfinite(s[live]).all() and (s[live] > 0).all() and np.isfinite(c[live][:, pa]).all()):
+                raise ValueError(f"{what}: variable {v} has a non-empty configuration whose intercept, sd or a coefficient at a "
+                                 f"continuous parent is not finite, or whose sd is not > 0")
+            cf[v], ic[v], s0[v] = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (c, i, s))
+        placed, left = 0, set(range(n))
+        while left:
+            free = [v for v in sorted(left) if not host[v] & ~placed]
+            if not free:
+                raise ValueError(f"{what}: the structure has a cycle")
+            placed |= 1 << free[0]
+            left.remove(free[0])
+        fitted = None
+        if dvars:
+            from .params import FittedBN
+            rank = {v: j for j, v in enumerate(dvars)}
+            fitted = FittedBN.from_tables([sum(1 << rank[u] for u in dvars if (host[v] >> u) & 1) for v in dvars],
+                                          [card[v] for v in dvars], [tables[v] for v in dvars], device=dev)
+        return cls(torch.tensor(np.asarray(host, np.uint64).view(np.int64), device=dev), ["discrete" if c else "continuous" for c in card],
+                   card, cf, ic, s0, cnt, fitted, dvars)
 
 
 def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
@@ -311,6 +398,7 @@ def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
     dvars = [v for v in range(n) if ev.card_host[v]]
     coef: List[Optional[torch.Tensor]] = [None] * n
     icpt, sd, cnt = list(coef), list(coef), list(coef)
+    flat = {}
     with torch.cuda.device(dev):
         if cvars:
             qs = [ev.configurations(host[v] & ev.disc_mask) for v in cvars]
@@ -339,16 +427,249 @@ def cg_fit(evaluator: MixedEvaluator, parents: torch.Tensor) -> FittedCGBN:
             for j, v in enumerate(cvars):
                 a, b = int(offset[j]), int(offset[j + 1])
                 coef[v], icpt[v], sd[v], cnt[v] = c[a:b], i0[a:b], s0[a:b], m0[a:b]
+            # dvs_cg_fit was given the continuous families in ascending variable order: its arrays are dvs_cgbn_*'s
+            full_off = np.zeros(n + 1, np.int64)
+            full_off[1:] = np.cumsum([qs[cvars.index(v)] if not ev.card_host[v] else 0 for v in range(n)])
+            flat = dict(offset=torch.from_numpy(full_off).to(dev), coef_flat=c, intercept_flat=i0, sd_flat=s0)
         fitted = None
         if dvars:
             # the discrete columns as a data set of their own, in ascending variable order; repacked on the device and not
             # by evaluator.pack_levels, which would take the rows through the host
-            codes = torch.stack([(ev.packed[:, v // 16] >> (4 * (v % 16))) & 15 for v in dvars], dim=1)
-            packed = torch.zeros(ev.n_samples, (len(dvars) + 15) // 16, dtype=torch.int64, device=dev)
-            for j in range(len(dvars)):
-                packed[:, j // 16] |= codes[:, j] << (4 * (j % 16))
-            sub = BNLearnWrapper.from_packed(ev.dataset_name, DISCRETE_METRIC[ev.metric_name], packed, [ev.card_host[v] for v in dvars])
+            sub = BNLearnWrapper.from_packed(ev.dataset_name, DISCRETE_METRIC[ev.metric_name], _sub_rows(ev.packed, dvars),
+                                             [ev.card_host[v] for v in dvars])
             rank = {v: j for j, v in enumerate(dvars)}
             fitted = bn_fit(sub, torch.tensor([sum(1 << rank[u] for u in dvars if (host[v] >> u) & 1) for v in dvars],
                                               dtype=torch.int64, device=dev))
-    return FittedCGBN(parents.to(dev), list(ev.kind), list(ev.card_host), coef, icpt, sd, cnt, fitted, dvars)
+    return FittedCGBN(parents.to(dev), list(ev.kind), list(ev.card_host), coef, icpt, sd, cnt, fitted, dvars, **flat)
+
+
+# ---- what is done with a fitted network (csrc/dvs_mixed_params.h) ----------------------------------------------
+CG_CV_LOSSES = ("logl-cg", "mse", "mse-exact", "pred", "pred-exact")
+
+
+def _sub_rows(packed, dvars):
+    """the discrete columns ``dvars`` of packed rows as a data set of their own, in that order, on the device"""
+    out = torch.zeros(packed.shape[0], (len(dvars) + 15) // 16, dtype=torch.int64, device=packed.device)
+    for j, v in enumerate(dvars):
+        out[:, j // 16] |= ((packed[:, v // 16] >> (4 * (v % 16))) & 15) << (4 * (j % 16))
+    return out
+
+
+def _spread_rows(sub, dvars, n):
+    """the reverse: column j of ``sub`` becomes the nibble of variable dvars[j] among n; every other nibble is zero"""
+    out = torch.zeros(sub.shape[0], (n + 15) // 16, dtype=torch.int64, device=sub.device)
+    for j, v in enumerate(dvars):
+        out[:, v // 16] |= ((sub[:, j // 16] >> (4 * (j % 16))) & 15) << (4 * (v % 16))
+    return out
+
+
+def _fitted(what, fitted):
+    if not isinstance(fitted, FittedCGBN):
+        raise ValueError(f"{what}: takes a FittedCGBN (cg_fit or FittedCGBN.from_parameters)")
+    dl.need_cuda(what, fitted.parents.device)
+    return fitted.n_vars, len(fitted.continuous_vars), fitted.parents.device
+
+
+def _rows(what, fitted, data):
+    """``data``: a MixedEvaluator or a (packed, x) pair over the network's variables -> (packed, x), contiguous"""
+    n, nc, dev = _fitted(what, fitted)
+    if isinstance(data, MixedEvaluator):
+        if data.card_host != list(fitted.card):
+            raise ValueError(f"{what}: the evaluator's kinds and level counts are not the network's")
+        data = (data.packed, data.x)
+    if not isinstance(data, (tuple, list)) or len(data) != 2:
+        raise ValueError(f"{what}: data must be a MixedEvaluator or a (packed, x) pair")
+    packed, x = data
+    S = packed.shape[0] if torch.is_tensor(packed) and packed.ndim == 2 else -1
+    if S < 1 or packed.dtype != torch.int64 or packed.shape[1] != (n + 15) // 16 or packed.device != dev:
+        raise ValueError(f"{what}: packed must be int64 [S >= 1, {(n + 15) // 16}] on {dev}")
+    if x is None and nc == 0:
+        x = torch.empty(S, 0, dtype=torch.float64, device=dev)
+    if not torch.is_tensor(x) or x.dtype != torch.float64 or tuple(x.shape) != (S, nc) or x.device != dev:
+        raise ValueError(f"{what}: x must be float64 [{S}, {nc}] on {dev}")
+    return packed.contiguous(), x.contiguous()
+
+
+def _network_status(what, st, rows=False):
+    """the refusals of include/dvs_mixed_params.h as ValueError; bit 7 (an empty configuration met: NaN) is information"""
+    if st & dl.STATUS_CYCLE:
+        raise ValueError(f"{what}: the structure has a cycle")
+    if st & dl.STATUS_REFUSED:
+        row = "a row has a level code at or above its variable's level count, or " if rows else ""
+        raise ValueError(f"{what}: {row}the network breaks a rule: a parent bit at or above n_vars, a discrete variable with a "
+                         f"continuous parent, a level count above 16, more than {dl.CG_MAX_CONFIGS} configurations of a variable's "
+                         f"discrete parents, or parameter arrays that do not match the structure")
+    if st & dl.STATUS_NOT_PROBABILITY:
+        raise ValueError(f"{what}: a non-empty configuration has an intercept, an sd or a coefficient at a continuous parent that is "
+                         f"not finite, or an sd that is not > 0")
+
+
+def _net_args(fitted):
+    card, offset, coef, icpt, sd = fitted.flat()
+    p = dl.ptr
+    return (fitted.n_vars, len(fitted.continuous_vars), int(sd.shape[0]), card, offset, coef, icpt, sd), \
+        (p(card), p(fitted.parents), p(offset), p(coef), p(icpt), p(sd))
+
+
+def cg_sample(fitted: FittedCGBN, n_rows: int, *, seed: int, row_offset: int = 0):
+    """bnlearn's ``rbn`` on a conditional Gaussian network: ``n_rows`` rows -> (packed int64 [n_rows, ceil(n / 16)], x float64
+    [n_rows, n_cont]) on the device, what ``MixedEvaluator.from_device`` takes.  The levels are, as bytes, ``sample(fitted.discrete,
+    ...)`` spread to their variables' nibbles on the device; dvs_cgbn_sample then fills the real columns.  Row i is a function
+    of (seed, row_offset + i) and the network alone, so a request may be cut into calls with consecutive ``row_offset``.  A
+    row that meets an empty configuration (sd NaN) has NaN in that column and in what is computed from it."""
+    from .params import sample
+    what = "cg_sample"
+    n, nc, dev = _fitted(what, fitted)
+    if int(n_rows) < 1 or int(row_offset) < 0:
+        raise ValueError(f"{what}: n_rows must be >= 1 and row_offset >= 0")
+    S, lib, p = int(n_rows), dl.load(), dl.ptr
+    with torch.cuda.device(dev):
+        if fitted.discrete is not None:
+            packed = _spread_rows(sample(fitted.discrete, S, seed=seed, row_offset=row_offset), fitted.discrete_vars, n)
+        else:
+            packed = torch.zeros(S, (n + 15) // 16, dtype=torch.int64, device=dev)
+        x = torch.empty(S, nc, dtype=torch.float64, device=dev)
+        if nc:
+            (_, _, cells, *keep), net = _net_args(fitted)
+            ws = torch.empty(dl.workspace_bytes(lib, "dvs_cgbn_sample_workspace_bytes", n), dtype=torch.uint8, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            dl.check(lib, lib.dvs_cgbn_sample(n, nc, S, cells, *net, p(packed), dl.seed64(seed), int(row_offset), p(ws), dl.nbytes(ws),
+                                              p(x), p(status), dl.stream()), "dvs_cgbn_sample")
+            _network_status(what, int(status.item()))
+    return packed, x
+
+
+def cg_log_likelihood(fitted: FittedCGBN, data, *, per_row: bool = False):
+    """bnlearn's ``logLik(fitted, newdata)`` on a conditional Gaussian network: ``data`` a ``MixedEvaluator`` or a (packed, x)
+    pair -> a float64 scalar on the device, with ``per_row`` (total, row terms [S]).  A row term is the discrete term
+    (``log_likelihood`` on ``fitted.discrete``) plus the continuous term (dvs_cgbn_loglik), one addition; the total is the
+    discrete total plus the continuous total, one addition: each half is summed by its own tree, so the total is NOT a tree
+    over the summed row terms.  Without factors or without real columns only the half that applies runs.  A row that meets an
+    empty configuration is NaN (and so is the total); a level code at or above its level count raises ValueError."""
+    from .params import log_likelihood
+    what = "cg_log_likelihood"
+    n, nc, dev = _fitted(what, fitted)
+    packed, x = _rows(what, fitted, data)
+    S, lib, p = packed.shape[0], dl.load(), dl.ptr
+    out = rows = None
+    with torch.cuda.device(dev):
+        if fitted.discrete is not None:
+            got = log_likelihood(fitted.discrete, _sub_rows(packed, fitted.discrete_vars), per_row=per_row)
+            out, rows = (got[0][0], got[1][0]) if per_row else (got[0], None)
+        if nc:
+            (_, _, cells, *keep), net = _net_args(fitted)
+            ws = torch.empty(dl.workspace_bytes(lib, "dvs_cgbn_loglik_workspace_bytes", n, S, cells), dtype=torch.uint8, device=dev)
+            crow = torch.empty(S, dtype=torch.float64, device=dev) if per_row else None
+            cout = torch.empty(1, dtype=torch.float64, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            dl.check(lib, lib.dvs_cgbn_loglik(n, nc, S, cells, *net, p(packed), p(x), p(crow), p(cout), p(ws), dl.nbytes(ws), p(status),
+                                              dl.stream()), "dvs_cgbn_loglik")
+            _network_status(what, int(status.item()), rows=True)
+            out = cout[0] if out is None else out + cout[0]
+            if per_row:
+                rows = crow if rows is None else rows + crow
+    return (out, rows) if per_row else out
+
+
+def cg_predict(fitted: FittedCGBN, target: int, data, *, method: str = "parents", prob: bool = False, var: bool = False):
+    """bnlearn's ``predict`` on a conditional Gaussian network; the target's own column or nibble is never read.
+    A real ``target``: float64 [S], from its parents (``method="parents"``: the conditional mean at the row's configuration) or
+    given every other variable (``"exact"``: the closed form over the Markov blanket); with ``var`` (predictions, the
+    conditional variance [S]).  A discrete ``target``: uint8 [S], with ``prob`` (predictions, posterior [S, levels]);
+    ``"parents"`` is ``infer.predict`` on ``fitted.discrete``; ``"exact"`` takes that sub-network's exact posterior over the
+    discrete Markov blanket as the prior of dvs_cgbn_predict's mode 2, which multiplies in the densities of the target's real
+    children in the log domain (a target without real children returns the sub-network's answer as it is).  The lowest level
+    wins a tie; a row whose posterior is NaN predicts 255; a row that meets an empty configuration is NaN / 255."""
+    from . import infer
+    what = "cg_predict"
+    n, nc, dev = _fitted(what, fitted)
+    if method not in ("parents", "exact"):
+        raise ValueError(f"{what}: method must be 'parents' or 'exact' (got {method!r})")
+    if not 0 <= int(target) < n:
+        raise ValueError(f"{what}: target must be in [0, {n})")
+    t = int(target)
+    discrete = bool(fitted.card[t])
+    if (prob and not discrete) or (var and discrete):
+        raise ValueError(f"{what}: prob is the argument of a discrete target, var of a continuous one")
+    packed, x = _rows(what, fitted, data)
+    S, lib, p = packed.shape[0], dl.load(), dl.ptr
+    with torch.cuda.device(dev):
+        prior = None
+        if discrete:
+            rank = fitted.discrete_vars.index(t)
+            sub = _sub_rows(packed, fitted.discrete_vars)
+            host = [int(m) for m in fitted.parents.cpu().tolist()]
+            kids = any((host[c] >> t) & 1 for c in fitted.continuous_vars)
+            if method == "parents" or not kids:
+                return infer.predict(fitted.discrete, rank, sub, method=method, prob=prob)
+            _, prior = infer.predict(fitted.discrete, rank, sub, method="exact", prob=True)
+            prior = prior.contiguous()
+        (_, _, cells, *keep), net = _net_args(fitted)
+        ws = torch.empty(dl.workspace_bytes(lib, "dvs_cgbn_predict_workspace_bytes", n, cells), dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if discrete:
+            pred = torch.empty(S, dtype=torch.uint8, device=dev)
+            post = torch.empty(S, fitted.card[t], dtype=torch.float64, device=dev) if prob else None
+            variance = None
+            mode = dl.CGBN_PREDICT_MODES["class"]
+        else:
+            pred, variance, post = torch.empty(S, dtype=torch.float64, device=dev), torch.empty(S, dtype=torch.float64, device=dev), None
+            mode = dl.CGBN_PREDICT_MODES[method]
+        dl.check(lib, lib.dvs_cgbn_predict(n, nc, S, cells, *net, p(packed), p(x), t, mode, p(prior), p(pred), p(variance), p(post), p(ws),
+                                           dl.nbytes(ws), p(status), dl.stream()), "dvs_cgbn_predict")
+        _network_status(what, int(status.item()), rows=True)
+    if discrete:
+        return (pred, post) if prob else pred
+    return (pred, variance) if var else pred
+
+
+def cg_cross_validate(evaluator: MixedEvaluator, parents: torch.Tensor, *, folds: int = 10, seed: int = 0, loss: str = "logl-cg",
+                      target=None) -> torch.Tensor:
+    """bnlearn's ``bn.cv`` for one fixed structure on mixed data -> a float64 scalar on the device.  A composition, no kernel of
+    its own: the rows are permuted (``params.cv_folds``), each part is held out in turn, the parameters are fitted on the rest
+    (``MixedEvaluator.from_device`` and ``cg_fit``) and the part is scored; the parts' values are added in order and divided
+    by the number of rows.  ``loss``: "logl-cg", minus the held-out ``cg_log_likelihood``; "mse" / "mse-exact", the squared
+    error of ``cg_predict`` (method "parents" / "exact") for the real ``target``; "pred" / "pred-exact", the share of rows
+    whose level of the discrete ``target`` is predicted wrongly (255 counts as wrong).  A part in which a held-out row meets a
+    configuration the rest never showed is NaN under "logl-cg" and the mse losses, and so is the result; ``cg_fit``'s
+    refusals (a configuration with 1 .. p + 1 training rows) are raised as they are."""
+    from .params import cv_folds
+    what = "cg_cross_validate"
+    if not isinstance(evaluator, MixedEvaluator):
+        raise ValueError(f"{what}: takes a MixedEvaluator (cross_validate and gaussian_cross_validate take discrete and real-valued data)")
+    ev, S, n = evaluator, evaluator.n_samples, evaluator.n_vars
+    if not 2 <= int(folds) <= S:
+        raise ValueError(f"{what}: folds must be in [2, {S}]")
+    if loss not in CG_CV_LOSSES:
+        raise ValueError(f"{what}: loss must be one of {CG_CV_LOSSES} (got {loss!r})")
+    if (loss == "logl-cg") != (target is None):
+        raise ValueError(f"{what}: target is the argument of the prediction losses, and they need it")
+    if target is not None:
+        if not 0 <= int(target) < n:
+            raise ValueError(f"{what}: target must be in [0, {n})")
+        if bool(ev.card_host[int(target)]) != loss.startswith("pred"):
+            raise ValueError(f"{what}: 'mse' and 'mse-exact' take a real target, 'pred' and 'pred-exact' a discrete one")
+    method = "exact" if loss.endswith("-exact") else "parents"
+    dev = ev.device
+    with torch.cuda.device(dev):
+        parts = [torch.from_numpy(p).to(dev) for p in cv_folds(S, int(folds), seed)]
+        total = None
+        for f, part in enumerate(parts):
+            rest = torch.cat([p for g, p in enumerate(parts) if g != f])
+            train = MixedEvaluator.from_device(ev.dataset_name, ev.metric_name, ev.packed[rest], ev.x[rest], ev.card_host, k=ev.k,
+                                               table_bytes=ev.table_bytes)
+            fitted = cg_fit(train, parents)
+            held = (ev.packed[part].contiguous(), ev.x[part].contiguous())
+            if loss == "logl-cg":
+                value = cg_log_likelihood(fitted, held)
+            else:
+                t = int(target)
+                pred = cg_predict(fitted, t, held, method=method)
+                if loss.startswith("mse"):
+                    err = pred - held[1][:, fitted.continuous_vars.index(t)]
+                    value = (err * err).sum()
+                else:
+                    truth = ((held[0][:, t // 16] >> (4 * (t % 16))) & 15).to(torch.uint8)
+                    value = (pred != truth).sum().to(torch.float64)
+            total = value if total is None else total + value
+    return (-total if loss == "logl-cg" else total) / torch.full_like(total, float(S))
