@@ -1,8 +1,9 @@
 // What the Bayesian-network kernels of k_bic.hip share: the packed data set and a packed row in registers,
 // the layout of a family's dense table, the dense count, and the launchers' table size and family dispatch.  k_bic.hip
-// includes it first; dvs_hillclimb.h, dvs_tabu.h, dvs_cpdag.h, dvs_citest.h, dvs_params.h, dvs_infer.h, dvs_exact.h, dvs_posterior.h
-// and dvs_strength.h include it for what they use.  The lane and workgroup primitives that are not about networks (64-bit
-// broadcasts and shuffles, wave reductions, dvs_block_sum256) are in dvs_device.h.  Everything here is forced inline.
+// includes it first; dvs_hillclimb.h, dvs_tabu.h, dvs_cpdag.h, dvs_citest.h, dvs_fitted.h (what the fitted-network kernels
+// share on top of it), dvs_infer.h, dvs_exact.h, dvs_posterior.h and dvs_strength.h include it for what they use.  The lane
+// and workgroup primitives that are not about networks (64-bit broadcasts and shuffles, wave reductions, dvs_block_sum256)
+// are in dvs_device.h.  Everything here is forced inline.
 #pragma once
 #include "dvs_search_args.h"
 

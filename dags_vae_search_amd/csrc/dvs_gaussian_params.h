@@ -1,7 +1,9 @@
 // A fitted Gaussian network on the device: its joint distribution, forward sampling, the log-likelihood of
 // held-out rows and prediction.  Included by k_bic.hip after dvs_gaussian_ci.h.  Semantics, operation orders and refusals:
 // include/dvs_gaussian_params.h.  Plain fp64 vector arithmetic: no f64 MFMA, no fused multiply-add (contraction is off in every
-// function that rounds), no floating-point atomics.
+// function that rounds), no floating-point atomics.  The order, the image of 256 rows and its load, the quantile, the density
+// term, the blanket update and the two levels of the sum are dvs_fitted.h's, shared with the other fitted networks; k_gbn_sample
+// spells out the noise draw and the write-out that k_cgbn_sample takes from there (the reason is at the kernel).
 //
 //   k_gbn_joint          one wave per network: lane 0 orders the variables, then for v in that order the lanes take the
 //                        variables u placed before v, one cov[v][u] each; the matrix lives in LDS (18 KB at n = 48).
@@ -15,18 +17,15 @@
 //   k_gbn_loglik_rows    one workgroup per (chunk of 256 rows, part of the batch): the chunk is staged once through the same
 //   k_gbn_predict        image (coalesced reads, the transposing LDS writes conflict-free by GPAR_LD = 257) and the structures
 //                        of the part are looped over inside the workgroup, so a row is read from memory once per part, not
-//                        once per structure.  k_gbn_loglik_rows ends in dvs_bn_loglik's tree, k_bn_loglik_sum adds the chunks.
+//                        once per structure.  k_gbn_loglik_rows ends in dvs_bn_loglik's tree (fit_chunk_sum), and the
+//                        launcher's second level is dvs_bn_loglik's too (k_bn_loglik_sum).
 // Every network's parents are kept once per workgroup as a compact (index, coefficient) list in LDS (gpar_stage_net): a DAG
 // on 48 variables has at most 1128 arcs, and only networks the rules passed are staged.
 #pragma once
-#include "dvs_bn_common.h"
+#include "dvs_fitted.h"
 
-constexpr int GPAR_ROWS = 256;                               // rows of a workgroup's image = dvs_bn_loglik's chunk
-constexpr int GPAR_LD = GPAR_ROWS + 1;                       // odd stride: the staging writes of a 16-lane group hit 16 bank pairs
 constexpr int GPAR_MAX_ARCS = DVS_WTOK * (DVS_WTOK - 1) / 2;
 static_assert((size_t)GPAR_LD * DVS_WTOK * sizeof(double) + 20 * 1024 <= 160 * 1024, "the image and the lists fit a compute unit's LDS");
-
-inline size_t gpar_image_lds(int n) { return (size_t)GPAR_LD * n * sizeof(double); }
 
 __device__ __forceinline__ bool gpar_finite(double x) { return x - x == 0.0; }
 
@@ -53,19 +52,7 @@ __device__ __forceinline__ int gpar_check(int n, const uint64_t* parents, const 
     __syncthreads();
     if (tid == 0) {
         const uint64_t low = n == 64 ? ~0ull : (1ull << n) - 1ull;
-        uint64_t placed = 0ull;
-        bool cycle = false;
-        for (int k = 0; k < n && !cycle; ++k) {
-            int pick = -1;
-            for (int v = 0; v < n && pick < 0; ++v)
-                if (!((placed >> v) & 1ull) && !(s_par[v] & low & ~(1ull << v) & ~placed)) pick = v;
-            if (pick < 0) cycle = true;
-            else {
-                s_order[k] = pick;
-                placed |= 1ull << pick;
-            }
-        }
-        if (cycle) *s_state |= 1;
+        if (!fit_order(n, [&](int v) { return s_par[v] & low & ~(1ull << v); }, s_order)) *s_state |= 1;
     }
     __syncthreads();
     return *s_state;
@@ -131,54 +118,8 @@ void dvs_launch_gbn_joint(const GbnJointArgs& a, dvs_stream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The quantile function: Wichura's AS 241, PPND16, on u = (k + 0.5) 2^-52
+// The quantile function (gpar_quantile, dvs_fitted.h) on its own
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double gpar_horner(const double* p, double r) {
-#pragma clang fp contract(off)
-    double t = p[7];
-#pragma unroll
-    for (int i = 6; i >= 0; --i) {
-        t = t * r;
-        t = t + p[i];
-    }
-    return t;
-}
-
-__device__ __forceinline__ double gpar_quantile(uint64_t k) {
-#pragma clang fp contract(off)
-    const double A[8] = {3.3871328727963666080, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
-                         4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3};
-    const double Bq[8] = {1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3, 2.1213794301586595867e+4,
-                          3.9307895800092710610e+4, 2.8729085735721942674e+4, 5.2264952788528545610e+3};
-    const double C[8] = {1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
-                         1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4};
-    const double D[8] = {1.0, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1, 1.48103976427480074590e-1,
-                         1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9};
-    const double E[8] = {6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
-                         2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7};
-    const double F[8] = {1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2, 7.86869131145613259100e-4,
-                         1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15};
-    if (k >= (1ull << 52)) return bn_nan();
-    const double scale = 2.220446049250313e-16;              // 2^-52
-    const double u = ((double)k + 0.5) * scale, uc = ((double)((1ull << 52) - 1ull - k) + 0.5) * scale;
-    const double q = u - 0.5;
-    if (fabs(q) <= 0.425) {
-        const double r = 0.180625 - q * q;
-        const double num = q * gpar_horner(A, r);
-        return num / gpar_horner(Bq, r);
-    }
-    const double p = u < uc ? u : uc;
-    double r = sqrt(-log(p)), z;
-    if (r <= 5.0) {
-        r = r - 1.6;
-        z = gpar_horner(C, r) / gpar_horner(D, r);
-    } else {
-        r = r - 5.0;
-        z = gpar_horner(E, r) / gpar_horner(F, r);
-    }
-    return q < 0.0 ? -z : z;
-}
-
 __global__ __launch_bounds__(256) void k_gbn_quantiles(GbnQuantileArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < a.count) a.z[i] = gpar_quantile(a.k[i]);
@@ -266,6 +207,9 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_sample(GbnSampleArgs a) {
     if (!a.header[GPAR_HDR_DRAWABLE]) return;                // uniform: the prep refused the network
     if (tid < n) s_order[tid] = a.header[tid];
     gpar_stage_net(a.net, 0, &s_net);
+    // The draw, the row count and the write-out are spelled out here as fit_noise, fit_chunk_len and fit_image_store spell them
+    // (k_cgbn_sample calls those): through the helpers the compiler allocates this kernel's registers another way and
+    // gaussian_sample at n = 37 measured 2.5 % slower, with this text it is the instruction stream it was.
     const long long row0 = (long long)blockIdx.x * GPAR_ROWS;
     const int len = a.rows - row0 < GPAR_ROWS ? (int)(a.rows - row0) : GPAR_ROWS;
     if (tid < len) {
@@ -300,20 +244,6 @@ void dvs_launch_gbn_sample(const GbnSampleArgs& in, uint64_t seed, dvs_stream_t 
 // ---------------------------------------------------------------------------------------------------------
 // Held-out log-likelihood and prediction
 // ---------------------------------------------------------------------------------------------------------
-// stages rows 256 chunk .. of data [rows][n] into the image; returns the rows it holds.  Every thread calls it; a barrier follows.
-__device__ __forceinline__ int gpar_stage_rows(const GbnRowArgs& a, int chunk, double* x) {
-    const int n = a.net.n;
-    const long long row0 = (long long)chunk * GPAR_ROWS;
-    const int len = a.rows - row0 < GPAR_ROWS ? (int)(a.rows - row0) : GPAR_ROWS;
-    const double* src = a.data + (size_t)row0 * n;
-    for (int e = threadIdx.x; e < len * n; e += blockDim.x) {
-        const int r = e / n, c = e - r * n;
-        x[c * GPAR_LD + r] = src[e];
-    }
-    __syncthreads();
-    return len;
-}
-
 __global__ __launch_bounds__(64) void k_gbn_params_prep(GbnRowArgs a) {
 #pragma clang fp contract(off)
     __shared__ int s_order[DVS_WTOK], s_state;
@@ -325,22 +255,22 @@ __global__ __launch_bounds__(64) void k_gbn_params_prep(GbnRowArgs a) {
         if (state) atomicOr(a.net.status, 16);
         a.ok[b] = state ? 0 : 1;
     }
-    if (a.c != nullptr && !state && tid < n) a.c[(size_t)b * n + tid] = log(sd[tid]) + 0.9189385332046727;
+    if (a.c != nullptr && !state && tid < n) a.c[(size_t)b * n + tid] = fit_log_norm(sd[tid]);
 }
 
 __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_loglik_rows(GbnRowArgs a) {
 #pragma clang fp contract(off)
     DVS_DYN_LDS(smem);
     __shared__ GparNet s_net;
-    __shared__ double red[GPAR_ROWS], s_c[DVS_WTOK];
+    __shared__ double s_c[DVS_WTOK];
     double* x = (double*)smem;
     const int tid = threadIdx.x, n = a.net.n;
     const int chunk = blockIdx.x / a.bsplit, part = blockIdx.x - chunk * a.bsplit;
-    const int len = gpar_stage_rows(a, chunk, x);
+    const int len = fit_image_load(a.data, a.rows, n, chunk, x);
     const long long row = (long long)chunk * GPAR_ROWS + tid;
     for (int b = part; b < a.net.B; b += a.bsplit) {
         const bool ok = a.ok[b] != 0;                        // uniform
-        __syncthreads();                                     // the lists and red of the structure before
+        __syncthreads();                                     // the lists and the tree of the structure before
         if (ok) {
             if (tid < n) s_c[tid] = a.c[(size_t)b * n + tid];
             gpar_stage_net(a.net, b, &s_net);
@@ -349,32 +279,12 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_loglik_rows(GbnRowArgs a) {
         if (tid < len) {
             if (!ok) term = bn_nan();
             else
-                for (int v = 0; v < n; ++v) {
-                    const double e = (x[v * GPAR_LD + tid] - gpar_mu(&s_net, x, tid, v, -1)) / s_net.sd[v];
-                    const double half = 0.5 * (e * e);
-                    term = term - (s_c[v] + half);
-                }
+                for (int v = 0; v < n; ++v)
+                    term = fit_log_density(term, x[v * GPAR_LD + tid], gpar_mu(&s_net, x, tid, v, -1), s_net.sd[v], s_c[v]);
             if (a.per_row) a.per_row[(size_t)b * a.rows + row] = term;
         }
-        red[tid] = term;
-        __syncthreads();
-        dvs_block_sum256(tid, red);
-        if (tid == 0) a.partials[(size_t)b * a.chunks + chunk] = red[0];
+        fit_chunk_sum(term, &a.partials[(size_t)b * a.chunks + chunk]);
     }
-}
-
-// out[b]: slot t adds the chunk sums t, t + 256, ... in ascending order, then the tree (k_bn_loglik_sum's order)
-__global__ __launch_bounds__(256) void k_gbn_loglik_sum(GbnRowArgs a) {
-#pragma clang fp contract(off)
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const double* p = a.partials + (size_t)blockIdx.x * a.chunks;
-    double s = 0.0;
-    for (int c = tid; c < a.chunks; c += 256) s = s + p[c];
-    red[tid] = s;
-    __syncthreads();
-    dvs_block_sum256(tid, red);
-    if (tid == 0) a.out[blockIdx.x] = red[0];
 }
 
 // the parts the batch is cut into: enough workgroups for the device when the rows alone give few chunks
@@ -389,7 +299,7 @@ void dvs_launch_gbn_loglik(const GbnRowArgs& in, dvs_stream_t st) {
     DVS_LAUNCH(k_gbn_params_prep, dim3((unsigned)a.net.B), dim3(64), 0, st, a);
     DVS_SET_LDS(k_gbn_loglik_rows, gpar_image_lds(DVS_WTOK));
     DVS_LAUNCH(k_gbn_loglik_rows, dim3((unsigned)a.chunks * a.bsplit), dim3(GPAR_ROWS), gpar_image_lds(a.net.n), st, a);
-    DVS_LAUNCH(k_gbn_loglik_sum, dim3((unsigned)a.net.B), dim3(256), 0, st, a);
+    fit_launch_loglik_sum(a.net.B, a.chunks, a.partials, a.out, st);
 }
 
 __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_predict(GbnRowArgs a) {
@@ -400,7 +310,7 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_predict(GbnRowArgs a) {
     double* x = (double*)smem;
     const int tid = threadIdx.x, n = a.net.n, t = a.target;
     const int chunk = blockIdx.x / a.bsplit, part = blockIdx.x - chunk * a.bsplit;
-    const int len = gpar_stage_rows(a, chunk, x);
+    const int len = fit_image_load(a.data, a.rows, n, chunk, x);
     const long long row = (long long)chunk * GPAR_ROWS + tid;
     for (int b = part; b < a.net.B; b += a.bsplit) {
         const bool ok = a.ok[b] != 0;                        // uniform
@@ -420,23 +330,15 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_gbn_predict(GbnRowArgs a) {
             const double s = s_net.sd[t] * s_net.sd[t];
             pred = gpar_mu(&s_net, x, tid, t, -1);
             var = s;
-            if (a.mode == DVS_GBN_PREDICT_EXACT) {
-                double prec = 1.0 / s;
-                double num = pred * prec;
-                for (int c = 0; c < n; ++c) {
+            if (a.mode == DVS_GBN_PREDICT_EXACT)
+                fit_blanket(n, s, pred, var, [&](int c, double& beta, double& sdc, double& res) {
                     const int at = s_child[c];
-                    if (at < 0) continue;                    // uniform: c is no child of t
-                    const double beta = s_net.coef[at];
-                    const double w = beta / (s_net.sd[c] * s_net.sd[c]);
-                    const double r = x[c * GPAR_LD + tid] - gpar_mu(&s_net, x, tid, c, t);
-                    const double wr = w * r;
-                    num = num + wr;
-                    const double bw = beta * w;
-                    prec = prec + bw;
-                }
-                pred = num / prec;
-                var = 1.0 / prec;
-            }
+                    if (at < 0) return false;                // uniform: c is no child of t
+                    beta = s_net.coef[at];
+                    sdc = s_net.sd[c];
+                    res = x[c * GPAR_LD + tid] - gpar_mu(&s_net, x, tid, c, t);
+                    return true;
+                });
         }
         if (tid < len) a.per_row[(size_t)b * a.rows + row] = pred;
         if (chunk == 0 && tid == 0) a.out[b] = var;

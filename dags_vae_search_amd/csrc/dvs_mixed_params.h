@@ -1,20 +1,21 @@
 // A fitted conditional Gaussian network on the device: forward sampling of its real columns, the continuous
-// part of the log-likelihood of held-out rows and prediction.  Included by k_bic.hip after dvs_mixed.h and dvs_params.h (whose
-// k_bn_loglik_sum adds the chunk sums).  Semantics, operation orders and refusals: include/dvs_mixed_params.h.  Plain fp64 vector
-// arithmetic: no f64 MFMA, no fused multiply-add (contraction is off in every function that rounds), no floating-point atomics.
+// part of the log-likelihood of held-out rows and prediction.  Included by k_bic.hip after dvs_mixed.h and
+// dvs_gaussian_params.h.  Semantics, operation orders and refusals: include/dvs_mixed_params.h.  Plain fp64 vector arithmetic:
+// no f64 MFMA, no fused multiply-add (contraction is off in every function that rounds), no floating-point atomics.  What makes
+// an all-continuous network give the Gaussian entry points' bytes is dvs_fitted.h's: the order, the image, the noise draw, the
+// density term, the blanket update and the two levels of the sum (k_bn_loglik_sum adds the chunk sums).
 //
 //   k_cgbn_prep          one wave: the rules on card / parents / offset and the topological order, into the workspace header.
 //   k_cgbn_cells         one thread per (continuous variable, configuration): the rule on the cell's parameters (bit 6) and
 //                        c = log(sd) + log(sqrt(2 pi)); an empty configuration (sd NaN) is skipped.
 //   k_cgbn_sample        one thread per row, 256 rows per workgroup, the row's packed words in registers, its real values in the
-//   k_cgbn_loglik_rows   image of dvs_gaussian_params.h (column c of row r at x[c * GPAR_LD + r]: coalesced global traffic and
+//   k_cgbn_loglik_rows   image of dvs_fitted.h (column c of row r at x[c * GPAR_LD + r]: coalesced global traffic and
 //   k_cgbn_predict       conflict-free LDS writes both ways).  k_cgbn_loglik_rows ends in dvs_bn_loglik's tree.
 // The network's arcs are a compact list in LDS (cgbn_stage): for every continuous variable its discrete parents with their radix
 // multipliers, its continuous parents with their columns of x, and its first cell.  The per-configuration parameters do not fit
 // LDS at q = 4096: a row reads them from global memory at cell * n + u, for its parents only.
 #pragma once
 #include "dvs_gaussian_params.h"
-#include "dvs_params.h"
 
 constexpr int CGBN_HDR_SOUND = 48;                           // header word after order [48], as dvs_bn_sample's
 constexpr int CGBN_HDR_BAD_CELL = 49;                        // set by k_cgbn_cells: a cell broke bit 6
@@ -70,19 +71,7 @@ __global__ __launch_bounds__(64) void k_cgbn_prep(CgbnRowArgs a) {
     if (bad) atomicOr(&s_state, bad);
     __syncthreads();
     if (tid == 0) {
-        uint64_t placed = 0ull;
-        bool cycle = false;
-        for (int k = 0; k < n && !cycle; ++k) {
-            int pick = -1;
-            for (int v = 0; v < n && pick < 0; ++v)
-                if (!((placed >> v) & 1ull) && !(s_par[v] & low & ~placed)) pick = v;
-            if (pick < 0) cycle = true;
-            else {
-                s_order[k] = pick;
-                placed |= 1ull << pick;
-            }
-        }
-        if (cycle) s_state |= 1;
+        if (!fit_order(n, [&](int v) { return s_par[v] & low; }, s_order)) s_state |= 1;
     }
     __syncthreads();
     const int state = s_state;
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(256) void k_cgbn_cells(CgbnRowArgs a) {
         atomicOr(a.net.status, 64);
         atomicOr(&a.header[CGBN_HDR_BAD_CELL], 1);
     }
-    if (a.c != nullptr) a.c[cell] = log(sd) + 0.9189385332046727;
+    if (a.c != nullptr) a.c[cell] = fit_log_norm(sd);
 }
 
 static void cgbn_launch_prep(const CgbnRowArgs& a, dvs_stream_t st) {
@@ -200,20 +189,6 @@ __device__ __forceinline__ double cgbn_mu(const CgbnLists* s, const CgbnNet& net
     return mu;
 }
 
-// stages rows 256 chunk .. of x [rows][nc] into the image; returns the rows it holds.  Every thread calls it; a barrier follows.
-__device__ __forceinline__ int cgbn_stage_rows(const CgbnRowArgs& a, int chunk, double* x) {
-    const int nc = a.net.nc;
-    const long long row0 = (long long)chunk * GPAR_ROWS;
-    const int len = a.rows - row0 < GPAR_ROWS ? (int)(a.rows - row0) : GPAR_ROWS;
-    const double* src = a.x + (size_t)row0 * nc;
-    for (int e = threadIdx.x; e < len * nc; e += blockDim.x) {
-        const int r = e / nc, c = e - r * nc;
-        x[c * GPAR_LD + r] = src[e];
-    }
-    __syncthreads();
-    return len;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Forward sampling of the real columns
 // ---------------------------------------------------------------------------------------------------------
@@ -223,13 +198,13 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_sample(CgbnRowArgs a) {
     __shared__ CgbnLists s_net;
     __shared__ int s_order[DVS_WTOK];
     double* x = (double*)smem;
-    const int tid = threadIdx.x, n = a.net.n, nc = a.net.nc;
+    const int tid = threadIdx.x, n = a.net.n;
     if (!cgbn_sound(a.header)) return;                       // uniform: the preparation refused the network
     if (tid < n) s_order[tid] = a.header[tid];
     cgbn_stage(a.net, &s_net);
     const long long row0 = (long long)blockIdx.x * GPAR_ROWS;
-    const int len = a.rows - row0 < GPAR_ROWS ? (int)(a.rows - row0) : GPAR_ROWS;
     int flags = 0;
+    const int len = fit_chunk_len(a.rows, blockIdx.x);
     if (tid < len) {
         const BnRow r = bn_row_load(a.packed + (size_t)(row0 + tid) * a.words, a.words);
         const uint32_t g = a.row_offset + (uint32_t)(row0 + tid);
@@ -245,9 +220,7 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_sample(CgbnRowArgs a) {
                 if (sd != sd) flags |= 128;
                 else {
                     const double mu = cgbn_mu(&s_net, a.net, x, tid, v, cell, -1);
-                    const uint32_t h1 = dvs_draw(key, 2u * (uint32_t)v), h2 = dvs_draw(key, 2u * (uint32_t)v + 1u);
-                    const uint64_t k = ((uint64_t)(h1 >> 6) << 26) + (uint64_t)(h2 >> 6);
-                    const double noise = sd * gpar_quantile(k);
+                    const double noise = sd * fit_noise(key, v);
                     value = mu + noise;
                 }
             }
@@ -255,12 +228,7 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_sample(CgbnRowArgs a) {
         }
     }
     if (flags) atomicOr(a.net.status, flags);
-    __syncthreads();
-    double* out = a.per_row + (size_t)row0 * nc;
-    for (int e = tid; e < len * nc; e += GPAR_ROWS) {
-        const int r = e / nc, c = e - r * nc;
-        out[e] = x[c * GPAR_LD + r];
-    }
+    fit_image_store(a.per_row, len, a.net.nc, blockIdx.x, x);
 }
 
 void dvs_launch_cgbn_sample(const CgbnRowArgs& in, uint64_t seed, dvs_stream_t st) {
@@ -281,11 +249,10 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_loglik_rows(CgbnRowArgs a) {
 #pragma clang fp contract(off)
     DVS_DYN_LDS(smem);
     __shared__ CgbnLists s_net;
-    __shared__ double red[GPAR_ROWS];
     double* x = (double*)smem;
     const int tid = threadIdx.x, n = a.net.n, chunk = blockIdx.x;
     const bool sound = cgbn_sound(a.header);                 // uniform
-    const int len = cgbn_stage_rows(a, chunk, x);
+    const int len = fit_image_load(a.x, a.rows, a.net.nc, chunk, x);
     if (sound) cgbn_stage(a.net, &s_net);
     const long long row = (long long)chunk * GPAR_ROWS + tid;
     double term = 0.0;
@@ -306,19 +273,15 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_loglik_rows(CgbnRowArgs a) {
                     flags |= 128;
                     continue;
                 }
-                const double e = (x[(int)s_net.col[v] * GPAR_LD + tid] - cgbn_mu(&s_net, a.net, x, tid, v, cell, -1)) / sd;
-                const double half = 0.5 * (e * e);
-                term = term - (a.c[cell] + half);
+                const double xv = x[(int)s_net.col[v] * GPAR_LD + tid];
+                term = fit_log_density(term, xv, cgbn_mu(&s_net, a.net, x, tid, v, cell, -1), sd, a.c[cell]);
             }
             if (flags) term = bn_nan();
         }
         if (a.per_row) a.per_row[row] = term;
     }
     if (flags) atomicOr(a.net.status, flags);
-    red[tid] = term;
-    __syncthreads();
-    dvs_block_sum256(tid, red);
-    if (tid == 0) a.partials[chunk] = red[0];
+    fit_chunk_sum(term, &a.partials[chunk]);
 }
 
 void dvs_launch_cgbn_loglik(const CgbnRowArgs& in, dvs_stream_t st) {
@@ -328,12 +291,7 @@ void dvs_launch_cgbn_loglik(const CgbnRowArgs& in, dvs_stream_t st) {
     cgbn_launch_prep(a, st);
     DVS_SET_LDS(k_cgbn_loglik_rows, gpar_image_lds(DVS_WTOK));
     DVS_LAUNCH(k_cgbn_loglik_rows, dim3((unsigned)a.chunks), dim3(GPAR_ROWS), gpar_image_lds(a.net.nc), st, a);
-    BnLoglikArgs sum = {};                                   // dvs_bn_loglik's second level over the one row of chunk sums
-    sum.B = 1;
-    sum.chunks = a.chunks;
-    sum.partials = a.partials;
-    sum.out = a.out;
-    DVS_LAUNCH(k_bn_loglik_sum, dim3(1), dim3(256), 0, st, sum);
+    fit_launch_loglik_sum(1, a.chunks, a.partials, a.out, st);                       // the one row of chunk sums
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -347,7 +305,7 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_predict(CgbnRowArgs a) {
     double* x = (double*)smem;
     const int tid = threadIdx.x, n = a.net.n, t = a.target, chunk = blockIdx.x;
     const bool sound = cgbn_sound(a.header);                 // uniform
-    const int len = cgbn_stage_rows(a, chunk, x);
+    const int len = fit_image_load(a.x, a.rows, a.net.nc, chunk, x);
     if (sound) cgbn_stage(a.net, &s_net);
     const long long row = (long long)chunk * GPAR_ROWS + tid;
     if (tid >= len) return;                                  // no barrier from here on
@@ -365,30 +323,22 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_predict(CgbnRowArgs a) {
                 pred = cgbn_mu(&s_net, a.net, x, tid, t, cell, -1);
                 var = s;
                 if (a.mode == DVS_CGBN_PREDICT_EXACT) {
-                    double prec = 1.0 / s;
-                    double num = pred * prec;
-                    for (int c = 0; c < n; ++c) {
-                        if (c == t || !((s_net.par[c] >> t) & 1ull)) continue;       // uniform: c is no child of t
+                    fit_blanket(n, s, pred, var, [&](int c, double& beta, double& sdc, double& res) {
+                        if (c == t || !((s_net.par[c] >> t) & 1ull)) return false;   // uniform: c is no child of t
                         const int cc = cgbn_cell(&s_net, r, c, -1, 0);
                         if (cc < 0) {
                             flags |= 16;
-                            continue;
+                            return false;
                         }
-                        const double sdc = a.net.sd[cc];
+                        sdc = a.net.sd[cc];
                         if (sdc != sdc) {
                             flags |= 128;
-                            continue;
+                            return false;
                         }
-                        const double beta = a.net.coef[(size_t)cc * n + t];
-                        const double w = beta / (sdc * sdc);
-                        const double res = x[(int)s_net.col[c] * GPAR_LD + tid] - cgbn_mu(&s_net, a.net, x, tid, c, cc, t);
-                        const double wr = w * res;
-                        num = num + wr;
-                        const double bw = beta * w;
-                        prec = prec + bw;
-                    }
-                    pred = num / prec;
-                    var = 1.0 / prec;
+                        beta = a.net.coef[(size_t)cc * n + t];
+                        res = x[(int)s_net.col[c] * GPAR_LD + tid] - cgbn_mu(&s_net, a.net, x, tid, c, cc, t);
+                        return true;
+                    });
                     if (flags) pred = var = bn_nan();
                 }
             }
@@ -414,11 +364,7 @@ __global__ __launch_bounds__(GPAR_ROWS) void k_cgbn_predict(CgbnRowArgs a) {
                     else {
                         const double sdc = a.net.sd[cc];
                         if (sdc != sdc) flags |= 128;
-                        else {
-                            const double e = (xc - cgbn_mu(&s_net, a.net, x, tid, c, cc, -1)) / sdc;
-                            const double half = 0.5 * (e * e);
-                            ak = s_a[k * GPAR_ROWS + tid] - (a.c[cc] + half);
-                        }
+                        else ak = fit_log_density(s_a[k * GPAR_ROWS + tid], xc, cgbn_mu(&s_net, a.net, x, tid, c, cc, -1), sdc, a.c[cc]);
                     }
                     s_a[k * GPAR_ROWS + tid] = ak;
                 }

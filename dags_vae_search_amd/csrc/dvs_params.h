@@ -1,21 +1,20 @@
 // Parameters of a discrete Bayesian network on the device (definitions in include/dvs.h): the conditional
 // probability tables of a structure, forward sampling from them and the log-likelihood of held-out rows.  Included by
 // k_bic.hip after dvs_citest.h.  Integer counts and fp64 arithmetic, every sum in a fixed order, no atomics but the integer LDS
-// histogram adds and the status atomicOr: two runs give equal bytes.
+// histogram adds and the status atomicOr: two runs give equal bytes.  The order and the two levels of the sum are dvs_fitted.h's.
 //
 //   k_bn_fit             one workgroup per (structure, variable): the dense (configuration, level) table in dynamic LDS, counted
 //                        by the scorer's routine (bn_dense_count, here with the range guard); the thread that owns configuration
 //                        j takes N_j and writes its r cells.  No sort path: a table above 36 864 cells is refused.
-//   k_bn_sample_prep     one workgroup: thread 0 orders the variables and checks the slots; all threads then check the rows of
-//                        the tables and write their u32 thresholds.
+//   k_bn_sample_prep     one workgroup: thread 0 checks the slots and orders the variables (fit_order); all threads then check
+//                        the rows of the tables and write their u32 thresholds.
 //   k_bn_sample          one thread per row: the variables in the prep's order, the row's levels in registers (BnRow), one
 //                        counter-based draw per (row, variable); thresholds from LDS when the tables fit DVS_BN_SAMPLE_LDS_CELLS.
 //   k_bn_loglik_prep     one workgroup per (structure, variable): checks the slot and writes log(theta) of its cells.
-//   k_bn_loglik_rows     one thread per row, one workgroup per 256 rows of one structure: the row term, then a fixed tree.
-//   k_bn_loglik_sum      one workgroup per structure: thread t adds the chunk partials t, t + 256, ... in ascending order, then
-//                        the same tree.
+//   k_bn_loglik_rows     one thread per row, one workgroup per 256 rows of one structure: the row term, then a fixed tree
+//                        (fit_chunk_sum); k_bn_loglik_sum of dvs_fitted.h adds the chunk partials of a structure.
 #pragma once
-#include "dvs_bn_common.h"
+#include "dvs_fitted.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // k_bn_fit
@@ -94,17 +93,8 @@ __global__ __launch_bounds__(256) void k_bn_sample_prep(BnSampleArgs a) {
             if (!ok || hi - lo != q * r) state = 16;
         }
         if (!state && a.offsets[n] - base != a.n_cells) state = 16;
-        uint64_t placed = 0ull;                              // the order: the lowest variable whose parents are all placed
-        for (int k = 0; k < n && !state; ++k) {
-            int pick = -1;
-            for (int v = 0; v < n && pick < 0; ++v)
-                if (!((placed >> v) & 1ull) && !(a.parents[v] & ~(1ull << v) & ~placed)) pick = v;
-            if (pick < 0) state = 1;
-            else {
-                a.header[k] = pick;
-                placed |= 1ull << pick;
-            }
-        }
+        // the slots have refused a parent bit >= n
+        if (!state && !fit_order(n, [&](int v) { return a.parents[v] & ~(1ull << v); }, a.header)) state = 1;
         s_state = state;
         s_bad = 0;
     }
@@ -194,7 +184,7 @@ void dvs_launch_bn_sample(const BnSampleArgs& in, uint64_t seed, dvs_stream_t st
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_bn_loglik_prep, k_bn_loglik_rows, k_bn_loglik_sum
+// k_bn_loglik_prep, k_bn_loglik_rows
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_bn_loglik_prep(BnLoglikArgs a) {
     __shared__ long long s_cells;
@@ -215,7 +205,6 @@ __global__ __launch_bounds__(256) void k_bn_loglik_prep(BnLoglikArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_bn_loglik_rows(BnLoglikArgs a) {
-    __shared__ double red[256];
     __shared__ int s_base[48], s_ok;
     __shared__ unsigned char s_card[48];
     __shared__ uint64_t s_par[48];
@@ -247,22 +236,7 @@ __global__ __launch_bounds__(256) void k_bn_loglik_rows(BnLoglikArgs a) {
         }
         if (a.per_row) a.per_row[(size_t)b * a.rows + row] = term;
     }
-    red[tid] = term;
-    __syncthreads();
-    dvs_block_sum256(tid, red);
-    if (tid == 0) a.partials[(size_t)b * a.chunks + chunk] = red[0];
-}
-
-__global__ __launch_bounds__(256) void k_bn_loglik_sum(BnLoglikArgs a) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const double* p = a.partials + (size_t)blockIdx.x * a.chunks;
-    double s = 0.0;
-    for (int c = tid; c < a.chunks; c += 256) s += p[c];
-    red[tid] = s;
-    __syncthreads();
-    dvs_block_sum256(tid, red);
-    if (tid == 0) a.out[blockIdx.x] = red[0];
+    fit_chunk_sum(term, &a.partials[(size_t)b * a.chunks + chunk]);
 }
 
 void dvs_launch_bn_loglik(const BnLoglikArgs& in, dvs_stream_t st) {
@@ -270,5 +244,5 @@ void dvs_launch_bn_loglik(const BnLoglikArgs& in, dvs_stream_t st) {
     a.words = bic_words(a.n);
     DVS_LAUNCH(k_bn_loglik_prep, dim3((unsigned)a.B * a.n), dim3(256), 0, st, a);
     DVS_LAUNCH(k_bn_loglik_rows, dim3((unsigned)a.B * a.chunks), dim3(256), 0, st, a);
-    DVS_LAUNCH(k_bn_loglik_sum, dim3((unsigned)a.B), dim3(256), 0, st, a);
+    fit_launch_loglik_sum(a.B, a.chunks, a.partials, a.out, st);
 }

@@ -279,6 +279,12 @@ struct BnLoglikArgs {
     int* status;
 };
 void dvs_launch_bn_loglik(const BnLoglikArgs& a, dvs_stream_t st);
+// The second level of dvs_bn_loglik, dvs_gbn_loglik and dvs_cgbn_loglik (dvs_fitted.h): one workgroup per structure
+struct BnLoglikSumArgs {
+    int chunks;
+    const double* partials;      // [B][chunks]
+    double* out;                 // [B]
+};
 
 // ---- inference on a fitted network: likelihood weighting, exact blanket posterior (dvs_infer.h) ------------------------
 // The workspace of dvs_bn_lw: the sampler's workspace (header, thresholds), then the per-query "evidence level >= card" flags
