@@ -38,7 +38,10 @@ from .incomplete import (EMResult, ExpectedCounts, StructuralEMResult, available
                          expected_counts, family_plans, fit_counts, impute, incomplete_rows, structural_em, target_plans)
 from .mixed import (FittedCGBN, MixedEvaluator, cg_cross_validate, cg_fit, cg_log_likelihood, cg_predict,  # noqa: F401
                     cg_sample)
-from .gaussian import (FittedGBN, GaussianEvaluator, gaussian_cross_validate, gaussian_fit, gaussian_joint,  # noqa: F401
-                       gaussian_log_likelihood, gaussian_predict, gaussian_sample)
+from .gaussian import (FittedGBN, GaussianEvaluator, GaussianMomentsEvaluator, gaussian_cross_validate, gaussian_fit,  # noqa: F401
+                       gaussian_joint, gaussian_log_likelihood, gaussian_predict, gaussian_sample)
+from .gaussian_incomplete import (ExpectedMoments, GaussianConditioned, GaussianEMResult, expected_moments,  # noqa: F401
+                                  gaussian_condition, gaussian_em_fit, gaussian_impute, gaussian_incomplete_log_likelihood,
+                                  gaussian_posterior, incomplete_real_rows)
 from .strength import (ArcStrength, AveragedNetwork, arc_strength, averaged_network, boot_strength, bootstrap_rows,  # noqa: F401
                        inclusion_threshold)

@@ -27,6 +27,7 @@ GCI_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_ci.h"
 GPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_params.h")  # the eighth: a fitted Gaussian network
 MIXED_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_mixed.h")       # the ninth: conditional Gaussian networks on mixed data
 MPAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_mixed_params.h")  # the tenth: a fitted conditional Gaussian network
+GINC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvs_gaussian_incomplete.h")  # the eleventh: a normal conditioned on partial evidence
 
 
 class DvsShape(Structure):
@@ -111,6 +112,8 @@ GPAR_SIGNATURES, _GP = _read_header(GPAR_HEADER)
 MIXED_SIGNATURES, _M = _read_header(MIXED_HEADER)
 # include/dvs_mixed_params.h, the tenth: sample, loglik and predict on a fitted CG network; the ten tables above stay what they are
 MPAR_SIGNATURES, _MP = _read_header(MPAR_HEADER)
+# include/dvs_gaussian_incomplete.h, the eleventh: dvs_gbn_condition and its workspace size; the eleven tables above stay what they are
+GINC_SIGNATURES, _ = _read_header(GINC_HEADER)
 
 
 def signature(fn: str):
@@ -137,10 +140,12 @@ def signature(fn: str):
         return MIXED_SIGNATURES[fn]
     if fn in MPAR_SIGNATURES:
         return MPAR_SIGNATURES[fn]
+    if fn in GINC_SIGNATURES:
+        return GINC_SIGNATURES[fn]
     raise KeyError(f"{fn} is declared in none of include/dvs.h, include/dvs_eliminate.h, include/dvs_incomplete.h, "
                    f"include/dvs_available.h, include/dvs_local.h, include/dvs_permtest.h, include/dvs_gaussian.h, "
                    f"include/dvs_gaussian_ci.h and include/dvs_gaussian_params.h, nor in include/dvs_mixed.h or "
-                   f"include/dvs_mixed_params.h")
+                   f"include/dvs_mixed_params.h, nor in include/dvs_gaussian_incomplete.h")
 
 D_MODEL, HEADS, LAYERS, LATENT, FC_HIDDEN, EMB = 64, 8, 3, 32, 32, 32
 MAX_TOKENS = 48           # 16 on the one-tile path (a wavefront owns a DAG); up to 48 on the tiled wide path
@@ -203,7 +208,7 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     for name, (restype, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *INC_SIGNATURES.items(), *AVAIL_SIGNATURES.items(),
                                   *LOCAL_SIGNATURES.items(), *PERM_SIGNATURES.items(), *GAUSS_SIGNATURES.items(),
                                   *GCI_SIGNATURES.items(), *GPAR_SIGNATURES.items(), *MIXED_SIGNATURES.items(),
-                                  *MPAR_SIGNATURES.items()):
+                                  *MPAR_SIGNATURES.items(), *GINC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = [ctype for _, ctype in args]

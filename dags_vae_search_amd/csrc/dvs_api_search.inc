@@ -1246,6 +1246,49 @@ extern "C" int dvs_gbn_predict(int32_t batch, int32_t n_vars, int64_t n_rows, co
     return call_end(fn);
 }
 
+// ---- a normal conditioned on every row's observed part (dvs_gaussian_incomplete.h; include/dvs_gaussian_incomplete.h) -----------
+extern "C" size_t dvs_gbn_condition_workspace_bytes(int32_t n_vars, int64_t n_rows) {
+    const char* fn = "dvs_gbn_condition_workspace_bytes";
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn), 0;
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn), 0;
+    return dvs_gbn_condition_layout(n_vars, n_rows).total;
+}
+
+extern "C" int dvs_gbn_condition(int32_t n_vars, int64_t n_rows, const double* mean, const double* cov, const double* x,
+                                 const uint64_t* observed, const int32_t* order, double* completed, double* cvar, double* quad,
+                                 double* logp, double* loglik, double* ccov, int64_t* counts, void* workspace,
+                                 size_t workspace_bytes, int32_t* status, void* stream) {
+    const char* fn = "dvs_gbn_condition";
+    if (n_rows < 1 || n_rows > (int64_t)0x7fffffff) return failf(2, "%s: n_rows must be in [1, 2^31 - 1]", fn);
+    if (n_vars < 1 || n_vars > DVS_WTOK) return failf(3, "%s: n_vars must be in [1, 48]", fn);
+    if (!mean || !cov || !x || !observed || !logp || !loglik || !workspace || !status) return failf(10, "%s: null pointer", fn);
+    const GbnConditionLayout l = dvs_gbn_condition_layout(n_vars, n_rows);
+    if (workspace_bytes < l.total) return fail_size("dvs_gbn_condition: workspace_bytes < dvs_gbn_condition_workspace_bytes", l.total);
+    GbnConditionArgs a = {};
+    a.n = n_vars;
+    a.chunks = (int)l.chunks;
+    a.rows = n_rows;
+    a.mean = mean;
+    a.cov = cov;
+    a.x = x;
+    a.observed = observed;
+    a.order = order;
+    a.completed = completed;
+    a.cvar = cvar;
+    a.quad = quad;
+    a.logp = logp;
+    a.loglik = loglik;
+    a.ccov = ccov;
+    a.counts = (long long*)counts;
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.refused = (int*)((char*)workspace + l.refused);
+    a.cov_partials = (double*)((char*)workspace + l.cov);
+    a.status = status;
+    call_begin();
+    dvs_launch_gbn_condition(a, (dvs_stream_t)stream);
+    return call_end(fn);
+}
+
 // What dvs_pc_expand and dvs_pc_reduce check alike, first: the pair count, n_vars and the level's test count.
 static int pc_dims(const char* fn, int n_pairs, int n_vars, int64_t n_tests) {
     if (n_pairs < 1 || n_pairs > DVS_WTOK * (DVS_WTOK - 1) / 2) return failf(2, "%s: n_pairs must be in [1, 1128]", fn);

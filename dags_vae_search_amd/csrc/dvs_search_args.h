@@ -2,7 +2,7 @@
 // generator (kernels in dvs_match.h / dvs_structs.h / dvs_generate.h, compiled into k_decode.hip), the BN scorers, hill
 // climbing, tabu, structure comparison, CI tests and PC-stable, BN parameters, exact search, the exact arc posterior and the GP
 // predictor (k_bic.hip with dvs_bn_common.h and dvs_hillclimb.h / dvs_tabu.h / dvs_cpdag.h / dvs_citest.h / dvs_params.h /
-// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h / dvs_mixed.h / dvs_mixed_params.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
+// dvs_infer.h / dvs_eliminate.h / dvs_incomplete.h / dvs_exact.h / dvs_posterior.h / dvs_strength.h / dvs_available.h / dvs_local.h / dvs_permtest.h / dvs_gaussian.h / dvs_gaussian_ci.h / dvs_gaussian_params.h / dvs_gaussian_incomplete.h / dvs_mixed.h / dvs_mixed_params.h; k_gp_acq.hip).  Plain C++, no device code: the kernel files and the C-ABI layer
 // (dvs_api_search.inc) both include it.  An entry point validates and fills the
 // block by field name; the launcher next to the kernel owns the grid, block, LDS size, the template or family choice, the
 // profile name and the fields marked "launcher" below, which it derives from kernel constants or from its extra arguments.
@@ -18,6 +18,7 @@
 #include "../../include/dvs_gaussian_params.h"
 #include "../../include/dvs_mixed.h"
 #include "../../include/dvs_mixed_params.h"
+#include "../../include/dvs_gaussian_incomplete.h"
 
 struct DvsDecodeState;           // dvs_decode.h
 
@@ -744,6 +745,44 @@ struct GbnRowArgs {
 };
 void dvs_launch_gbn_loglik(const GbnRowArgs& a, dvs_stream_t st);
 void dvs_launch_gbn_predict(const GbnRowArgs& a, dvs_stream_t st);
+
+// ---- a multivariate normal conditioned on every row's observed part (dvs_gaussian_incomplete.h; include/dvs_gaussian_incomplete.h)
+// The workspace of dvs_gbn_condition: the chunk sums f64 [chunks], the refused rows per chunk i32 [chunks], the chunks' covariance
+// cells f64 [n (n + 1) / 2][chunks]; each array starts at a multiple of 256 bytes.
+struct GbnConditionLayout {
+    size_t partials, refused, cov, total, chunks;
+};
+inline GbnConditionLayout dvs_gbn_condition_layout(int n_vars, long long rows) {
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    GbnConditionLayout l;
+    l.chunks = (size_t)((rows + 255) / 256);
+    l.partials = 0;
+    l.refused = up(l.chunks * 8);
+    l.cov = l.refused + up(l.chunks * 4);
+    l.total = l.cov + (size_t)n_vars * (n_vars + 1) / 2 * l.chunks * 8;
+    return l;
+}
+struct GbnConditionArgs {
+    int n, chunks;
+    long long rows;
+    const double* mean;          // [n]
+    const double* cov;           // [n][n], the lower triangle is read
+    const double* x;             // [rows][n]
+    const uint64_t* observed;    // [rows]
+    const int* order;            // null or [rows]
+    double* completed;           // null or [rows][n]
+    double* cvar;                // null or [rows][n]
+    double* quad;                // null or [rows]
+    double* logp;                // [rows]
+    double* loglik;              // [1]
+    double* ccov;                // null or [n][n]
+    long long* counts;           // null or [1]
+    double* partials;            // workspace [chunks]
+    int* refused;                // workspace [chunks]
+    double* cov_partials;        // workspace [n (n + 1) / 2][chunks]
+    int* status;
+};
+void dvs_launch_gbn_condition(const GbnConditionArgs& a, dvs_stream_t st);
 
 // ---- conditional Gaussian networks on mixed data (dvs_mixed.h; include/dvs_mixed.h) ----------------------------------------------
 struct CgPartitionArgs {

@@ -267,6 +267,7 @@ __global__ __launch_bounds__(256) void k_bic_sum(BicArgs a) {
 #include "dvs_mixed.h"
 #include "dvs_params.h"
 #include "dvs_mixed_params.h"
+#include "dvs_gaussian_incomplete.h"
 #include "dvs_infer.h"
 #include "dvs_eliminate.h"
 #include "dvs_incomplete.h"

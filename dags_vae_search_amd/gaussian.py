@@ -175,6 +175,31 @@ class GaussianRowSetEvaluator(_GaussianScorer):
         raise NotImplementedError("row sets over a row-set view are not built: index the base evaluator's rows")
 
 
+class GaussianMomentsEvaluator(_GaussianScorer):
+    """A Gaussian scorer over moments that are given, not taken from rows: f64 [1, 1 + n + n n] in ``dvs_gbn_moments``'s layout
+    (size, means, centred cross-products), e.g. the expected moments of incomplete data (``ExpectedMoments.evaluator``,
+    gaussian_incomplete.py).  It has the whole evaluator surface, so the searches and ``gaussian_fit`` take it as they take a
+    ``GaussianEvaluator``; it has no rows (no ``x``), so what reads rows refuses it, and the CI tests do too: whether a test on
+    expected moments should count the rows as observed is not decided here."""
+    ci_refusal = ("the evaluator holds given (expected) moments, not rows: a CI test would count every row as observed, and what a "
+                  "test on expected moments means is not decided")
+
+    def __init__(self, dataset_name: str, metric_name: str, moments: torch.Tensor, *, k=None, iss_mu=None, iss_w=None):
+        if not torch.is_tensor(moments) or moments.device.type != "cuda":
+            raise RuntimeError("dags_vae_search_amd: GaussianMomentsEvaluator takes moments on the GPU; this package has no CPU path")
+        if moments.dtype != torch.float64 or moments.ndim != 2 or moments.shape[0] != 1 or moments.shape[1] < 3:
+            raise ValueError("moments must be float64 [1, 1 + n + n n] (dvs_gbn_moments's layout)")
+        n = int(round((math.sqrt(4 * moments.shape[1] - 3) - 1) / 2))
+        if not 1 <= n <= dl.MAX_TOKENS or dl.gbn_stride(n) != moments.shape[1]:
+            raise ValueError("moments must be float64 [1, 1 + n + n n] with 1 <= n <= 48")
+        GaussianEvaluator._set_score(self, dataset_name, metric_name, k, iss_mu, iss_w, n)
+        self.lib, self.device, self.moments = dl.load(), moments.device, moments.contiguous()
+        self.n_vars, self.n_samples = n, int(moments[0, 0].item())
+
+    def with_rows(self, rows, set_of=None):
+        raise NotImplementedError("a GaussianMomentsEvaluator holds moments, not rows: there is nothing to index")
+
+
 @dataclass
 class FittedGBN:
     parents: torch.Tensor                  # int64 [B, n]: the structures

@@ -56,6 +56,8 @@ def _evaluator(what, evaluator, test=None):
         if not _gaussian(evaluator):
             raise ValueError(f"{what}: test {test!r} reads real-valued data and the evaluator holds discrete levels: pass a "
                              f"GaussianEvaluator, or one of {sorted(dl.CI_TYPES) + sorted(dl.CI_PERM_TYPES)}")
+        if getattr(evaluator, "ci_refusal", None):           # GaussianMomentsEvaluator (gaussian.py)
+            raise ValueError(f"{what}: {evaluator.ci_refusal}")
         dl.need_cuda(what, evaluator.device)
         return None
     dl.need_discrete(what, evaluator)
